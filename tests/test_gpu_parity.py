@@ -1640,6 +1640,30 @@ def test_bench_line_contract(tmp_path, force_gather):
         assert 0.0 < rf["mix"]["valu_pipe_busy"] <= 1.05
 
 
+@pytest.mark.parametrize("protocol", ["batch", "lanes"])
+def test_bench_dump_outputs(tmp_path, protocol):
+    """--dump-outputs writes the last timed step's frames, one float32 [h, w] file per scene, and they are the oracle's images
+    (the checksum bench.py verifies against, recomputed from the dumped pixels)."""
+    import json
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--repeats", "1",
+                          "--protocol", protocol, "--no-serial-extra", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["irreg_1000x1000.npy", "rgbbox_1000x1000.npy"]
+    for scene in ("rgbbox", "irreg"):
+        px = np.load(tmp_path / f"{scene}_1000x1000.npy")
+        assert px.dtype == np.float32 and px.shape == (1000, 1000)
+        c = 0
+        for v in px.reshape(-1).astype(np.int64).tolist():
+            c = (c * 31 + v) & 0xffffffff
+        assert c == bench.FRAME_CHECKSUM[(scene, 1000, 1000)], scene
+
+
 def test_bench_line_two_ranks_sharing_the_gpu():
     """The driver's N > 1 command line (torch.distributed.run, one rank per GPU) with both ranks on cuda:0
     (RT_SHARE_GPU=1: gloo, host-staged gather): the sharded steps are verified against the oracle's checksums and the

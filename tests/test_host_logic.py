@@ -271,6 +271,46 @@ def test_spilling_box_stack_discipline(height, cap):
             assert high_all > cap                                  # (the greedy adversary does make it spill)
 
 
+def _bench_module():
+    import importlib
+    import sys
+    saved = dict(os.environ)
+    try:
+        if ROOT not in sys.path:
+            sys.path.insert(0, ROOT)
+        return importlib.import_module("bench")
+    finally:                        # (bench.py sets HIP runtime defaults at import: not this process's business)
+        os.environ.clear()
+        os.environ.update(saved)
+
+
+def test_bench_dump_outputs_writer(tmp_path):
+    """bench.py --dump-outputs: frames that fit in 64 MB are written whole as float32 (packed pixels are exact), larger ones as
+    the same seeded sample of every run, with its indices; never more than 64 MB in all."""
+    B = _bench_module()
+    rng = np.random.default_rng(3)
+    small = {("rgbbox", 20, 30): rng.integers(0, 1 << 24, (20, 30), dtype=np.int32),
+             ("irreg", 10, 10): rng.integers(0, 1 << 24, (10, 10), dtype=np.int32)}
+    B.dump_outputs(str(tmp_path / "a"), small)
+    assert sorted(os.listdir(tmp_path / "a")) == ["irreg_10x10.npy", "rgbbox_30x20.npy"]
+    for (scene, h, w), img in small.items():
+        got = np.load(tmp_path / "a" / f"{scene}_{w}x{h}.npy")
+        assert got.dtype == np.float32 and got.shape == (h, w)
+        assert np.array_equal(got.astype(np.int64), img.astype(np.int64))
+    big = {("irreg", 4000, 4000): rng.integers(0, 1 << 24, (4000, 4000), dtype=np.int32)}
+    for run in ("b", "c"):
+        B.dump_outputs(str(tmp_path / run), big)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["irreg_4000x4000.npy", "irreg_4000x4000_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= B.DUMP_LIMIT_BYTES
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)), f
+    idx = np.load(tmp_path / "b" / "irreg_4000x4000_index.npy").astype(np.int64)
+    vals = np.load(tmp_path / "b" / "irreg_4000x4000.npy")
+    assert vals.dtype == np.float32 and len(idx) == B.DUMP_SAMPLE == len(np.unique(idx))
+    assert np.array_equal(vals.astype(np.int64), big[("irreg", 4000, 4000)].reshape(-1)[idx])
+
+
 def test_reference_harness_builds_against_our_header():
     """/root/reference/futhark/main.c must compile and link unmodified (build container only)."""
     if not os.path.exists("/root/reference/futhark/main.c"):
