@@ -70,10 +70,12 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
 /* What the last render entry of this context enqueued, for benches and profiles that want to assert which kernel ran (pixels never
  * depend on it).  Owned by ctx; "" before the first render.  (A multi-device context: the first device's part.)  Values:
  *   "family=none (memset)"        max_depth == 0: every pixel is the initial colour, no kernel
+ *   "family=none (no rays)"       a caller-ray entry with n == 0
+ *   "family=pixel (rays)" | "family=intersect" | "family=camera-rays"   the caller-ray entries (below)
  *   "family=none (no rows)"       the part owns no row of the image
  *   "family=pixel" | "family=pixel (instrumented)" | "family=persistent"
  *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2"
- *     T = pixel-list | tiles-ordered | tiles-bit-reversed (a view's first frame with nothing to borrow, first_order = 1) | tiles-raster,
+ *     T = rays (rt_trace_rays: blocks of 64 caller rays, instantiation plain[+SPILL]) | pixel-list | tiles-ordered | tiles-bit-reversed (a view's first frame with nothing to borrow, first_order = 1) | tiles-raster,
  *         followed by "(borrowed)" when the order / list is another view's (a new view of a prepared scene that has rendered a view of the same shape)
  *     I = plain | SOLO | COLD | COLD+SOLO | DONATE | DONATE+SOLO | ORD | ORD+SOLO | ORD+DONATE | ORD+SOLO+DONATE;  +CULL: boxes tested against the best hit so far; +SPILL: a box stack that may overflow into device memory (twenty waves per CU, trees taller than 15 levels)
  *     recording: 0 nothing, 1 the tiles' longest chains, 2 also every pixel's chain length */
@@ -197,10 +199,38 @@ int rt_render_timed(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w
                     int32_t rows_per_tile, int32_t part, int32_t nparts, int32_t *out_dev,
                     int32_t warmup, int32_t iters, float *ms_out);
 
+/* ---- caller-supplied rays: objs_hit and ray_colour (ray.fut:76-86, :126-148) on a prepared scene ----------------
+ * Rays are n x 6 contiguous float32 in the context's device memory, {origin.xyz, dir.xyz}.  Every entry enqueues its
+ * work on the context's stream and returns (completion: rt_context_sync), holding the context lock like the render
+ * entries.  Refused (non-zero, rt_last_error set, nothing launched): n < 0, n >= 2^31, a NULL rays pointer, no output,
+ * and a multi-device context.  n == 0 succeeds without a launch.  Results are the reference's, bit for bit, for every
+ * ray with finite components and a non-zero direction; for other rays they are unspecified (but nothing is read or
+ * written out of range). */
+/* ray_colour objs r max_depth (ray.fut:126-148) of each ray, with objs_hit r 0 1e9 as the render path has it.
+ * colour3_dev: n x 3 float32, the colour before colour_to_pixel; pixel_dev: n int32, colour_to_pixel of it
+ * (ray.fut:156-162).  Either may be NULL, not both.  The pooled family traces the rays under RT_VARIANT_AUTO /
+ * RT_VARIANT_POOLED (64 consecutive rays per ticket of its raster queue; the pixel family beyond its limits, as
+ * rt_render); the pixel family, one lane per ray, under RT_VARIANT_PIXEL and RT_VARIANT_PERSISTENT.
+ * rt_context_last_launch: "family=pooled tickets=rays ..." or "family=pixel (rays)". */
+int rt_trace_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, int32_t max_depth,
+                  float *colour3_dev, int32_t *pixel_dev);
+/* objs_hit bvh r t_min t_max (ray.fut:76-86) of each ray: boxes tested with aabb_hit over (t_min, t_max), spheres folded
+ * over (scene_epsilon, best) from best = t_max (ties to the lowest leaf index), the winner re-intersected over
+ * (t_min, t + 1).  index_dev: n int32, the sphere's index in the prepared scene's L (rt_prepared_get_bvh), -1 for #none
+ * (no sphere, or a failed re-intersection); hit7_dev: n x 7 float32 {t, p.xyz, normal.xyz} of the returned hit
+ * (ray.fut:40-46), seven zeros for #none; may be NULL.  Refused as well: t_min or t_max non-finite or negative,
+ * t_min > t_max, t_max > 1e9.  One lane per ray (rt_context_last_launch: "family=intersect"). */
+int rt_intersect_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
+                      int32_t *index_dev, float *hit7_dev);
+/* The primary rays rt_render_image would trace (get_ray at pixel_u / pixel_v), row-major from the top row: h * w x 6
+ * float32 at rays_dev.  cam12 == NULL: the prepared camera.  rt_context_last_launch: "family=camera-rays". */
+int rt_camera_rays(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, const float cam12[12], float *rays_dev);
+
 /* ---- device buffers for hosts that have no allocator of their own (the C harness) -- */
 int rt_device_alloc(rt_context *ctx, void **out_dev, int64_t bytes);
 int rt_device_free(rt_context *ctx, void *dev);
 int rt_copy_to_host(rt_context *ctx, void *dst_host, const void *src_dev, int64_t bytes);  /* synchronous */
+int rt_copy_to_device(rt_context *ctx, void *dst_dev, const void *src_host, int64_t bytes);  /* synchronous */
 
 #ifdef __cplusplus
 }

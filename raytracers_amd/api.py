@@ -149,8 +149,8 @@ class DeviceBuffer:
         # (the device that owns the buffer, not torch's current one: a context on another GPU would get a mislabelled tensor)
         return torch.as_tensor(holder, device=torch.device("cuda", self.ctx.device_info()["device"]))
 
-    def to_host(self, shape):
-        out = np.empty(shape, dtype=np.int32)
+    def to_host(self, shape, dtype=np.int32):
+        out = np.empty(shape, dtype=dtype)
         assert out.nbytes <= self.nbytes
         self.ctx._check(lib.rt_copy_to_host(self.ctx._h, out.ctypes.data, self.ptr, out.nbytes))
         return out
@@ -367,3 +367,94 @@ def place_parts_batch(ctx, h, w, nparts, part_stride, nframes, frame_stride_in, 
     ctx._check(lib.rt_place_parts_batch(ctx._h, int(h), int(w), int(rows_per_tile), int(nparts), int(part_stride), int(nframes),
                                         int(frame_stride_in), int(h * w if frame_stride_out is None else frame_stride_out),
                                         C.c_void_p(stacked_ptr), C.c_void_p(images_ptr)))
+
+
+# -- caller-supplied rays: objs_hit / ray_colour (ray.fut:76-86, :126-148) on a prepared scene.  Rays are n x 6 float32
+# {origin.xyz, dir.xyz} in the context's device memory.
+
+def trace_rays_into(rays_ptr, n, prepared, colour_ptr=None, pixel_ptr=None, max_depth=MAX_DEPTH):
+    """Enqueue ray_colour of `n` rays at the device pointer `rays_ptr`: colours (n x 3 float32) to colour_ptr and / or packed
+    pixels (n int32) to pixel_ptr (rt_trace_rays).  Asynchronous: ctx.sync() completes it."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_trace_rays(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), int(max_depth), C.c_void_p(colour_ptr),
+                                 C.c_void_p(pixel_ptr)))
+
+
+def intersect_rays_into(rays_ptr, n, prepared, index_ptr, hit_ptr=None, t_min=0.0, t_max=1e9):
+    """Enqueue objs_hit bvh r t_min t_max of `n` rays (rt_intersect_rays): sphere index (n int32, -1 for none) to index_ptr,
+    {t, p.xyz, normal.xyz} (n x 7 float32) to hit_ptr if given."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_intersect_rays(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), float(t_min), float(t_max),
+                                     C.c_void_p(index_ptr), C.c_void_p(hit_ptr)))
+
+
+def camera_rays_into(rays_ptr, h, w, prepared, cam=None):
+    """Enqueue the h * w primary rays rt_render_image would trace (rt_camera_rays) into rays_ptr (h * w x 6 float32)."""
+    ctx = prepared.ctx
+    c = None
+    if cam is not None:
+        c = np.ascontiguousarray(cam, dtype=np.float32)
+        assert c.size == 12
+    ctx._check(lib.rt_camera_rays(ctx._h, prepared._h, int(h), int(w), None if c is None else c.ctypes.data, C.c_void_p(rays_ptr)))
+
+
+def _device_rays(ctx, rays):
+    """(pointer, n, keep-alive) for `rays`: a numpy array is uploaded to a fresh device buffer; a contiguous float32 torch
+    tensor on the context's device is used in place."""
+    if hasattr(rays, "data_ptr"):
+        dev = ctx.device_info()["device"]
+        if str(rays.dtype) != "torch.float32" or not rays.is_contiguous() or rays.device.type != "cuda" or rays.device.index != dev:
+            raise ValueError(f"rays: a contiguous float32 tensor on cuda:{dev} is required")
+        if rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError("rays must be (n, 6): origin.xyz, dir.xyz")
+        return rays.data_ptr(), int(rays.shape[0]), None
+    a = np.ascontiguousarray(rays, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 6:
+        raise ValueError("rays must be (n, 6): origin.xyz, dir.xyz")
+    buf = DeviceBuffer(ctx, max(a.nbytes, 4))
+    if a.nbytes:
+        ctx._check(lib.rt_copy_to_device(ctx._h, C.c_void_p(buf.ptr), a.ctypes.data, a.nbytes))
+    return buf.ptr, a.shape[0], buf
+
+
+def trace_rays(prepared, rays, max_depth=MAX_DEPTH):
+    """ray_colour of every ray (ray.fut:126-148) -> (colour (n, 3) float32, pixel (n,) int32) numpy arrays."""
+    ctx = prepared.ctx
+    ptr, n, keep = _device_rays(ctx, rays)
+    col = DeviceBuffer(ctx, max(12 * n, 4))
+    px = DeviceBuffer(ctx, max(4 * n, 4))
+    try:
+        trace_rays_into(ptr, n, prepared, col.ptr, px.ptr, max_depth)
+        return col.to_host((n, 3), np.float32), px.to_host((n,))
+    finally:
+        col.free()
+        px.free()
+        if keep is not None:
+            keep.free()
+
+
+def intersect_rays(prepared, rays, t_min=0.0, t_max=1e9):
+    """objs_hit bvh r t_min t_max of every ray (ray.fut:76-86) -> (index (n,) int32, hit (n, 7) float32) numpy arrays."""
+    ctx = prepared.ctx
+    ptr, n, keep = _device_rays(ctx, rays)
+    idx = DeviceBuffer(ctx, max(4 * n, 4))
+    hit = DeviceBuffer(ctx, max(28 * n, 4))
+    try:
+        intersect_rays_into(ptr, n, prepared, idx.ptr, hit.ptr, t_min, t_max)
+        return idx.to_host((n,)), hit.to_host((n, 7), np.float32)
+    finally:
+        idx.free()
+        hit.free()
+        if keep is not None:
+            keep.free()
+
+
+def camera_rays(prepared, h, w, cam=None):
+    """The primary rays of an h x w frame (rt_camera_rays) -> (h * w, 6) float32 numpy array, row-major from the top row."""
+    ctx = prepared.ctx
+    buf = DeviceBuffer(ctx, 24 * int(h) * int(w))
+    try:
+        camera_rays_into(buf.ptr, h, w, prepared, cam)
+        return buf.to_host((int(h) * int(w), 6), np.float32)
+    finally:
+        buf.free()

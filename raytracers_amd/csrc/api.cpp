@@ -1789,6 +1789,150 @@ extern "C" int rt_copy_to_host(rt_context *ctx, void *dst_host, const void *src_
   return 0;
 }
 
+extern "C" int rt_copy_to_device(rt_context *ctx, void *dst_dev, const void *src_host, int64_t bytes) {
+  RT_LOCK(ctx);
+  if (!ctx || !dst_dev || !src_host || bytes < 0) return fail(ctx, "bad argument");
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  RT_HIP(ctx, hipMemcpyAsync(dst_dev, src_host, static_cast<size_t>(bytes), hipMemcpyHostToDevice, ctx->stream));
+  RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->synced_since_render = true;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------ caller rays
+namespace {
+// The checks every caller-ray entry shares; on success p holds the prepared scene's traversal copy and the ray count.
+int ray_entry_params(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, rtk::KParams *p) {
+  if (!ps) return fail(ctx, "null prepared scene");
+  if (ctx->group) return fail(ctx, "caller rays: a multi-device context is not supported (use a context on one device)");
+  if (n < 0 || n >= (int64_t(1) << 31)) return fail(ctx, "ray count out of range: 0 <= n < 2^31");
+  if (!rays_dev) return fail(ctx, "null rays pointer");
+  *p = rtk::KParams{};
+  p->nodes = ps->nodes; p->nodes64 = ps->nodes64; p->sph = ps->sph; p->col = ps->col;
+  std::copy(ps->root_lo, ps->root_lo + 3, p->root_lo);
+  std::copy(ps->root_hi, ps->root_hi + 3, p->root_hi);
+  p->n_nodes = static_cast<int>(ps->n - 1); p->n_sph = static_cast<int>(ps->n);
+  p->rays = rays_dev;
+  p->nrays = static_cast<int>(n);
+  return 0;
+}
+}  // namespace
+
+extern "C" int rt_trace_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, int32_t max_depth,
+                             float *colour3_dev, int32_t *pixel_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!colour3_dev && !pixel_dev) return fail(ctx, "rt_trace_rays: both outputs are NULL");
+  if (max_depth < 0) return fail(ctx, "negative max_depth");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  if (n == 0) {
+    ctx->last_launch = "family=none (no rays)";
+    return 0;
+  }
+  if (max_depth == 0) {
+    // `while depth < 0`: every ray's colour is the initial (0,0,0)
+    if (colour3_dev) RT_HIP(ctx, hipMemsetAsync(colour3_dev, 0, sizeof(float) * 3 * static_cast<size_t>(n), ctx->stream));
+    if (pixel_dev) RT_HIP(ctx, hipMemsetAsync(pixel_dev, 0, sizeof(int32_t) * static_cast<size_t>(n), ctx->stream));
+    ctx->last_launch = "family=none (memset)";
+    return 0;
+  }
+  p.max_depth = max_depth;
+  p.out = pixel_dev;
+  p.colour3 = colour3_dev;
+  p.nframes = 1;
+  // the pooled family's plan for a frame of as many 64-ray blocks (its LDS staging, the wide shape); the pixel family beyond its limits
+  // (AUTO), or under RT_VARIANT_PIXEL / RT_VARIANT_PERSISTENT
+  Plan pl{};
+  pl.variant = RT_VARIANT_PIXEL;
+  const int64_t nblocks = (n + 63) / 64;
+  if (ctx->variant == RT_VARIANT_AUTO || ctx->variant == RT_VARIANT_POOLED) {
+    const bool huge = rt_scene_exceeds_l2(ps);
+    const bool wide = ctx->wide_waves == 2 || (ctx->wide_waves == 1 && nblocks >= (huge ? 40000 : 100000) && nblocks > ctx->px_max_tiles);
+    if (int rc = make_plan(ctx, ps, &pl, nblocks, 0, wide)) return rc;
+  }
+  if (pl.variant != RT_VARIANT_POOLED) {
+    RT_HIP(ctx, rtk::launch_pixel_rays(p, ctx->stream));
+    ctx->last_launch = "family=pixel (rays)";
+    return 0;
+  }
+  if (ps->n >= (int64_t(1) << 22)) return fail(ctx, "pooled kernel: at most 2^22 spheres (work items and hit keys carry the leaf index in 22 bits)");
+  p.queue = ctx->queue_dev;
+  p.w = 64; p.h = 1;
+  p.rows_local = 1; p.rows_per_tile = 1; p.part = 0; p.nparts = 1; p.rpt_log2 = 0;
+  p.tiles_x = static_cast<int>(nblocks); p.tiles_y = 1;
+  p.nchunks = static_cast<int>(nblocks);
+  p.tpt_log2 = 0;
+  // the eight counters take turns over the one raster queue (strips of tile columns are a 2D layout; the rays have none)
+  p.nshards = pl.grid % rtk::kMaxShards == 0 && ctx->xcd_queues != 0 ? rtk::kMaxShards : 1;
+  p.interleave = p.nshards > 1;
+  p.static_first = ctx->static_first;
+  p.lds_nodes = pl.lds_nodes; p.lds_sph = pl.lds_sph;
+  p.smax = pl.smax; p.lmax = pl.lmax;
+  p.thr_shade = ctx->thr_shade; p.thr_leaf = ctx->thr_leaf;
+  p.capb = pl.capb; p.capl = pl.capl; p.ray_planes = pl.ray_planes;
+  if (pl.spill_stride > 0) {
+    if (int rc = ensure_spill(ctx, pl.spill_stride)) return rc;
+    p.spill = ctx->spill_dev;
+    p.spill_stride = pl.spill_stride;
+  }
+  const bool twenty = pl.waves * (pl.grid_full / std::max(1, ctx->num_cu)) == 20;
+  p.prio_depth = ctx->prio_depth;
+  p.box2 = ctx->box2;
+  p.look_max = ctx->look_max > 0 ? ctx->look_max : (twenty ? 16 : p.nchunks > 16384 ? 32 : 64);
+  p.tl_log2 = ps->tl_depth;
+  RT_HIP(ctx, rtk::launch_pooled_rays(p, pl.grid, pl.waves, ctx->stream));
+  char buf[256];
+  std::snprintf(buf, sizeof buf, "family=pooled tickets=rays instantiation=plain%s frames=1 tiles=%d grid=%d waves=%d counters=%d%s deep_class=0 deep_split=0 recording=0",
+                p.spill ? "+SPILL" : "", p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "");
+  ctx->last_launch = buf;
+  return 0;
+}
+
+extern "C" int rt_intersect_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
+                                 int32_t *index_dev, float *hit7_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!index_dev) return fail(ctx, "rt_intersect_rays: null index pointer");
+  // (aabb_hit's NaN argument in lane_core.h -- the last slab test decides -- needs a finite interval)
+  if (!std::isfinite(t_min) || !std::isfinite(t_max) || t_min < 0.0f || t_min > t_max || t_max > rtk::kTMax)
+    return fail(ctx, "rt_intersect_rays: need 0 <= t_min <= t_max <= 1e9, both finite");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  if (n == 0) {
+    ctx->last_launch = "family=none (no rays)";
+    return 0;
+  }
+  RT_HIP(ctx, rtk::launch_intersect_rays(p, t_min, t_max, index_dev, hit7_dev, ctx->stream));
+  ctx->last_launch = "family=intersect";
+  return 0;
+}
+
+extern "C" int rt_camera_rays(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, const float cam12[12], float *rays_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  if (!ps) return fail(ctx, "null prepared scene");
+  if (ctx->group) return fail(ctx, "caller rays: a multi-device context is not supported (use a context on one device)");
+  if (!rays_dev) return fail(ctx, "null rays pointer");
+  if (h <= 0 || w <= 0 || h > (1 << 20) || w > (1 << 20) || h * w > (int64_t(1) << 30)) return fail(ctx, "image size out of range");
+  rtk::Cam cam;
+  std::memcpy(&cam, cam12 ? static_cast<const void *>(cam12) : static_cast<const void *>(&ps->cam), sizeof(cam));
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  RT_HIP(ctx, rtk::launch_camera_rays(cam, static_cast<int>(h), static_cast<int>(w), rays_dev, ctx->stream));
+  ctx->last_launch = "family=camera-rays";
+  return 0;
+}
+
 // ====================================================================================
 // The Futhark-shaped boundary (include/ray.h) -- thin wrappers over the rt_* surface.
 // ====================================================================================

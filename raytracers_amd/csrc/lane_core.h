@@ -88,9 +88,10 @@ RT_HD Ray primary_ray(const Cam &c, int col, int row, int width, int height) {
 // (The per-axis swap on `invD < 0` must stay a select: with a zero direction component,
 // 0 * inf = NaN bounds arise that min/max-based swapping would treat differently.)
 typedef float rt_f2 __attribute__((vector_size(8)));
-// `tclamp`: the interval's upper end.  kTMax gives aabb_hit itself (box_hit below); the CULL instantiations of the pooled kernel pass
+// box_hit_clamped's `tclamp`: the interval's upper end (lower end 0).  kTMax gives aabb_hit itself (box_hit below); the CULL instantiations of the pooled kernel pass
 // min(kTMax, a proven lower bound on every sphere root the box's subtree could still contribute) -- see cull_limit.
-RT_HD bool box_hit_clamped(const Ray &r, float lox, float loy, float loz, float hix, float hiy, float hiz, float tclamp) {
+// box_hit_interval: aabb_hit box r tlo thi with the caller's interval (rt_intersect_rays); tlo, thi finite, tlo <= thi.
+RT_HD bool box_hit_interval(const Ray &r, float lox, float loy, float loz, float hix, float hiy, float hiz, float tlo, float thi) {
   // x and y as a pair: two packed subtracts + two packed multiplies (v_pk_add/mul_f32 round
   // each lane exactly like the scalar instructions)
   const rt_f2 o2 = {r.ox, r.oy}, i2 = {r.ix, r.iy};
@@ -98,13 +99,16 @@ RT_HD bool box_hit_clamped(const Ray &r, float lox, float loy, float loz, float 
   const rt_f2 t0 = (lo2 - o2) * i2, t1 = (hi2 - o2) * i2;
   const float t0z = (loz - r.oz) * r.iz, t1z = (hiz - r.oz) * r.iz;
   const bool nx = r.ix < 0.0f, ny = r.iy < 0.0f, nz = r.iz < 0.0f;
-  float tmin = fmaxf(nx ? t1[0] : t0[0], 0.0f);
-  float tmax = fminf(nx ? t0[0] : t1[0], tclamp);
+  float tmin = fmaxf(nx ? t1[0] : t0[0], tlo);
+  float tmax = fminf(nx ? t0[0] : t1[0], thi);
   tmin = fmaxf(ny ? t1[1] : t0[1], tmin);
   tmax = fminf(ny ? t0[1] : t1[1], tmax);
   tmin = fmaxf(nz ? t1z : t0z, tmin);
   tmax = fminf(nz ? t0z : t1z, tmax);
   return !(tmax <= tmin);
+}
+RT_HD bool box_hit_clamped(const Ray &r, float lox, float loy, float loz, float hix, float hiy, float hiz, float tclamp) {
+  return box_hit_interval(r, lox, loy, loz, hix, hiy, hiz, 0.0f, tclamp);
 }
 RT_HD bool box_hit(const Ray &r, float lox, float loy, float loz, float hix, float hiy, float hiz) {
   return box_hit_clamped(r, lox, loy, loz, hix, hiy, hiz, kTMax);
@@ -191,9 +195,10 @@ RT_HD float sphere_root_flag(const Ray &r, float px, float py, float pz, float r
   return t;
 }
 
-// The literal re-intersection of the winning sphere, `sphere_hit s r 0.0 (best+1)`
-// (ray.fut:83-85, :32-51): may pick the OTHER root than the fold did, or none.
-RT_HD bool rehit_full(const Ray &r, float best, float spx, float spy, float spz, float srad, float *t_out) {
+// The literal re-intersection of the winning sphere, `sphere_hit s r t_min (best+1)`
+// (ray.fut:83-85, :32-51): may pick the OTHER root than the fold did, or none.  ray_colour's
+// objs_hit has t_min = 0.0 (rehit_full); rt_intersect_rays passes the caller's.
+RT_HD bool rehit_range(const Ray &r, float tlo, float best, float spx, float spy, float spz, float srad, float *t_out) {
   const float ocx = r.ox - spx, ocy = r.oy - spy, ocz = r.oz - spz;
   const float b = dot3(ocx, ocy, ocz, r.dx, r.dy, r.dz);
   const float c = dot3(ocx, ocy, ocz, ocx, ocy, ocz) - srad * srad;
@@ -204,14 +209,17 @@ RT_HD bool rehit_full(const Ray &r, float best, float spx, float spy, float spz,
     const float sq = sqrtf(disc);
     const float lim = best + 1.0f;
     t = (-b - sq) / r.a;
-    have = (t < lim) && (t > 0.0f);
+    have = (t < lim) && (t > tlo);
     if (!have) {
       t = (-b + sq) / r.a;
-      have = (t < lim) && (t > 0.0f);
+      have = (t < lim) && (t > tlo);
     }
   }
   *t_out = t;
   return have;
+}
+RT_HD bool rehit_full(const Ray &r, float best, float spx, float spy, float spz, float srad, float *t_out) {
+  return rehit_range(r, 0.0f, best, spx, spy, spz, srad, t_out);
 }
 
 // Shortcut for the same call when the fold's accepted root `best` is known not to be
@@ -223,12 +231,16 @@ RT_HD bool rehit_is_best(float best, bool near_root) { return !near_root && (bes
 // The rest of one ray_colour iteration (ray.fut:126-148, :119-124): scatter or terminate.
 // `have`/`t`: result of the re-intersection.  Returns true when the pixel continues with the
 // scattered ray: r.o/r.d, light and depth are updated (and, if DERIVE, r's derived fields;
-// otherwise the caller runs ray_derive); false when the pixel is finished and *pixel holds
-// its packed colour.  sph = {pos.xyz}, col = colour, inv_rad = 1.0f / radius as an IEEE
-// division (tabulated by the host).
-template <bool DERIVE>
-RT_HD bool shade_ray(Ray &r, bool have, float t, float spx, float spy, float spz, float scr, float scg, float scb,
-                     float inv_rad, float &lr, float &lg, float &lb, int &depth, int max_depth, int32_t *pixel) {
+// otherwise the caller runs ray_derive); false when the pixel is finished, after emit(r, g, b)
+// was called with ray_colour's result -- the operand of colour_to_pixel.  sph = {pos.xyz},
+// col = colour, inv_rad = 1.0f / radius as an IEEE division (tabulated by the host).
+// (The absorbed colour is written light * 0: ray_colour's running colour stays (0,0,0) until the
+// sky is reached -- the same value for scenes whose colours are not negative.)
+// (emit is called in each of the two finishing branches, not once behind them: merging them costs
+// the pooled kernels a VGPR.)
+template <bool DERIVE, class Emit>
+RT_HD bool shade_ray_emit(Ray &r, bool have, float t, float spx, float spy, float spz, float scr, float scg, float scb,
+                          float inv_rad, float &lr, float &lg, float &lb, int &depth, int max_depth, Emit &&emit) {
   const float inv_norm = 1.0f / sqrtf(r.a);   // normalise r.dir = scale (1/norm d) d
   if (have) {
     // hit record (ray.fut:40-46)
@@ -247,7 +259,7 @@ RT_HD bool shade_ray(Ray &r, bool have, float t, float spx, float spy, float spz
       return true;
     }
     // absorbed, or the bounce budget is spent: colour = light * (0,0,0)
-    *pixel = pack_pixel(lr * 0.0f, lg * 0.0f, lb * 0.0f);
+    emit(lr * 0.0f, lg * 0.0f, lb * 0.0f);
     return false;
   }
   // miss: sky gradient (ray.fut:140-148)
@@ -255,8 +267,16 @@ RT_HD bool shade_ray(Ray &r, bool have, float t, float spx, float spy, float spz
   const float tt = 0.5f * (uy + 1.0f);
   const float w = 1.0f - tt;
   const float sr = w * 1.0f + tt * 0.5f, sg = w * 1.0f + tt * 0.7f, sb = w * 1.0f + tt * 1.0f;
-  *pixel = pack_pixel(lr * sr, lg * sg, lb * sb);
+  emit(lr * sr, lg * sg, lb * sb);
   return false;
+}
+
+// The render path's form: *pixel = colour_to_pixel of the finished colour.
+template <bool DERIVE>
+RT_HD bool shade_ray(Ray &r, bool have, float t, float spx, float spy, float spz, float scr, float scg, float scb,
+                     float inv_rad, float &lr, float &lg, float &lb, int &depth, int max_depth, int32_t *pixel) {
+  return shade_ray_emit<DERIVE>(r, have, t, spx, spy, spz, scr, scg, scb, inv_rad, lr, lg, lb, depth, max_depth,
+                                [&](float cr, float cg, float cb) { *pixel = pack_pixel(cr, cg, cb); });
 }
 
 // One whole iteration of ray_colour's loop body AFTER the fold: re-intersect the winning
@@ -267,6 +287,14 @@ RT_HD bool finish_ray(Ray &r, float best, int bestj, float spx, float spy, float
   float t = 0.0f;
   const bool have = bestj >= 0 && rehit_full(r, best, spx, spy, spz, srad, &t);
   return shade_ray<true>(r, have, t, spx, spy, spz, scr, scg, scb, inv_rad, lr, lg, lb, depth, max_depth, pixel);
+}
+template <class Emit>
+RT_HD bool finish_ray_emit(Ray &r, float best, int bestj, float spx, float spy, float spz, float srad,
+                           float scr, float scg, float scb, float inv_rad, float &lr, float &lg, float &lb,
+                           int &depth, int max_depth, Emit &&emit) {
+  float t = 0.0f;
+  const bool have = bestj >= 0 && rehit_full(r, best, spx, spy, spz, srad, &t);
+  return shade_ray_emit<true>(r, have, t, spx, spy, spz, scr, scg, scb, inv_rad, lr, lg, lb, depth, max_depth, emit);
 }
 
 }  // namespace rtk

@@ -65,19 +65,43 @@ __device__ __forceinline__ size_t out_index(const KParams &p, int lrow, int col)
 // ---------------------------------------------------------------------------------
 // Family 1: one thread per pixel.
 // ---------------------------------------------------------------------------------
-template <bool STATS>
+// RAYS: one lane per caller ray (rt_trace_rays) instead of one per pixel: ray blockIdx.x * 64 + lane of p.rays, its colour
+// to p.colour3 and / or its pixel to p.out at the ray's index.
+__device__ __forceinline__ Ray load_ray(const float *rays, int i) {
+  const float *const q = rays + (size_t)i * 6;
+  Ray r;
+  r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
+  r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
+  ray_derive(r);
+  return r;
+}
+__device__ __forceinline__ void store_ray_result(const KParams &p, int i, float cr, float cg, float cb) {
+  if (p.colour3 != nullptr) {
+    float *const c = p.colour3 + (size_t)i * 3;
+    c[0] = cr; c[1] = cg; c[2] = cb;
+  }
+  if (p.out != nullptr) p.out[i] = pack_pixel(cr, cg, cb);
+}
+
+template <bool STATS, bool RAYS = false>
 __global__ __launch_bounds__(64) void pixel_kernel(KParams p) {
   // Traversal stack: [entry][lane] so a wave's accesses to one entry hit 64 distinct
   // dwords.  Depth bound: a Karras tree over 32-bit keys + 32-bit index tie-break has
   // height <= 64, and depth-first order keeps at most one pending sibling per level.
   __shared__ int stack[kStackPixel][64];
   const int lane = threadIdx.x;
-  const int tx = blockIdx.x % p.tiles_x, ty = blockIdx.x / p.tiles_x;
-  const int col = tx * 8 + (lane & 7), lrow = ty * 8 + (lane >> 3);
-  if (col >= p.w || lrow >= p.rows_local) return;
+  int col = 0, lrow = 0, ri = 0;
+  if constexpr (RAYS) {
+    ri = blockIdx.x * 64 + lane;
+    if (ri >= p.nrays) return;
+  } else {
+    const int tx = blockIdx.x % p.tiles_x, ty = blockIdx.x / p.tiles_x;
+    col = tx * 8 + (lane & 7); lrow = ty * 8 + (lane >> 3);
+    if (col >= p.w || lrow >= p.rows_local) return;
+  }
   const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
   const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
-  Ray r = primary_ray(p.cam, col, global_row(p, lrow), p.w, p.h);
+  Ray r = RAYS ? load_ray(p.rays, ri) : primary_ray(p.cam, col, global_row(p, lrow), p.w, p.h);
   float lr = 1.0f, lg = 1.0f, lb = 1.0f;
   int depth = 0;
   int32_t pixel = 0;
@@ -113,8 +137,15 @@ __global__ __launch_bounds__(64) void pixel_kernel(KParams p) {
       s = p.sph[bestj];
       c = p.col[bestj];
     }
-    if (!finish_ray(r, best, bestj, s.x, s.y, s.z, s.w, c.x, c.y, c.z, c.w, lr, lg, lb, depth, p.max_depth, &pixel)) break;
+    if constexpr (RAYS) {
+      if (!finish_ray_emit(r, best, bestj, s.x, s.y, s.z, s.w, c.x, c.y, c.z, c.w, lr, lg, lb, depth, p.max_depth,
+                           [&](float cr, float cg, float cb) { store_ray_result(p, ri, cr, cg, cb); }))
+        break;
+    } else {
+      if (!finish_ray(r, best, bestj, s.x, s.y, s.z, s.w, c.x, c.y, c.z, c.w, lr, lg, lb, depth, p.max_depth, &pixel)) break;
+    }
   }
+  if constexpr (RAYS) return;
   p.out[out_index(p, lrow, col)] = pixel;
   if (STATS) {
     atomicAdd(&p.stats[0], n_rays);
@@ -607,9 +638,13 @@ __device__ __attribute__((noinline)) void solo_trace(KParamsArg pp_v, unsigned s
 // SPILL: the instantiation of that shape for trees TALLER than 15 levels, whose box stacks may outgrow the LDS a twentieth of a CU leaves them (below); its
 // value is the stack size beyond which a full BOX operation spills first -- a literal: p.capb - 64 with p.capb = 1 088 (production) or 192 (stack_cap, testing);
 // compared with p.capb itself the check was a scalar load and its wait in every BOX operation of a well-filled stack: the 10^6-sphere frame 7 % slower.
-template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0>
+// RAYS: caller-supplied rays (rt_trace_rays) on the plain loop.  A ticket is 64 consecutive rays of p.rays (a "tile" of the raster queue, no
+// order); a refill loads the ray's six floats instead of deriving a primary ray, and the finished colour is stored at the ray's index (p.colour3,
+// and / or the packed pixel at p.out).  No CULL: its bound is proved for rays from the camera origin only.
+template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, bool RAYS = false>
 __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 4) void pooled_kernel(KParams p) {
   constexpr bool COLD = TAIL == 1, DONATE = TAIL == 2;
+  static_assert(!RAYS || (!STATS && !SOLO && TAIL == 0 && !ORD && !CULL), "RAYS: the plain instantiations only");
   static_assert(!ORD || TAIL != 1, "ORD: no COLD variant");   // (ORD + DONATE: a frame rendered through a pixel list BORROWED from a neighbouring view, round 6)
   static_assert(!CULL || !ALL_LDS, "CULL: instantiated for the general scene path only");
   extern __shared__ float4 smem[];
@@ -872,9 +907,19 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
             bool have = hit;
             float t = best;
             if (hit && !rehit_is_best(best, ((unsigned)key & 1u) != 0u)) have = rehit_full(r, best, s.x, s.y, s.z, s.w, &t);
+            // (RAYS: the finished colour is stored at the ray's index, from the branch of shade_ray that produces it; the render
+            // path's store stays behind the call -- inside it the SPILL kernels spilled one more VGPR)
             int32_t pixel;
-            if (shade_ray<false>(r, have, t, s.x, s.y, s.z, c.x, c.y, c.z, c.w, lr, lg, lb, depth, p.max_depth, &pixel)) {
+            bool more;
+            if constexpr (RAYS)
+              more = shade_ray_emit<false>(r, have, t, s.x, s.y, s.z, c.x, c.y, c.z, c.w, lr, lg, lb, depth, p.max_depth,
+                                           [&](float cr, float cg, float cb) { store_ray_result(p, pix, cr, cg, cb); });
+            else
+              more = shade_ray<false>(r, have, t, s.x, s.y, s.z, c.x, c.y, c.z, c.w, lr, lg, lb, depth, p.max_depth, &pixel);
+            if (more) {
               root = true;
+            } else if constexpr (RAYS) {
+              pix = -1;
             } else {
               p.out[pix] = pixel;
               // cost record for the adaptive order: the longest bounce chain seen in the tile, and the pixel's own
@@ -1010,7 +1055,16 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
             const unsigned rest = 64u - (q_next & 63u), avail = rest < q_end - q_next ? rest : q_end - q_next;   // rest of the current tile / piece
             const unsigned rank = (unsigned)lane_rank(m);
             const unsigned cnt = (unsigned)__popcll(m);
-            if (want & (rank < avail)) {
+            if (RAYS && (want & (rank < avail))) {
+              const int i = q_tile * 64 + (int)((q_next + rank) & 63u);   // (the queue's "tiles" are blocks of 64 rays)
+              if (i < p.nrays) {
+                const float *const q = p.rays + (size_t)i * 6;
+                r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
+                r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
+                slot = i;
+                want = false;
+              }
+            } else if (want & (rank < avail)) {
               const int within = (int)((q_next + rank) & 63u);
               const int col = q_col0 + (within & 7), lrow = q_row0 + (within >> 3);
               if (col < p.w && lrow < p.rows_local) {
@@ -1793,10 +1847,10 @@ size_t pooled_lds_bytes(int lds_nodes, int lds_sph, int capb, int capl, int ray_
   return (size_t)lds_nodes * 64 + (size_t)lds_sph * 16 + (size_t)waves_per_wg * pooled_wave_dw(ray_planes, capb, capl) * sizeof(unsigned);
 }
 
-template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO = false, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0>
+template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO = false, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, bool RAYS = false>
 static hipError_t launch_pooled_t(const KParams &p, int grid, hipStream_t stream) {
   const size_t lds = pooled_lds_bytes(p.lds_nodes, p.lds_sph, p.capb, p.capl, p.ray_planes, THREADS / 64);
-  auto kfn = pooled_kernel<THREADS, ALL_LDS, STATS, SOLO, TAIL, ORD, CULL, SPILL>;
+  auto kfn = pooled_kernel<THREADS, ALL_LDS, STATS, SOLO, TAIL, ORD, CULL, SPILL, RAYS>;
   if (hipError_t e = allow_full_lds(reinterpret_cast<const void *>(kfn)); e != hipSuccess) return e;
   hipLaunchKernelGGL(kfn, dim3(grid), dim3(THREADS), lds, stream, p);
   return hipGetLastError();
@@ -1860,6 +1914,111 @@ hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_w
   default: return hipErrorInvalidValue;
   }
 #undef RT_POOLED_CASE
+}
+
+// ---------------------------------------------------------------------------------
+// Caller rays (rt_trace_rays, rt_intersect_rays, rt_camera_rays)
+// ---------------------------------------------------------------------------------
+hipError_t launch_pixel_rays(const KParams &p, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  hipLaunchKernelGGL((pixel_kernel<false, true>), dim3((unsigned)((p.nrays + 63) / 64)), dim3(64), 0, stream, p);
+  return hipGetLastError();
+}
+
+// The plain pooled loop with the RAYS source, in the shapes make_plan picks for a frame of as many 64-ray blocks: workgroups of 16
+// waves (whole scene in LDS or not), or the twenty-wave shape of four-wave workgroups, with the spilling box stack for tall trees.
+hipError_t launch_pooled_rays(const KParams &p, int grid, int waves_per_wg, hipStream_t stream) {
+  if (grid <= 0 || p.nrays <= 0) return hipSuccess;
+  if (p.cull || p.px_hdr != nullptr || p.order != nullptr || p.nframes != 1) return hipErrorInvalidValue;
+  const bool all_lds = p.lds_nodes == p.n_nodes && p.lds_sph == p.n_sph;
+  if (p.spill != nullptr) {
+    if (waves_per_wg != 4) return hipErrorInvalidValue;
+    if (p.capb == kSpillCapbTest) return launch_pooled_t<256, false, false, false, 0, false, false, kSpillCapbTest - 64, true>(p, grid, stream);
+    if (p.capb == kSpillCapb) return launch_pooled_t<256, false, false, false, 0, false, false, kSpillCapb - 64, true>(p, grid, stream);
+    return hipErrorInvalidValue;
+  }
+  switch (waves_per_wg) {
+  case 16: return all_lds ? launch_pooled_t<1024, true, false, false, 0, false, false, 0, true>(p, grid, stream)
+                          : launch_pooled_t<1024, false, false, false, 0, false, false, 0, true>(p, grid, stream);
+  case 4: return launch_pooled_t<256, false, false, false, 0, false, false, 0, true>(p, grid, stream);
+  default: return hipErrorInvalidValue;
+  }
+}
+
+// objs_hit bvh r t_min t_max (ray.fut:76-86), one lane per ray: the pixel family's stack fold with the caller's interval on every box,
+// the spheres folded over (scene_epsilon, best) from best = t_max, then one re-intersection of the winner over (t_min, best + 1).
+__global__ __launch_bounds__(64) void intersect_kernel(KParams p, float t_min, float t_max, int32_t *index, float *hit7) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const Ray r = load_ray(p.rays, i);
+  float best = t_max;
+  int bestj = -1;
+  int sp = 0;
+  stack[sp++][lane] = 0;
+  while (sp > 0) {
+    const int ni = stack[--sp][lane];
+    const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+    if (!box_hit_interval(r, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, t_min, t_max)) continue;
+    const int kids[2] = {f2i(lo.w), f2i(hi.w)};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int c = kids[k];
+      if (c < 0) {
+        const int j = ~c;
+        const float4 s = buf_load16(rs_sph, j * 16);
+        closest_update(sphere_root(r, s.x, s.y, s.z, s.w), j, best, bestj);
+      } else {
+        stack[sp++][lane] = c;   // (at most one pending sibling per level: sp <= tree height + 1 <= kStackPixel)
+      }
+    }
+  }
+  float t = 0.0f, h[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  bool have = false;
+  if (bestj >= 0) {
+    const float4 s = p.sph[bestj];
+    have = rehit_range(r, t_min, best, s.x, s.y, s.z, s.w, &t);
+    if (have) {
+      const float inv_rad = p.col[bestj].w;   // 1.0f / radius, the bits of scale (1.0/s.radius) (ray.fut:43)
+      h[0] = r.ox + t * r.dx; h[1] = r.oy + t * r.dy; h[2] = r.oz + t * r.dz;   // point_at_param
+      h[3] = inv_rad * (h[0] - s.x); h[4] = inv_rad * (h[1] - s.y); h[5] = inv_rad * (h[2] - s.z);
+    }
+  }
+  index[i] = have ? bestj : -1;
+  if (hit7 != nullptr) {
+    float *const o = hit7 + (size_t)i * 7;
+    o[0] = have ? t : 0.0f;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[1 + k] = h[k];
+  }
+}
+
+hipError_t launch_intersect_rays(const KParams &p, float t_min, float t_max, int32_t *index, float *hit7, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  hipLaunchKernelGGL(intersect_kernel, dim3((unsigned)((p.nrays + 63) / 64)), dim3(64), 0, stream, p, t_min, t_max, index, hit7);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void camera_rays_kernel(Cam cam, int h, int w, float *rays) {
+  const int64_t n = (int64_t)h * w;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int row = (int)(i / w), col = (int)(i - (int64_t)row * w);
+    const Ray r = primary_ray(cam, col, row, w, h);
+    float *const o = rays + i * 6;
+    o[0] = r.ox; o[1] = r.oy; o[2] = r.oz;
+    o[3] = r.dx; o[4] = r.dy; o[5] = r.dz;
+  }
+}
+
+hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStream_t stream) {
+  const int64_t n = (int64_t)h * w;
+  if (n <= 0) return hipSuccess;
+  const unsigned grid = (unsigned)((n + 255) / 256 < 16384 ? (n + 255) / 256 : 16384);
+  hipLaunchKernelGGL(camera_rays_kernel, dim3(grid), dim3(256), 0, stream, cam, h, w, rays);
+  return hipGetLastError();
 }
 
 // Loads this file's code object and resolves the default kernels (HIP loads modules lazily, at

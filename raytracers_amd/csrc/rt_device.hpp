@@ -266,9 +266,22 @@ struct KParams {
   // than 15 levels) keeps its oldest items in device memory when it would overflow -- [waves][spill_stride] dwords, a wave's own region (nullptr: capb holds the bound)
   unsigned *spill;
   int spill_stride;
+  // caller-supplied rays (rt_trace_rays: the RAYS instantiations of the pixel and pooled kernels): ray i is rays[6 i .. 6 i + 6) = {o.xyz, d.xyz};
+  // its colour goes to colour3[3 i ..] and / or its packed pixel to out[i] (either pointer may be nullptr, not both)
+  const float *rays;
+  float *colour3;
+  int nrays;
 };
 
 hipError_t launch_pixel(const KParams &p, bool stats, hipStream_t stream);
+// caller rays (render_kernels.hip): ray_colour of p.nrays rays, one lane per ray (the pixel family) ...
+hipError_t launch_pixel_rays(const KParams &p, hipStream_t stream);
+// ... or in the pooled family's plain loop, 64 consecutive rays per ticket (grid / waves_per_wg as make_plan says; p.spill: the SPILL shape)
+hipError_t launch_pooled_rays(const KParams &p, int grid, int waves_per_wg, hipStream_t stream);
+// objs_hit bvh r t_min t_max of n rays (ray.fut:76-86): index[i] = the winning leaf or -1, hit7 (may be nullptr) = {t, p.xyz, normal.xyz}
+hipError_t launch_intersect_rays(const KParams &p, float t_min, float t_max, int32_t *index, float *hit7, hipStream_t stream);
+// the primary rays of an h x w frame through p.cam (get_ray at pixel_u / pixel_v), row-major from the top row: rays[6 (row w + col) ..]
+hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStream_t stream);
 // block = 64 * waves_per_wg threads (4, 8 or 16 waves); grid = persistent workgroups
 hipError_t launch_persistent(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream);
 size_t persistent_lds_bytes(int lds_nodes, int lds_sph, int smax, int lmax, int waves_per_wg);
