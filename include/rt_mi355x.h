@@ -71,11 +71,11 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  * depend on it).  Owned by ctx; "" before the first render.  (A multi-device context: the first device's part.)  Values:
  *   "family=none (memset)"        max_depth == 0: every pixel is the initial colour, no kernel
  *   "family=none (no rays)"       a caller-ray entry with n == 0
- *   "family=pixel (rays)" | "family=intersect" | "family=camera-rays"   the caller-ray entries (below)
+ *   "family=pixel (rays)" | "family=intersect" | "family=occluded" | "family=camera-rays"   the caller-ray entries (below)
  *   "family=none (no rows)"       the part owns no row of the image
  *   "family=pixel" | "family=pixel (instrumented)" | "family=persistent"
  *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2"
- *     T = rays (rt_trace_rays: blocks of 64 caller rays, instantiation plain[+SPILL]) | pixel-list | tiles-ordered | tiles-bit-reversed (a view's first frame with nothing to borrow, first_order = 1) | tiles-raster,
+ *     T = rays (rt_trace_rays: blocks of 64 caller rays, instantiation plain[+SPILL]; rt_occluded_rays: instantiation any[+SPILL]) | pixel-list | tiles-ordered | tiles-bit-reversed (a view's first frame with nothing to borrow, first_order = 1) | tiles-raster,
  *         followed by "(borrowed)" when the order / list is another view's (a new view of a prepared scene that has rendered a view of the same shape)
  *     I = plain | SOLO | COLD | COLD+SOLO | DONATE | DONATE+SOLO | ORD | ORD+SOLO | ORD+DONATE | ORD+SOLO+DONATE;  +CULL: boxes tested against the best hit so far; +SPILL: a box stack that may overflow into device memory (twenty waves per CU, trees taller than 15 levels)
  *     recording: 0 nothing, 1 the tiles' longest chains, 2 also every pixel's chain length */
@@ -199,7 +199,7 @@ int rt_render_timed(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w
                     int32_t rows_per_tile, int32_t part, int32_t nparts, int32_t *out_dev,
                     int32_t warmup, int32_t iters, float *ms_out);
 
-/* ---- caller-supplied rays: objs_hit and ray_colour (ray.fut:76-86, :126-148) on a prepared scene ----------------
+/* ---- caller-supplied rays: objs_hit, occlusion and ray_colour (ray.fut:76-86, :126-148) on a prepared scene ------
  * Rays are n x 6 contiguous float32 in the context's device memory, {origin.xyz, dir.xyz}.  Every entry enqueues its
  * work on the context's stream and returns (completion: rt_context_sync), holding the context lock like the render
  * entries.  Refused (non-zero, rt_last_error set, nothing launched): n < 0, n >= 2^31, a NULL rays pointer, no output,
@@ -222,6 +222,19 @@ int rt_trace_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float
  * t_min > t_max, t_max > 1e9.  One lane per ray (rt_context_last_launch: "family=intersect"). */
 int rt_intersect_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
                       int32_t *index_dev, float *hit7_dev);
+/* Occlusion (any-hit) of each ray over (t_min, t_max): occluded_dev[i] = 1 iff some leaf j of the prepared scene's BVH has
+ * every inner node on its root path passing aabb_hit node r t_min t_max (ray.fut:53-70) and sphere_hit L[j] r t_min t_max
+ * is #some (ray.fut:32-51: root1 or root2 strictly inside (t_min, t_max)); else 0.  n bytes.  This is bvh_fold
+ * (bvh.fut:61-84) with that fixed interval and a logical OR of the sphere tests: it does not depend on the order of the
+ * walk, so a ray stops at its first accepted sphere.  The caller's t_min bounds the spheres (objs_hit's fold uses
+ * scene_epsilon instead); with t_min = 0.1 the result is rt_intersect_rays(.., 0.1, t_max) index >= 0 for every ray whose
+ * closest accepted root is below 2^23.  A shadow ray from p to a point light L: d = L - p over (eps, 1).  Refused as
+ * rt_intersect_rays is (interval included), and for a NULL occluded_dev; t_min == t_max gives all zeros.  The pooled
+ * family's any-hit loop under RT_VARIANT_POOLED ("family=pooled tickets=rays instantiation=any..."), one lane per ray under
+ * RT_VARIANT_PIXEL / RT_VARIANT_PERSISTENT ("family=occluded").  RT_VARIANT_AUTO: the pooled loop when the whole scene is
+ * staged in LDS and t_max > 1, where it was measured faster; otherwise (and beyond the pooled family's limits) the lane kernel. */
+int rt_occluded_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
+                     uint8_t *occluded_dev);
 /* The primary rays rt_render_image would trace (get_ray at pixel_u / pixel_v), row-major from the top row: h * w x 6
  * float32 at rays_dev.  cam12 == NULL: the prepared camera.  rt_context_last_launch: "family=camera-rays". */
 int rt_camera_rays(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, const float cam12[12], float *rays_dev);

@@ -388,6 +388,14 @@ def intersect_rays_into(rays_ptr, n, prepared, index_ptr, hit_ptr=None, t_min=0.
                                      C.c_void_p(index_ptr), C.c_void_p(hit_ptr)))
 
 
+def occluded_rays_into(rays_ptr, n, prepared, out_ptr, t_min=0.0, t_max=1e9):
+    """Enqueue the occlusion of `n` rays over (t_min, t_max) (rt_occluded_rays): n bytes at out_ptr, 1 where some sphere the BVH
+    walk reaches has a root strictly inside the interval, else 0."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_occluded_rays(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), float(t_min), float(t_max),
+                                    C.c_void_p(out_ptr)))
+
+
 def camera_rays_into(rays_ptr, h, w, prepared, cam=None):
     """Enqueue the h * w primary rays rt_render_image would trace (rt_camera_rays) into rays_ptr (h * w x 6 float32)."""
     ctx = prepared.ctx
@@ -445,6 +453,20 @@ def intersect_rays(prepared, rays, t_min=0.0, t_max=1e9):
     finally:
         idx.free()
         hit.free()
+        if keep is not None:
+            keep.free()
+
+
+def occluded_rays(prepared, rays, t_min=0.0, t_max=1e9):
+    """Occlusion of every ray over (t_min, t_max) (rt_occluded_rays) -> (n,) bool numpy array."""
+    ctx = prepared.ctx
+    ptr, n, keep = _device_rays(ctx, rays)
+    out = DeviceBuffer(ctx, max(n, 4))
+    try:
+        occluded_rays_into(ptr, n, prepared, out.ptr, t_min, t_max)
+        return out.to_host((n,), np.uint8).astype(bool)
+    finally:
+        out.free()
         if keep is not None:
             keep.free()
 

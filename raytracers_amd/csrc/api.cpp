@@ -1816,6 +1816,66 @@ int ray_entry_params(rt_context *ctx, const rt_prepared *ps, int64_t n, const fl
   p->nrays = static_cast<int>(n);
   return 0;
 }
+
+// The interval rule of the entries that take one (aabb_hit's NaN argument in lane_core.h -- the last slab test decides -- needs a
+// finite interval; its one-test form needs a finite start).
+bool ray_interval_ok(float t_min, float t_max) {
+  return std::isfinite(t_min) && std::isfinite(t_max) && t_min >= 0.0f && t_min <= t_max && t_max <= rtk::kTMax;
+}
+
+// The pooled family's plan for a frame of as many 64-ray blocks as there are rays (its LDS staging, the wide shape), under RT_VARIANT_AUTO /
+// RT_VARIANT_POOLED; pl->variant is RT_VARIANT_PIXEL under the other variants, and AUTO's beyond the family's limits (make_plan).
+int pooled_rays_plan(rt_context *ctx, const rt_prepared *ps, int64_t n, Plan *pl) {
+  *pl = Plan{};
+  pl->variant = RT_VARIANT_PIXEL;
+  const int64_t nblocks = (n + 63) / 64;
+  if (ctx->variant == RT_VARIANT_AUTO || ctx->variant == RT_VARIANT_POOLED) {
+    const bool huge = rt_scene_exceeds_l2(ps);
+    const bool wide = ctx->wide_waves == 2 || (ctx->wide_waves == 1 && nblocks >= (huge ? 40000 : 100000) && nblocks > ctx->px_max_tiles);
+    if (int rc = make_plan(ctx, ps, pl, nblocks, 0, wide)) return rc;
+  }
+  return 0;
+}
+
+// p's fields for the plain pooled loop over those blocks: the raster queue, the plan's shape and staging, the spill region.
+int pooled_rays_params(rt_context *ctx, const rt_prepared *ps, const Plan &pl, rtk::KParams *pp) {
+  rtk::KParams &p = *pp;
+  if (ps->n >= (int64_t(1) << 22)) return fail(ctx, "pooled kernel: at most 2^22 spheres (work items and hit keys carry the leaf index in 22 bits)");
+  const int64_t nblocks = (static_cast<int64_t>(p.nrays) + 63) / 64;
+  p.nframes = 1;
+  p.queue = ctx->queue_dev;
+  p.w = 64; p.h = 1;
+  p.rows_local = 1; p.rows_per_tile = 1; p.part = 0; p.nparts = 1; p.rpt_log2 = 0;
+  p.tiles_x = static_cast<int>(nblocks); p.tiles_y = 1;
+  p.nchunks = static_cast<int>(nblocks);
+  p.tpt_log2 = 0;
+  // the eight counters take turns over the one raster queue (strips of tile columns are a 2D layout; the rays have none)
+  p.nshards = pl.grid % rtk::kMaxShards == 0 && ctx->xcd_queues != 0 ? rtk::kMaxShards : 1;
+  p.interleave = p.nshards > 1;
+  p.static_first = ctx->static_first;
+  p.lds_nodes = pl.lds_nodes; p.lds_sph = pl.lds_sph;
+  p.smax = pl.smax; p.lmax = pl.lmax;
+  p.thr_shade = ctx->thr_shade; p.thr_leaf = ctx->thr_leaf;
+  p.capb = pl.capb; p.capl = pl.capl; p.ray_planes = pl.ray_planes;
+  if (pl.spill_stride > 0) {
+    if (int rc = ensure_spill(ctx, pl.spill_stride)) return rc;
+    p.spill = ctx->spill_dev;
+    p.spill_stride = pl.spill_stride;
+  }
+  const bool twenty = pl.waves * (pl.grid_full / std::max(1, ctx->num_cu)) == 20;
+  p.prio_depth = ctx->prio_depth;
+  p.box2 = ctx->box2;
+  p.look_max = ctx->look_max > 0 ? ctx->look_max : (twenty ? 16 : p.nchunks > 16384 ? 32 : 64);
+  p.tl_log2 = ps->tl_depth;
+  return 0;
+}
+
+void pooled_rays_launch_record(rt_context *ctx, const char *instantiation, const rtk::KParams &p, const Plan &pl) {
+  char buf[256];
+  std::snprintf(buf, sizeof buf, "family=pooled tickets=rays instantiation=%s%s frames=1 tiles=%d grid=%d waves=%d counters=%d%s deep_class=0 deep_split=0 recording=0",
+                instantiation, p.spill ? "+SPILL" : "", p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "");
+  ctx->last_launch = buf;
+}
 }  // namespace
 
 extern "C" int rt_trace_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, int32_t max_depth,
@@ -1845,51 +1905,17 @@ extern "C" int rt_trace_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, 
   p.out = pixel_dev;
   p.colour3 = colour3_dev;
   p.nframes = 1;
-  // the pooled family's plan for a frame of as many 64-ray blocks (its LDS staging, the wide shape); the pixel family beyond its limits
-  // (AUTO), or under RT_VARIANT_PIXEL / RT_VARIANT_PERSISTENT
-  Plan pl{};
-  pl.variant = RT_VARIANT_PIXEL;
-  const int64_t nblocks = (n + 63) / 64;
-  if (ctx->variant == RT_VARIANT_AUTO || ctx->variant == RT_VARIANT_POOLED) {
-    const bool huge = rt_scene_exceeds_l2(ps);
-    const bool wide = ctx->wide_waves == 2 || (ctx->wide_waves == 1 && nblocks >= (huge ? 40000 : 100000) && nblocks > ctx->px_max_tiles);
-    if (int rc = make_plan(ctx, ps, &pl, nblocks, 0, wide)) return rc;
-  }
+  // the pooled family's plan; the pixel family beyond its limits (AUTO), or under RT_VARIANT_PIXEL / RT_VARIANT_PERSISTENT
+  Plan pl;
+  if (int rc = pooled_rays_plan(ctx, ps, n, &pl)) return rc;
   if (pl.variant != RT_VARIANT_POOLED) {
     RT_HIP(ctx, rtk::launch_pixel_rays(p, ctx->stream));
     ctx->last_launch = "family=pixel (rays)";
     return 0;
   }
-  if (ps->n >= (int64_t(1) << 22)) return fail(ctx, "pooled kernel: at most 2^22 spheres (work items and hit keys carry the leaf index in 22 bits)");
-  p.queue = ctx->queue_dev;
-  p.w = 64; p.h = 1;
-  p.rows_local = 1; p.rows_per_tile = 1; p.part = 0; p.nparts = 1; p.rpt_log2 = 0;
-  p.tiles_x = static_cast<int>(nblocks); p.tiles_y = 1;
-  p.nchunks = static_cast<int>(nblocks);
-  p.tpt_log2 = 0;
-  // the eight counters take turns over the one raster queue (strips of tile columns are a 2D layout; the rays have none)
-  p.nshards = pl.grid % rtk::kMaxShards == 0 && ctx->xcd_queues != 0 ? rtk::kMaxShards : 1;
-  p.interleave = p.nshards > 1;
-  p.static_first = ctx->static_first;
-  p.lds_nodes = pl.lds_nodes; p.lds_sph = pl.lds_sph;
-  p.smax = pl.smax; p.lmax = pl.lmax;
-  p.thr_shade = ctx->thr_shade; p.thr_leaf = ctx->thr_leaf;
-  p.capb = pl.capb; p.capl = pl.capl; p.ray_planes = pl.ray_planes;
-  if (pl.spill_stride > 0) {
-    if (int rc = ensure_spill(ctx, pl.spill_stride)) return rc;
-    p.spill = ctx->spill_dev;
-    p.spill_stride = pl.spill_stride;
-  }
-  const bool twenty = pl.waves * (pl.grid_full / std::max(1, ctx->num_cu)) == 20;
-  p.prio_depth = ctx->prio_depth;
-  p.box2 = ctx->box2;
-  p.look_max = ctx->look_max > 0 ? ctx->look_max : (twenty ? 16 : p.nchunks > 16384 ? 32 : 64);
-  p.tl_log2 = ps->tl_depth;
+  if (int rc = pooled_rays_params(ctx, ps, pl, &p)) return rc;
   RT_HIP(ctx, rtk::launch_pooled_rays(p, pl.grid, pl.waves, ctx->stream));
-  char buf[256];
-  std::snprintf(buf, sizeof buf, "family=pooled tickets=rays instantiation=plain%s frames=1 tiles=%d grid=%d waves=%d counters=%d%s deep_class=0 deep_split=0 recording=0",
-                p.spill ? "+SPILL" : "", p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "");
-  ctx->last_launch = buf;
+  pooled_rays_launch_record(ctx, "plain", p, pl);
   return 0;
 }
 
@@ -1900,9 +1926,7 @@ extern "C" int rt_intersect_rays(rt_context *ctx, const rt_prepared *ps, int64_t
   rtk::KParams p;
   if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
   if (!index_dev) return fail(ctx, "rt_intersect_rays: null index pointer");
-  // (aabb_hit's NaN argument in lane_core.h -- the last slab test decides -- needs a finite interval)
-  if (!std::isfinite(t_min) || !std::isfinite(t_max) || t_min < 0.0f || t_min > t_max || t_max > rtk::kTMax)
-    return fail(ctx, "rt_intersect_rays: need 0 <= t_min <= t_max <= 1e9, both finite");
+  if (!ray_interval_ok(t_min, t_max)) return fail(ctx, "rt_intersect_rays: need 0 <= t_min <= t_max <= 1e9, both finite");
   RT_LOCK_PS(ps);
   RT_HIP(ctx, hipSetDevice(ctx->device));
   (void)hipGetLastError();
@@ -1913,6 +1937,44 @@ extern "C" int rt_intersect_rays(rt_context *ctx, const rt_prepared *ps, int64_t
   }
   RT_HIP(ctx, rtk::launch_intersect_rays(p, t_min, t_max, index_dev, hit7_dev, ctx->stream));
   ctx->last_launch = "family=intersect";
+  return 0;
+}
+
+extern "C" int rt_occluded_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
+                                uint8_t *occluded_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!occluded_dev) return fail(ctx, "rt_occluded_rays: null output pointer");
+  if (!ray_interval_ok(t_min, t_max)) return fail(ctx, "rt_occluded_rays: need 0 <= t_min <= t_max <= 1e9, both finite");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  if (n == 0) {
+    ctx->last_launch = "family=none (no rays)";
+    return 0;
+  }
+  p.occluded = occluded_dev;
+  p.ray_tlo = t_min;
+  p.ray_thi = t_max;
+  // the pooled family's any-hit loop under RT_VARIANT_POOLED; the lane kernel under RT_VARIANT_PIXEL / RT_VARIANT_PERSISTENT.  AUTO takes the
+  // pooled loop only where it was measured faster: the whole scene staged in LDS, and rays rather than segments (t_max > 1;
+  // a shadow ray's (eps, 1) is a segment) -- elsewhere, and beyond the pooled family's limits, the lane kernel
+  Plan pl;
+  if (int rc = pooled_rays_plan(ctx, ps, n, &pl)) return rc;
+  if (ctx->variant == RT_VARIANT_AUTO && pl.variant == RT_VARIANT_POOLED &&
+      !(pl.lds_nodes == static_cast<int>(ps->n - 1) && pl.lds_sph == static_cast<int>(ps->n) && t_max > 1.0f))
+    pl.variant = RT_VARIANT_PIXEL;
+  if (pl.variant != RT_VARIANT_POOLED) {
+    RT_HIP(ctx, rtk::launch_occluded_rays(p, ctx->stream));
+    ctx->last_launch = "family=occluded";
+    return 0;
+  }
+  if (int rc = pooled_rays_params(ctx, ps, pl, &p)) return rc;
+  RT_HIP(ctx, rtk::launch_pooled_occluded(p, pl.grid, pl.waves, ctx->stream));
+  pooled_rays_launch_record(ctx, "any", p, pl);
   return 0;
 }
 

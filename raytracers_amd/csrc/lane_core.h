@@ -222,6 +222,19 @@ RT_HD bool rehit_full(const Ray &r, float best, float spx, float spy, float spz,
   return rehit_range(r, 0.0f, best, spx, spy, spz, srad, t_out);
 }
 
+// `sphere_hit s r tlo thi is #some` (ray.fut:32-51): root1 or root2 strictly inside (tlo, thi).  The any-hit
+// predicate of rt_occluded_rays -- rehit_range's arithmetic with the caller's upper end, and no t kept.
+RT_HD bool sphere_hit_any(const Ray &r, float tlo, float thi, float spx, float spy, float spz, float srad) {
+  const float ocx = r.ox - spx, ocy = r.oy - spy, ocz = r.oz - spz;
+  const float b = dot3(ocx, ocy, ocz, r.dx, r.dy, r.dz);
+  const float c = dot3(ocx, ocy, ocz, ocx, ocy, ocz) - srad * srad;
+  const float disc = b * b - r.a * c;
+  if (disc <= 0.0f) return false;
+  const float sq = sqrtf(disc);
+  const float t1 = (-b - sq) / r.a, t2 = (-b + sq) / r.a;
+  return ((t1 < thi) && (t1 > tlo)) || ((t2 < thi) && (t2 > tlo));
+}
+
 // Shortcut for the same call when the fold's accepted root `best` is known not to be
 // displaced: with near_root clear, root1 (if it was the fold's root) or root2 passes
 // `0 < t < best + 1` iff best + 1 > best, and the re-intersection returns t = best.

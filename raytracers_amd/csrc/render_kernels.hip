@@ -396,6 +396,10 @@ __global__ __launch_bounds__(THREADS) void persistent_kernel(KParams p) {
 // ---------------------------------------------------------------------------------
 constexpr int kOrderClasses = 8;   // cost classes of the adaptive tile order (tile_order_kernel)
 constexpr unsigned long long kKeyInit = ((unsigned long long)0x4e6e6b28u << 32) | 0xffffffffull;   // (1e9, no leaf)
+// pooled_kernel's RAYS mode: 0 the render path's pixels, kRaysColour rt_trace_rays, kRaysAny rt_occluded_rays; in the any-hit mode a slot's
+// key is kKeyAnyHit once one of its spheres is accepted (its high word, read as the boxes' upper end, then empties their interval)
+constexpr int kRaysColour = 1, kRaysAny = 2;
+constexpr unsigned long long kKeyAnyHit = 0ull;
 
 __device__ __forceinline__ float pull(int lane_byte, float v) {   // v of the lane at byte address lane_byte (ds_bpermute)
   return __int_as_float(__builtin_amdgcn_ds_bpermute(lane_byte, __float_as_int(v)));
@@ -640,10 +644,14 @@ __device__ __attribute__((noinline)) void solo_trace(KParamsArg pp_v, unsigned s
 // compared with p.capb itself the check was a scalar load and its wait in every BOX operation of a well-filled stack: the 10^6-sphere frame 7 % slower.
 // RAYS: caller-supplied rays (rt_trace_rays) on the plain loop.  A ticket is 64 consecutive rays of p.rays (a "tile" of the raster queue, no
 // order); a refill loads the ray's six floats instead of deriving a primary ray, and the finished colour is stored at the ray's index (p.colour3,
-// and / or the packed pixel at p.out).  No CULL: its bound is proved for rays from the camera origin only.
-template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, bool RAYS = false>
+// and / or the packed pixel at p.out).  No CULL: its bound is proved for rays from the camera origin only.  (RAYS == kRaysColour)
+// RAYS == kRaysAny (ANY): rt_occluded_rays on the same loop and tickets.  Every box is tested over the caller's (p.ray_tlo, p.ray_thi); LEAF
+// marks the slot's key when the sphere has a root inside that interval, and from then on the slot's boxes are tested over (p.ray_tlo, 0) --
+// empty, so its remaining items drain without appending anything; SHADE stores key != kKeyInit at the ray's index (no re-hit, no bounce).
+template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, int RAYS = 0>
 __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 4) void pooled_kernel(KParams p) {
   constexpr bool COLD = TAIL == 1, DONATE = TAIL == 2;
+  constexpr bool ANY = RAYS == kRaysAny;
   static_assert(!RAYS || (!STATS && !SOLO && TAIL == 0 && !ORD && !CULL), "RAYS: the plain instantiations only");
   static_assert(!ORD || TAIL != 1, "ORD: no COLD variant");   // (ORD + DONATE: a frame rendered through a pixel list BORROWED from a neighbouring view, round 6)
   static_assert(!CULL || !ALL_LDS, "CULL: instantiated for the general scene path only");
@@ -881,7 +889,12 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           bool root = false;
           if (STATS) tr_ops[2]++;
           const unsigned long long tr_s0 = STATS ? clock64() : 0ull;
-          if (done) {
+          if constexpr (ANY) {
+            if (done) {             // the fold is over: occluded iff a LEAF operation marked the key
+              p.occluded[pix] = wkey[lane] != kKeyInit ? 1 : 0;
+              pix = -1;
+            }
+          } else if (done) {
             if (STATS) tr_maxdepth = depth > tr_maxdepth ? depth : tr_maxdepth;
             const unsigned long long key = wkey[lane];
             const float best = __uint_as_float((unsigned)(key >> 32));
@@ -1141,7 +1154,8 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           }
           // A new fold starts with the ROOT's box test (items are nodes whose own box passed).
           if (root) ray_derive(r);   // one place for both scattered and primary rays
-          const bool root_hit = root && box_hit(r, p.root_lo[0], p.root_lo[1], p.root_lo[2], p.root_hi[0], p.root_hi[1], p.root_hi[2]);
+          const bool root_hit = root && (ANY ? box_hit_interval(r, p.root_lo[0], p.root_lo[1], p.root_lo[2], p.root_hi[0], p.root_hi[1], p.root_hi[2], p.ray_tlo, p.ray_thi)
+                                             : box_hit(r, p.root_lo[0], p.root_lo[1], p.root_lo[2], p.root_hi[0], p.root_hi[1], p.root_hi[2]));
           if (root) {
             wkey[lane] = kKeyInit;
             wcnt[lane] = root_hit ? 1 : 0;    // 0: the fold is already complete (a miss), shaded next time
@@ -1202,12 +1216,17 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         if (jj >= p.lds_sph) s = buf_load16(rs_sph, jj * 16);
       }
       if (STATS) n_sph += act ? 1 : 0;
-      bool near_root;
-      const float g = sphere_root_flag(q, s.x, s.y, s.z, s.w, &near_root);
-      // key = (bits(t), leaf << 1 | near_root): min = smallest t, ties to the lowest leaf
-      if (act & (g < kTMax))
-        atomicMin(&wkey[sl],
-                  ((unsigned long long)__float_as_uint(g) << 32) | ((unsigned)jj << 1) | (near_root ? 1u : 0u));
+      if constexpr (ANY) {
+        // (every lane that accepts its sphere writes the same value: no atomic)
+        if (act && sphere_hit_any(q, p.ray_tlo, p.ray_thi, s.x, s.y, s.z, s.w)) wkey[sl] = kKeyAnyHit;
+      } else {
+        bool near_root;
+        const float g = sphere_root_flag(q, s.x, s.y, s.z, s.w, &near_root);
+        // key = (bits(t), leaf << 1 | near_root): min = smallest t, ties to the lowest leaf
+        if (act & (g < kTMax))
+          atomicMin(&wkey[sl],
+                    ((unsigned long long)__float_as_uint(g) << 32) | ((unsigned)jj << 1) | (near_root ? 1u : 0u));
+      }
       if (STATS) { __builtin_amdgcn_s_waitcnt(0); tr_cyc[3] += clock64() - tr_l0; }
       RT_MARK("LEAF_END");
     } else {
@@ -1244,11 +1263,16 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         const int cl8 = f2i(q0.w), cr8 = f2i(q1.w);   // child references, stored pre-shifted by 8 (sign = leaf)
         // (CULL: the interval's upper end is the slot's best root so far -- the high word of its hit key, one ds_read_b32 -- widened by
         // the proven margin; the ray's weight W2 travels in the spare dword of the {1/d} entry.  Two v_fma + one v_min per item.)
-        float limc = kTMax;
+        float limc = kTMax, limlo = 0.0f;
         if constexpr (CULL) limc = cull_limit(__uint_as_float(*reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(wkey) + 2 * sl4 + 4)), ri.w, p.cull_kappa);
+        // (ANY: the caller's interval; a slot whose key is marked reads 0.0 from its high word -- nothing passes)
+        if constexpr (ANY) {
+          limlo = p.ray_tlo;
+          limc = fminf(p.ray_thi, __uint_as_float(*reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(wkey) + 2 * sl4 + 4)));
+        }
         // lane masks straight from the compares; the rest is 64-bit scalar logic
-        const unsigned long long m_hl = bal(box_hit_clamped(q, q0.x, q0.y, q0.z, q1.x, q1.y, q1.z, limc));
-        const unsigned long long m_hr = bal(box_hit_clamped(q, q2.x, q2.y, q2.z, q3.x, q3.y, q3.z, limc));
+        const unsigned long long m_hl = bal(box_hit_interval(q, q0.x, q0.y, q0.z, q1.x, q1.y, q1.z, limlo, limc));
+        const unsigned long long m_hr = bal(box_hit_interval(q, q2.x, q2.y, q2.z, q3.x, q3.y, q3.z, limlo, limc));
         const unsigned long long m_ln = bal(cl8 < 0), m_rn = bal(cr8 < 0);
         // an inner child continues iff its box passes; a leaf child is tested because this node passed
         const unsigned long long m_inl = m_act & ~m_ln & m_hl, m_inr = m_act & ~m_rn & m_hr;
@@ -1310,10 +1334,14 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
             ref = f2i(buf_load16(rs_nodes, ni16 * 4 + 16 * role).w);
           }
         }
-        float limc = kTMax;
+        float limc = kTMax, limlo = 0.0f;
         if constexpr (CULL) limc = cull_limit(__uint_as_float(*reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(wkey) + 2 * sl4 + 4)), ri.w, p.cull_kappa);
+        if constexpr (ANY) {
+          limlo = p.ray_tlo;
+          limc = fminf(p.ray_thi, __uint_as_float(*reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(wkey) + 2 * sl4 + 4)));
+        }
         const bool child_leaf = act & (ref < 0);
-        const bool pass = act & (ref >= 0) && box_hit_clamped(q, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, limc);
+        const bool pass = act & (ref >= 0) && box_hit_interval(q, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, limlo, limc);
         if (STATS) n_box += (act & (ref >= 0)) ? 1 : 0;
         // second level: the child's own record (a virtual item `ref | sl4`)
         const int ci16 = pass ? (int)(((unsigned)ref >> 4) & 0xfffffff0u) : 0;
@@ -1332,8 +1360,8 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         asm volatile("" ::"v"(q2.w), "v"(q3.w), "v"(ra.w), "v"(ri.w), "v"(lo.w), "v"(hi.w));
         const int cl8 = f2i(q0.w), cr8 = f2i(q1.w);
         const unsigned long long m_pass = bal(pass), m_cleaf = bal(child_leaf);
-        const unsigned long long m_hl = bal(box_hit_clamped(q, q0.x, q0.y, q0.z, q1.x, q1.y, q1.z, limc));
-        const unsigned long long m_hr = bal(box_hit_clamped(q, q2.x, q2.y, q2.z, q3.x, q3.y, q3.z, limc));
+        const unsigned long long m_hl = bal(box_hit_interval(q, q0.x, q0.y, q0.z, q1.x, q1.y, q1.z, limlo, limc));
+        const unsigned long long m_hr = bal(box_hit_interval(q, q2.x, q2.y, q2.z, q3.x, q3.y, q3.z, limlo, limc));
         const unsigned long long m_ln = bal(cl8 < 0), m_rn = bal(cr8 < 0);
         const unsigned long long m_inl = m_pass & ~m_ln & m_hl, m_inr = m_pass & ~m_rn & m_hr;
         // leaf appends: the child itself (lanes whose child is a leaf), or its leaf children -- never both for one lane
@@ -1847,7 +1875,7 @@ size_t pooled_lds_bytes(int lds_nodes, int lds_sph, int capb, int capl, int ray_
   return (size_t)lds_nodes * 64 + (size_t)lds_sph * 16 + (size_t)waves_per_wg * pooled_wave_dw(ray_planes, capb, capl) * sizeof(unsigned);
 }
 
-template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO = false, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, bool RAYS = false>
+template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO = false, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, int RAYS = 0>
 static hipError_t launch_pooled_t(const KParams &p, int grid, hipStream_t stream) {
   const size_t lds = pooled_lds_bytes(p.lds_nodes, p.lds_sph, p.capb, p.capl, p.ray_planes, THREADS / 64);
   auto kfn = pooled_kernel<THREADS, ALL_LDS, STATS, SOLO, TAIL, ORD, CULL, SPILL, RAYS>;
@@ -1927,22 +1955,31 @@ hipError_t launch_pixel_rays(const KParams &p, hipStream_t stream) {
 
 // The plain pooled loop with the RAYS source, in the shapes make_plan picks for a frame of as many 64-ray blocks: workgroups of 16
 // waves (whole scene in LDS or not), or the twenty-wave shape of four-wave workgroups, with the spilling box stack for tall trees.
-hipError_t launch_pooled_rays(const KParams &p, int grid, int waves_per_wg, hipStream_t stream) {
+// MODE: kRaysColour (rt_trace_rays) or kRaysAny (rt_occluded_rays).
+template <int MODE>
+static hipError_t launch_pooled_rays_t(const KParams &p, int grid, int waves_per_wg, hipStream_t stream) {
   if (grid <= 0 || p.nrays <= 0) return hipSuccess;
   if (p.cull || p.px_hdr != nullptr || p.order != nullptr || p.nframes != 1) return hipErrorInvalidValue;
   const bool all_lds = p.lds_nodes == p.n_nodes && p.lds_sph == p.n_sph;
   if (p.spill != nullptr) {
     if (waves_per_wg != 4) return hipErrorInvalidValue;
-    if (p.capb == kSpillCapbTest) return launch_pooled_t<256, false, false, false, 0, false, false, kSpillCapbTest - 64, true>(p, grid, stream);
-    if (p.capb == kSpillCapb) return launch_pooled_t<256, false, false, false, 0, false, false, kSpillCapb - 64, true>(p, grid, stream);
+    if (p.capb == kSpillCapbTest) return launch_pooled_t<256, false, false, false, 0, false, false, kSpillCapbTest - 64, MODE>(p, grid, stream);
+    if (p.capb == kSpillCapb) return launch_pooled_t<256, false, false, false, 0, false, false, kSpillCapb - 64, MODE>(p, grid, stream);
     return hipErrorInvalidValue;
   }
   switch (waves_per_wg) {
-  case 16: return all_lds ? launch_pooled_t<1024, true, false, false, 0, false, false, 0, true>(p, grid, stream)
-                          : launch_pooled_t<1024, false, false, false, 0, false, false, 0, true>(p, grid, stream);
-  case 4: return launch_pooled_t<256, false, false, false, 0, false, false, 0, true>(p, grid, stream);
+  case 16: return all_lds ? launch_pooled_t<1024, true, false, false, 0, false, false, 0, MODE>(p, grid, stream)
+                          : launch_pooled_t<1024, false, false, false, 0, false, false, 0, MODE>(p, grid, stream);
+  case 4: return launch_pooled_t<256, false, false, false, 0, false, false, 0, MODE>(p, grid, stream);
   default: return hipErrorInvalidValue;
   }
+}
+hipError_t launch_pooled_rays(const KParams &p, int grid, int waves_per_wg, hipStream_t stream) {
+  return launch_pooled_rays_t<kRaysColour>(p, grid, waves_per_wg, stream);
+}
+hipError_t launch_pooled_occluded(const KParams &p, int grid, int waves_per_wg, hipStream_t stream) {
+  if (p.occluded == nullptr) return hipErrorInvalidValue;
+  return launch_pooled_rays_t<kRaysAny>(p, grid, waves_per_wg, stream);
 }
 
 // objs_hit bvh r t_min t_max (ray.fut:76-86), one lane per ray: the pixel family's stack fold with the caller's interval on every box,
@@ -1999,6 +2036,46 @@ __global__ __launch_bounds__(64) void intersect_kernel(KParams p, float t_min, f
 hipError_t launch_intersect_rays(const KParams &p, float t_min, float t_max, int32_t *index, float *hit7, hipStream_t stream) {
   if (p.nrays <= 0) return hipSuccess;
   hipLaunchKernelGGL(intersect_kernel, dim3((unsigned)((p.nrays + 63) / 64)), dim3(64), 0, stream, p, t_min, t_max, index, hit7);
+  return hipGetLastError();
+}
+
+// rt_occluded_rays, one lane per ray: intersect_kernel's stack fold with the caller's interval on every box and on every sphere
+// (sphere_hit_any); the lane leaves the walk at its first accepted sphere -- the fold is an OR, so no order can change the answer.
+__global__ __launch_bounds__(64) void occluded_kernel(KParams p) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const Ray r = load_ray(p.rays, i);
+  const float t_min = p.ray_tlo, t_max = p.ray_thi;
+  bool hit = false;
+  int sp = 0;
+  stack[sp++][lane] = 0;
+  while (sp > 0 && !hit) {
+    const int ni = stack[--sp][lane];
+    const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+    if (!box_hit_interval(r, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, t_min, t_max)) continue;
+    const int kids[2] = {f2i(lo.w), f2i(hi.w)};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int c = kids[k];
+      if (c < 0) {
+        const float4 s = buf_load16(rs_sph, ~c * 16);
+        hit = hit || sphere_hit_any(r, t_min, t_max, s.x, s.y, s.z, s.w);
+      } else {
+        stack[sp++][lane] = c;   // (at most one pending sibling per level: sp <= tree height + 1 <= kStackPixel)
+      }
+    }
+  }
+  p.occluded[i] = hit ? 1 : 0;
+}
+
+hipError_t launch_occluded_rays(const KParams &p, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (p.occluded == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(occluded_kernel, dim3((unsigned)((p.nrays + 63) / 64)), dim3(64), 0, stream, p);
   return hipGetLastError();
 }
 

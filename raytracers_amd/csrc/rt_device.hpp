@@ -271,6 +271,10 @@ struct KParams {
   const float *rays;
   float *colour3;
   int nrays;
+  // rt_occluded_rays (the any-hit instantiations of the pooled kernel): occluded[i] = 1 iff some leaf is reached with every box tested over
+  // (ray_tlo, ray_thi) and its sphere has a root strictly inside that interval, else 0
+  unsigned char *occluded;
+  float ray_tlo, ray_thi;
 };
 
 hipError_t launch_pixel(const KParams &p, bool stats, hipStream_t stream);
@@ -278,6 +282,10 @@ hipError_t launch_pixel(const KParams &p, bool stats, hipStream_t stream);
 hipError_t launch_pixel_rays(const KParams &p, hipStream_t stream);
 // ... or in the pooled family's plain loop, 64 consecutive rays per ticket (grid / waves_per_wg as make_plan says; p.spill: the SPILL shape)
 hipError_t launch_pooled_rays(const KParams &p, int grid, int waves_per_wg, hipStream_t stream);
+// occlusion of p.nrays rays over (p.ray_tlo, p.ray_thi) into p.occluded: the pooled family's any-hit loop (same shapes as launch_pooled_rays) ...
+hipError_t launch_pooled_occluded(const KParams &p, int grid, int waves_per_wg, hipStream_t stream);
+// ... or one lane per ray, each leaving its traversal at its first accepted sphere
+hipError_t launch_occluded_rays(const KParams &p, hipStream_t stream);
 // objs_hit bvh r t_min t_max of n rays (ray.fut:76-86): index[i] = the winning leaf or -1, hit7 (may be nullptr) = {t, p.xyz, normal.xyz}
 hipError_t launch_intersect_rays(const KParams &p, float t_min, float t_max, int32_t *index, float *hit7, hipStream_t stream);
 // the primary rays of an h x w frame through p.cam (get_ray at pixel_u / pixel_v), row-major from the top row: rays[6 (row w + col) ..]
