@@ -55,7 +55,12 @@ build/hip_touch: tools/hip_touch.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -o $@ $<
 
 # the pooled kernel's tile-queue protocol (rt_device.hpp) played on the CPU; in the CPU test suite
-build/queue_check: tools/queue_check.cpp $(CSRC)/rt_device.hpp $(CSRC)/lane_core.h
+build/queue_check: tools/queue_check.cpp $(CSRC)/rt_device.hpp $(CSRC)/lane_core.h $(CSRC)/treelet.h
+	@mkdir -p build
+	$(HIPCC) -O2 -std=c++17 -Wall -I$(CSRC) -o $@ $<
+
+# the choice of the pooled kernel's instantiation (rt_device.hpp: choose_pooled) over its inputs, against the compiled set; in the CPU test suite
+build/pooled_choice_check: tools/pooled_choice_check.cpp $(CSRC)/rt_device.hpp $(CSRC)/lane_core.h $(CSRC)/treelet.h
 	@mkdir -p build
 	$(HIPCC) -O2 -std=c++17 -Wall -I$(CSRC) -o $@ $<
 
@@ -107,7 +112,7 @@ build/first_call_probe: tools/first_call_probe.c include/ray.h $(LIB)
 	@mkdir -p build
 	$(CC) -O2 -std=gnu99 -Wall -Iinclude -o $@ tools/first_call_probe.c -Lraytracers_amd -lray_mi355x -Wl,-rpath,'$$ORIGIN/../raytracers_amd'
 
-tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_pooled
+tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_pooled
 
 oracle:
 	$(MAKE) -s -C oracle

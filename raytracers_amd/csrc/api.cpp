@@ -506,17 +506,332 @@ int ensure_spill(rt_context *ctx, int stride) {
 // Is the traversal copy of the scene (64 bytes per inner node, 16 per sphere) larger than the eight L2s together?
 bool rt_scene_exceeds_l2(const rt_prepared *ps) { return static_cast<int64_t>(ps->n) * 80 > (int64_t(32) << 20); }
 
-// May this launch cull (lane_core.h: cull_limit)?  The scene's guards (rt_prepared::cull), the launch shape the CULL instantiations
-// exist for, and every camera origin of the launch inside the scene guard -- a batch's cameras are read from the context's pinned
-// copy of them (stage_cams); cameras that live only on the device switch culling off.
-bool cull_allowed(const rt_context *ctx, const rt_prepared *ps, const Plan &pl, const rtk::KParams &p, const float *cams_dev, int nframes) {
-  if (ctx->cull == 0 || !ps->cull.ok || pl.variant != RT_VARIANT_POOLED || (pl.waves != 16 && pl.waves != 4)) return false;
-  if (ctx->cull < 0 && pl.lds_nodes == p.n_nodes && pl.lds_sph == p.n_sph) return false;
-  if (cams_dev == nullptr) return rt::cull_origin_ok(ps->cull, &p.cam.ox);
-  if (cams_dev != ctx->cams_dev || ctx->cams_host == nullptr) return false;
-  for (int f = 0; f < nframes; ++f)
-    if (!rt::cull_origin_ok(ps->cull, ctx->cams_host + 12 * f)) return false;
-  return true;
+// Culling by the best hit so far (the CULL instantiations; lane_core.h: cull_limit): where the scene's and the
+// camera's guards pass.  Auto leaves wholly LDS-resident scenes alone: their walks are short and LDS-fast, and the limit's three
+// instructions per item cost more than the tests it saves (rgbbox 1000 x 1000: -3 % box tests; tools/cull_pooled.cpp).
+// The scene's guards (rt_prepared::cull), the launch shape the CULL instantiations exist for, and every camera origin of the launch inside
+// the scene guard -- a batch's cameras are read from the context's pinned copy of them (stage_cams); cameras that live only on the device
+// switch culling off.
+void set_cull(const rt_context *ctx, const rt_prepared *ps, const Plan &pl, const float *cams_dev, rtk::KParams *p) {
+  if (ctx->cull == 0 || !ps->cull.ok || pl.variant != RT_VARIANT_POOLED || (pl.waves != 16 && pl.waves != 4)) return;
+  if (ctx->cull < 0 && pl.lds_nodes == p->n_nodes && pl.lds_sph == p->n_sph) return;
+  if (cams_dev == nullptr ? !rt::cull_origin_ok(ps->cull, &p->cam.ox) : (cams_dev != ctx->cams_dev || ctx->cams_host == nullptr)) return;
+  for (int f = 0; cams_dev != nullptr && f < p->nframes; ++f)
+    if (!rt::cull_origin_ok(ps->cull, ctx->cams_host + 12 * f)) return;
+  p->cull = 1;
+  p->cull_c2 = ps->cull.c2;
+  p->cull_kappa = ps->cull.kappa;
+}
+
+// The name of the pooled instantiation these parameters launch (rt_context_last_launch)
+std::string pooled_launch_name(const rtk::KParams &p, int waves, int rays = 0) {
+  rtk::PooledKey k{};
+  return rtk::choose_pooled(p, false, waves, rays, &k) ? rtk::pooled_name(k) : "none";
+}
+
+// p's scene fields: the prepared scene's traversal copy
+void scene_params(const rt_prepared *ps, rtk::KParams *p) {
+  p->nodes = ps->nodes; p->nodes64 = ps->nodes64; p->sph = ps->sph; p->col = ps->col;
+  std::copy(ps->root_lo, ps->root_lo + 3, p->root_lo);
+  std::copy(ps->root_hi, ps->root_hi + 3, p->root_hi);
+  p->n_nodes = static_cast<int>(ps->n - 1); p->n_sph = static_cast<int>(ps->n);
+}
+// ... and those of one frame: part `part` of `nparts` of an h x w image through camera cam12 (nullptr: the prepared scene's)
+void frame_params(const rt_prepared *ps, int64_t h, int64_t w, int rows_per_tile, int part, int nparts, int max_depth, const float *cam12, rtk::KParams *p) {
+  scene_params(ps, p);
+  std::memcpy(&p->cam, cam12 ? static_cast<const void *>(cam12) : static_cast<const void *>(&ps->cam), sizeof(p->cam));
+  p->w = static_cast<int>(w); p->h = static_cast<int>(h);
+  p->rows_local = static_cast<int>(rt::part_rows(h, rows_per_tile, part, nparts));
+  p->rows_per_tile = rows_per_tile; p->part = part; p->nparts = nparts;
+  p->rpt_log2 = (rows_per_tile & (rows_per_tile - 1)) == 0 ? __builtin_ctz(rows_per_tile) : -1;
+  p->tiles_x = (p->w + 7) / 8;
+  p->tiles_y = (p->rows_local + 7) / 8;
+  p->max_depth = max_depth;
+  p->nframes = 1;
+}
+
+// Is the plan in the shape of twenty waves per CU?
+bool twenty_waves(const rt_context *ctx, const Plan &pl) { return pl.waves * (pl.grid_full / std::max(1, ctx->num_cu)) == 20; }
+
+// p's fields for the plan's launch shape: LDS staging, stack capacities, the spill region, the context's tuning.  p.nframes and p.nchunks are set.
+int pooled_shape_params(rt_context *ctx, const rt_prepared *ps, const Plan &pl, rtk::KParams *p) {
+  p->static_first = ctx->static_first;
+  p->lds_nodes = pl.lds_nodes; p->lds_sph = pl.lds_sph;
+  p->smax = pl.smax; p->lmax = pl.lmax;
+  p->thr_shade = ctx->thr_shade; p->thr_leaf = ctx->thr_leaf;
+  p->capb = pl.capb; p->capl = pl.capl; p->ray_planes = pl.ray_planes;
+  if (pl.spill_stride > 0) {
+    // (the overflow regions of the waves' box stacks: there since rt_prepare_scene for a tall tree; a no-op then)
+    if (int rc = ensure_spill(ctx, pl.spill_stride)) return rc;
+    p->spill = ctx->spill_dev;
+    p->spill_stride = pl.spill_stride;
+  }
+  p->prio_depth = ctx->prio_depth;
+  p->box2 = ctx->box2;
+  // (twenty waves per CU: the look from 16 items down -- a wave there has a quarter of a SIMD's issue slots less and waits longer for each of its
+  // loads; irreg's batch 0.104 -> 0.101-0.103 ms per frame, a floor of 6 400 spheres 0.101 -> 0.096, profiles/r06/exp/e11.  Batches, and launches
+  // of more than 16 384 tiles -- frames beyond 1000 x 1000 and a rank's share of a 4000 x 4000 one: -1.8 .. -3.6 % with 32, profiles/r04/exp/e10,
+  // e11; a 1000 x 1000 frame is the same within +-1 % either way and keeps 64)
+  p->look_max = ctx->look_max > 0 ? ctx->look_max : (twenty_waves(ctx, pl) ? 16 : (p->nframes > 1 || p->nchunks > 16384) ? 32 : 64);
+  p->tl_log2 = ps->tl_depth;
+  return 0;
+}
+
+// Eight ticket counters (one per XCD: workgroup b runs on XCD b % 8).  Default: they take turns over ONE queue (counter
+// s hands out tickets s, s + 8, ...): the adaptive order stays global and one word no longer carries every draw --
+// measured against one counter: irreg 1000x1000 -8 %, 4000x4000 -38 %, the 10^6-sphere frame -18 %, rgbbox +-1 %.
+// xcd_queues=1 gives every counter its own strip of tile columns instead (an XCD's L2 then serves one strip of the scene:
+// the 10^6-sphere frame's L2 hit rate 65.9 -> 66.9 %; slower than taking turns because the deepest tiles -- the ones
+// handed out in pieces -- are not spread evenly over the strips); single frames only: a batch's class-major ticket
+// order is defined over one queue.
+// (... except for one frame of a scene larger than the L2s in the twenty-wave shape: there the strips win -- an XCD's L2 then serves the part of the scene its
+// strip of the image looks at; 10^6 spheres at 2000 x 2000: 0.99-1.05 ms taking turns, 0.925 in strips; with 16 waves per CU 1.01 / 1.00)
+int xcd_rule(const rt_context *ctx, const rt_prepared *ps, const Plan &pl, int nframes) {
+  if (ctx->xcd_queues >= 0) return ctx->xcd_queues;
+  return nframes == 1 && pl.variant == RT_VARIANT_POOLED && twenty_waves(ctx, pl) && rt_scene_exceeds_l2(ps) ? 1 : 2;
+}
+// p's ticket counters for a launch of `grid` workgroups under the rule `xq` (0: one; 1: strips; 2: they take turns)
+void set_counters(rtk::KParams *p, int xq, int grid) {
+  p->nshards = xq && (p->nframes == 1 || xq == 2) && grid % rtk::kMaxShards == 0 ? rtk::kMaxShards : 1;
+  p->interleave = p->nshards > 1 && xq == 2;
+}
+// the layout of a view's order table for p's counters
+int order_shards(const rtk::KParams &p) { return p.interleave ? 1 : p.nshards; }
+// p's counters follow a launch of `grid` workgroups -- as long as the view's order table (laid out for the present ones) still fits them
+bool counters_follow(rtk::KParams *p, int xq, int grid) {
+  const int ns = p->nshards, il = p->interleave, shards = order_shards(*p);
+  set_counters(p, xq, grid);
+  if (order_shards(*p) == shards) return true;
+  p->nshards = ns;
+  p->interleave = il;
+  return false;
+}
+
+// May a view of this shape ever render through a pixel list (the ORD launch condition's static part)?  Only then does it get the
+// per-pixel buffers (5 bytes per pixel) and does its first frame store the per-pixel record.
+bool px_static_ok(const rt_context *ctx, const rtk::KParams &p, const Plan &pl) {
+  return ctx->pixel_order == 2 ||
+         (ctx->pixel_order == 1 && ctx->deep_class < 0 && p.max_depth > 4 && pl.waves == 16 && ctx->adaptive_order == 1 && p.nchunks <= ctx->px_max_tiles &&
+          (p.nchunks >= 1024 || (pl.lds_nodes == p.n_nodes && pl.lds_sph == p.n_sph)));
+}
+// Does a frame drawn through view v's order render through v's pixel list (pixel tickets, the ORD instantiation)?
+bool px_list_launch(const rt_context *ctx, const rtk::KParams &p, const Plan &pl, const TileOrder *v) {
+  return v && v->valid && v->px_valid && p.nframes == 1 && pl.waves == 16 && ctx->adaptive_order == 1 && (p.nshards == 1 || p.interleave) &&
+         v->px_elems >= static_cast<size_t>(p.rows_local) * p.w && px_static_ok(ctx, p, pl);
+}
+
+// Is view o of the shape of p's frame (its record and order would fit it)?
+bool same_shape(const TileOrder &o, const rtk::KParams &p) {
+  return o.h == p.h && o.w == p.w && o.rows_per_tile == p.rows_per_tile && o.part == p.part && o.nparts == p.nparts && o.max_depth == p.max_depth &&
+         o.ntiles == p.nchunks && o.nshards == order_shards(p);
+}
+
+// The view p's frame belongs to (its record, its order, its pixel list).  A view not seen before: at most 8 are kept; the least recently used
+// one gives up its buffers, which are reused as they are when the sizes match (a camera path rendered frame by frame: stream-ordered, no
+// synchronisation and no hipFree / hipMalloc per new view).
+int find_view(rt_context *ctx, const rt_prepared *ps, const rtk::KParams &p, const Plan &pl, TileOrder **out) {
+  TileOrder *to = nullptr;
+  for (auto &o : ps->orders)
+    if (same_shape(o, p) && std::memcmp(o.cam, &p.cam, sizeof o.cam) == 0) to = &o;
+  if (!to) {
+    TileOrder o{};
+    // (pixel tickets: the per-pixel record and the pixel list of the view, if this context may use them)
+    const bool px_ok = px_static_ok(ctx, p, pl) && p.w < 65536 && p.rows_local < 65536;
+    const size_t px_bytes = px_ok ? static_cast<size_t>(p.h) * static_cast<size_t>(p.w) : 0;
+    const size_t px_elems = px_ok ? static_cast<size_t>(p.rows_local) * static_cast<size_t>(p.w) : 0;
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t off_order = up(sizeof(int) * static_cast<size_t>(p.nchunks)), off_cost_px = off_order + up(sizeof(int) * static_cast<size_t>(rtk::order_table_ints(p.nchunks))),
+                 off_px_list = off_cost_px + up(px_bytes), need_bytes = off_px_list + up(sizeof(unsigned) * (px_elems + (px_ok ? rtk::kPxHdrInts : 0)));
+    if (ps->orders.size() >= 8) {
+      size_t lru = 0;
+      for (size_t i = 1; i < ps->orders.size(); ++i)
+        if (ps->orders[i].stamp < ps->orders[lru].stamp) lru = i;
+      TileOrder &v = ps->orders[lru];
+      o.classes_event = v.classes_event;   // (a copy still in flight lands in the slot before any later one: same stream)
+      o.classes_slot = v.classes_slot;
+      o.sort_event = v.sort_event;
+      o.sort_event_px = v.sort_event_px;
+      if (int rc = await_view(ctx, &v)) return rc;   // (sorts of the evicted view still running on the sort stream touch these buffers: the main stream goes behind them)
+      if (v.block_bytes >= need_bytes) {       // the evicted view's block as it is
+        o.block = v.block;
+        o.block_bytes = v.block_bytes;
+        o.block_owner = v.block_owner;
+      } else {
+        drain_streams(ctx);
+        free_view_block(ctx, v);
+      }
+      ps->orders.erase(ps->orders.begin() + static_cast<std::ptrdiff_t>(lru));
+    }
+    o.h = p.h; o.w = p.w; o.rows_per_tile = p.rows_per_tile; o.part = p.part; o.nparts = p.nparts; o.max_depth = p.max_depth;
+    std::memcpy(o.cam, &p.cam, sizeof o.cam);
+    o.ntiles = p.nchunks;
+    o.nshards = order_shards(p);
+    // one block of the context's arena / block pool behind the view's four arrays (a hipMalloc each inside a view's first render call
+    // cost the reference's harness ~0.3 ms of its first frame)
+    if (!o.block) {
+      o.block_bytes = need_bytes;
+      if (ctx == ps->home) {
+        RT_HIP(ctx, pool_alloc(ctx, &o.block, &o.block_bytes));
+        o.block_owner = ctx;
+      } else {      // (rendered through another context than the one that prepared the scene: no arena of ours to take it from)
+        RT_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&o.block), o.block_bytes));
+      }
+    }
+    o.cost = reinterpret_cast<int *>(o.block);
+    o.order = reinterpret_cast<int *>(o.block + off_order);
+    if (px_ok) {
+      o.cost_px = reinterpret_cast<unsigned char *>(o.block + off_cost_px);
+      o.px_list = reinterpret_cast<unsigned *>(o.block + off_px_list);
+      o.cost_px_bytes = px_bytes;
+      o.px_elems = px_elems;
+    }
+    RT_HIP(ctx, hipMemsetAsync(o.cost, 0, sizeof(int) * static_cast<size_t>(o.ntiles), ctx->stream));
+    ps->orders.push_back(o);
+    to = &ps->orders.back();
+  }
+  to->stamp = ++ps->order_clock;
+  *out = to;
+  return 0;
+}
+
+// How a pooled render launch draws its tickets: through which view's order or pixel list, with which deep-tile policy, grid and instantiation flags.
+struct Tickets {
+  TileOrder *use = nullptr;   // the view whose order / pixel list the frame is rendered through: its own (`to`), or the one it borrows from
+  bool borrowed = false;
+  bool first_order = false;   // the bit-reversed order of a frame nothing is known about
+};
+// `to`: the frame's view (nullptr: no adaptive order); `xq`: the frame's xcd_queues rule
+int choose_tickets(rt_context *ctx, const rt_prepared *ps, TileOrder *to, int xq, Ticks &tick, rtk::KParams &p, Plan &pl, Tickets *t) {
+  const int nframes = p.nframes, max_depth = p.max_depth;
+  if (to) {
+    // the view's last frame left a record that nothing has sorted yet (eager_sort = 0, or a record made before the option was set)
+    if (int rc = sort_view(ctx, ps, to, p, pl)) return rc;
+    t->use = to->valid ? to : nullptr;
+    // A NEW view (no order of its own yet) borrows the order / pixel list of the most recently rendered view of the same shape
+    // (`borrow`): the reference's render is stateless (ray.fut:246) and a caller that moves the camera renders nothing but first
+    // frames -- which were unordered (tiles in bit-reversed order, DONATE tail).  Neighbouring views agree on WHERE the long chains
+    // are (they cluster at the walls' edges / at grazing angles, profiles/r04/README.md) even though single pixels do not; the
+    // chains the borrowed list places wrongly are what the DONATE tail catches.  Only the order of independent pixels changes.
+    // WHICH view: one of the two views rendered before this one whose sorts are THROUGH on the device (an event query: a borrowed frame never
+    // waits for anything) -- a caller that synchronises after every frame finds the previous view there, or the one before it.  A caller
+    // that enqueues new views back to back is far ahead of the device, finds none and renders unordered as before: waiting for sorts that
+    // cannot start before their frame ends serialises frame, sorts, frame, and measured 0.45-0.54 ms per irreg 1000 x 1000 view against
+    // 0.43 unordered, from run to run; an OLDER sorted view predicts worse than no order at all (0.54).  (sync_policy = 1: the most recent
+    // view whatever its state, behind a stream wait -- the same launches in every run, for tests and measurements; eager_sort = 0: the
+    // pending sorts run in line, which waits for nothing either.)
+    // (borrow = 1, auto: scenes read from L2 only.  A scene that lives in LDS has nothing pixel-stable to borrow -- rgbbox's long chains are chaotic
+    // pixel by pixel -- and its unordered frame, whose tail the DONATE waves walk in 4-level treelets, is now as fast as one through a neighbour's
+    // TILE order: rgbbox 1000 x 1000 0.462 ms unordered against 0.483 borrowed, 500 x 500 0.272 / 0.276; irreg 0.431 / 0.355, 0.273 / 0.229 --
+    // profiles/r06/cold_probe_*.txt.  borrow = 2 / 3 force the tile order / the list for either kind.)
+    const bool scene_in_lds = pl.lds_nodes == p.n_nodes && pl.lds_sph == p.n_sph;
+    if (!t->use && ctx->borrow && !(ctx->borrow == 1 && scene_in_lds) && nframes == 1 && ctx->adaptive_order == 1) {
+      TileOrder *from = nullptr;
+      for (auto &o : ps->orders) {
+        if (&o == to || !same_shape(o, p) || !(o.valid || o.sort_pending)) continue;
+        const bool ok = ctx->sync_policy ? true : (o.stamp + 2 >= to->stamp && (o.sort_pending ? !ctx->eager_sort : sorts_complete(&o)));
+        if (ok && (!from || o.stamp > from->stamp)) from = &o;
+      }
+      if (from) {
+        if (int rc = sort_view(ctx, ps, from, p, pl)) return rc;
+        t->use = from;
+      }
+    }
+    t->borrowed = t->use != nullptr && t->use != to;
+    // The record of a view is a deterministic function of the view, so the table is computed
+    // once (after the view's first frame) and kept; adaptive_order == 2 re-records and
+    // recomputes every frame (testing aid).
+    // (a view whose tiles were first recorded by a batch has no per-pixel record yet: its first single frame records again)
+    const bool px_can = px_static_ok(ctx, p, pl) && nframes == 1 && to->px_list != nullptr && to->px_elems >= static_cast<size_t>(p.rows_local) * p.w &&
+                        to->cost_px_bytes >= static_cast<size_t>(p.h) * p.w && p.w < 65536 && p.rows_local < 65536 && (p.nshards == 1 || p.interleave);
+    const bool rerecord = !to->valid || ctx->adaptive_order == 2 || (px_can && !to->px_valid);
+    p.cost = rerecord ? to->cost : nullptr;
+    p.cost_px = rerecord && px_can ? to->cost_px : nullptr;
+    p.order = t->use ? t->use->order : nullptr;
+    DeepPolicy dp;
+    if (int rc = deep_policy(ctx, ps, (nframes == 1 && !t->borrowed) ? to : nullptr, pl.grid_full * pl.waves, &dp)) return rc;
+    if (t->borrowed) dp = DeepPolicy{0, 0, ctx->deep_cap_log2, true};   // (a borrowed order: no tile holds its wave -- which tiles are deep is the other view's truth)
+    // A view's FIRST frame (no order yet): every workgroup -- the half-size launch that serves a partly LDS-resident scene's
+    // ordered frames best lets an unordered one wait for its late chains with half the chip (irreg, first frame: 700 x 700
+    // 0.605 -> 0.545 ms, 1000 x 1000 0.714 -> 0.625, 1400 x 1400 0.909 -> 0.738; profiles/r04/exp/e7).
+    if (!to->valid && nframes == 1 && ctx->adaptive_order == 1 && ctx->deep_class < 0 && ctx->grid_div == 0 && p.nchunks <= 32768) {
+      dp.sparse = true;
+    }
+    // Small ORDERED single frames (2 048 .. 10 000 tiles) are what their last bounce chains take: the COLD instantiation hands a
+    // wave's last three rays to the solo loop from inside the pooled loop -- rgbbox 500 x 500 0.280 -> 0.225 ms; neutral to +2 %
+    // from 1000 x 1000 on, where it is not used (profiles/r04/exp/e7, e8).
+    if (ctx->handover && nframes == 1 && to->valid && p.nchunks >= 2048 && p.nchunks <= 10000 && max_depth > 4 && pl.waves == 16 && ctx->solo &&
+        ps->tl_depth == rtk::kTreeletDepth && ctx->deep_class < 0 && ctx->adaptive_order == 1)
+      p.cold = 3;
+    p.deep_class = dp.deep_class;
+    p.deep_split = dp.deep_split;
+    p.deep_cap_log2 = dp.cap_log2;
+    if (dp.sparse && ctx->grid_div == 0 && pl.grid != pl.grid_full) {
+      pl.grid = pl.grid_full;
+      (void)counters_follow(&p, xq, pl.grid);
+    }
+  }
+  // Pixel tickets (the ORD instantiation): an ordered single frame of a view that has its pixel list draws from it -- every
+  // workgroup is launched (the longest chains ride in waves of their own from t = 0: the work bounds the frame, not they).
+  // (a BORROWED order goes through the other view's pixel list, holds and all; borrow = 2: through its TILE order.  Camera path view by view, mean of
+  // the views behind the first, none / tiles / list / list without holds, with 2-level treelets, profiles/r06/exp/e4_borrow_modes_*.txt: irreg 500 x 500
+  // 0.315 / 0.308 / 0.267 / 0.271 ms, 1000 x 1000 0.506 / 0.453 / 0.376 / 0.402, 1400 x 1400 0.620 / 0.556 / 0.498 / 0.516; rgbbox 0.335 / 0.313 / 0.343 / 0.347,
+  // 0.561 / 0.508 / 0.551 / 0.553, 0.785 / 0.734 / 0.791 / 0.803.)
+  const bool borrow_tiles_only = t->borrowed && ctx->borrow == 2;
+  if (!borrow_tiles_only && px_list_launch(ctx, p, pl, t->use)) {
+    p.px_list = t->use->px_list;
+    p.px_hdr = reinterpret_cast<const int *>(t->use->px_list + t->use->px_elems);
+    p.px_hold = (t->borrowed && ctx->borrow == 4) ? 0 : ctx->px_hold;   // (borrow = 4, testing: a borrowed list without its holds)
+    p.px_prio = ctx->px_prio;
+    p.cold = 0;
+    p.solo = (t->use->px_solo && ctx->solo && ps->tl_depth == rtk::kTreeletDepth) ? 1 : 0;
+    if (ctx->grid_div == 0 && pl.grid != pl.grid_full && counters_follow(&p, xq, pl.grid_full)) pl.grid = pl.grid_full;
+  }
+  // An UNORDERED single frame (a view's first; every frame when adaptive_order is 0) ends long after its first waves have run
+  // dry -- its long chains start whenever the raster reaches them.  The DONATE instantiation: a wave that cannot refill gives
+  // the rays it is left with, at a bounce boundary, to sibling waves of its workgroup that have left the loop and wait, one ray
+  // each, walked in the solo loop (LDS mailboxes, workgroup-scope atomics only).  First frames, profiles/r04/exp/e13, e14: irreg
+  // 500 x 500 0.519 -> 0.373 ms, 1000 x 1000 0.588 -> 0.486, a rank's eighth of 4000 x 4000 0.83 / 0.92 -> 0.67 / 0.72, the
+  // 10^6-sphere frame 1.74 -> 1.50, rgbbox 1000 x 1000 0.617 -> 0.549; ordered frames do not gain (within 1 % at every size)
+  // and keep their kernels.  handover=2 (testing): every single frame, a wave offers its rays when it holds <= donate_max.
+  // (... and a frame rendered through a BORROWED order / pixel list: the long chains that list places wrongly start late too)
+  if (nframes == 1 && max_depth > 4 && pl.waves == 16 && ctx->solo && ps->tl_depth == rtk::kTreeletDepth &&
+      (ctx->handover == 2 || (ctx->handover == 1 && (p.order == nullptr || t->borrowed)))) {
+    p.cold = 0;
+    p.donate = ctx->handover == 2 ? ctx->donate_max : 64;
+  }
+  // The sorts this launch depends on (they may still be running on the side streams): the list's when it draws pixel tickets, the tile order's when it draws
+  // tiles; both when it records (the sorts read -- and the tile order's clears -- the record this frame writes) or borrows (its own view is new: nothing of it is in flight).
+  if (t->use) {
+    const bool records = p.cost != nullptr && t->use == to;
+    if (int rc = await_view(ctx, t->use, p.px_hdr == nullptr || records, p.px_hdr != nullptr || records)) return rc;
+  }
+  if (ctx->first_order && nframes == 1 && p.order == nullptr && !p.px_hdr && (p.nshards == 1 || p.interleave) && p.tiles_y > 1 &&
+      p.tiles_y <= 4096 && p.tiles_x <= 32768) {
+    // a frame nothing is known about: not top to bottom (the kernel reads the table like a view's order, with no deep tiles)
+    tick("view, sorts, borrow");
+    if (int rc = get_first_order(ctx, p.tiles_x, p.tiles_y, &p.order)) return rc;
+    tick("first order");
+    p.deep_class = 0;
+    t->first_order = true;
+  }
+  return 0;
+}
+
+// `while depth < 0`: no ray is traced, every pixel is the initial colour (0,0,0)
+int clear_frames(rt_context *ctx, const rtk::KParams &p, int32_t *out_dev, int nframes, int64_t frame_stride, bool inplace) {
+  for (int f = 0; f < nframes; ++f) {
+    if (!inplace) {
+      RT_HIP(ctx, hipMemsetAsync(out_dev + f * frame_stride, 0, sizeof(int32_t) * static_cast<size_t>(p.rows_local) * p.w, ctx->stream));
+      continue;
+    }
+    for (int64_t k = 0; k * p.rows_per_tile < p.rows_local; ++k) {   // the part's row tiles, one by one, at their places
+      const int64_t rows = std::min<int64_t>(p.rows_per_tile, p.rows_local - k * p.rows_per_tile);
+      RT_HIP(ctx, hipMemsetAsync(out_dev + f * frame_stride + (k * p.nparts + p.part) * p.rows_per_tile * p.w, 0,
+                                 sizeof(int32_t) * static_cast<size_t>(rows * p.w), ctx->stream));
+    }
+  }
+  ctx->last_launch = "family=none (memset)";
+  return 0;
 }
 
 }  // namespace
@@ -547,21 +862,9 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
     (void)hipGetLastError();
   }
   rtk::KParams p{};
-  p.nodes = ps->nodes; p.nodes64 = ps->nodes64; p.sph = ps->sph; p.col = ps->col;
-  std::copy(ps->root_lo, ps->root_lo + 3, p.root_lo);
-  std::copy(ps->root_hi, ps->root_hi + 3, p.root_hi);
-  p.n_nodes = static_cast<int>(ps->n - 1); p.n_sph = static_cast<int>(ps->n);
-  std::memcpy(&p.cam, cam12 ? static_cast<const void *>(cam12) : static_cast<const void *>(&ps->cam), sizeof(p.cam));
-  p.w = static_cast<int>(w); p.h = static_cast<int>(h);
-  p.rows_local = static_cast<int>(rt::part_rows(h, rows_per_tile, part, nparts));
-  p.rows_per_tile = rows_per_tile; p.part = part; p.nparts = nparts;
-  p.rpt_log2 = (rows_per_tile & (rows_per_tile - 1)) == 0 ? __builtin_ctz(rows_per_tile) : -1;
-  p.tiles_x = (p.w + 7) / 8;
-  p.tiles_y = (p.rows_local + 7) / 8;
-  p.max_depth = max_depth;
+  frame_params(ps, h, w, rows_per_tile, part, nparts, max_depth, cam12, &p);
   p.out = out_dev;
   p.stats = ctx->stats_dev;
-  p.nframes = 1;
   if (p.rows_local == 0) {
     ctx->last_launch = "family=none (no rows)";
     return 0;
@@ -576,22 +879,7 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
     p.out = out_dev + static_cast<int64_t>(part) * rows_per_tile * w;
     p.out_skip = static_cast<int>(static_cast<int64_t>(nparts - 1) * rows_per_tile * w);
   }
-  if (max_depth == 0) {
-    // `while depth < 0`: no ray is traced, every pixel is the initial colour (0,0,0)
-    for (int f = 0; f < nframes; ++f) {
-      if (!inplace) {
-        RT_HIP(ctx, hipMemsetAsync(out_dev + f * frame_stride, 0, sizeof(int32_t) * static_cast<size_t>(p.rows_local) * p.w, ctx->stream));
-        continue;
-      }
-      for (int64_t k = 0; k * rows_per_tile < p.rows_local; ++k) {   // the part's row tiles, one by one, at their places
-        const int64_t rows = std::min<int64_t>(rows_per_tile, p.rows_local - k * rows_per_tile);
-        RT_HIP(ctx, hipMemsetAsync(out_dev + f * frame_stride + (k * nparts + part) * rows_per_tile * w, 0,
-                                   sizeof(int32_t) * static_cast<size_t>(rows * w), ctx->stream));
-      }
-    }
-    ctx->last_launch = "family=none (memset)";
-    return 0;
-  }
+  if (max_depth == 0) return clear_frames(ctx, p, out_dev, nframes, frame_stride, inplace);
   Ticks tick;
   Plan pl{};
   if (stats) pl.variant = RT_VARIANT_PIXEL;
@@ -601,7 +889,7 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
     // frames of 1000 x 1000 0.110 -> 0.104 ms per frame, one frame of 4000 x 4000 1.72 -> 1.63 ms, 2000 x 2000 -- 62 500 tiles -- the same; single frames
     // within the pixel list's range keep the 16-wave kernels, whose ORD / SOLO / DONATE instantiations they are rendered by)
     // (a scene larger than the chip's L2s -- 32 MB; the 10^6-sphere scene is 80 -- takes the shape from every frame beyond the pixel list's range, together with a
-    // ticket counter per XCD over its own STRIP of the image, below: 2000 x 2000 1.01 -> 0.925 ms, 4000 x 4000 2.47 -> 2.30; e13.  Trees taller than 15 levels run
+    // ticket counter per XCD over its own STRIP of the image, xcd_rule: 2000 x 2000 1.01 -> 0.925 ms, 4000 x 4000 2.47 -> 2.30; e13.  Trees taller than 15 levels run
     // the SPILL kernels in that shape)
     const bool huge = rt_scene_exceeds_l2(ps);
     const bool wide = ctx->wide_waves == 2 || (ctx->wide_waves == 1 && ntiles1 * nframes >= (huge ? 40000 : 100000) && (nframes > 1 || ntiles1 > ctx->px_max_tiles));
@@ -631,289 +919,57 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
   p.frame_stride = static_cast<int>(frame_stride);
   p.cams = reinterpret_cast<const rtk::Cam *>(cams_dev);
   p.queue = ctx->queue_dev;
-  p.nchunks = p.tiles_x * ((p.rows_local + 7) / 8);
+  p.nchunks = p.tiles_x * p.tiles_y;
   // Tiles per ticket.  A frame: one (with eight counters nothing saturates, and several tiles per ticket cost the 10^6-sphere
   // frame 37 %: a wave then walks adjacent expensive tiles one after the other).
   // (a batch: four tiles per ticket while every wave still gets a few dozen tiles -- the bench's 20 frames of 1000x1000 are 76
   // tiles per wave -- fewer when a launch is small: a rank's eighth of those frames is 10-20 tiles per wave, and with four per
   // ticket the waves' loads differ by whole tickets)
+  // (twenty waves per CU: two tiles per ticket at most, profiles/r06/exp/e11)
   const int64_t tiles_per_wave = static_cast<int64_t>(p.nchunks) * nframes / std::max(1, pl.grid * pl.waves);
-  // (twenty waves per CU: two tiles per ticket at most, and the look from 16 items down -- a wave there has a quarter of a SIMD's issue slots
-  // less and waits longer for each of its loads; irreg's batch 0.104 -> 0.101-0.103 ms per frame, a floor of 6 400 spheres 0.101 -> 0.096, profiles/r06/exp/e11)
-  const bool twenty = pl.waves * (pl.grid_full / std::max(1, ctx->num_cu)) == 20;
-  p.tpt_log2 = ctx->tpt_log2 >= 0 ? ctx->tpt_log2 : (nframes > 1 ? (tiles_per_wave >= 48 && !twenty ? 2 : tiles_per_wave >= 24 ? 1 : 0) : 0);
-  // Eight ticket counters (one per XCD: workgroup b runs on XCD b % 8).  Default: they take turns over ONE queue (counter
-  // s hands out tickets s, s + 8, ...): the adaptive order stays global and one word no longer carries every draw --
-  // measured against one counter: irreg 1000x1000 -8 %, 4000x4000 -38 %, the 10^6-sphere frame -18 %, rgbbox +-1 %.
-  // xcd_queues=1 gives every counter its own strip of tile columns instead (an XCD's L2 then serves one strip of the scene:
-  // the 10^6-sphere frame's L2 hit rate 65.9 -> 66.9 %; slower than taking turns because the deepest tiles -- the ones
-  // handed out in pieces -- are not spread evenly over the strips); single frames only: a batch's class-major ticket
-  // order is defined over one queue.
-  // (... except for one frame of a scene larger than the L2s in the twenty-wave shape: there the strips win -- an XCD's L2 then serves the part of the scene its
-  // strip of the image looks at; 10^6 spheres at 2000 x 2000: 0.99-1.05 ms taking turns, 0.925 in strips; with 16 waves per CU 1.01 / 1.00)
-  const int xq = ctx->xcd_queues < 0 ? ((nframes == 1 && pl.variant == RT_VARIANT_POOLED && pl.waves * (pl.grid_full / std::max(1, ctx->num_cu)) == 20 && rt_scene_exceeds_l2(ps)) ? 1 : 2) : ctx->xcd_queues;
-  p.nshards = (xq && (nframes == 1 || xq == 2) && pl.variant == RT_VARIANT_POOLED && pl.grid % rtk::kMaxShards == 0) ? rtk::kMaxShards : 1;
-  p.interleave = p.nshards > 1 && xq == 2;
-  const int order_shards = p.interleave ? 1 : p.nshards;   // layout of the view's order table
-  p.static_first = ctx->static_first;
-  p.lds_nodes = pl.lds_nodes; p.lds_sph = pl.lds_sph;
-  p.smax = pl.smax; p.lmax = pl.lmax;
-  p.thr_shade = ctx->thr_shade; p.thr_leaf = ctx->thr_leaf;
-  p.capb = pl.capb; p.capl = pl.capl; p.ray_planes = pl.ray_planes;
-  if (pl.spill_stride > 0) {
-    // (the overflow regions of the waves' box stacks: there since rt_prepare_scene for a tall tree; a no-op then)
-    if (int rc = ensure_spill(ctx, pl.spill_stride)) return rc;
-    p.spill = ctx->spill_dev;
-    p.spill_stride = pl.spill_stride;
-  }
-  p.prio_depth = ctx->prio_depth;
-  p.box2 = ctx->box2;
-  // (batches, and launches of more than 16 384 tiles -- frames beyond 1000 x 1000 and a rank's share of a 4000 x 4000 one: -1.8 .. -3.6 %
-  // with 32, profiles/r04/exp/e10, e11; a 1000 x 1000 frame is the same within +-1 % either way and keeps 64)
-  p.look_max = ctx->look_max > 0 ? ctx->look_max : (twenty ? 16 : (nframes > 1 || p.nchunks > 16384) ? 32 : 64);
-  p.tl_log2 = ps->tl_depth;
+  p.tpt_log2 = ctx->tpt_log2 >= 0 ? ctx->tpt_log2 : (nframes > 1 ? (tiles_per_wave >= 48 && !twenty_waves(ctx, pl) ? 2 : tiles_per_wave >= 24 ? 1 : 0) : 0);
+  const int xq = xcd_rule(ctx, ps, pl, nframes);
+  set_counters(&p, pl.variant == RT_VARIANT_POOLED ? xq : 0, pl.grid);
+  if (int rc = pooled_shape_params(ctx, ps, pl, &p)) return rc;
   p.solo = ctx->solo;
-  if (pl.variant == RT_VARIANT_POOLED) {
-    if (ps->n >= (int64_t(1) << 22)) return fail(ctx, "pooled kernel: at most 2^22 spheres (work items and hit keys carry the leaf index in 22 bits)");
-    if (p.rpt_log2 < 0) return fail(ctx, "pooled kernel: rows_per_tile must be a power of two");
-    if (int rc = get_uv(ctx, w, h, &p.u_tab, &p.v_tab)) return rc;
-    tick("uv tables");
-    // May a view of this shape ever render through a pixel list (the ORD launch condition's static part)?  Only then does it get the
-    // per-pixel buffers (5 bytes per pixel) and does its first frame store the per-pixel record.
-    const bool px_static_ok = ctx->pixel_order == 2 ||
-                              (ctx->pixel_order == 1 && ctx->deep_class < 0 && max_depth > 4 && pl.waves == 16 && ctx->adaptive_order == 1 && p.nchunks <= ctx->px_max_tiles &&
-                               (p.nchunks >= 1024 || (pl.lds_nodes == p.n_nodes && pl.lds_sph == p.n_sph)));
-    TileOrder *to = nullptr;      // the view this frame belongs to (its record, its order, its pixel list)
-    TileOrder *use = nullptr;     // the view whose order / pixel list this frame is rendered through: `to`, or the view it borrows from
-    bool borrowed = false;
-    if (ctx->adaptive_order && !p.cams) {   // (a batch with its own cameras has no single view to order tiles by)
-      auto same_shape = [&](const TileOrder &o) {
-        return o.h == h && o.w == w && o.rows_per_tile == rows_per_tile && o.part == part && o.nparts == nparts && o.max_depth == max_depth &&
-               o.ntiles == p.nchunks && o.nshards == order_shards;
-      };
-      for (auto &o : ps->orders)
-        if (same_shape(o) && std::memcmp(o.cam, &p.cam, sizeof o.cam) == 0) to = &o;
-      if (!to) {
-        // A view not seen before: at most 8 are kept; the least recently used one gives up its buffers, which are reused as
-        // they are when the sizes match (a camera path rendered frame by frame: stream-ordered, no synchronisation and no
-        // hipFree / hipMalloc per new view).
-        TileOrder o{};
-        // (pixel tickets: the per-pixel record and the pixel list of the view, if this context may use them)
-        const bool px_ok = px_static_ok && w < 65536 && p.rows_local < 65536;
-        const size_t px_bytes = px_ok ? static_cast<size_t>(h) * static_cast<size_t>(w) : 0;
-        const size_t px_elems = px_ok ? static_cast<size_t>(p.rows_local) * static_cast<size_t>(p.w) : 0;
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-        const size_t off_order = up(sizeof(int) * static_cast<size_t>(p.nchunks)), off_cost_px = off_order + up(sizeof(int) * static_cast<size_t>(rtk::order_table_ints(p.nchunks))),
-                     off_px_list = off_cost_px + up(px_bytes), need_bytes = off_px_list + up(sizeof(unsigned) * (px_elems + (px_ok ? rtk::kPxHdrInts : 0)));
-        if (ps->orders.size() >= 8) {
-          size_t lru = 0;
-          for (size_t i = 1; i < ps->orders.size(); ++i)
-            if (ps->orders[i].stamp < ps->orders[lru].stamp) lru = i;
-          TileOrder &v = ps->orders[lru];
-          o.classes_event = v.classes_event;   // (a copy still in flight lands in the slot before any later one: same stream)
-          o.classes_slot = v.classes_slot;
-          o.sort_event = v.sort_event;
-          o.sort_event_px = v.sort_event_px;
-          if (int rc = await_view(ctx, &v)) return rc;   // (sorts of the evicted view still running on the sort stream touch these buffers: the main stream goes behind them)
-          if (v.block_bytes >= need_bytes) {       // the evicted view's block as it is
-            o.block = v.block;
-            o.block_bytes = v.block_bytes;
-            o.block_owner = v.block_owner;
-          } else {
-            drain_streams(ctx);
-            free_view_block(ctx, v);
-          }
-          ps->orders.erase(ps->orders.begin() + static_cast<std::ptrdiff_t>(lru));
-        }
-        o.h = h; o.w = w; o.rows_per_tile = rows_per_tile; o.part = part; o.nparts = nparts; o.max_depth = max_depth;
-        std::memcpy(o.cam, &p.cam, sizeof o.cam);
-        o.ntiles = p.nchunks;
-        o.nshards = order_shards;
-        // one block of the context's arena / block pool behind the view's four arrays (a hipMalloc each inside a view's first render call
-        // cost the reference's harness ~0.3 ms of its first frame)
-        if (!o.block) {
-          o.block_bytes = need_bytes;
-          if (ctx == ps->home) {
-            RT_HIP(ctx, pool_alloc(ctx, &o.block, &o.block_bytes));
-            o.block_owner = ctx;
-          } else {      // (rendered through another context than the one that prepared the scene: no arena of ours to take it from)
-            RT_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&o.block), o.block_bytes));
-          }
-        }
-        o.cost = reinterpret_cast<int *>(o.block);
-        o.order = reinterpret_cast<int *>(o.block + off_order);
-        if (px_ok) {
-          o.cost_px = reinterpret_cast<unsigned char *>(o.block + off_cost_px);
-          o.px_list = reinterpret_cast<unsigned *>(o.block + off_px_list);
-          o.cost_px_bytes = px_bytes;
-          o.px_elems = px_elems;
-        }
-        RT_HIP(ctx, hipMemsetAsync(o.cost, 0, sizeof(int) * static_cast<size_t>(o.ntiles), ctx->stream));
-        ps->orders.push_back(o);
-        to = &ps->orders.back();
-      }
-      to->stamp = ++ps->order_clock;
-      // the view's last frame left a record that nothing has sorted yet (eager_sort = 0, or a record made before the option was set)
-      if (int rc = sort_view(ctx, ps, to, p, pl)) return rc;
-      use = to->valid ? to : nullptr;
-      // A NEW view (no order of its own yet) borrows the order / pixel list of the most recently rendered view of the same shape
-      // (`borrow`): the reference's render is stateless (ray.fut:246) and a caller that moves the camera renders nothing but first
-      // frames -- which were unordered (tiles in bit-reversed order, DONATE tail).  Neighbouring views agree on WHERE the long chains
-      // are (they cluster at the walls' edges / at grazing angles, profiles/r04/README.md) even though single pixels do not; the
-      // chains the borrowed list places wrongly are what the DONATE tail catches.  Only the order of independent pixels changes.
-      // WHICH view: one of the two views rendered before this one whose sorts are THROUGH on the device (an event query: a borrowed frame never
-      // waits for anything) -- a caller that synchronises after every frame finds the previous view there, or the one before it.  A caller
-      // that enqueues new views back to back is far ahead of the device, finds none and renders unordered as before: waiting for sorts that
-      // cannot start before their frame ends serialises frame, sorts, frame, and measured 0.45-0.54 ms per irreg 1000 x 1000 view against
-      // 0.43 unordered, from run to run; an OLDER sorted view predicts worse than no order at all (0.54).  (sync_policy = 1: the most recent
-      // view whatever its state, behind a stream wait -- the same launches in every run, for tests and measurements; eager_sort = 0: the
-      // pending sorts run in line, which waits for nothing either.)
-      // (borrow = 1, auto: scenes read from L2 only.  A scene that lives in LDS has nothing pixel-stable to borrow -- rgbbox's long chains are chaotic
-      // pixel by pixel -- and its unordered frame, whose tail the DONATE waves walk in 4-level treelets, is now as fast as one through a neighbour's
-      // TILE order: rgbbox 1000 x 1000 0.462 ms unordered against 0.483 borrowed, 500 x 500 0.272 / 0.276; irreg 0.431 / 0.355, 0.273 / 0.229 --
-      // profiles/r06/cold_probe_*.txt.  borrow = 2 / 3 force the tile order / the list for either kind.)
-      const bool scene_in_lds = pl.lds_nodes == p.n_nodes && pl.lds_sph == p.n_sph;
-      if (!use && ctx->borrow && !(ctx->borrow == 1 && scene_in_lds) && nframes == 1 && ctx->adaptive_order == 1) {
-        TileOrder *from = nullptr;
-        for (auto &o : ps->orders) {
-          if (&o == to || !same_shape(o) || !(o.valid || o.sort_pending)) continue;
-          const bool ok = ctx->sync_policy ? true : (o.stamp + 2 >= to->stamp && (o.sort_pending ? !ctx->eager_sort : sorts_complete(&o)));
-          if (ok && (!from || o.stamp > from->stamp)) from = &o;
-        }
-        if (from) {
-          if (int rc = sort_view(ctx, ps, from, p, pl)) return rc;
-          use = from;
-        }
-      }
-      borrowed = use != nullptr && use != to;
-      // The record of a view is a deterministic function of the view, so the table is computed
-      // once (after the view's first frame) and kept; adaptive_order == 2 re-records and
-      // recomputes every frame (testing aid).
-      // (a view whose tiles were first recorded by a batch has no per-pixel record yet: its first single frame records again)
-      const bool px_can = px_static_ok && nframes == 1 && to->px_list != nullptr && to->px_elems >= static_cast<size_t>(p.rows_local) * p.w &&
-                          to->cost_px_bytes >= static_cast<size_t>(h) * w && w < 65536 && p.rows_local < 65536 && (p.nshards == 1 || p.interleave);
-      const bool rerecord = !to->valid || ctx->adaptive_order == 2 || (px_can && !to->px_valid);
-      p.cost = rerecord ? to->cost : nullptr;
-      p.cost_px = rerecord && px_can ? to->cost_px : nullptr;
-      p.order = use ? use->order : nullptr;
-      DeepPolicy dp;
-      if (int rc = deep_policy(ctx, ps, (nframes == 1 && !borrowed) ? to : nullptr, pl.grid_full * pl.waves, &dp)) return rc;
-      if (borrowed) dp = DeepPolicy{0, 0, ctx->deep_cap_log2, true};   // (a borrowed order: no tile holds its wave -- which tiles are deep is the other view's truth)
-      // A view's FIRST frame (no order yet): every workgroup -- the half-size launch that serves a partly LDS-resident scene's
-      // ordered frames best lets an unordered one wait for its late chains with half the chip (irreg, first frame: 700 x 700
-      // 0.605 -> 0.545 ms, 1000 x 1000 0.714 -> 0.625, 1400 x 1400 0.909 -> 0.738; profiles/r04/exp/e7).
-      if (!to->valid && nframes == 1 && ctx->adaptive_order == 1 && ctx->deep_class < 0 && ctx->grid_div == 0 && p.nchunks <= 32768) {
-        dp.sparse = true;
-      }
-      // Small ORDERED single frames (2 048 .. 10 000 tiles) are what their last bounce chains take: the COLD instantiation hands a
-      // wave's last three rays to the solo loop from inside the pooled loop -- rgbbox 500 x 500 0.280 -> 0.225 ms; neutral to +2 %
-      // from 1000 x 1000 on, where it is not used (profiles/r04/exp/e7, e8).
-      if (ctx->handover && nframes == 1 && to->valid && p.nchunks >= 2048 && p.nchunks <= 10000 && max_depth > 4 && pl.waves == 16 && ctx->solo &&
-          ps->tl_depth == rtk::kTreeletDepth && ctx->deep_class < 0 && ctx->adaptive_order == 1)
-        p.cold = 3;
-      p.deep_class = dp.deep_class;
-      p.deep_split = dp.deep_split;
-      p.deep_cap_log2 = dp.cap_log2;
-      if (dp.sparse && ctx->grid_div == 0 && pl.grid != pl.grid_full) {
-        pl.grid = pl.grid_full;
-        // the queue layout follows the grid that is launched -- as long as the view's order table (laid out for
-        // `order_shards` shards) still fits it
-        const int ns = (xq && (nframes == 1 || xq == 2) && pl.grid % rtk::kMaxShards == 0) ? rtk::kMaxShards : 1;
-        const int il = ns > 1 && xq == 2;
-        if ((il ? 1 : ns) == order_shards) { p.nshards = ns; p.interleave = il; }
-      }
-    }
-    // Pixel tickets (the ORD instantiation): an ordered single frame of a view that has its pixel list draws from it -- every
-    // workgroup is launched (the longest chains ride in waves of their own from t = 0: the work bounds the frame, not they).
-    // (a BORROWED order goes through the other view's pixel list, holds and all; borrow = 2: through its TILE order.  Camera path view by view, mean of
-    // the views behind the first, none / tiles / list / list without holds, with 2-level treelets, profiles/r06/exp/e4_borrow_modes_*.txt: irreg 500 x 500
-    // 0.315 / 0.308 / 0.267 / 0.271 ms, 1000 x 1000 0.506 / 0.453 / 0.376 / 0.402, 1400 x 1400 0.620 / 0.556 / 0.498 / 0.516; rgbbox 0.335 / 0.313 / 0.343 / 0.347,
-    // 0.561 / 0.508 / 0.551 / 0.553, 0.785 / 0.734 / 0.791 / 0.803.)
-    const bool borrow_tiles_only = borrowed && ctx->borrow == 2;
-    if (use && use->valid && use->px_valid && nframes == 1 && pl.waves == 16 && ctx->adaptive_order == 1 && !borrow_tiles_only &&
-        (p.nshards == 1 || p.interleave) && use->px_elems >= static_cast<size_t>(p.rows_local) * p.w && px_static_ok) {
-      p.px_list = use->px_list;
-      p.px_hdr = reinterpret_cast<const int *>(use->px_list + use->px_elems);
-      p.px_hold = (borrowed && ctx->borrow == 4) ? 0 : ctx->px_hold;   // (borrow = 4, testing: a borrowed list without its holds)
-      p.px_prio = ctx->px_prio;
-      p.cold = 0;
-      p.solo = (use->px_solo && ctx->solo && ps->tl_depth == rtk::kTreeletDepth) ? 1 : 0;
-      if (ctx->grid_div == 0 && pl.grid != pl.grid_full) {
-        const int ns = (xq && pl.grid_full % rtk::kMaxShards == 0) ? rtk::kMaxShards : 1;
-        const int il = ns > 1 && xq == 2;
-        if (ns == 1 || il) { pl.grid = pl.grid_full; p.nshards = ns; p.interleave = il; }
-      }
-    }
-    // An UNORDERED single frame (a view's first; every frame when adaptive_order is 0) ends long after its first waves have run
-    // dry -- its long chains start whenever the raster reaches them.  The DONATE instantiation: a wave that cannot refill gives
-    // the rays it is left with, at a bounce boundary, to sibling waves of its workgroup that have left the loop and wait, one ray
-    // each, walked in the solo loop (LDS mailboxes, workgroup-scope atomics only).  First frames, profiles/r04/exp/e13, e14: irreg
-    // 500 x 500 0.519 -> 0.373 ms, 1000 x 1000 0.588 -> 0.486, a rank's eighth of 4000 x 4000 0.83 / 0.92 -> 0.67 / 0.72, the
-    // 10^6-sphere frame 1.74 -> 1.50, rgbbox 1000 x 1000 0.617 -> 0.549; ordered frames do not gain (within 1 % at every size)
-    // and keep their kernels.  handover=2 (testing): every single frame, a wave offers its rays when it holds <= donate_max.
-    // (... and a frame rendered through a BORROWED order / pixel list: the long chains that list places wrongly start late too)
-    if (nframes == 1 && max_depth > 4 && pl.waves == 16 && ctx->solo && ps->tl_depth == rtk::kTreeletDepth &&
-        (ctx->handover == 2 || (ctx->handover == 1 && (p.order == nullptr || borrowed)))) {
-      p.cold = 0;
-      p.donate = ctx->handover == 2 ? ctx->donate_max : 64;
-    }
-    // The sorts this launch depends on (they may still be running on the side streams): the list's when it draws pixel tickets, the tile order's when it draws
-    // tiles; both when it records (the sorts read -- and the tile order's clears -- the record this frame writes) or borrows (its own view is new: nothing of it is in flight).
-    if (use) {
-      const bool records = p.cost != nullptr && use == to;
-      if (int rc = await_view(ctx, use, p.px_hdr == nullptr || records, p.px_hdr != nullptr || records)) return rc;
-    }
-    bool first_order = false;
-    if (ctx->first_order && nframes == 1 && p.order == nullptr && !p.px_hdr && (p.nshards == 1 || p.interleave) && p.tiles_y > 1 &&
-        p.tiles_y <= 4096 && p.tiles_x <= 32768) {
-      // a frame nothing is known about: not top to bottom (the kernel reads the table like a view's order, with no deep tiles)
-      tick("view, sorts, borrow");
-      if (int rc = get_first_order(ctx, p.tiles_x, p.tiles_y, &p.order)) return rc;
-      tick("first order");
-      p.deep_class = 0;
-      first_order = true;
-    }
-    // Culling by the best hit so far (the CULL instantiations; lane_core.h: cull_limit): where the scene's and the
-    // camera's guards pass.  Auto leaves wholly LDS-resident scenes alone: their walks are short and LDS-fast, and the limit's three
-    // instructions per item cost more than the tests it saves (rgbbox 1000 x 1000: -3 % box tests; tools/cull_pooled.cpp).
-    if (cull_allowed(ctx, ps, pl, p, cams_dev, nframes)) {
-      p.cull = 1;
-      p.cull_c2 = ps->cull.c2;
-      p.cull_kappa = ps->cull.kappa;
-    }
-    tick("before launch");
-    RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream));
-    tick("launch_pooled");
-    {
-      // (which instantiation launch_pooled picks, in its own order of precedence)
-      const bool single_px = p.solo && p.nframes == 1 && p.order != nullptr && p.deep_class > 0 && p.deep_split == 6 && p.tl_log2 == rtk::kTreeletDepth;
-      const char *inst = p.px_hdr ? (p.donate ? (p.solo ? "ORD+SOLO+DONATE" : "ORD+DONATE") : (p.solo ? "ORD+SOLO" : "ORD")) : (p.cold && pl.waves == 16) ? (single_px ? "COLD+SOLO" : "COLD")
-                         : (p.donate && pl.waves == 16) ? (single_px ? "DONATE+SOLO" : "DONATE") : (single_px ? "SOLO" : "plain");
-      char buf[256];
-      std::snprintf(buf, sizeof buf, "family=pooled tickets=%s%s instantiation=%s%s%s frames=%d tiles=%d grid=%d waves=%d counters=%d%s deep_class=%d deep_split=%d recording=%d",
-                    p.px_hdr ? "pixel-list" : first_order ? "tiles-bit-reversed" : (p.order ? "tiles-ordered" : "tiles-raster"), borrowed ? "(borrowed)" : "", inst, p.cull ? "+CULL" : "", p.spill ? "+SPILL" : "", p.nframes, p.nchunks, pl.grid, pl.waves, p.nshards,
-                    p.interleave ? "(turns)" : "", p.px_hdr ? 0 : p.deep_class, p.px_hdr ? 0 : p.deep_split, p.cost ? (p.cost_px ? 2 : 1) : 0);
-      ctx->last_launch = buf;
-    }
-    if (to && p.cost) {
-      // This frame recorded the view's bounce chains.  The sorts that turn the record into the view's tile order and pixel list are
-      // NOT launched here: a caller that never renders the view again (the reference's `render` keeps nothing between calls,
-      // ray.fut:246; a camera path rendered view by view) should not pay for them -- ~0.07 ms behind a 1000 x 1000 frame.  They run
-      // ahead of the view's next frame (sort_pending_record, above).
-      to->sort_pending = true;
-      to->sort_px = p.cost_px != nullptr;
-      to->rec_out_skip = p.out_skip;
-      // (eager_sort, the default: ... but they are LAUNCHED here, on the context's second stream, behind this frame: they run while the caller
-      // synchronises and sets up its next call, off every frame's critical path -- the view's second frame no longer carries them, and a
-      // new view can borrow this one's order at once)
-      if (ctx->eager_sort && (stream_was_idle || ctx->sync_policy))
-        if (int rc = sort_view(ctx, ps, to, p, pl)) return rc;
-      tick("record: eager sorts");
-    }
-  }
-  else {
+  if (pl.variant != RT_VARIANT_POOLED) {
     RT_HIP(ctx, rtk::launch_persistent(p, false, pl.grid, pl.waves, ctx->stream));
     ctx->last_launch = "family=persistent";
+    return 0;
+  }
+  if (ps->n >= (int64_t(1) << 22)) return fail(ctx, "pooled kernel: at most 2^22 spheres (work items and hit keys carry the leaf index in 22 bits)");
+  if (p.rpt_log2 < 0) return fail(ctx, "pooled kernel: rows_per_tile must be a power of two");
+  if (int rc = get_uv(ctx, w, h, &p.u_tab, &p.v_tab)) return rc;
+  tick("uv tables");
+  TileOrder *to = nullptr;      // the view this frame belongs to (its record, its order, its pixel list)
+  if (ctx->adaptive_order && !p.cams)   // (a batch with its own cameras has no single view to order tiles by)
+    if (int rc = find_view(ctx, ps, p, pl, &to)) return rc;
+  Tickets t;
+  if (int rc = choose_tickets(ctx, ps, to, xq, tick, p, pl, &t)) return rc;
+  set_cull(ctx, ps, pl, cams_dev, &p);
+  tick("before launch");
+  RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream));
+  tick("launch_pooled");
+  char buf[256];
+  std::snprintf(buf, sizeof buf, "family=pooled tickets=%s%s instantiation=%s frames=%d tiles=%d grid=%d waves=%d counters=%d%s deep_class=%d deep_split=%d recording=%d",
+                p.px_hdr ? "pixel-list" : t.first_order ? "tiles-bit-reversed" : (p.order ? "tiles-ordered" : "tiles-raster"), t.borrowed ? "(borrowed)" : "",
+                pooled_launch_name(p, pl.waves).c_str(), p.nframes, p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "", p.px_hdr ? 0 : p.deep_class,
+                p.px_hdr ? 0 : p.deep_split, p.cost ? (p.cost_px ? 2 : 1) : 0);
+  ctx->last_launch = buf;
+  if (to && p.cost) {
+    // This frame recorded the view's bounce chains.  The sorts that turn the record into the view's tile order and pixel list are
+    // NOT launched here: a caller that never renders the view again (the reference's `render` keeps nothing between calls,
+    // ray.fut:246; a camera path rendered view by view) should not pay for them -- ~0.07 ms behind a 1000 x 1000 frame.  They run
+    // ahead of the view's next frame (sort_pending_record, above).
+    to->sort_pending = true;
+    to->sort_px = p.cost_px != nullptr;
+    to->rec_out_skip = p.out_skip;
+    // (eager_sort, the default: ... but they are LAUNCHED here, on the context's second stream, behind this frame: they run while the caller
+    // synchronises and sets up its next call, off every frame's critical path -- the view's second frame no longer carries them, and a
+    // new view can borrow this one's order at once)
+    if (ctx->eager_sort && (stream_was_idle || ctx->sync_policy))
+      if (int rc = sort_view(ctx, ps, to, p, pl)) return rc;
+    tick("record: eager sorts");
   }
   return 0;
 }
@@ -1650,47 +1706,25 @@ extern "C" int rt_render_trace(rt_context *ctx, const rt_prepared *ps, int64_t h
     (void)hipFree(trace);
     return hip_fail(ctx, em, "hipMemsetAsync(trace)");
   }
-  rtk::KParams p{};
-  p.nodes = ps->nodes; p.nodes64 = ps->nodes64; p.sph = ps->sph; p.col = ps->col;
-  std::copy(ps->root_lo, ps->root_lo + 3, p.root_lo);
-  std::copy(ps->root_hi, ps->root_hi + 3, p.root_hi);
-  p.n_nodes = static_cast<int>(ps->n - 1); p.n_sph = static_cast<int>(ps->n);
-  std::memcpy(&p.cam, &ps->cam, sizeof(p.cam));
-  p.w = static_cast<int>(w); p.h = static_cast<int>(h);
   // (diagnostic knobs trace_part / trace_nparts: the timeline of one part of the cyclic row-tile partition -- a band alone on the chip)
-  p.rows_per_tile = 8; p.part = ctx->trace_part; p.nparts = std::max(1, ctx->trace_nparts); p.rpt_log2 = 3;
-  if (p.part < 0 || p.part >= p.nparts) p.part = 0;
-  p.rows_local = static_cast<int>(rt::part_rows(h, 8, p.part, p.nparts));
-  p.tiles_x = (p.w + 7) / 8;
-  p.tiles_y = (p.rows_local + 7) / 8;
-  p.max_depth = max_depth;
+  const int nparts = std::max(1, ctx->trace_nparts), part = ctx->trace_part >= 0 && ctx->trace_part < nparts ? ctx->trace_part : 0;
+  rtk::KParams p{};
+  frame_params(ps, h, w, 8, part, nparts, max_depth, nullptr, &p);
   p.out = tmp;
-  p.nframes = 1;
   p.stats = ctx->stats_dev;
   p.trace = trace;
   p.queue = ctx->queue_dev;
-  p.nchunks = p.tiles_x * ((p.rows_local + 7) / 8);
+  p.nchunks = p.tiles_x * p.tiles_y;
   p.tpt_log2 = ctx->tpt_log2 >= 0 ? ctx->tpt_log2 : 0;
-  const int xq = ctx->xcd_queues < 0 ? 2 : ctx->xcd_queues;
-  p.nshards = (xq && pl.grid % rtk::kMaxShards == 0) ? rtk::kMaxShards : 1;
-  p.interleave = p.nshards > 1 && xq == 2;
-  p.static_first = ctx->static_first;
-  p.lds_nodes = pl.lds_nodes; p.lds_sph = pl.lds_sph;
-  p.smax = pl.smax; p.lmax = pl.lmax;
-  p.thr_shade = ctx->thr_shade; p.thr_leaf = ctx->thr_leaf;
-  p.capb = pl.capb; p.capl = pl.capl; p.ray_planes = pl.ray_planes;
-  p.prio_depth = ctx->prio_depth;
-  p.box2 = ctx->box2;
-  p.look_max = ctx->look_max > 0 ? ctx->look_max : (p.nchunks > 16384 ? 32 : 64);
-  p.tl_log2 = ps->tl_depth;
+  const int xq = xcd_rule(ctx, ps, pl, 1);
+  set_counters(&p, xq, pl.grid);
   hipError_t e = hipSuccess;
-  if (get_uv(ctx, w, h, &p.u_tab, &p.v_tab)) rc = 1;
+  if (pooled_shape_params(ctx, ps, pl, &p) || get_uv(ctx, w, h, &p.u_tab, &p.v_tab)) rc = 1;
   if (!rc) {
     // use the adaptive order of the matching view if one exists (a record nothing has sorted yet is sorted first: production would, ahead
     // of the view's next frame)
     for (auto &o : ps->orders)
-      if (o.h == h && o.w == w && o.part == p.part && o.nparts == p.nparts && o.max_depth == max_depth && o.rows_per_tile == 8 &&
-          std::memcmp(o.cam, &p.cam, sizeof o.cam) == 0 && ctx->adaptive_order && o.ntiles == p.nchunks && o.nshards == (p.interleave ? 1 : p.nshards)) {
+      if (same_shape(o, p) && std::memcmp(o.cam, &p.cam, sizeof o.cam) == 0 && ctx->adaptive_order) {
         if (sort_view(ctx, ps, &o, p, pl) || await_view(ctx, &o)) rc = 1;
         if (!o.valid) continue;
         p.order = o.order;
@@ -1699,12 +1733,8 @@ extern "C" int rt_render_trace(rt_context *ctx, const rt_prepared *ps, int64_t h
         p.deep_class = dp.deep_class;
         p.deep_split = dp.deep_split;
         p.deep_cap_log2 = dp.cap_log2;
-        if (dp.sparse && ctx->grid_div == 0) pl.grid = pl.grid_full;   // as enqueue_render launches this view
-        // ... through its pixel list when enqueue_render would (same conditions)
-        if (o.px_valid && pl.waves == 16 && ctx->adaptive_order == 1 && (p.nshards == 1 || p.interleave) &&
-            o.px_elems >= static_cast<size_t>(p.rows_local) * p.w && o.rows_per_tile == 8 &&
-            (ctx->pixel_order == 2 || (ctx->pixel_order == 1 && ctx->deep_class < 0 && max_depth > 4 && p.nchunks <= ctx->px_max_tiles &&
-                                       (p.nchunks >= 1024 || (pl.lds_nodes == p.n_nodes && pl.lds_sph == p.n_sph))))) {
+        if (dp.sparse && ctx->grid_div == 0) pl.grid = pl.grid_full;   // (the grid enqueue_render launches this view with; its counters stay)
+        if (px_list_launch(ctx, p, pl, &o)) {
           p.px_list = o.px_list;
           p.px_hdr = reinterpret_cast<const int *>(o.px_list + o.px_elems);
           p.px_hold = ctx->px_hold;
@@ -1713,19 +1743,11 @@ extern "C" int rt_render_trace(rt_context *ctx, const rt_prepared *ps, int64_t h
           // counts are then the frame's complete work --, unless trace_solo asks for the production path: solo_trace with its own cycle
           // counters, words 13 .. 15 of a wave's record)
           p.solo = (ctx->trace_solo && o.px_solo && ctx->solo && ps->tl_depth == rtk::kTreeletDepth) ? 1 : 0;
-          if (ctx->grid_div == 0 && pl.grid != pl.grid_full) {
-            const int ns = (xq && pl.grid_full % rtk::kMaxShards == 0) ? rtk::kMaxShards : 1;
-            const int il = ns > 1 && xq == 2;
-            if (ns == 1 || il) { pl.grid = pl.grid_full; p.nshards = ns; p.interleave = il; }
-          }
+          if (ctx->grid_div == 0 && pl.grid != pl.grid_full && counters_follow(&p, xq, pl.grid_full)) pl.grid = pl.grid_full;
         }
       }
     nw = pl.grid * pl.waves;
-    if (cull_allowed(ctx, ps, pl, p, nullptr, 1)) {   // as enqueue_render launches this view
-      p.cull = 1;
-      p.cull_c2 = ps->cull.c2;
-      p.cull_kappa = ps->cull.kappa;
-    }
+    set_cull(ctx, ps, pl, nullptr, &p);   // as enqueue_render launches this view
     e = rtk::launch_pooled(p, true, pl.grid, pl.waves, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) e = hipMemcpy(records, trace, sizeof(unsigned long long) * rtk::kTraceWords * static_cast<size_t>(nw), hipMemcpyDeviceToHost);
@@ -1808,10 +1830,7 @@ int ray_entry_params(rt_context *ctx, const rt_prepared *ps, int64_t n, const fl
   if (n < 0 || n >= (int64_t(1) << 31)) return fail(ctx, "ray count out of range: 0 <= n < 2^31");
   if (!rays_dev) return fail(ctx, "null rays pointer");
   *p = rtk::KParams{};
-  p->nodes = ps->nodes; p->nodes64 = ps->nodes64; p->sph = ps->sph; p->col = ps->col;
-  std::copy(ps->root_lo, ps->root_lo + 3, p->root_lo);
-  std::copy(ps->root_hi, ps->root_hi + 3, p->root_hi);
-  p->n_nodes = static_cast<int>(ps->n - 1); p->n_sph = static_cast<int>(ps->n);
+  scene_params(ps, p);
   p->rays = rays_dev;
   p->nrays = static_cast<int>(n);
   return 0;
@@ -1850,31 +1869,18 @@ int pooled_rays_params(rt_context *ctx, const rt_prepared *ps, const Plan &pl, r
   p.nchunks = static_cast<int>(nblocks);
   p.tpt_log2 = 0;
   // the eight counters take turns over the one raster queue (strips of tile columns are a 2D layout; the rays have none)
-  p.nshards = pl.grid % rtk::kMaxShards == 0 && ctx->xcd_queues != 0 ? rtk::kMaxShards : 1;
-  p.interleave = p.nshards > 1;
-  p.static_first = ctx->static_first;
-  p.lds_nodes = pl.lds_nodes; p.lds_sph = pl.lds_sph;
-  p.smax = pl.smax; p.lmax = pl.lmax;
-  p.thr_shade = ctx->thr_shade; p.thr_leaf = ctx->thr_leaf;
-  p.capb = pl.capb; p.capl = pl.capl; p.ray_planes = pl.ray_planes;
-  if (pl.spill_stride > 0) {
-    if (int rc = ensure_spill(ctx, pl.spill_stride)) return rc;
-    p.spill = ctx->spill_dev;
-    p.spill_stride = pl.spill_stride;
-  }
-  const bool twenty = pl.waves * (pl.grid_full / std::max(1, ctx->num_cu)) == 20;
-  p.prio_depth = ctx->prio_depth;
-  p.box2 = ctx->box2;
-  p.look_max = ctx->look_max > 0 ? ctx->look_max : (twenty ? 16 : p.nchunks > 16384 ? 32 : 64);
-  p.tl_log2 = ps->tl_depth;
-  return 0;
+  set_counters(&p, ctx->xcd_queues != 0 ? 2 : 0, pl.grid);
+  return pooled_shape_params(ctx, ps, pl, &p);
 }
 
-void pooled_rays_launch_record(rt_context *ctx, const char *instantiation, const rtk::KParams &p, const Plan &pl) {
+// The launch of the pooled family's loop on caller rays (`rays`: kRaysColour, kRaysAny), and its rt_context_last_launch
+int launch_pooled_rays(rt_context *ctx, const rtk::KParams &p, const Plan &pl, int rays) {
+  RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream, rays));
   char buf[256];
-  std::snprintf(buf, sizeof buf, "family=pooled tickets=rays instantiation=%s%s frames=1 tiles=%d grid=%d waves=%d counters=%d%s deep_class=0 deep_split=0 recording=0",
-                instantiation, p.spill ? "+SPILL" : "", p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "");
+  std::snprintf(buf, sizeof buf, "family=pooled tickets=rays instantiation=%s frames=1 tiles=%d grid=%d waves=%d counters=%d%s deep_class=0 deep_split=0 recording=0",
+                pooled_launch_name(p, pl.waves, rays).c_str(), p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "");
   ctx->last_launch = buf;
+  return 0;
 }
 }  // namespace
 
@@ -1914,9 +1920,7 @@ extern "C" int rt_trace_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, 
     return 0;
   }
   if (int rc = pooled_rays_params(ctx, ps, pl, &p)) return rc;
-  RT_HIP(ctx, rtk::launch_pooled_rays(p, pl.grid, pl.waves, ctx->stream));
-  pooled_rays_launch_record(ctx, "plain", p, pl);
-  return 0;
+  return launch_pooled_rays(ctx, p, pl, rtk::kRaysColour);
 }
 
 extern "C" int rt_intersect_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
@@ -1973,9 +1977,7 @@ extern "C" int rt_occluded_rays(rt_context *ctx, const rt_prepared *ps, int64_t 
     return 0;
   }
   if (int rc = pooled_rays_params(ctx, ps, pl, &p)) return rc;
-  RT_HIP(ctx, rtk::launch_pooled_occluded(p, pl.grid, pl.waves, ctx->stream));
-  pooled_rays_launch_record(ctx, "any", p, pl);
-  return 0;
+  return launch_pooled_rays(ctx, p, pl, rtk::kRaysAny);
 }
 
 extern "C" int rt_camera_rays(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, const float cam12[12], float *rays_dev) {

@@ -21,6 +21,7 @@
 
 #include <mutex>
 #include <type_traits>
+#include <utility>
 
 #include "lane_core.h"
 #include "rt_device.hpp"
@@ -396,9 +397,8 @@ __global__ __launch_bounds__(THREADS) void persistent_kernel(KParams p) {
 // ---------------------------------------------------------------------------------
 constexpr int kOrderClasses = 8;   // cost classes of the adaptive tile order (tile_order_kernel)
 constexpr unsigned long long kKeyInit = ((unsigned long long)0x4e6e6b28u << 32) | 0xffffffffull;   // (1e9, no leaf)
-// pooled_kernel's RAYS mode: 0 the render path's pixels, kRaysColour rt_trace_rays, kRaysAny rt_occluded_rays; in the any-hit mode a slot's
-// key is kKeyAnyHit once one of its spheres is accepted (its high word, read as the boxes' upper end, then empties their interval)
-constexpr int kRaysColour = 1, kRaysAny = 2;
+// pooled_kernel's RAYS mode (rt_device.hpp: kRaysColour, kRaysAny): in the any-hit mode a slot's key is kKeyAnyHit once one of its spheres
+// is accepted (its high word, read as the boxes' upper end, then empties their interval)
 constexpr unsigned long long kKeyAnyHit = 0ull;
 
 __device__ __forceinline__ float pull(int lane_byte, float v) {   // v of the lane at byte address lane_byte (ds_bpermute)
@@ -1875,73 +1875,36 @@ size_t pooled_lds_bytes(int lds_nodes, int lds_sph, int capb, int capl, int ray_
   return (size_t)lds_nodes * 64 + (size_t)lds_sph * 16 + (size_t)waves_per_wg * pooled_wave_dw(ray_planes, capb, capl) * sizeof(unsigned);
 }
 
-template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO = false, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, int RAYS = 0>
+// pooled_kernel with the template arguments kPooledKeys[I]
+template <int I>
+static auto pooled_fn() {
+  constexpr const PooledKey &k = kPooledKeys[I];
+  return pooled_kernel<k.threads, k.all_lds, k.stats, k.solo, k.tail, k.ord, k.cull, k.spill, k.rays>;
+}
+
+template <int I>
 static hipError_t launch_pooled_t(const KParams &p, int grid, hipStream_t stream) {
-  const size_t lds = pooled_lds_bytes(p.lds_nodes, p.lds_sph, p.capb, p.capl, p.ray_planes, THREADS / 64);
-  auto kfn = pooled_kernel<THREADS, ALL_LDS, STATS, SOLO, TAIL, ORD, CULL, SPILL, RAYS>;
+  constexpr int threads = kPooledKeys[I].threads;
+  const size_t lds = pooled_lds_bytes(p.lds_nodes, p.lds_sph, p.capb, p.capl, p.ray_planes, threads / 64);
+  auto kfn = pooled_fn<I>();
   if (hipError_t e = allow_full_lds(reinterpret_cast<const void *>(kfn)); e != hipSuccess) return e;
-  hipLaunchKernelGGL(kfn, dim3(grid), dim3(THREADS), lds, stream, p);
+  hipLaunchKernelGGL(kfn, dim3(grid), dim3(threads), lds, stream, p);
   return hipGetLastError();
 }
 
-// The workgroups of 16 waves: every flavour, with and without CULL (a CULL launch always takes the general scene path: ALL_LDS is
-// an instantiation of the un-culled kernel only).
-template <bool STATS, bool SOLO, int TAIL, bool ORD>
-static hipError_t launch_pooled_16(const KParams &p, bool all_lds, int grid, hipStream_t stream) {
-  if (p.cull) return launch_pooled_t<1024, false, STATS, SOLO, TAIL, ORD, true>(p, grid, stream);
-  if constexpr (!STATS)
-    if (all_lds) return launch_pooled_t<1024, true, STATS, SOLO, TAIL, ORD>(p, grid, stream);
-  return launch_pooled_t<1024, false, STATS, SOLO, TAIL, ORD>(p, grid, stream);
+template <int... I>
+static hipError_t launch_pooled_key(const PooledKey &k, const KParams &p, int grid, hipStream_t stream, std::integer_sequence<int, I...>) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)((kPooledKeys[I] == k && ((e = launch_pooled_t<I>(p, grid, stream)), true)) || ...);
+  return e;
 }
 
-// (p.cull is honoured by the workgroups of 16 waves -- what every scene within the pooled kernel's limits runs with unless an option
-// says otherwise; api.cpp clears it for the other shapes)
-hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream) {
-  if (grid <= 0) return hipSuccess;
-  const bool all_lds = p.lds_nodes == p.n_nodes && p.lds_sph == p.n_sph;
-  if (p.cull && waves_per_wg != 16 && waves_per_wg != 4) return hipErrorInvalidValue;
-  // (workgroups of four waves, CULL: the plain kernel -- batches and large frames in the shape of five workgroups per CU, api.cpp: make_plan;
-  // p.spill: that shape for a tree taller than 15 levels -- the kernels whose box stack may overflow into device memory)
-  if (p.spill != nullptr) {
-    if (waves_per_wg != 4 || stats || p.px_hdr != nullptr || (p.capb != kSpillCapb && p.capb != kSpillCapbTest)) return hipErrorInvalidValue;
-    if (p.capb == kSpillCapbTest)
-      return p.cull ? launch_pooled_t<256, false, false, false, 0, false, true, kSpillCapbTest - 64>(p, grid, stream) : launch_pooled_t<256, false, false, false, 0, false, false, kSpillCapbTest - 64>(p, grid, stream);
-    return p.cull ? launch_pooled_t<256, false, false, false, 0, false, true, kSpillCapb - 64>(p, grid, stream) : launch_pooled_t<256, false, false, false, 0, false, false, kSpillCapb - 64>(p, grid, stream);
-  }
-  if (p.cull && waves_per_wg == 4) {
-    if (stats || p.px_hdr != nullptr) return hipErrorInvalidValue;
-    return launch_pooled_t<256, false, false, false, 0, false, true>(p, grid, stream);
-  }
-  if (stats && p.px_hdr != nullptr && waves_per_wg == 16)   // (the instrumented launch of a view that renders through its pixel list)
-    return p.solo ? launch_pooled_16<true, true, 0, true>(p, all_lds, grid, stream) : launch_pooled_16<true, false, 0, true>(p, all_lds, grid, stream);
-  if (stats) return waves_per_wg == 16 ? launch_pooled_16<true, false, 0, false>(p, all_lds, grid, stream) : launch_pooled_t<512, false, true>(p, grid, stream);
-  // (SOLO: the instantiation with the solo prologue, for launches whose first tickets are single pixels)
-  const bool solo = p.solo && p.nframes == 1 && p.order != nullptr && p.deep_class > 0 && p.deep_split == 6 && p.tl_log2 == kTreeletDepth;
-  // (ORD: pixel tickets; workgroups of 16 waves only)
-  if (p.px_hdr != nullptr) {
-    if (waves_per_wg != 16 || p.nframes != 1) return hipErrorInvalidValue;
-    // (p.solo clear: a list without a one-pixel class; p.donate: with the DONATE tail -- a list borrowed from another view)
-    if (p.donate) return p.solo ? launch_pooled_16<false, true, 2, true>(p, all_lds, grid, stream) : launch_pooled_16<false, false, 2, true>(p, all_lds, grid, stream);
-    return p.solo ? launch_pooled_16<false, true, 0, true>(p, all_lds, grid, stream) : launch_pooled_16<false, false, 0, true>(p, all_lds, grid, stream);
-  }
-  // (COLD: small ordered single frames; DONATE: the first frame of a view; workgroups of 16 waves only -- other shapes render them with the ordinary kernels)
-  if (p.cold && waves_per_wg == 16)
-    return solo ? launch_pooled_16<false, true, 1, false>(p, all_lds, grid, stream) : launch_pooled_16<false, false, 1, false>(p, all_lds, grid, stream);
-  if (p.donate && waves_per_wg == 16)
-    return solo ? launch_pooled_16<false, true, 2, false>(p, all_lds, grid, stream) : launch_pooled_16<false, false, 2, false>(p, all_lds, grid, stream);
-  if (waves_per_wg == 16)
-    return solo ? launch_pooled_16<false, true, 0, false>(p, all_lds, grid, stream) : launch_pooled_16<false, false, 0, false>(p, all_lds, grid, stream);
-#define RT_POOLED_CASE(W)                                                                                               \
-  case W:                                                                                                               \
-    return all_lds ? (solo ? launch_pooled_t<64 * W, true, false, true>(p, grid, stream) : launch_pooled_t<64 * W, true, false>(p, grid, stream)) \
-                   : (solo ? launch_pooled_t<64 * W, false, false, true>(p, grid, stream) : launch_pooled_t<64 * W, false, false>(p, grid, stream));
-  switch (waves_per_wg) {
-    RT_POOLED_CASE(4)
-    RT_POOLED_CASE(8)
-    RT_POOLED_CASE(12)
-  default: return hipErrorInvalidValue;
-  }
-#undef RT_POOLED_CASE
+hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays) {
+  if (rays == kRaysAny && p.occluded == nullptr) return hipErrorInvalidValue;
+  if (grid <= 0 || (rays && p.nrays <= 0)) return hipSuccess;
+  PooledKey k;
+  if (!choose_pooled(p, stats, waves_per_wg, rays, &k)) return hipErrorInvalidValue;
+  return launch_pooled_key(k, p, grid, stream, std::make_integer_sequence<int, kNumPooledKeys>{});
 }
 
 // ---------------------------------------------------------------------------------
@@ -1951,35 +1914,6 @@ hipError_t launch_pixel_rays(const KParams &p, hipStream_t stream) {
   if (p.nrays <= 0) return hipSuccess;
   hipLaunchKernelGGL((pixel_kernel<false, true>), dim3((unsigned)((p.nrays + 63) / 64)), dim3(64), 0, stream, p);
   return hipGetLastError();
-}
-
-// The plain pooled loop with the RAYS source, in the shapes make_plan picks for a frame of as many 64-ray blocks: workgroups of 16
-// waves (whole scene in LDS or not), or the twenty-wave shape of four-wave workgroups, with the spilling box stack for tall trees.
-// MODE: kRaysColour (rt_trace_rays) or kRaysAny (rt_occluded_rays).
-template <int MODE>
-static hipError_t launch_pooled_rays_t(const KParams &p, int grid, int waves_per_wg, hipStream_t stream) {
-  if (grid <= 0 || p.nrays <= 0) return hipSuccess;
-  if (p.cull || p.px_hdr != nullptr || p.order != nullptr || p.nframes != 1) return hipErrorInvalidValue;
-  const bool all_lds = p.lds_nodes == p.n_nodes && p.lds_sph == p.n_sph;
-  if (p.spill != nullptr) {
-    if (waves_per_wg != 4) return hipErrorInvalidValue;
-    if (p.capb == kSpillCapbTest) return launch_pooled_t<256, false, false, false, 0, false, false, kSpillCapbTest - 64, MODE>(p, grid, stream);
-    if (p.capb == kSpillCapb) return launch_pooled_t<256, false, false, false, 0, false, false, kSpillCapb - 64, MODE>(p, grid, stream);
-    return hipErrorInvalidValue;
-  }
-  switch (waves_per_wg) {
-  case 16: return all_lds ? launch_pooled_t<1024, true, false, false, 0, false, false, 0, MODE>(p, grid, stream)
-                          : launch_pooled_t<1024, false, false, false, 0, false, false, 0, MODE>(p, grid, stream);
-  case 4: return launch_pooled_t<256, false, false, false, 0, false, false, 0, MODE>(p, grid, stream);
-  default: return hipErrorInvalidValue;
-  }
-}
-hipError_t launch_pooled_rays(const KParams &p, int grid, int waves_per_wg, hipStream_t stream) {
-  return launch_pooled_rays_t<kRaysColour>(p, grid, waves_per_wg, stream);
-}
-hipError_t launch_pooled_occluded(const KParams &p, int grid, int waves_per_wg, hipStream_t stream) {
-  if (p.occluded == nullptr) return hipErrorInvalidValue;
-  return launch_pooled_rays_t<kRaysAny>(p, grid, waves_per_wg, stream);
 }
 
 // objs_hit bvh r t_min t_max (ray.fut:76-86), one lane per ray: the pixel family's stack fold with the caller's interval on every box,
@@ -2116,44 +2050,15 @@ hipError_t warm_scratch(hipStream_t stream, int *sink_dev) {
   hipLaunchKernelGGL(scratch_warm_kernel, dim3(cus * 32), dim3(64), 0, stream, sink_dev, 1);
   return hipGetLastError();
 }
-void warm_render_kernels() {
+template <int... I>
+static void warm_pooled(std::integer_sequence<int, I...>) {
   hipFuncAttributes a;
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, true, false, false>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, false>);
-  // (the instantiations a view's first frames and its policy may switch to: a first use inside somebody's timed loop is 0.2-0.3 ms)
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, true, false, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, true, false, false, 1>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, false, 1>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, true, false, false, 2>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, false, 2>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, true, false, true, 2>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, true, 2>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, true, false, true, 1>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, true, 1>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, true, false, true, 0, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, true, 0, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, true, false, false, 0, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, false, 0, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, true, false, true, 2, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, true, 2, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, true, false, false, 2, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, false, 2, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<256, false, false, false>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<256, false, false, false, 0, false, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<256, false, false, false, 0, false, false, kSpillCapb - 64>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<256, false, false, false, 0, false, true, kSpillCapb - 64>);
-  // ... and their CULL flavours
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, false, 2, true, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, true, 2, true, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, false, 0, false, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, true, 0, false, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, false, 1, false, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, true, 1, false, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, false, 2, false, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, true, 2, false, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, false, 0, true, true>);
-  (void)hipFuncGetAttributes(&a, (const void *)pooled_kernel<1024, false, false, true, 0, true, true>);
+  ((void)(pooled_warmed(kPooledKeys[I]) && hipFuncGetAttributes(&a, reinterpret_cast<const void *>(pooled_fn<I>())) == hipSuccess), ...);
+}
+void warm_render_kernels() {
+  // (the pooled instantiations a view's first frames and its policy may switch to: a first use inside somebody's timed loop is 0.2-0.3 ms)
+  warm_pooled(std::make_integer_sequence<int, kNumPooledKeys>{});
+  hipFuncAttributes a;
   (void)hipFuncGetAttributes(&a, (const void *)px_count_kernel);
   (void)hipFuncGetAttributes(&a, (const void *)px_scan_kernel);
   (void)hipFuncGetAttributes(&a, (const void *)px_place_kernel);

@@ -3,7 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
 #include "lane_core.h"
+#include "treelet.h"
 
 namespace rtk {
 
@@ -277,14 +280,115 @@ struct KParams {
   float ray_tlo, ray_thi;
 };
 
+// ---- the pooled kernel's instantiations ----------------------------------------------------------
+// pooled_kernel's RAYS mode: 0 the render path's pixels, kRaysColour rt_trace_rays, kRaysAny rt_occluded_rays
+constexpr int kRaysColour = 1, kRaysAny = 2;
+// The template arguments of one pooled_kernel instantiation: pooled_kernel<threads, all_lds, stats, solo, tail, ord, cull, spill, rays>
+struct PooledKey {
+  int threads;
+  bool all_lds, stats, solo;
+  int tail;      // 1: COLD, 2: DONATE
+  bool ord, cull;
+  int spill;     // the LDS box stack's capacity minus 64 (kSpillCapb, kSpillCapbTest), or 0
+  int rays;
+  constexpr bool operator==(const PooledKey &o) const {
+    return threads == o.threads && all_lds == o.all_lds && stats == o.stats && solo == o.solo && tail == o.tail && ord == o.ord && cull == o.cull &&
+           spill == o.spill && rays == o.rays;
+  }
+};
+// Every compiled instantiation (render_kernels.hip launches these and no others).  Abbreviations: T / F for true / false.
+namespace pooled_keys {
+constexpr bool T = true, F = false;
+constexpr int SP = kSpillCapb - 64, ST = kSpillCapbTest - 64, RC = kRaysColour, RA = kRaysAny;
+constexpr PooledKey kPooledKeys[] = {
+    // workgroups of 16 waves: each flavour on the scene wholly in LDS, in general, and with CULL (the general scene path only)
+    {1024, T, F, F, 0, F, F, 0, 0}, {1024, F, F, F, 0, F, F, 0, 0}, {1024, F, F, F, 0, F, T, 0, 0},   // plain
+    {1024, T, F, T, 0, F, F, 0, 0}, {1024, F, F, T, 0, F, F, 0, 0}, {1024, F, F, T, 0, F, T, 0, 0},   // SOLO
+    {1024, T, F, F, 1, F, F, 0, 0}, {1024, F, F, F, 1, F, F, 0, 0}, {1024, F, F, F, 1, F, T, 0, 0},   // COLD
+    {1024, T, F, T, 1, F, F, 0, 0}, {1024, F, F, T, 1, F, F, 0, 0}, {1024, F, F, T, 1, F, T, 0, 0},   // COLD+SOLO
+    {1024, T, F, F, 2, F, F, 0, 0}, {1024, F, F, F, 2, F, F, 0, 0}, {1024, F, F, F, 2, F, T, 0, 0},   // DONATE
+    {1024, T, F, T, 2, F, F, 0, 0}, {1024, F, F, T, 2, F, F, 0, 0}, {1024, F, F, T, 2, F, T, 0, 0},   // DONATE+SOLO
+    {1024, T, F, F, 0, T, F, 0, 0}, {1024, F, F, F, 0, T, F, 0, 0}, {1024, F, F, F, 0, T, T, 0, 0},   // ORD
+    {1024, T, F, T, 0, T, F, 0, 0}, {1024, F, F, T, 0, T, F, 0, 0}, {1024, F, F, T, 0, T, T, 0, 0},   // ORD+SOLO
+    {1024, T, F, F, 2, T, F, 0, 0}, {1024, F, F, F, 2, T, F, 0, 0}, {1024, F, F, F, 2, T, T, 0, 0},   // ORD+DONATE
+    {1024, T, F, T, 2, T, F, 0, 0}, {1024, F, F, T, 2, T, F, 0, 0}, {1024, F, F, T, 2, T, T, 0, 0},   // ORD+SOLO+DONATE
+    // ... instrumented (rt_render_trace)
+    {1024, F, T, F, 0, F, F, 0, 0}, {1024, F, T, F, 0, F, T, 0, 0}, {1024, F, T, F, 0, T, F, 0, 0}, {1024, F, T, F, 0, T, T, 0, 0},
+    {1024, F, T, T, 0, T, F, 0, 0}, {1024, F, T, T, 0, T, T, 0, 0}, {512, F, T, F, 0, F, F, 0, 0},
+    // workgroups of 4, 8 and 12 waves
+    {256, T, F, F, 0, F, F, 0, 0}, {256, F, F, F, 0, F, F, 0, 0}, {256, T, F, T, 0, F, F, 0, 0}, {256, F, F, T, 0, F, F, 0, 0},
+    {512, T, F, F, 0, F, F, 0, 0}, {512, F, F, F, 0, F, F, 0, 0}, {512, T, F, T, 0, F, F, 0, 0}, {512, F, F, T, 0, F, F, 0, 0},
+    {768, T, F, F, 0, F, F, 0, 0}, {768, F, F, F, 0, F, F, 0, 0}, {768, T, F, T, 0, F, F, 0, 0}, {768, F, F, T, 0, F, F, 0, 0},
+    // four waves: CULL, and the SPILL kernels for trees taller than 15 levels (production and stack_cap capacity)
+    {256, F, F, F, 0, F, T, 0, 0}, {256, F, F, F, 0, F, F, SP, 0}, {256, F, F, F, 0, F, T, SP, 0}, {256, F, F, F, 0, F, F, ST, 0}, {256, F, F, F, 0, F, T, ST, 0},
+    // caller rays: 16 waves (scene in LDS or not), 4 waves, SPILL
+    {1024, T, F, F, 0, F, F, 0, RC}, {1024, F, F, F, 0, F, F, 0, RC}, {256, F, F, F, 0, F, F, 0, RC}, {256, F, F, F, 0, F, F, SP, RC}, {256, F, F, F, 0, F, F, ST, RC},
+    {1024, T, F, F, 0, F, F, 0, RA}, {1024, F, F, F, 0, F, F, 0, RA}, {256, F, F, F, 0, F, F, 0, RA}, {256, F, F, F, 0, F, F, SP, RA}, {256, F, F, F, 0, F, F, ST, RA},
+};
+}  // namespace pooled_keys
+using pooled_keys::kPooledKeys;
+constexpr int kNumPooledKeys = sizeof(kPooledKeys) / sizeof(kPooledKeys[0]);
+// What warm_render_kernels resolves at context creation: the instantiations a single-GPU render may switch to between a view's frames --
+// workgroups of 16 waves, and the four-wave plain / CULL / SPILL kernels of the twenty-wave shape
+constexpr bool pooled_warmed(const PooledKey &k) {
+  return !k.stats && k.rays == 0 && (k.threads == 1024 || (k.threads == 256 && !k.all_lds && !k.solo && k.spill != kSpillCapbTest - 64));
+}
+
+// Which instantiation renders a launch with these parameters (false: none -- hipErrorInvalidValue).  `rays`: 0, kRaysColour, kRaysAny.
+// No HIP runtime calls: the CPU check tools/pooled_choice_check.cpp runs it over its inputs.
+inline bool choose_pooled(const KParams &p, bool stats, int waves_per_wg, int rays, PooledKey *out) {
+  const bool all_lds = p.lds_nodes == p.n_nodes && p.lds_sph == p.n_sph;
+  PooledKey k{64 * waves_per_wg, false, stats, false, 0, false, p.cull != 0, 0, rays};
+  if (rays && (stats || p.cull || p.px_hdr != nullptr || p.order != nullptr || p.nframes != 1)) return false;
+  if (p.cull && waves_per_wg != 16 && waves_per_wg != 4) return false;
+  if (p.spill != nullptr) {
+    // (workgroups of four waves, for a tree taller than 15 levels: the kernels whose box stack may overflow into device memory)
+    if (waves_per_wg != 4 || stats || p.px_hdr != nullptr || (p.capb != kSpillCapb && p.capb != kSpillCapbTest)) return false;
+    k.spill = p.capb - 64;
+  } else if (p.cull && waves_per_wg == 4) {
+    // (workgroups of four waves, CULL: the plain kernel -- batches and large frames in the shape of five workgroups per CU, api.cpp: make_plan)
+    if (stats || p.px_hdr != nullptr) return false;
+  } else if (rays) {
+    if (waves_per_wg != 16 && waves_per_wg != 4) return false;
+    k.all_lds = waves_per_wg == 16 && all_lds;
+  } else if (stats) {
+    // (the instrumented launch: no ALL_LDS; ORD for a view that renders through its pixel list; other shapes than 16 waves take 8)
+    if (waves_per_wg != 16) k.threads = 512;
+    else if (p.px_hdr != nullptr) { k.ord = true; k.solo = p.solo != 0; }
+  } else if (p.px_hdr != nullptr) {
+    // (ORD: pixel tickets, workgroups of 16 waves only; p.solo clear: a list without a one-pixel class; p.donate: with the DONATE tail --
+    // a list borrowed from another view)
+    if (waves_per_wg != 16 || p.nframes != 1) return false;
+    k.ord = true; k.solo = p.solo != 0; k.tail = p.donate ? 2 : 0;
+    k.all_lds = all_lds && !k.cull;
+  } else {
+    // (SOLO: the instantiation with the solo prologue, for launches whose first tickets are single pixels.  COLD: small ordered single frames;
+    // DONATE: the first frame of a view; workgroups of 16 waves only -- other shapes render them with the ordinary kernels)
+    k.solo = p.solo && p.nframes == 1 && p.order != nullptr && p.deep_class > 0 && p.deep_split == 6 && p.tl_log2 == kTreeletDepth;
+    if (waves_per_wg == 16) k.tail = p.cold ? 1 : p.donate ? 2 : 0;
+    else if (waves_per_wg != 4 && waves_per_wg != 8 && waves_per_wg != 12) return false;
+    k.all_lds = all_lds && !k.cull;
+  }
+  *out = k;
+  return true;
+}
+
+// The instantiation's name in rt_context_last_launch: plain, SOLO, COLD, COLD+SOLO, DONATE, DONATE+SOLO, ORD, ORD+SOLO, ORD+DONATE, ORD+SOLO+DONATE,
+// any (the occlusion loop); then +CULL, +SPILL
+inline std::string pooled_name(const PooledKey &k) {
+  std::string s = k.rays == kRaysAny ? "any" : k.ord ? "ORD" : k.tail == 1 ? "COLD" : k.tail == 2 ? "DONATE" : "";
+  if (k.solo) s += s.empty() ? "SOLO" : "+SOLO";
+  if (k.ord && k.tail == 2) s += "+DONATE";
+  if (s.empty()) s = "plain";
+  if (k.cull) s += "+CULL";
+  if (k.spill) s += "+SPILL";
+  return s;
+}
+
 hipError_t launch_pixel(const KParams &p, bool stats, hipStream_t stream);
-// caller rays (render_kernels.hip): ray_colour of p.nrays rays, one lane per ray (the pixel family) ...
+// caller rays (render_kernels.hip): ray_colour of p.nrays rays, one lane per ray (the pixel family); rt_occluded_rays's lane kernel, each
+// lane leaving its traversal at its first accepted sphere
 hipError_t launch_pixel_rays(const KParams &p, hipStream_t stream);
-// ... or in the pooled family's plain loop, 64 consecutive rays per ticket (grid / waves_per_wg as make_plan says; p.spill: the SPILL shape)
-hipError_t launch_pooled_rays(const KParams &p, int grid, int waves_per_wg, hipStream_t stream);
-// occlusion of p.nrays rays over (p.ray_tlo, p.ray_thi) into p.occluded: the pooled family's any-hit loop (same shapes as launch_pooled_rays) ...
-hipError_t launch_pooled_occluded(const KParams &p, int grid, int waves_per_wg, hipStream_t stream);
-// ... or one lane per ray, each leaving its traversal at its first accepted sphere
 hipError_t launch_occluded_rays(const KParams &p, hipStream_t stream);
 // objs_hit bvh r t_min t_max of n rays (ray.fut:76-86): index[i] = the winning leaf or -1, hit7 (may be nullptr) = {t, p.xyz, normal.xyz}
 hipError_t launch_intersect_rays(const KParams &p, float t_min, float t_max, int32_t *index, float *hit7, hipStream_t stream);
@@ -293,7 +397,9 @@ hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStre
 // block = 64 * waves_per_wg threads (4, 8 or 16 waves); grid = persistent workgroups
 hipError_t launch_persistent(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream);
 size_t persistent_lds_bytes(int lds_nodes, int lds_sph, int smax, int lmax, int waves_per_wg);
-hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream);
+// the pooled family: the instantiation choose_pooled picks (grid workgroups of 64 * waves_per_wg threads).  `rays`: 64 consecutive caller rays
+// per ticket (the plain loop; kRaysAny: occlusion of p.nrays rays over (p.ray_tlo, p.ray_thi) into p.occluded)
+hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays = 0);
 size_t pooled_lds_bytes(int lds_nodes, int lds_sph, int capb, int capl, int ray_planes, int waves_per_wg);
 // prepare_scene on the GPU (bvh_build.hip).  Canonical {L, I} arrays + the traversal copy.
 struct GpuBvhOut {

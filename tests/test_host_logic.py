@@ -120,6 +120,17 @@ def test_tile_queue_protocol_on_the_cpu():
         assert "random cases" in out.stdout and "passed" in out.stdout
 
 
+def test_pooled_instantiation_choice_on_the_cpu():
+    """tools/pooled_choice_check runs rtk::choose_pooled (rt_device.hpp: which pooled_kernel instantiation a launch takes, and its name in
+    rt_context_last_launch) over the cross product of the parameters it reads: every accepted launch is a compiled instantiation, every
+    compiled one is reachable, warm_render_kernels resolves the same 34, and the names are the ones the GPU tests and tools read."""
+    exe = os.path.join(ROOT, "build", "pooled_choice_check")
+    subprocess.run(["make", "-s", "build/pooled_choice_check"], cwd=ROOT, check=True)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "passed" in out.stdout, out.stdout + out.stderr
+    assert "64 instantiations all reachable, 34 warmed, 24 names" in out.stdout, out.stdout
+
+
 def test_ray_donation_protocol_on_the_cpu():
     """tools/donate_check plays the mailbox protocol of the pooled kernel's DONATE instantiation (waves that have left the
     loop offer themselves in a workgroup word; waves that cannot refill give them one ray each through their idle ray
