@@ -72,10 +72,12 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *   "family=none (memset)"        max_depth == 0: every pixel is the initial colour, no kernel
  *   "family=none (no rays)"       a caller-ray entry with n == 0
  *   "family=pixel (rays)" | "family=intersect" | "family=occluded" | "family=camera-rays"   the caller-ray entries (below)
+ *   "family=intersect (per-ray)" | "family=occluded (per-ray)"   their lane kernels with per-ray intervals (rt_*_rays_ranged)
  *   "family=none (no rows)"       the part owns no row of the image
  *   "family=pixel" | "family=pixel (instrumented)" | "family=persistent"
  *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2"
- *     T = rays (rt_trace_rays: blocks of 64 caller rays, instantiation plain[+SPILL]; rt_occluded_rays: instantiation any[+SPILL]) | pixel-list | tiles-ordered | tiles-bit-reversed (a view's first frame with nothing to borrow, first_order = 1) | tiles-raster,
+ *     T = rays (rt_trace_rays: blocks of 64 caller rays, instantiation plain[+SPILL]; rt_occluded_rays: instantiation any[+SPILL]; rt_occluded_rays_ranged:
+ *         the same, with " intervals=per-ray" appended to the string) | pixel-list | tiles-ordered | tiles-bit-reversed (a view's first frame with nothing to borrow, first_order = 1) | tiles-raster,
  *         followed by "(borrowed)" when the order / list is another view's (a new view of a prepared scene that has rendered a view of the same shape)
  *     I = plain | SOLO | COLD | COLD+SOLO | DONATE | DONATE+SOLO | ORD | ORD+SOLO | ORD+DONATE | ORD+SOLO+DONATE;  +CULL: boxes tested against the best hit so far; +SPILL: a box stack that may overflow into device memory (twenty waves per CU, trees taller than 15 levels)
  *     recording: 0 nothing, 1 the tiles' longest chains, 2 also every pixel's chain length */
@@ -235,6 +237,22 @@ int rt_intersect_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const f
  * staged in LDS and t_max > 1, where it was measured faster; otherwise (and beyond the pooled family's limits) the lane kernel. */
 int rt_occluded_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
                      uint8_t *occluded_dev);
+/* The same two queries with an interval per ray: t_min_dev and t_max_dev are n float32 each in the context's device memory, and
+ * ray i gets exactly what rt_intersect_rays / rt_occluded_rays give it alone at (t_min_dev[i], t_max_dev[i]), bit for bit, under
+ * every variant and launch shape.  The intervals are device data and are not read back: a ray whose interval fails
+ * 0 <= t_min <= t_max <= 1e9 (NaN, +-inf and t_min > t_max included) is answered as a miss -- index -1 and seven zero floats,
+ * occluded 0 -- and its walk does not start.  -0.0 behaves as 0.0.  Refused as the scalar entries are (n out of range, NULL rays
+ * or output pointer, a multi-device context), and for a NULL t_min_dev or t_max_dev.
+ * rt_intersect_rays_ranged: one lane per ray ("family=intersect (per-ray)").
+ * rt_occluded_rays_ranged: the pooled family's any-hit loop in its per-ray mode under RT_VARIANT_POOLED ("family=pooled tickets=rays
+ * instantiation=any[+SPILL] ... intervals=per-ray"), the lane kernel ("family=occluded (per-ray)") under RT_VARIANT_PIXEL /
+ * RT_VARIANT_PERSISTENT.  RT_VARIANT_AUTO: the lane kernel (the host cannot see t_max; measured).
+ * Raising t_min is NOT depth peeling: objs_hit folds the spheres over (scene_epsilon, best) whatever t_min is, so a sphere nearer
+ * than t_min still wins the fold (and then fails its re-intersection: #none) -- it does not skip to the next sphere. */
+int rt_intersect_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *t_min_dev,
+                             const float *t_max_dev, int32_t *index_dev, float *hit7_dev);
+int rt_occluded_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *t_min_dev,
+                            const float *t_max_dev, uint8_t *occluded_dev);
 /* The primary rays rt_render_image would trace (get_ray at pixel_u / pixel_v), row-major from the top row: h * w x 6
  * float32 at rays_dev.  cam12 == NULL: the prepared camera.  rt_context_last_launch: "family=camera-rays". */
 int rt_camera_rays(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, const float cam12[12], float *rays_dev);

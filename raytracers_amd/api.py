@@ -396,6 +396,22 @@ def occluded_rays_into(rays_ptr, n, prepared, out_ptr, t_min=0.0, t_max=1e9):
                                     C.c_void_p(out_ptr)))
 
 
+def intersect_rays_ranged_into(rays_ptr, n, prepared, t_min_ptr, t_max_ptr, index_ptr, hit_ptr=None):
+    """intersect_rays_into with ray i's own interval (t_min_ptr[i], t_max_ptr[i]): n float32 each at device pointers
+    (rt_intersect_rays_ranged).  A ray whose interval fails 0 <= t_min <= t_max <= 1e9 (NaN included) is a miss."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_intersect_rays_ranged(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), C.c_void_p(t_min_ptr), C.c_void_p(t_max_ptr),
+                                            C.c_void_p(index_ptr), C.c_void_p(hit_ptr)))
+
+
+def occluded_rays_ranged_into(rays_ptr, n, prepared, t_min_ptr, t_max_ptr, out_ptr):
+    """occluded_rays_into with ray i's own interval (t_min_ptr[i], t_max_ptr[i]) (rt_occluded_rays_ranged); an invalid interval
+    gives 0."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_occluded_rays_ranged(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), C.c_void_p(t_min_ptr), C.c_void_p(t_max_ptr),
+                                           C.c_void_p(out_ptr)))
+
+
 def camera_rays_into(rays_ptr, h, w, prepared, cam=None):
     """Enqueue the h * w primary rays rt_render_image would trace (rt_camera_rays) into rays_ptr (h * w x 6 float32)."""
     ctx = prepared.ctx
@@ -425,6 +441,49 @@ def _device_rays(ctx, rays):
     return buf.ptr, a.shape[0], buf
 
 
+def _is_bound_array(b):
+    return hasattr(b, "data_ptr") or np.ndim(b) > 0
+
+
+def _device_bounds(ctx, n, t_min, t_max):
+    """(t_min pointer, t_max pointer, keep-alive buffers) for the ranged entries: each bound an (n,) array -- numpy (a floating dtype,
+    uploaded as float32) or a contiguous float32 torch tensor on the context's device (used in place) -- or a scalar, checked by the
+    scalar entries' rule and broadcast."""
+    dev = ctx.device_info()["device"]
+    ptrs, keep = [], []
+    try:
+        for name, b in (("t_min", t_min), ("t_max", t_max)):
+            if hasattr(b, "data_ptr"):
+                if str(b.dtype) != "torch.float32" or not b.is_contiguous() or b.device.type != "cuda" or b.device.index != dev:
+                    raise ValueError(f"{name}: a contiguous float32 tensor on cuda:{dev} is required")
+                if b.dim() != 1 or b.shape[0] != n:
+                    raise ValueError(f"{name} must be ({n},), one bound per ray; got {tuple(b.shape)}")
+                ptrs.append(b.data_ptr())
+                continue
+            if np.ndim(b) > 0:
+                a = np.asarray(b)
+                if not np.issubdtype(a.dtype, np.floating):
+                    raise ValueError(f"{name}: a floating-point array is required; got {a.dtype}")
+                if a.shape != (n,):
+                    raise ValueError(f"{name} must be ({n},), one bound per ray; got {a.shape}")
+                a = np.ascontiguousarray(a, dtype=np.float32)
+            else:
+                v = np.float32(b)
+                if not (np.isfinite(v) and 0.0 <= v <= 1e9):
+                    raise RtError(f"{name} = {b!r}: a scalar bound must be finite and in [0, 1e9]")
+                a = np.full(n, v, dtype=np.float32)
+            buf = DeviceBuffer(ctx, max(a.nbytes, 4))
+            keep.append(buf)
+            if a.nbytes:
+                ctx._check(lib.rt_copy_to_device(ctx._h, C.c_void_p(buf.ptr), a.ctypes.data, a.nbytes))
+            ptrs.append(buf.ptr)
+    except BaseException:
+        for buf in keep:
+            buf.free()
+        raise
+    return ptrs[0], ptrs[1], keep
+
+
 def trace_rays(prepared, rays, max_depth=MAX_DEPTH):
     """ray_colour of every ray (ray.fut:126-148) -> (colour (n, 3) float32, pixel (n,) int32) numpy arrays."""
     ctx = prepared.ctx
@@ -442,31 +501,52 @@ def trace_rays(prepared, rays, max_depth=MAX_DEPTH):
 
 
 def intersect_rays(prepared, rays, t_min=0.0, t_max=1e9):
-    """objs_hit bvh r t_min t_max of every ray (ray.fut:76-86) -> (index (n,) int32, hit (n, 7) float32) numpy arrays."""
+    """objs_hit bvh r t_min t_max of every ray (ray.fut:76-86) -> (index (n,) int32, hit (n, 7) float32) numpy arrays.
+    Either bound may be an (n,) array, one per ray (rt_intersect_rays_ranged; a scalar next to it is broadcast)."""
     ctx = prepared.ctx
+    ranged = _is_bound_array(t_min) or _is_bound_array(t_max)
     ptr, n, keep = _device_rays(ctx, rays)
-    idx = DeviceBuffer(ctx, max(4 * n, 4))
-    hit = DeviceBuffer(ctx, max(28 * n, 4))
+    bounds = []
+    idx = hit = None
     try:
-        intersect_rays_into(ptr, n, prepared, idx.ptr, hit.ptr, t_min, t_max)
+        if ranged:
+            lo_ptr, hi_ptr, bounds = _device_bounds(ctx, n, t_min, t_max)
+        idx = DeviceBuffer(ctx, max(4 * n, 4))
+        hit = DeviceBuffer(ctx, max(28 * n, 4))
+        if ranged:
+            intersect_rays_ranged_into(ptr, n, prepared, lo_ptr, hi_ptr, idx.ptr, hit.ptr)
+        else:
+            intersect_rays_into(ptr, n, prepared, idx.ptr, hit.ptr, t_min, t_max)
         return idx.to_host((n,)), hit.to_host((n, 7), np.float32)
     finally:
-        idx.free()
-        hit.free()
+        for buf in [idx, hit] + bounds:
+            if buf is not None:
+                buf.free()
         if keep is not None:
             keep.free()
 
 
 def occluded_rays(prepared, rays, t_min=0.0, t_max=1e9):
-    """Occlusion of every ray over (t_min, t_max) (rt_occluded_rays) -> (n,) bool numpy array."""
+    """Occlusion of every ray over (t_min, t_max) (rt_occluded_rays) -> (n,) bool numpy array.  Either bound may be an (n,)
+    array, one per ray (rt_occluded_rays_ranged; a scalar next to it is broadcast)."""
     ctx = prepared.ctx
+    ranged = _is_bound_array(t_min) or _is_bound_array(t_max)
     ptr, n, keep = _device_rays(ctx, rays)
-    out = DeviceBuffer(ctx, max(n, 4))
+    bounds = []
+    out = None
     try:
-        occluded_rays_into(ptr, n, prepared, out.ptr, t_min, t_max)
+        if ranged:
+            lo_ptr, hi_ptr, bounds = _device_bounds(ctx, n, t_min, t_max)
+        out = DeviceBuffer(ctx, max(n, 4))
+        if ranged:
+            occluded_rays_ranged_into(ptr, n, prepared, lo_ptr, hi_ptr, out.ptr)
+        else:
+            occluded_rays_into(ptr, n, prepared, out.ptr, t_min, t_max)
         return out.to_host((n,), np.uint8).astype(bool)
     finally:
-        out.free()
+        for buf in [out] + bounds:
+            if buf is not None:
+                buf.free()
         if keep is not None:
             keep.free()
 

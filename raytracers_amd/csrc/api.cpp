@@ -1873,12 +1873,14 @@ int pooled_rays_params(rt_context *ctx, const rt_prepared *ps, const Plan &pl, r
   return pooled_shape_params(ctx, ps, pl, &p);
 }
 
-// The launch of the pooled family's loop on caller rays (`rays`: kRaysColour, kRaysAny), and its rt_context_last_launch
+// The launch of the pooled family's loop on caller rays (`rays`: kRaysColour, kRaysAny), and its rt_context_last_launch (" intervals=per-ray"
+// appended when each ray carries its own interval)
 int launch_pooled_rays(rt_context *ctx, const rtk::KParams &p, const Plan &pl, int rays) {
   RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream, rays));
   char buf[256];
-  std::snprintf(buf, sizeof buf, "family=pooled tickets=rays instantiation=%s frames=1 tiles=%d grid=%d waves=%d counters=%d%s deep_class=0 deep_split=0 recording=0",
-                pooled_launch_name(p, pl.waves, rays).c_str(), p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "");
+  std::snprintf(buf, sizeof buf, "family=pooled tickets=rays instantiation=%s frames=1 tiles=%d grid=%d waves=%d counters=%d%s deep_class=0 deep_split=0 recording=0%s",
+                pooled_launch_name(p, pl.waves, rays).c_str(), p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "",
+                p.ray_tlo_dev != nullptr ? " intervals=per-ray" : "");
   ctx->last_launch = buf;
   return 0;
 }
@@ -1944,6 +1946,31 @@ extern "C" int rt_intersect_rays(rt_context *ctx, const rt_prepared *ps, int64_t
   return 0;
 }
 
+// The per-ray form: the intervals are device data, so they are not checked here -- the kernel answers a ray whose interval fails the rule
+// above (NaN included) as a miss (lane_core.h: interval_ok).
+extern "C" int rt_intersect_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *t_min_dev,
+                                        const float *t_max_dev, int32_t *index_dev, float *hit7_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!index_dev) return fail(ctx, "rt_intersect_rays_ranged: null index pointer");
+  if (!t_min_dev || !t_max_dev) return fail(ctx, "rt_intersect_rays_ranged: null t_min or t_max pointer");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  if (n == 0) {
+    ctx->last_launch = "family=none (no rays)";
+    return 0;
+  }
+  p.ray_tlo_dev = t_min_dev;
+  p.ray_thi_dev = t_max_dev;
+  RT_HIP(ctx, rtk::launch_intersect_rays_ranged(p, index_dev, hit7_dev, ctx->stream));
+  ctx->last_launch = "family=intersect (per-ray)";
+  return 0;
+}
+
 extern "C" int rt_occluded_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
                                 uint8_t *occluded_dev) {
   if (!ctx) return 1;
@@ -1974,6 +2001,41 @@ extern "C" int rt_occluded_rays(rt_context *ctx, const rt_prepared *ps, int64_t 
   if (pl.variant != RT_VARIANT_POOLED) {
     RT_HIP(ctx, rtk::launch_occluded_rays(p, ctx->stream));
     ctx->last_launch = "family=occluded";
+    return 0;
+  }
+  if (int rc = pooled_rays_params(ctx, ps, pl, &p)) return rc;
+  return launch_pooled_rays(ctx, p, pl, rtk::kRaysAny);
+}
+
+extern "C" int rt_occluded_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *t_min_dev,
+                                       const float *t_max_dev, uint8_t *occluded_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!occluded_dev) return fail(ctx, "rt_occluded_rays_ranged: null output pointer");
+  if (!t_min_dev || !t_max_dev) return fail(ctx, "rt_occluded_rays_ranged: null t_min or t_max pointer");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  if (n == 0) {
+    ctx->last_launch = "family=none (no rays)";
+    return 0;
+  }
+  p.occluded = occluded_dev;
+  p.ray_tlo_dev = t_min_dev;
+  p.ray_thi_dev = t_max_dev;
+  // the pooled family's any-hit loop in its per-ray mode under RT_VARIANT_POOLED; the lane kernel under RT_VARIANT_PIXEL / RT_VARIANT_PERSISTENT.
+  // AUTO: the host cannot see the rays' t_max, so the scalar rule's t_max > 1 clause cannot be asked.  Measured, the pooled
+  // loop won only long random rays on a scene staged in LDS (1.3x) and lost normalised shadow rays on the same scene (1.8x): AUTO takes the
+  // lane kernel
+  Plan pl;
+  if (int rc = pooled_rays_plan(ctx, ps, n, &pl)) return rc;
+  if (ctx->variant == RT_VARIANT_AUTO) pl.variant = RT_VARIANT_PIXEL;
+  if (pl.variant != RT_VARIANT_POOLED) {
+    RT_HIP(ctx, rtk::launch_occluded_rays_ranged(p, ctx->stream));
+    ctx->last_launch = "family=occluded (per-ray)";
     return 0;
   }
   if (int rc = pooled_rays_params(ctx, ps, pl, &p)) return rc;

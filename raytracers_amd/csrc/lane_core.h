@@ -235,6 +235,11 @@ RT_HD bool sphere_hit_any(const Ray &r, float tlo, float thi, float spx, float s
   return ((t1 < thi) && (t1 > tlo)) || ((t2 < thi) && (t2 > tlo));
 }
 
+// The interval rule of the queries that take one: 0 <= tlo <= thi <= 1e9.  Three compares, each false on a NaN operand, so NaN and +-inf fail
+// too (+inf exceeds 1e9, -inf is below 0).  A per-ray interval is checked with it once, where the ray is loaded: box_hit_interval's
+// fmaxf / fminf drop a NaN bound rather than empty the box interval.
+RT_HD bool interval_ok(float tlo, float thi) { return (tlo >= 0.0f) & (tlo <= thi) & (thi <= kTMax); }
+
 // Shortcut for the same call when the fold's accepted root `best` is known not to be
 // displaced: with near_root clear, root1 (if it was the fold's root) or root2 passes
 // `0 < t < best + 1` iff best + 1 > best, and the re-intersection returns t = best.

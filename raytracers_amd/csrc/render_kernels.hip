@@ -397,9 +397,14 @@ __global__ __launch_bounds__(THREADS) void persistent_kernel(KParams p) {
 // ---------------------------------------------------------------------------------
 constexpr int kOrderClasses = 8;   // cost classes of the adaptive tile order (tile_order_kernel)
 constexpr unsigned long long kKeyInit = ((unsigned long long)0x4e6e6b28u << 32) | 0xffffffffull;   // (1e9, no leaf)
-// pooled_kernel's RAYS mode (rt_device.hpp: kRaysColour, kRaysAny): in the any-hit mode a slot's key is kKeyAnyHit once one of its spheres
-// is accepted (its high word, read as the boxes' upper end, then empties their interval)
+// pooled_kernel's RAYS mode (rt_device.hpp: kRaysColour, kRaysAny): in the any-hit mode a slot's key starts as any_key_seed(t_max) -- the ray's
+// upper end in its high word, which the boxes and spheres read as such -- and is kKeyAnyHit once one of its spheres is accepted (its high
+// word then empties their interval; the seed's low word keeps every seed apart from it)
 constexpr unsigned long long kKeyAnyHit = 0ull;
+__device__ __forceinline__ unsigned long long any_key_seed(float t_max) { return ((unsigned long long)__float_as_uint(t_max) << 32) | 0xffffffffull; }
+__device__ __forceinline__ float key_hi(const unsigned long long *wkey, int sl) {   // a slot's key's high word as a float (one ds_read_b32)
+  return __uint_as_float(reinterpret_cast<const unsigned *>(wkey + sl)[1]);
+}
 
 __device__ __forceinline__ float pull(int lane_byte, float v) {   // v of the lane at byte address lane_byte (ds_bpermute)
   return __int_as_float(__builtin_amdgcn_ds_bpermute(lane_byte, __float_as_int(v)));
@@ -645,9 +650,12 @@ __device__ __attribute__((noinline)) void solo_trace(KParamsArg pp_v, unsigned s
 // RAYS: caller-supplied rays (rt_trace_rays) on the plain loop.  A ticket is 64 consecutive rays of p.rays (a "tile" of the raster queue, no
 // order); a refill loads the ray's six floats instead of deriving a primary ray, and the finished colour is stored at the ray's index (p.colour3,
 // and / or the packed pixel at p.out).  No CULL: its bound is proved for rays from the camera origin only.  (RAYS == kRaysColour)
-// RAYS == kRaysAny (ANY): rt_occluded_rays on the same loop and tickets.  Every box is tested over the caller's (p.ray_tlo, p.ray_thi); LEAF
-// marks the slot's key when the sphere has a root inside that interval, and from then on the slot's boxes are tested over (p.ray_tlo, 0) --
-// empty, so its remaining items drain without appending anything; SHADE stores key != kKeyInit at the ray's index (no re-hit, no bounce).
+// RAYS == kRaysAny (ANY): rt_occluded_rays on the same loop and tickets.  Every box is tested over the ray's interval (t_min, t_max): the
+// caller's (p.ray_tlo, p.ray_thi), or the ray's own (p.ray_tlo_dev[i], p.ray_thi_dev[i]) -- a uniform choice at refill, the loop is the same.
+// A slot keeps t_max in its key's high word (any_key_seed) and t_min in the spare .w of its {1/d} entry; LEAF marks the slot's key when the
+// sphere has a root inside the interval, and from then on the slot's boxes are tested over (t_min, 0) -- empty, so its remaining items drain
+// without appending anything; SHADE stores key == kKeyAnyHit at the ray's index (no re-hit, no bounce).  A ray whose own interval fails
+// interval_ok misses the root box and is stored as 0.
 template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, int RAYS = 0>
 __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 4) void pooled_kernel(KParams p) {
   constexpr bool COLD = TAIL == 1, DONATE = TAIL == 2;
@@ -891,7 +899,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           const unsigned long long tr_s0 = STATS ? clock64() : 0ull;
           if constexpr (ANY) {
             if (done) {             // the fold is over: occluded iff a LEAF operation marked the key
-              p.occluded[pix] = wkey[lane] != kKeyInit ? 1 : 0;
+              p.occluded[pix] = wkey[lane] == kKeyAnyHit ? 1 : 0;
               pix = -1;
             }
           } else if (done) {
@@ -945,6 +953,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           }
           bool want = (pix < 0) & !exhausted & !hold;
           int slot = -1;
+          float a_lo = p.ray_tlo, a_hi = p.ray_thi;   // (ANY: the interval of the ray a lane draws)
           unsigned long long m = bal(want);
           while (ORD && m != 0ull) {     // pixel tickets: the next pixels of the view's list
             if (__builtin_expect(q_next == q_end, 0)) {
@@ -1074,6 +1083,10 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
                 const float *const q = p.rays + (size_t)i * 6;
                 r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
                 r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
+                if (ANY && p.ray_tlo_dev != nullptr) {
+                  a_lo = p.ray_tlo_dev[i];
+                  a_hi = p.ray_thi_dev[i];
+                }
                 slot = i;
                 want = false;
               }
@@ -1154,13 +1167,13 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           }
           // A new fold starts with the ROOT's box test (items are nodes whose own box passed).
           if (root) ray_derive(r);   // one place for both scattered and primary rays
-          const bool root_hit = root && (ANY ? box_hit_interval(r, p.root_lo[0], p.root_lo[1], p.root_lo[2], p.root_hi[0], p.root_hi[1], p.root_hi[2], p.ray_tlo, p.ray_thi)
+          const bool root_hit = root && (ANY ? interval_ok(a_lo, a_hi) && box_hit_interval(r, p.root_lo[0], p.root_lo[1], p.root_lo[2], p.root_hi[0], p.root_hi[1], p.root_hi[2], a_lo, a_hi)
                                              : box_hit(r, p.root_lo[0], p.root_lo[1], p.root_lo[2], p.root_hi[0], p.root_hi[1], p.root_hi[2]));
           if (root) {
-            wkey[lane] = kKeyInit;
+            wkey[lane] = ANY ? any_key_seed(a_hi) : kKeyInit;
             wcnt[lane] = root_hit ? 1 : 0;    // 0: the fold is already complete (a miss), shaded next time
             wray[lane] = make_float4(r.ox, r.oy, r.oz, r.a);
-            wray[64 + lane] = make_float4(r.ix, r.iy, r.iz, CULL ? cull_weight(r, p.cull_c2) : 0.0f);   // (CULL: the ray's W2)
+            wray[64 + lane] = make_float4(r.ix, r.iy, r.iz, CULL ? cull_weight(r, p.cull_c2) : ANY ? a_lo : 0.0f);   // (CULL: the ray's W2; ANY: t_min)
             if (p.ray_planes == 3) wray[128 + lane] = make_float4(r.dx, r.dy, r.dz, 0.0f);
             if (STATS) { n_rays++; n_box++; }
           }
@@ -1217,8 +1230,10 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
       }
       if (STATS) n_sph += act ? 1 : 0;
       if constexpr (ANY) {
-        // (every lane that accepts its sphere writes the same value: no atomic)
-        if (act && sphere_hit_any(q, p.ray_tlo, p.ray_thi, s.x, s.y, s.z, s.w)) wkey[sl] = kKeyAnyHit;
+        // the slot's interval: t_max from its key (read before any mark; a marked key gives 0.0, and the mark stands), t_min from its {1/d}
+        // entry.  (every lane that accepts its sphere writes the same value: no atomic)
+        const float tlo = reinterpret_cast<const float *>(wray + 64 + sl)[3], thi = key_hi(wkey, sl);
+        if (act && sphere_hit_any(q, tlo, thi, s.x, s.y, s.z, s.w)) wkey[sl] = kKeyAnyHit;
       } else {
         bool near_root;
         const float g = sphere_root_flag(q, s.x, s.y, s.z, s.w, &near_root);
@@ -1265,10 +1280,10 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         // the proven margin; the ray's weight W2 travels in the spare dword of the {1/d} entry.  Two v_fma + one v_min per item.)
         float limc = kTMax, limlo = 0.0f;
         if constexpr (CULL) limc = cull_limit(__uint_as_float(*reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(wkey) + 2 * sl4 + 4)), ri.w, p.cull_kappa);
-        // (ANY: the caller's interval; a slot whose key is marked reads 0.0 from its high word -- nothing passes)
+        // (ANY: the slot's interval -- t_min in ri.w, t_max in its key's high word; a slot whose key is marked reads 0.0 there: nothing passes)
         if constexpr (ANY) {
-          limlo = p.ray_tlo;
-          limc = fminf(p.ray_thi, __uint_as_float(*reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(wkey) + 2 * sl4 + 4)));
+          limlo = ri.w;
+          limc = __uint_as_float(*reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(wkey) + 2 * sl4 + 4));
         }
         // lane masks straight from the compares; the rest is 64-bit scalar logic
         const unsigned long long m_hl = bal(box_hit_interval(q, q0.x, q0.y, q0.z, q1.x, q1.y, q1.z, limlo, limc));
@@ -1337,8 +1352,8 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         float limc = kTMax, limlo = 0.0f;
         if constexpr (CULL) limc = cull_limit(__uint_as_float(*reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(wkey) + 2 * sl4 + 4)), ri.w, p.cull_kappa);
         if constexpr (ANY) {
-          limlo = p.ray_tlo;
-          limc = fminf(p.ray_thi, __uint_as_float(*reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(wkey) + 2 * sl4 + 4)));
+          limlo = ri.w;
+          limc = __uint_as_float(*reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(wkey) + 2 * sl4 + 4));
         }
         const bool child_leaf = act & (ref < 0);
         const bool pass = act & (ref >= 0) && box_hit_interval(q, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, limlo, limc);
@@ -1901,6 +1916,8 @@ static hipError_t launch_pooled_key(const PooledKey &k, const KParams &p, int gr
 
 hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays) {
   if (rays == kRaysAny && p.occluded == nullptr) return hipErrorInvalidValue;
+  // (per-ray intervals: the any-hit loop only, both bounds)
+  if ((p.ray_tlo_dev != nullptr || p.ray_thi_dev != nullptr) && (rays != kRaysAny || p.ray_tlo_dev == nullptr || p.ray_thi_dev == nullptr)) return hipErrorInvalidValue;
   if (grid <= 0 || (rays && p.nrays <= 0)) return hipSuccess;
   PooledKey k;
   if (!choose_pooled(p, stats, waves_per_wg, rays, &k)) return hipErrorInvalidValue;
@@ -1916,9 +1933,20 @@ hipError_t launch_pixel_rays(const KParams &p, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// A lane's interval in the lane kernels: the caller's (t_min, t_max), or with RANGED ray i's own -- two coalesced 4-byte loads next to its ray.
+// A ray whose own interval fails interval_ok does not start its walk: it is a miss.
+template <bool RANGED>
+__device__ __forceinline__ bool lane_interval(const KParams &p, int i, float &t_min, float &t_max) {
+  if constexpr (!RANGED) return true;
+  t_min = p.ray_tlo_dev[i];
+  t_max = p.ray_thi_dev[i];
+  return interval_ok(t_min, t_max);
+}
+
 // objs_hit bvh r t_min t_max (ray.fut:76-86), one lane per ray: the pixel family's stack fold with the caller's interval on every box,
 // the spheres folded over (scene_epsilon, best) from best = t_max, then one re-intersection of the winner over (t_min, best + 1).
-__global__ __launch_bounds__(64) void intersect_kernel(KParams p, float t_min, float t_max, int32_t *index, float *hit7) {
+template <bool RANGED>
+__device__ __forceinline__ void intersect_lane(const KParams &p, float t_min, float t_max, int32_t *index, float *hit7) {
   __shared__ int stack[kStackPixel][64];
   const int lane = threadIdx.x;
   const int i = blockIdx.x * 64 + lane;
@@ -1926,10 +1954,11 @@ __global__ __launch_bounds__(64) void intersect_kernel(KParams p, float t_min, f
   const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
   const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
   const Ray r = load_ray(p.rays, i);
+  const bool valid = lane_interval<RANGED>(p, i, t_min, t_max);
   float best = t_max;
   int bestj = -1;
   int sp = 0;
-  stack[sp++][lane] = 0;
+  if (valid) stack[sp++][lane] = 0;
   while (sp > 0) {
     const int ni = stack[--sp][lane];
     const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
@@ -1966,16 +1995,29 @@ __global__ __launch_bounds__(64) void intersect_kernel(KParams p, float t_min, f
     for (int k = 0; k < 6; ++k) o[1 + k] = h[k];
   }
 }
+__global__ __launch_bounds__(64) void intersect_kernel(KParams p, float t_min, float t_max, int32_t *index, float *hit7) {
+  intersect_lane<false>(p, t_min, t_max, index, hit7);
+}
+__global__ __launch_bounds__(64) void intersect_ranged_kernel(KParams p, int32_t *index, float *hit7) {
+  intersect_lane<true>(p, 0.0f, 0.0f, index, hit7);
+}
 
 hipError_t launch_intersect_rays(const KParams &p, float t_min, float t_max, int32_t *index, float *hit7, hipStream_t stream) {
   if (p.nrays <= 0) return hipSuccess;
   hipLaunchKernelGGL(intersect_kernel, dim3((unsigned)((p.nrays + 63) / 64)), dim3(64), 0, stream, p, t_min, t_max, index, hit7);
   return hipGetLastError();
 }
+hipError_t launch_intersect_rays_ranged(const KParams &p, int32_t *index, float *hit7, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (p.ray_tlo_dev == nullptr || p.ray_thi_dev == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(intersect_ranged_kernel, dim3((unsigned)((p.nrays + 63) / 64)), dim3(64), 0, stream, p, index, hit7);
+  return hipGetLastError();
+}
 
 // rt_occluded_rays, one lane per ray: intersect_kernel's stack fold with the caller's interval on every box and on every sphere
 // (sphere_hit_any); the lane leaves the walk at its first accepted sphere -- the fold is an OR, so no order can change the answer.
-__global__ __launch_bounds__(64) void occluded_kernel(KParams p) {
+template <bool RANGED>
+__device__ __forceinline__ void occluded_lane(const KParams &p) {
   __shared__ int stack[kStackPixel][64];
   const int lane = threadIdx.x;
   const int i = blockIdx.x * 64 + lane;
@@ -1983,10 +2025,11 @@ __global__ __launch_bounds__(64) void occluded_kernel(KParams p) {
   const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
   const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
   const Ray r = load_ray(p.rays, i);
-  const float t_min = p.ray_tlo, t_max = p.ray_thi;
+  float t_min = p.ray_tlo, t_max = p.ray_thi;
+  const bool valid = lane_interval<RANGED>(p, i, t_min, t_max);
   bool hit = false;
   int sp = 0;
-  stack[sp++][lane] = 0;
+  if (valid) stack[sp++][lane] = 0;
   while (sp > 0 && !hit) {
     const int ni = stack[--sp][lane];
     const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
@@ -2005,11 +2048,19 @@ __global__ __launch_bounds__(64) void occluded_kernel(KParams p) {
   }
   p.occluded[i] = hit ? 1 : 0;
 }
+__global__ __launch_bounds__(64) void occluded_kernel(KParams p) { occluded_lane<false>(p); }
+__global__ __launch_bounds__(64) void occluded_ranged_kernel(KParams p) { occluded_lane<true>(p); }
 
 hipError_t launch_occluded_rays(const KParams &p, hipStream_t stream) {
   if (p.nrays <= 0) return hipSuccess;
   if (p.occluded == nullptr) return hipErrorInvalidValue;
   hipLaunchKernelGGL(occluded_kernel, dim3((unsigned)((p.nrays + 63) / 64)), dim3(64), 0, stream, p);
+  return hipGetLastError();
+}
+hipError_t launch_occluded_rays_ranged(const KParams &p, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (p.occluded == nullptr || p.ray_tlo_dev == nullptr || p.ray_thi_dev == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(occluded_ranged_kernel, dim3((unsigned)((p.nrays + 63) / 64)), dim3(64), 0, stream, p);
   return hipGetLastError();
 }
 

@@ -278,6 +278,9 @@ struct KParams {
   // (ray_tlo, ray_thi) and its sphere has a root strictly inside that interval, else 0
   unsigned char *occluded;
   float ray_tlo, ray_thi;
+  // rt_intersect_rays_ranged / rt_occluded_rays_ranged: ray i's own interval (ray_tlo_dev[i], ray_thi_dev[i]) in place of (ray_tlo, ray_thi); a ray
+  // whose interval fails 0 <= t_min <= t_max <= 1e9 (NaN included) is a miss.  nullptr: the scalar interval (both set, or neither)
+  const float *ray_tlo_dev, *ray_thi_dev;
 };
 
 // ---- the pooled kernel's instantiations ----------------------------------------------------------
@@ -392,13 +395,16 @@ hipError_t launch_pixel_rays(const KParams &p, hipStream_t stream);
 hipError_t launch_occluded_rays(const KParams &p, hipStream_t stream);
 // objs_hit bvh r t_min t_max of n rays (ray.fut:76-86): index[i] = the winning leaf or -1, hit7 (may be nullptr) = {t, p.xyz, normal.xyz}
 hipError_t launch_intersect_rays(const KParams &p, float t_min, float t_max, int32_t *index, float *hit7, hipStream_t stream);
+// ... the two lane kernels with ray i's interval from (p.ray_tlo_dev[i], p.ray_thi_dev[i]) (both non-null)
+hipError_t launch_intersect_rays_ranged(const KParams &p, int32_t *index, float *hit7, hipStream_t stream);
+hipError_t launch_occluded_rays_ranged(const KParams &p, hipStream_t stream);
 // the primary rays of an h x w frame through p.cam (get_ray at pixel_u / pixel_v), row-major from the top row: rays[6 (row w + col) ..]
 hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStream_t stream);
 // block = 64 * waves_per_wg threads (4, 8 or 16 waves); grid = persistent workgroups
 hipError_t launch_persistent(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream);
 size_t persistent_lds_bytes(int lds_nodes, int lds_sph, int smax, int lmax, int waves_per_wg);
 // the pooled family: the instantiation choose_pooled picks (grid workgroups of 64 * waves_per_wg threads).  `rays`: 64 consecutive caller rays
-// per ticket (the plain loop; kRaysAny: occlusion of p.nrays rays over (p.ray_tlo, p.ray_thi) into p.occluded)
+// per ticket (the plain loop; kRaysAny: occlusion of p.nrays rays over (p.ray_tlo, p.ray_thi), or each over its own with p.ray_tlo_dev, into p.occluded)
 hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays = 0);
 size_t pooled_lds_bytes(int lds_nodes, int lds_sph, int capb, int capl, int ray_planes, int waves_per_wg);
 // prepare_scene on the GPU (bvh_build.hip).  Canonical {L, I} arrays + the traversal copy.
