@@ -73,6 +73,7 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *   "family=none (no rays)"       a caller-ray entry with n == 0
  *   "family=pixel (rays)" | "family=intersect" | "family=occluded" | "family=camera-rays"   the caller-ray entries (below)
  *   "family=intersect (per-ray)" | "family=occluded (per-ray)"   their lane kernels with per-ray intervals (rt_*_rays_ranged)
+ *   "family=multi-hit k=K" | "family=multi-hit k=K (per-ray)"   rt_multi_hit_rays / rt_multi_hit_rays_ranged (K: the caller's k)
  *   "family=none (no rows)"       the part owns no row of the image
  *   "family=pixel" | "family=pixel (instrumented)" | "family=persistent"
  *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2"
@@ -248,11 +249,32 @@ int rt_occluded_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const fl
  * instantiation=any[+SPILL] ... intervals=per-ray"), the lane kernel ("family=occluded (per-ray)") under RT_VARIANT_PIXEL /
  * RT_VARIANT_PERSISTENT.  RT_VARIANT_AUTO: the lane kernel (the host cannot see t_max; measured).
  * Raising t_min is NOT depth peeling: objs_hit folds the spheres over (scene_epsilon, best) whatever t_min is, so a sphere nearer
- * than t_min still wins the fold (and then fails its re-intersection: #none) -- it does not skip to the next sphere. */
+ * than t_min still wins the fold (and then fails its re-intersection: #none) -- it does not skip to the next sphere (rt_multi_hit_rays,
+ * below, gives the surfaces behind the first). */
 int rt_intersect_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *t_min_dev,
                              const float *t_max_dev, int32_t *index_dev, float *hit7_dev);
 int rt_occluded_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *t_min_dev,
                             const float *t_max_dev, uint8_t *occluded_dev);
+/* Multi-hit: the k nearest sphere crossings of each ray -- what lies behind the first hit (layers, entry and exit points, crossing
+ * counts).  The crossings of ray r over (t_min, t_max) are every (t, j, root) with leaf j visited (every inner node on its root path
+ * passes aabb_hit node r t_min t_max, the leaves rt_occluded_rays reaches) and t = root 1 (-b - sq)/a or root 2 (-b + sq)/a of
+ * sphere_hit L[j] r (ray.fut:32-51) strictly inside (t_min, t_max); a sphere gives up to two, entry and exit.  They are ordered by t,
+ * then j, then root, all ascending.  count_dev: n int32, the number of crossings (not capped at k; > 0 iff rt_occluded_rays gives 1).
+ * The first min(count, k) crossings, row-major per ray: index_dev n x k int32 (j), root_dev n x k uint8 (1 or 2), hit7_dev n x k x 7
+ * float32 {t, p.xyz, normal.xyz} (rt_intersect_rays's arithmetic: p = o + t d, normal = (1 / radius) (p - centre)); the slots past
+ * min(count, k) are -1, 0 and seven zero floats.  Any output may be NULL, not all four.  Exact, bit for bit, for every k: the answer for
+ * k = a is a prefix of the answer for k = b > a.  No culling and no early exit: every visited sphere is tested.  Refused (nothing
+ * launched): as rt_intersect_rays (n out of range, NULL rays, a multi-device context, the scalar interval rule), and k < 1 or k > 32.
+ * One lane per ray under every variant (rt_context_last_launch: "family=multi-hit k=<k>").
+ * rt_multi_hit_rays_ranged: the interval of ray i is (t_min_dev[i], t_max_dev[i]), as rt_intersect_rays_ranged -- a ray whose interval
+ * fails 0 <= t_min <= t_max <= 1e9 is a miss (count 0, every slot padded), -0.0 behaves as 0.0; refused also for a NULL t_min_dev or
+ * t_max_dev ("family=multi-hit k=<k> (per-ray)").  Unlike raising t_min in rt_intersect_rays, this is depth peeling: crossing s + 1 is
+ * the next surface behind crossing s. */
+int rt_multi_hit_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
+                      int32_t k, int32_t *count_dev, int32_t *index_dev, uint8_t *root_dev, float *hit7_dev);
+int rt_multi_hit_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev,
+                             const float *t_min_dev, const float *t_max_dev, int32_t k,
+                             int32_t *count_dev, int32_t *index_dev, uint8_t *root_dev, float *hit7_dev);
 /* The primary rays rt_render_image would trace (get_ray at pixel_u / pixel_v), row-major from the top row: h * w x 6
  * float32 at rays_dev.  cam12 == NULL: the prepared camera.  rt_context_last_launch: "family=camera-rays". */
 int rt_camera_rays(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, const float cam12[12], float *rays_dev);

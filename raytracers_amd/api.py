@@ -412,6 +412,24 @@ def occluded_rays_ranged_into(rays_ptr, n, prepared, t_min_ptr, t_max_ptr, out_p
                                            C.c_void_p(out_ptr)))
 
 
+def multi_hit_rays_into(rays_ptr, n, prepared, k, count_ptr, index_ptr, root_ptr=None, hit_ptr=None, t_min=0.0, t_max=1e9):
+    """Enqueue the first k (1 <= k <= 32) sphere crossings of `n` rays over (t_min, t_max), ordered by (t, sphere, root)
+    (rt_multi_hit_rays): their count (n int32, not capped at k) to count_ptr, sphere indices (n x k int32, -1 past the count) to
+    index_ptr, roots (n x k uint8: 1 entry-side, 2 exit-side; 0 past the count) to root_ptr and {t, p.xyz, normal.xyz} (n x k x 7
+    float32) to hit_ptr.  Any pointer may be None, not all four."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_multi_hit_rays(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), float(t_min), float(t_max), int(k),
+                                     C.c_void_p(count_ptr), C.c_void_p(index_ptr), C.c_void_p(root_ptr), C.c_void_p(hit_ptr)))
+
+
+def multi_hit_rays_ranged_into(rays_ptr, n, prepared, t_min_ptr, t_max_ptr, k, count_ptr, index_ptr, root_ptr=None, hit_ptr=None):
+    """multi_hit_rays_into with ray i's own interval (t_min_ptr[i], t_max_ptr[i]) (rt_multi_hit_rays_ranged); a ray whose interval
+    fails 0 <= t_min <= t_max <= 1e9 (NaN included) has no crossing."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_multi_hit_rays_ranged(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), C.c_void_p(t_min_ptr), C.c_void_p(t_max_ptr),
+                                            int(k), C.c_void_p(count_ptr), C.c_void_p(index_ptr), C.c_void_p(root_ptr), C.c_void_p(hit_ptr)))
+
+
 def camera_rays_into(rays_ptr, h, w, prepared, cam=None):
     """Enqueue the h * w primary rays rt_render_image would trace (rt_camera_rays) into rays_ptr (h * w x 6 float32)."""
     ctx = prepared.ctx
@@ -545,6 +563,37 @@ def occluded_rays(prepared, rays, t_min=0.0, t_max=1e9):
         return out.to_host((n,), np.uint8).astype(bool)
     finally:
         for buf in [out] + bounds:
+            if buf is not None:
+                buf.free()
+        if keep is not None:
+            keep.free()
+
+
+def multi_hit_rays(prepared, rays, k, t_min=0.0, t_max=1e9):
+    """The first k sphere crossings of every ray over (t_min, t_max) (rt_multi_hit_rays) -> (count (n,) int32, index (n, k) int32,
+    root (n, k) uint8, hit (n, k, 7) float32) numpy arrays.  Either bound may be an (n,) array, one per ray (rt_multi_hit_rays_ranged;
+    a scalar next to it is broadcast)."""
+    ctx = prepared.ctx
+    k = int(k)
+    ranged = _is_bound_array(t_min) or _is_bound_array(t_max)
+    ptr, n, keep = _device_rays(ctx, rays)
+    bounds = []
+    cnt = idx = root = hit = None
+    try:
+        if ranged:
+            lo_ptr, hi_ptr, bounds = _device_bounds(ctx, n, t_min, t_max)
+        nk = n * max(k, 0)
+        cnt = DeviceBuffer(ctx, max(4 * n, 4))
+        idx = DeviceBuffer(ctx, max(4 * nk, 4))
+        root = DeviceBuffer(ctx, max(nk, 4))
+        hit = DeviceBuffer(ctx, max(28 * nk, 4))
+        if ranged:
+            multi_hit_rays_ranged_into(ptr, n, prepared, lo_ptr, hi_ptr, k, cnt.ptr, idx.ptr, root.ptr, hit.ptr)
+        else:
+            multi_hit_rays_into(ptr, n, prepared, k, cnt.ptr, idx.ptr, root.ptr, hit.ptr, t_min, t_max)
+        return (cnt.to_host((n,)), idx.to_host((n, k)), root.to_host((n, k), np.uint8), hit.to_host((n, k, 7), np.float32))
+    finally:
+        for buf in [cnt, idx, root, hit] + bounds:
             if buf is not None:
                 buf.free()
         if keep is not None:

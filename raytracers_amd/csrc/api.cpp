@@ -2042,6 +2042,53 @@ extern "C" int rt_occluded_rays_ranged(rt_context *ctx, const rt_prepared *ps, i
   return launch_pooled_rays(ctx, p, pl, rtk::kRaysAny);
 }
 
+// The multi-hit entries' checks past ray_entry_params and their launch: the lane kernel under every variant, k crossings per ray.  The caller
+// holds the context lock and has set p's interval (scalar, or per-ray).
+static int multi_hit_launch(rt_context *ctx, const rt_prepared *ps, int64_t n, rtk::KParams &p, int32_t k, int32_t *count_dev,
+                            int32_t *index_dev, uint8_t *root_dev, float *hit7_dev, bool ranged) {
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  if (n == 0) {
+    ctx->last_launch = "family=none (no rays)";
+    return 0;
+  }
+  RT_HIP(ctx, rtk::launch_multi_hit_rays(p, k, count_dev, index_dev, root_dev, hit7_dev, ctx->stream));
+  ctx->last_launch = "family=multi-hit k=" + std::to_string(k) + (ranged ? " (per-ray)" : "");
+  return 0;
+}
+
+extern "C" int rt_multi_hit_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max, int32_t k,
+                                 int32_t *count_dev, int32_t *index_dev, uint8_t *root_dev, float *hit7_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!count_dev && !index_dev && !root_dev && !hit7_dev) return fail(ctx, "rt_multi_hit_rays: all four outputs are NULL");
+  if (k < 1 || k > rtk::kMultiHitMaxK) return fail(ctx, "rt_multi_hit_rays: need 1 <= k <= 32");
+  if (!ray_interval_ok(t_min, t_max)) return fail(ctx, "rt_multi_hit_rays: need 0 <= t_min <= t_max <= 1e9, both finite");
+  p.ray_tlo = t_min;
+  p.ray_thi = t_max;
+  return multi_hit_launch(ctx, ps, n, p, k, count_dev, index_dev, root_dev, hit7_dev, false);
+}
+
+// The per-ray form: as rt_intersect_rays_ranged, a ray whose interval fails the rule is a miss in the kernel (count 0, every slot padded).
+extern "C" int rt_multi_hit_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *t_min_dev,
+                                        const float *t_max_dev, int32_t k, int32_t *count_dev, int32_t *index_dev, uint8_t *root_dev,
+                                        float *hit7_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!count_dev && !index_dev && !root_dev && !hit7_dev) return fail(ctx, "rt_multi_hit_rays_ranged: all four outputs are NULL");
+  if (k < 1 || k > rtk::kMultiHitMaxK) return fail(ctx, "rt_multi_hit_rays_ranged: need 1 <= k <= 32");
+  if (!t_min_dev || !t_max_dev) return fail(ctx, "rt_multi_hit_rays_ranged: null t_min or t_max pointer");
+  p.ray_tlo_dev = t_min_dev;
+  p.ray_thi_dev = t_max_dev;
+  return multi_hit_launch(ctx, ps, n, p, k, count_dev, index_dev, root_dev, hit7_dev, true);
+}
+
 extern "C" int rt_camera_rays(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, const float cam12[12], float *rays_dev) {
   if (!ctx) return 1;
   RT_LOCK(ctx);

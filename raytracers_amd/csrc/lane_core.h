@@ -235,6 +235,20 @@ RT_HD bool sphere_hit_any(const Ray &r, float tlo, float thi, float spx, float s
   return ((t1 < thi) && (t1 > tlo)) || ((t2 < thi) && (t2 > tlo));
 }
 
+// `sphere_hit`'s two roots (ray.fut:32-51) with sphere_hit_any's arithmetic, both kept: the crossings of rt_multi_hit_rays.  False (roots
+// not written) when the discriminant is not positive; a NaN discriminant gives two NaN roots, which lie inside no interval.
+RT_HD bool sphere_roots(const Ray &r, float spx, float spy, float spz, float srad, float *t1, float *t2) {
+  const float ocx = r.ox - spx, ocy = r.oy - spy, ocz = r.oz - spz;
+  const float b = dot3(ocx, ocy, ocz, r.dx, r.dy, r.dz);
+  const float c = dot3(ocx, ocy, ocz, ocx, ocy, ocz) - srad * srad;
+  const float disc = b * b - r.a * c;
+  if (disc <= 0.0f) return false;
+  const float sq = sqrtf(disc);
+  *t1 = (-b - sq) / r.a;
+  *t2 = (-b + sq) / r.a;
+  return true;
+}
+
 // The interval rule of the queries that take one: 0 <= tlo <= thi <= 1e9.  Three compares, each false on a NaN operand, so NaN and +-inf fail
 // too (+inf exceeds 1e9, -inf is below 0).  A per-ray interval is checked with it once, where the ray is loaded: box_hit_interval's
 // fmaxf / fminf drop a NaN bound rather than empty the box interval.

@@ -2064,6 +2064,123 @@ hipError_t launch_occluded_rays_ranged(const KParams &p, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// rt_multi_hit_rays: a lane's crossings -- (t, j, root) for every root of every visited sphere strictly inside (t_min, t_max) -- kept as
+// one 64-bit key each, bits(t) << 32 | j << 1 | (root - 1).  t > t_min >= 0 (-0.0 included) and t < t_max <= 1e9, so t is positive and
+// finite and its bits order as t does; j < 2^26 (rt_scene's sphere limit; any j < 2^31 would do) fills the low word below bit 27 next to
+// the root bit.  The key carries no ray index, so the order is (t, j, root) for every ray count.  An empty slot is ~0: no crossing has a
+// high word of 0xffffffff.
+__device__ __forceinline__ unsigned long long crossing_key(float t, int j, int root2) {
+  return ((unsigned long long)__float_as_uint(t) << 32) | ((unsigned)j << 1) | (unsigned)root2;
+}
+// Insert x into the sorted list of the CAP smallest keys: x is carried down the list, each slot keeping the smaller of the two.  Every index
+// is a compile-time constant after unrolling, so the list stays in VGPRs (a runtime index would put it in scratch).  Skipped when x is
+// not below the last slot.
+template <int CAP>
+__device__ __forceinline__ void crossing_insert(unsigned long long (&list)[CAP], unsigned long long x) {
+  if (!(x < list[CAP - 1])) return;
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) {
+    const unsigned long long y = list[s];
+    list[s] = x < y ? x : y;
+    x = x < y ? y : x;
+  }
+}
+
+// One lane per ray: occluded_lane's walk (box_hit_interval over the lane's interval on every box) without its early exit and without
+// culling.  At each leaf both roots are computed once (sphere_roots); each one inside the interval is counted and inserted into the
+// lane's list of the CAP smallest crossings (k <= CAP of them are written).  At write-out slot s < min(count, k) gets j, its root and
+// {t, p.xyz, normal.xyz} with intersect_lane's arithmetic; slots up to k are padded with -1, 0 and seven zeros.  Outputs are at
+// 64-bit offsets (n * k * 7 passes 2^31); any of them may be nullptr.
+template <bool RANGED, int CAP>
+__device__ __forceinline__ void multi_hit_lane(const KParams &p, int k, int32_t *count, int32_t *index, uint8_t *root, float *hit7) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const Ray r = load_ray(p.rays, i);
+  float t_min = p.ray_tlo, t_max = p.ray_thi;
+  const bool valid = lane_interval<RANGED>(p, i, t_min, t_max);
+  unsigned long long list[CAP];
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) list[s] = ~0ull;
+  int cnt = 0;
+  int sp = 0;
+  if (valid) stack[sp++][lane] = 0;
+  while (sp > 0) {
+    const int ni = stack[--sp][lane];
+    const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+    if (!box_hit_interval(r, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, t_min, t_max)) continue;
+    const int kids[2] = {f2i(lo.w), f2i(hi.w)};
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      const int c = kids[c2];
+      if (c < 0) {
+        const int j = ~c;
+        const float4 s = buf_load16(rs_sph, j * 16);
+        float t1, t2;
+        if (sphere_roots(r, s.x, s.y, s.z, s.w, &t1, &t2)) {
+          const bool in1 = (t1 < t_max) && (t1 > t_min), in2 = (t2 < t_max) && (t2 > t_min);   // (sphere_hit_any's tests)
+          cnt += (in1 ? 1 : 0) + (in2 ? 1 : 0);
+          if (in1) crossing_insert<CAP>(list, crossing_key(t1, j, 0));
+          if (in2) crossing_insert<CAP>(list, crossing_key(t2, j, 1));
+        }
+      } else {
+        stack[sp++][lane] = c;   // (at most one pending sibling per level: sp <= tree height + 1 <= kStackPixel)
+      }
+    }
+  }
+  if (count != nullptr) count[i] = cnt;
+  const size_t base = (size_t)i * (size_t)k;
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) {
+    if (s < k) {
+      const bool have = s < cnt;
+      const int j = have ? (int)((unsigned)list[s] >> 1) : -1;
+      if (index != nullptr) index[base + s] = j;
+      if (root != nullptr) root[base + s] = have ? (uint8_t)(((unsigned)list[s] & 1u) + 1u) : (uint8_t)0;
+      if (hit7 != nullptr) {
+        float h[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (have) {
+          const float t = __uint_as_float((unsigned)(list[s] >> 32));
+          const float4 ce = p.sph[j];
+          const float inv_rad = p.col[j].w;   // 1.0f / radius, as intersect_lane
+          h[0] = t;
+          h[1] = r.ox + t * r.dx; h[2] = r.oy + t * r.dy; h[3] = r.oz + t * r.dz;   // point_at_param
+          h[4] = inv_rad * (h[1] - ce.x); h[5] = inv_rad * (h[2] - ce.y); h[6] = inv_rad * (h[3] - ce.z);
+        }
+        float *const o = hit7 + (base + s) * 7;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) o[q] = h[q];
+      }
+    }
+  }
+}
+template <bool RANGED, int CAP>
+__global__ __launch_bounds__(64) void multi_hit_kernel(KParams p, int k, int32_t *count, int32_t *index, uint8_t *root, float *hit7) {
+  multi_hit_lane<RANGED, CAP>(p, k, count, index, root, hit7);
+}
+
+template <bool RANGED>
+static hipError_t launch_multi_hit_cap(const KParams &p, int k, int32_t *count, int32_t *index, uint8_t *root, float *hit7, hipStream_t stream) {
+  const dim3 grid((unsigned)((p.nrays + 63) / 64)), block(64);
+  if (k <= 4) hipLaunchKernelGGL((multi_hit_kernel<RANGED, 4>), grid, block, 0, stream, p, k, count, index, root, hit7);
+  else if (k <= 8) hipLaunchKernelGGL((multi_hit_kernel<RANGED, 8>), grid, block, 0, stream, p, k, count, index, root, hit7);
+  else if (k <= 16) hipLaunchKernelGGL((multi_hit_kernel<RANGED, 16>), grid, block, 0, stream, p, k, count, index, root, hit7);
+  else hipLaunchKernelGGL((multi_hit_kernel<RANGED, 32>), grid, block, 0, stream, p, k, count, index, root, hit7);
+  return hipGetLastError();
+}
+
+hipError_t launch_multi_hit_rays(const KParams &p, int k, int32_t *count, int32_t *index, uint8_t *root, float *hit7, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (k < 1 || k > kMultiHitMaxK) return hipErrorInvalidValue;
+  if (count == nullptr && index == nullptr && root == nullptr && hit7 == nullptr) return hipErrorInvalidValue;
+  if ((p.ray_tlo_dev == nullptr) != (p.ray_thi_dev == nullptr)) return hipErrorInvalidValue;
+  return p.ray_tlo_dev != nullptr ? launch_multi_hit_cap<true>(p, k, count, index, root, hit7, stream)
+                                  : launch_multi_hit_cap<false>(p, k, count, index, root, hit7, stream);
+}
+
 __global__ __launch_bounds__(256) void camera_rays_kernel(Cam cam, int h, int w, float *rays) {
   const int64_t n = (int64_t)h * w;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {

@@ -398,6 +398,11 @@ hipError_t launch_intersect_rays(const KParams &p, float t_min, float t_max, int
 // ... the two lane kernels with ray i's interval from (p.ray_tlo_dev[i], p.ray_thi_dev[i]) (both non-null)
 hipError_t launch_intersect_rays_ranged(const KParams &p, int32_t *index, float *hit7, hipStream_t stream);
 hipError_t launch_occluded_rays_ranged(const KParams &p, hipStream_t stream);
+// rt_multi_hit_rays[_ranged]: the first k (1 <= k <= kMultiHitMaxK) crossings of each ray in (t, j, root) order and their count, one lane per
+// ray: count[i], index / root [i * k + s], hit7 [(i * k + s) * 7 ..] (any may be nullptr, not all).  The interval: (p.ray_tlo, p.ray_thi), or
+// ray i's own with p.ray_tlo_dev / p.ray_thi_dev (both set, or neither)
+constexpr int kMultiHitMaxK = 32;
+hipError_t launch_multi_hit_rays(const KParams &p, int k, int32_t *count, int32_t *index, uint8_t *root, float *hit7, hipStream_t stream);
 // the primary rays of an h x w frame through p.cam (get_ray at pixel_u / pixel_v), row-major from the top row: rays[6 (row w + col) ..]
 hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStream_t stream);
 // block = 64 * waves_per_wg threads (4, 8 or 16 waves); grid = persistent workgroups
