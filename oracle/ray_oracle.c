@@ -402,8 +402,9 @@ static inline aabb node_aabb(const orc_bvh *t, int32_t i) {
 static const float scene_epsilon = 0.1f;                /* ray.fut:3 */
 
 /* objs_hit (ray.fut:76-86) with bvh_fold (bvh.fut:61-84) inlined as the literal
- * parent-pointer walk: state (acc=(j,tmax), cur, prev). */
-static inline int objs_hit(const orc_bvh *bvh, ray r, float t_min, float t_max, hit *out, orc_counters *cnt) {
+ * parent-pointer walk: state (acc=(j,tmax), cur, prev).  *winner (if given) receives the
+ * fold's j on #some. */
+static inline int objs_hit_j(const orc_bvh *bvh, ray r, float t_min, float t_max, hit *out, orc_counters *cnt, int32_t *winner) {
   int32_t j = -1;
   float tbest = t_max;
   int32_t cur = 0, prev = PTR_INNER(-1);
@@ -436,8 +437,13 @@ static inline int objs_hit(const orc_bvh *bvh, ray r, float t_min, float t_max, 
   }
   cnt->steps += steps;
   if (steps > cnt->max_steps) cnt->max_steps = steps;
+  if (winner) *winner = j;
   if (j >= 0) return sphere_hit(&bvh->L[j], r, t_min, tbest + 1.0f, out);              /* ray.fut:83-85 */
   return 0;
+}
+
+static inline int objs_hit(const orc_bvh *bvh, ray r, float t_min, float t_max, hit *out, orc_counters *cnt) {
+  return objs_hit_j(bvh, r, t_min, t_max, out, cnt, NULL);
 }
 
 /* ------------------------------------------------------------------ ray.fut: camera, scatter, colour */
@@ -568,6 +574,183 @@ int orc_render_rows(const orc_bvh *objs, const orc_camera *cam, int64_t width, i
 int orc_render(const orc_bvh *objs, const orc_camera *cam, int64_t width, int64_t height,
                int32_t max_depth, int threads, int32_t *out, orc_counters *counters) {
   return orc_render_rows(objs, cam, width, height, 0, height, max_depth, threads, out, counters);
+}
+
+/* ------------------------------------------------------------------ caller rays
+ *
+ * Thin loops over caller-supplied rays for the ray-query tests: rays are n x 6 float32
+ * {origin.xyz, dir.xyz}, and the entries with an interval take one (t_min, t_max) per ray.
+ * The interval rule 0 <= t_min <= t_max <= 1e9 (NaN and +-inf fail it) is the library's
+ * (lane_core.h: interval_ok), not the reference's: the reference only ever calls objs_hit with
+ * (0, 1e9).  A ray whose interval fails it is a miss here, as in the library's ranged entries. */
+
+static inline ray ray_at(const float *rays, int64_t i) {
+  const float *q = rays + 6 * i;
+  ray r;
+  r.origin = vec(q[0], q[1], q[2]);
+  r.dir = vec(q[3], q[4], q[5]);
+  return r;
+}
+
+static inline int interval_ok(float t_min, float t_max) {
+  return t_min >= 0.0f && t_min <= t_max && t_max <= 1000000000.0f;
+}
+
+static inline void put_hit7(float *out, const hit *h) {
+  out[0] = h->t;
+  out[1] = h->p.x; out[2] = h->p.y; out[3] = h->p.z;
+  out[4] = h->normal.x; out[5] = h->normal.y; out[6] = h->normal.z;
+}
+
+/* objs_hit with the caller's interval: index (-1 for #none) and {t, p, normal} (zeros for #none). */
+void orc_objs_hit_rays(const orc_bvh *bvh, int64_t n, const float *rays, const float *t_min, const float *t_max,
+                       int32_t *index, float *hit7) {
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t i = 0; i < n; i++) {
+    orc_counters c;
+    memset(&c, 0, sizeof c);
+    hit h;
+    int32_t j = -1;
+    memset(hit7 + 7 * i, 0, 7 * sizeof(float));
+    if (interval_ok(t_min[i], t_max[i]) && objs_hit_j(bvh, ray_at(rays, i), t_min[i], t_max[i], &h, &c, &j))
+      put_hit7(hit7 + 7 * i, &h);
+    else
+      j = -1;
+    index[i] = j;
+  }
+}
+
+/* bvh_fold's parent-pointer walk (bvh.fut:61-84) with `contains = aabb_hit _ r t_min t_max` and
+ * every leaf it reaches handed to `visit`, in the walk's order; nothing is accumulated, so there is
+ * no early exit. */
+typedef void (*leaf_fn)(void *acc, int32_t leaf);
+
+static void leaf_walk(const orc_bvh *bvh, ray r, float t_min, float t_max, leaf_fn visit, void *acc) {
+  int32_t cur = 0, prev = PTR_INNER(-1);
+  while (cur != -1) {
+    int32_t nl = bvh->left[cur], nr = bvh->right[cur];
+    int from_left = prev == nl, from_right = prev == nr;
+    int rec = 0;
+    int32_t ptr = 0;
+    if (from_left) { rec = 1; ptr = nr; }
+    else if (!from_right) {
+      if (aabb_hit(node_aabb(bvh, cur), r, t_min, t_max)) { rec = 1; ptr = nl; }
+    }
+    if (!rec) {
+      prev = PTR_INNER(cur);
+      cur = bvh->parent[cur];
+    } else if (!PTR_IS_LEAF(ptr)) {
+      prev = PTR_INNER(cur);
+      cur = ptr;
+    } else {
+      visit(acc, PTR_LEAF_IDX(ptr));
+      prev = ptr;
+    }
+  }
+}
+
+/* sphere_hit's two roots (ray.fut:32-51) in its own arithmetic; 0 when the discriminant is not positive. */
+static inline int sphere_roots(const orc_sphere *s, ray r, float *t1, float *t2) {
+  vec3 oc = vec_sub(r.origin, s->pos);
+  float a = dot(r.dir, r.dir);
+  float b = dot(oc, r.dir);
+  float c = dot(oc, oc) - s->radius * s->radius;
+  float discriminant = b * b - a * c;
+  if (discriminant <= 0.0f) return 0;
+  *t1 = (-b - sqrtf(b * b - a * c)) / a;
+  *t2 = (-b + sqrtf(b * b - a * c)) / a;
+  return 1;
+}
+
+typedef struct { const orc_bvh *bvh; ray r; float t_min, t_max; int any; } occ_acc;
+
+static void occ_visit(void *p, int32_t j) {
+  occ_acc *a = (occ_acc *)p;
+  hit h;
+  if (sphere_hit(&a->bvh->L[j], a->r, a->t_min, a->t_max, &h)) a->any = 1;
+}
+
+/* Occlusion: 1 where some leaf the walk reaches over (t_min, t_max) has `sphere_hit L[j] r t_min t_max`
+ * = #some, else 0.  The walk runs to its end. */
+void orc_occluded_rays(const orc_bvh *bvh, int64_t n, const float *rays, const float *t_min, const float *t_max, uint8_t *out) {
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t i = 0; i < n; i++) {
+    occ_acc a = {bvh, ray_at(rays, i), t_min[i], t_max[i], 0};
+    if (interval_ok(a.t_min, a.t_max)) leaf_walk(bvh, a.r, a.t_min, a.t_max, occ_visit, &a);
+    out[i] = (uint8_t)a.any;
+  }
+}
+
+typedef struct { float t; int32_t j; int32_t root; } crossing;
+typedef struct { const orc_bvh *bvh; ray r; float t_min, t_max; crossing *c; int64_t n, cap; } cross_acc;
+
+static void cross_push(cross_acc *a, float t, int32_t j, int32_t root) {
+  if (a->n == a->cap) {
+    a->cap = a->cap ? 2 * a->cap : 64;
+    a->c = (crossing *)realloc(a->c, sizeof(crossing) * (size_t)a->cap);
+  }
+  crossing x = {t, j, root};
+  a->c[a->n++] = x;
+}
+
+static void cross_visit(void *p, int32_t j) {
+  cross_acc *a = (cross_acc *)p;
+  float t1, t2;
+  if (!sphere_roots(&a->bvh->L[j], a->r, &t1, &t2)) return;
+  if (t1 < a->t_max && t1 > a->t_min) cross_push(a, t1, j, 1);
+  if (t2 < a->t_max && t2 > a->t_min) cross_push(a, t2, j, 2);
+}
+
+static int crossing_cmp(const void *pa, const void *pb) {   /* by (t, j, root); every t is finite */
+  const crossing *a = (const crossing *)pa, *b = (const crossing *)pb;
+  if (a->t != b->t) return a->t < b->t ? -1 : 1;
+  if (a->j != b->j) return a->j < b->j ? -1 : 1;
+  return (a->root > b->root) - (a->root < b->root);
+}
+
+/* Crossings: every root 1 / root 2 of a leaf the walk reaches, strictly inside (t_min, t_max).  Per ray
+ * the count and the first k (n x k each) in (t, j, root) order: index (-1 past the count), root (1 or 2;
+ * 0 past it) and {t, p, normal} (zeros past it), p and normal as sphere_hit forms them (ray.fut:40-46). */
+void orc_crossings_rays(const orc_bvh *bvh, int64_t n, const float *rays, const float *t_min, const float *t_max, int32_t k,
+                        int32_t *count, int32_t *index, uint8_t *root, float *hit7) {
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t i = 0; i < n; i++) {
+    cross_acc a = {bvh, ray_at(rays, i), t_min[i], t_max[i], NULL, 0, 0};
+    if (interval_ok(a.t_min, a.t_max)) leaf_walk(bvh, a.r, a.t_min, a.t_max, cross_visit, &a);
+    qsort(a.c, (size_t)a.n, sizeof(crossing), crossing_cmp);
+    count[i] = (int32_t)a.n;
+    for (int32_t s = 0; s < k; s++) {
+      int32_t *ix = index + i * k + s;
+      uint8_t *rt = root + i * k + s;
+      float *h7 = hit7 + 7 * (i * k + s);
+      memset(h7, 0, 7 * sizeof(float));
+      *ix = -1;
+      *rt = 0;
+      if (s < a.n) {
+        const orc_sphere *sp = &bvh->L[a.c[s].j];
+        hit h;
+        h.t = a.c[s].t;
+        h.p = point_at_param(a.r, h.t);
+        h.normal = scale(1.0f / sp->radius, vec_sub(point_at_param(a.r, h.t), sp->pos));
+        put_hit7(h7, &h);
+        *ix = a.c[s].j;
+        *rt = (uint8_t)a.c[s].root;
+      }
+    }
+    free(a.c);
+  }
+}
+
+/* ray_colour (ray.fut:126-148) of each ray with the given max_depth: its colour before colour_to_pixel
+ * (n x 3).  The interval is ray_colour's own, (0, 1e9). */
+void orc_ray_colour_rays(const orc_bvh *bvh, int64_t n, const float *rays, int32_t max_depth, float *colour3) {
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t i = 0; i < n; i++) {
+    orc_counters c;
+    memset(&c, 0, sizeof c);
+    vec3 col = ray_colour(bvh, ray_at(rays, i), max_depth, &c);
+    colour3[3 * i + 0] = col.x; colour3[3 * i + 1] = col.y; colour3[3 * i + 2] = col.z;
+  }
 }
 
 int orc_num_threads(void) {

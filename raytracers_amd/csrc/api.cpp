@@ -1852,6 +1852,17 @@ int pooled_rays_plan(rt_context *ctx, const rt_prepared *ps, int64_t n, Plan *pl
     const bool huge = rt_scene_exceeds_l2(ps);
     const bool wide = ctx->wide_waves == 2 || (ctx->wide_waves == 1 && nblocks >= (huge ? 40000 : 100000) && nblocks > ctx->px_max_tiles);
     if (int rc = make_plan(ctx, ps, pl, nblocks, 0, wide)) return rc;
+    // The caller-ray loops exist for workgroups of 16 and 4 waves only (choose_pooled).  A scene that fits in LDS whole beside 12 or 8 waves
+    // but not beside 16 (about 600 spheres) made the plan pick one of those, and the launch failed: plan 16 waves instead, else 4.
+    if (pl->variant == RT_VARIANT_POOLED && pl->waves != 16 && pl->waves != 4) {
+      Plan p16{};
+      if (make_plan(ctx, ps, &p16, nblocks, 16, wide) == 0) {
+        *pl = p16;
+      } else {
+        *pl = Plan{};
+        if (int rc = make_plan(ctx, ps, pl, nblocks, 4, wide)) return rc;
+      }
+    }
   }
   return 0;
 }

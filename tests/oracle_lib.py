@@ -71,6 +71,13 @@ def lib():
         L.orc_checksum.argtypes = [C.c_void_p, C.c_int64]
         L.orc_checksum.restype = C.c_uint32
         L.orc_num_threads.restype = C.c_int
+        L.orc_objs_hit_rays.argtypes = [C.POINTER(Bvh), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_occluded_rays.argtypes = [C.POINTER(Bvh), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_crossings_rays.argtypes = [C.POINTER(Bvh), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_ray_colour_rays.argtypes = [C.POINTER(Bvh), C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
+        for f in (L.orc_objs_hit_rays, L.orc_occluded_rays, L.orc_crossings_rays, L.orc_ray_colour_rays):
+            f.restype = None
         L.rust_bvh_build.argtypes = [C.POINTER(Sphere), C.c_int64, C.c_void_p]
         L.rust_bvh_free.argtypes = [C.c_void_p]
         L.rust_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
@@ -132,6 +139,51 @@ class OracleScene:
                                    out.ctypes.data, C.byref(cnt))
         assert rc == 0
         return out, cnt.as_dict()
+
+    # --- caller rays: the literal walk over n x 6 float32 rays, one (t_min, t_max) per ray (scalars are broadcast); an interval that fails
+    # 0 <= t_min <= t_max <= 1e9 is a miss (the library's rule)
+    def _ray_args(self, rays, t_min=None, t_max=None):
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        if t_min is None:
+            return r, n
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(t_min, dtype=np.float32), (n,)))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, dtype=np.float32), (n,)))
+        return r, n, lo, hi
+
+    def objs_hit_rays(self, rays, t_min, t_max):
+        """objs_hit bvh r t_min t_max (ray.fut:76-86) -> (index (n,) int32, -1 for #none; hit (n, 7) float32 {t, p, normal})."""
+        r, n, lo, hi = self._ray_args(rays, t_min, t_max)
+        idx = np.empty(n, np.int32)
+        hit = np.empty((n, 7), np.float32)
+        lib().orc_objs_hit_rays(C.byref(self.bvh), n, r.ctypes.data, lo.ctypes.data, hi.ctypes.data, idx.ctypes.data, hit.ctypes.data)
+        return idx, hit
+
+    def occluded_rays(self, rays, t_min, t_max):
+        """(n,) bool: some leaf the walk reaches over (t_min, t_max) has sphere_hit L[j] r t_min t_max = #some."""
+        r, n, lo, hi = self._ray_args(rays, t_min, t_max)
+        out = np.empty(n, np.uint8)
+        lib().orc_occluded_rays(C.byref(self.bvh), n, r.ctypes.data, lo.ctypes.data, hi.ctypes.data, out.ctypes.data)
+        return out.astype(bool)
+
+    def crossings_rays(self, rays, t_min, t_max, k):
+        """(count (n,) int32, index (n, k) int32, root (n, k) uint8, hit (n, k, 7) float32): every root of a reached leaf strictly inside
+        (t_min, t_max), the first k in (t, j, root) order."""
+        r, n, lo, hi = self._ray_args(rays, t_min, t_max)
+        cnt = np.empty(n, np.int32)
+        idx = np.empty((n, k), np.int32)
+        root = np.empty((n, k), np.uint8)
+        hit = np.empty((n, k, 7), np.float32)
+        lib().orc_crossings_rays(C.byref(self.bvh), n, r.ctypes.data, lo.ctypes.data, hi.ctypes.data, int(k), cnt.ctypes.data,
+                                 idx.ctypes.data, root.ctypes.data, hit.ctypes.data)
+        return cnt, idx, root, hit
+
+    def ray_colour_rays(self, rays, max_depth):
+        """ray_colour objs r max_depth (ray.fut:126-148) -> (n, 3) float32, before colour_to_pixel."""
+        r, n = self._ray_args(rays)
+        col = np.empty((n, 3), np.float32)
+        lib().orc_ray_colour_rays(C.byref(self.bvh), n, r.ctypes.data, int(max_depth), col.ctypes.data)
+        return col
 
     # --- canonical arrays for I/L parity checks -------------------------------------
     def arrays(self):
