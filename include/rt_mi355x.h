@@ -121,6 +121,25 @@ int rt_prepared_get_bvh(rt_context *ctx, const rt_prepared *ps, float *L7, float
                         int32_t *left, int32_t *right, int32_t *parent);
 int rt_prepared_get_camera(rt_context *ctx, const rt_prepared *ps, float cam12[12]);
 
+/* ---- scenes from spheres in device memory: prepare, and update in place ---------------------------------------------
+ * spheres7_dev: n x 7 float32 {pos.xyz, colour.rgb, radius} in the context's device memory (a hipMalloc'd buffer, a torch tensor).
+ * A scene prepared from device spheres, or updated to them, is indistinguishable from rt_scene_from_spheres + rt_prepare_scene on
+ * the same bytes: the BVH arrays (rt_prepared_get_bvh, byte for byte), the tree height, the camera, the culling guards and with them
+ * every later launch's instantiation (rt_context_last_launch), every pixel and every caller-ray output, under every variant.  Spheres
+ * with NaN / inf components or a radius below 2^-20 are accepted as that route accepts them (the same BVH bytes; culling off).
+ * Both entries run on the context's stream and return after the build has completed: the caller may then overwrite or free
+ * spheres7_dev -- nothing of the prepared scene points at it.  The option gpu_build = 0 copies the spheres to the host and builds there.
+ * Refused (non-zero, rt_last_error set, nothing launched, ps unchanged): a NULL pointer, h or w <= 0, n < 2 or n > 2^26 (as
+ * rt_scene_from_spheres), a multi-device context. */
+int rt_prepare_scene_device(rt_context *ctx, rt_prepared **out, int64_t h, int64_t w, const float *spheres7_dev, int64_t n,
+                            const float look_from[3], const float look_at[3], float fov);
+/* The BVH of ps rebuilt in place from n new spheres (same n, same camera, same handle and device block).  It first drains the work
+ * on the context's streams that may still read the old arrays, then puts every view of ps (tile orders, pixel lists, class tables)
+ * back into the state of a view never rendered.  Refused as above, and also: n != rt_prepared_num_spheres(ps), and ctx other than the
+ * context that prepared ps.  The caller must not render ps through another context while an update is in flight, and must have
+ * synchronised any other context that rendered it.  After a HIP failure (not a refusal) the scene's contents are unspecified: free it. */
+int rt_prepared_update_spheres(rt_context *ctx, rt_prepared *ps, const float *spheres7_dev, int64_t n);
+
 /* ---- render (ray.fut:246-247 -> render_image :166-169) -------------------------- */
 /* Whole image: out_dev = device pointer to h*w int32, row-major from the top row. */
 int rt_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, int32_t *out_dev);

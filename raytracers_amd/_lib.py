@@ -17,7 +17,7 @@ RT_SYMBOLS = [
     "rt_scene_rgbbox", "rt_scene_irreg", "rt_scene_floor", "rt_scene_from_spheres", "rt_scene_num_spheres",
     "rt_scene_free",
     "rt_prepare_scene", "rt_prepared_free", "rt_prepared_num_spheres", "rt_prepared_height", "rt_prepared_get_bvh",
-    "rt_prepared_get_camera",
+    "rt_prepared_get_camera", "rt_prepare_scene_device", "rt_prepared_update_spheres",
     "rt_render", "rt_render_part", "rt_render_image", "rt_render_batch", "rt_render_part_inplace", "rt_ipc_export", "rt_ipc_import", "rt_ipc_close", "rt_part_rows", "rt_place_part", "rt_place_parts", "rt_place_parts_strided", "rt_place_parts_batch", "rt_render_stats", "rt_render_trace",
     "rt_render_timed",
     "rt_trace_rays", "rt_intersect_rays", "rt_occluded_rays", "rt_intersect_rays_ranged", "rt_occluded_rays_ranged",
@@ -79,6 +79,8 @@ def _load():
         "rt_prepared_height": (i32, [vp]),
         "rt_prepared_get_bvh": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
         "rt_prepared_get_camera": (C.c_int, [vp, vp, vp]),
+        "rt_prepare_scene_device": (C.c_int, [vp, C.POINTER(vp), i64, i64, vp, i64, pf, pf, C.c_float]),
+        "rt_prepared_update_spheres": (C.c_int, [vp, vp, vp, i64]),
         "rt_render": (C.c_int, [vp, vp, i64, i64, vp]),
         "rt_render_part": (C.c_int, [vp, vp, i64, i64, i32, i32, i32, i32, vp]),
         "rt_render_image": (C.c_int, [vp, vp, i64, i64, vp, i32, i32, i32, i32, vp]),

@@ -218,6 +218,17 @@ class Prepared:
                                                                        ("L", "bmin", "bmax", "left", "right", "parent")]))
         return A
 
+    def update_spheres(self, spheres):
+        """Rebuild this prepared scene in place from new spheres (rt_prepared_update_spheres): the same count, camera and handle;
+        every view's tile order / pixel list starts afresh.  `spheres` as for prepare_scene_from_spheres.  Returns after the build:
+        the caller may then overwrite the source."""
+        ptr, n, keep = _device_spheres(self.ctx, spheres)
+        try:
+            self.ctx._check(lib.rt_prepared_update_spheres(self.ctx._h, self._h, C.c_void_p(ptr), n))
+        finally:
+            if keep is not None:
+                keep.free()
+
     def stats(self, max_depth=MAX_DEPTH):
         s = (C.c_uint64 * 3)()
         self.ctx._check(lib.rt_render_stats(self.ctx._h, self._h, self.h, self.w, int(max_depth), s))
@@ -240,6 +251,45 @@ def prepare_scene(h, w, scene):
     ctx = scene.ctx
     p = C.c_void_p()
     ctx._check(lib.rt_prepare_scene(ctx._h, C.byref(p), int(h), int(w), scene._h))
+    return Prepared(ctx, p, h, w)
+
+
+def _device_spheres(ctx, spheres):
+    """(pointer, n, keep-alive) for `spheres` (n x 7 {pos.xyz, colour.rgb, radius}): a numpy array is uploaded to a fresh device
+    buffer; a contiguous float32 torch tensor on the context's device is used in place."""
+    if hasattr(spheres, "data_ptr"):
+        dev = ctx.device_info()["device"]
+        if str(spheres.dtype) != "torch.float32" or not spheres.is_contiguous() or spheres.device.type != "cuda" or spheres.device.index != dev:
+            raise ValueError(f"spheres: a contiguous float32 tensor on cuda:{dev} is required")
+        if spheres.dim() != 2 or spheres.shape[1] != 7:
+            raise ValueError("spheres must be (n, 7): pos.xyz, colour.rgb, radius")
+        return spheres.data_ptr(), int(spheres.shape[0]), None
+    a = np.ascontiguousarray(spheres, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 7:
+        raise ValueError("spheres must be (n, 7): pos.xyz, colour.rgb, radius")
+    buf = DeviceBuffer(ctx, max(a.nbytes, 4))
+    try:
+        if a.nbytes:
+            ctx._check(lib.rt_copy_to_device(ctx._h, C.c_void_p(buf.ptr), a.ctypes.data, a.nbytes))
+    except BaseException:
+        buf.free()
+        raise
+    return buf.ptr, a.shape[0], buf
+
+
+def prepare_scene_from_spheres(ctx, spheres, h, w, look_from, look_at, fov):
+    """prepare_scene of the scene {look_from, look_at, fov, spheres} straight from device memory (rt_prepare_scene_device): the same
+    prepared scene as prepare_scene(h, w, ctx.scene_from_spheres(...)) on the same bytes.  `spheres`: (n, 7) float32 -- a numpy array
+    (uploaded to a temporary device buffer) or a contiguous torch tensor on the context's device, read in place on the context's stream."""
+    ptr, n, keep = _device_spheres(ctx, spheres)
+    lf = (C.c_float * 3)(*look_from)
+    la = (C.c_float * 3)(*look_at)
+    p = C.c_void_p()
+    try:
+        ctx._check(lib.rt_prepare_scene_device(ctx._h, C.byref(p), int(h), int(w), C.c_void_p(ptr), n, lf, la, float(fov)))
+    finally:
+        if keep is not None:
+            keep.free()
     return Prepared(ctx, p, h, w)
 
 

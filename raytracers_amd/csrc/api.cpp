@@ -1289,6 +1289,60 @@ extern "C" int rt_scene_free(rt_context *ctx, rt_scene *scene) {
 }
 
 // ------------------------------------------------------------------------------------ prepare_scene
+namespace {
+// One device allocation for every array of the prepared scene (256-byte aligned pieces), for ps->n spheres.
+hipError_t alloc_prepared_block(rt_context *ctx, rt_prepared *ps) {
+  const size_t n = static_cast<size_t>(ps->n), ni = n - 1;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~size_t(255); return at; };
+  const size_t o_L7 = carve(n * 28), o_bmin = carve(ni * 12), o_bmax = carve(ni * 12), o_left = carve(ni * 4),
+               o_right = carve(ni * 4), o_parent = carve(ni * 4), o_nodes = carve(ni * 32), o_nodes64 = carve(ni * 64),
+               o_sph = carve(n * 16), o_col = carve(n * 16);
+  ps->block_bytes = off;
+  const hipError_t e = pool_alloc(ctx, &ps->block, &ps->block_bytes);
+  if (e != hipSuccess) {
+    ps->block = nullptr;
+    return e;
+  }
+  char *b = ps->block;
+  ps->L7 = reinterpret_cast<float *>(b + o_L7); ps->bmin = reinterpret_cast<float *>(b + o_bmin);
+  ps->bmax = reinterpret_cast<float *>(b + o_bmax); ps->left = reinterpret_cast<int32_t *>(b + o_left);
+  ps->right = reinterpret_cast<int32_t *>(b + o_right); ps->parent = reinterpret_cast<int32_t *>(b + o_parent);
+  ps->nodes = reinterpret_cast<float4 *>(b + o_nodes); ps->nodes64 = reinterpret_cast<float4 *>(b + o_nodes64);
+  ps->sph = reinterpret_cast<float4 *>(b + o_sph); ps->col = reinterpret_cast<float4 *>(b + o_col);
+  return hipSuccess;
+}
+
+// gpu_build = 0: the BVH built on the host and uploaded into ps's block (height, treelet depth, root box set).  Returns non-zero with
+// the context's error set when a copy cannot be enqueued; *e: the final synchronisation's status.
+int host_build_upload(rt_context *ctx, rt_prepared *ps, const std::vector<rt::Sphere> &spheres, hipError_t *e) {
+  const size_t n = spheres.size(), ni = n - 1;
+  int rc = 0;
+  auto put = [&](void *dst, const void *src, size_t bytes) {
+    if (!rc && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(ctx, "hipMemcpyAsync failed");
+  };
+  const rt::Lbvh bvh = rt::build_lbvh(spheres);
+  const rt::TravLayout tl = rt::make_trav_layout(bvh, ctx->treelet);
+  ps->height = tl.height;
+  ps->tl_depth = tl.treelet_depth;
+  put(ps->L7, bvh.L.data(), n * sizeof(rt::Sphere));
+  put(ps->bmin, bvh.bmin.data(), ni * 3 * sizeof(float));
+  put(ps->bmax, bvh.bmax.data(), ni * 3 * sizeof(float));
+  put(ps->left, bvh.left.data(), ni * sizeof(int32_t));
+  put(ps->right, bvh.right.data(), ni * sizeof(int32_t));
+  put(ps->parent, bvh.parent.data(), ni * sizeof(int32_t));
+  put(ps->nodes, tl.nodes.data(), ni * sizeof(rt::TravNode));
+  put(ps->nodes64, tl.nodes64.data(), ni * 64);
+  std::copy(tl.root_lo, tl.root_lo + 3, ps->root_lo);
+  std::copy(tl.root_hi, tl.root_hi + 3, ps->root_hi);
+  put(ps->sph, tl.sph.data(), n * 16);
+  put(ps->col, tl.col.data(), n * 16);
+  // the host staging vectors die at scope exit: drain the copies first
+  *e = hipStreamSynchronize(ctx->stream);
+  return rc;
+}
+}  // namespace
+
 extern "C" int rt_prepare_scene(rt_context *ctx, rt_prepared **out, int64_t h, int64_t w, const rt_scene *scene) {
   RT_LOCK(ctx);
   if (!ctx || !out || !scene) return fail(ctx, "null argument");
@@ -1297,35 +1351,17 @@ extern "C" int rt_prepare_scene(rt_context *ctx, rt_prepared **out, int64_t h, i
   RT_HIP(ctx, hipSetDevice(ctx->device));
   (void)hipGetLastError();   // (as in enqueue_render)
   auto ps = std::make_unique<rt_prepared>();
-  const size_t n = scene->desc.spheres.size(), ni = n - 1;
+  const size_t n = scene->desc.spheres.size();
   ps->n = static_cast<int64_t>(n);
   ps->home = ctx;
   ps->h = h; ps->w = w;
   ps->cam = rt::scene_camera(scene->desc, h, w);
   int rc = 0;
   hipError_t e = hipSuccess;
-  // one device allocation for every array of the prepared scene (256-byte aligned pieces)
-  {
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~size_t(255); return at; };
-    const size_t o_L7 = carve(n * 28), o_bmin = carve(ni * 12), o_bmax = carve(ni * 12), o_left = carve(ni * 4),
-                 o_right = carve(ni * 4), o_parent = carve(ni * 4), o_nodes = carve(ni * 32), o_nodes64 = carve(ni * 64),
-                 o_sph = carve(n * 16), o_col = carve(n * 16);
-    ps->block_bytes = off;
-    RT_HIP(ctx, pool_alloc(ctx, &ps->block, &ps->block_bytes));
-    char *b = ps->block;
-    ps->L7 = reinterpret_cast<float *>(b + o_L7); ps->bmin = reinterpret_cast<float *>(b + o_bmin);
-    ps->bmax = reinterpret_cast<float *>(b + o_bmax); ps->left = reinterpret_cast<int32_t *>(b + o_left);
-    ps->right = reinterpret_cast<int32_t *>(b + o_right); ps->parent = reinterpret_cast<int32_t *>(b + o_parent);
-    ps->nodes = reinterpret_cast<float4 *>(b + o_nodes); ps->nodes64 = reinterpret_cast<float4 *>(b + o_nodes64);
-    ps->sph = reinterpret_cast<float4 *>(b + o_sph); ps->col = reinterpret_cast<float4 *>(b + o_col);
-  }
+  RT_HIP(ctx, alloc_prepared_block(ctx, ps.get()));
   // multi-device context: the other devices build their replicas while this one builds its own (no early return from
   // here to group_prepare_end)
   if (ctx->group) rti::group_prepare_begin(ctx, ps.get(), h, w, scene);
-  auto put = [&](void *dst, const void *src, size_t bytes) {
-    if (!rc && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(ctx, "hipMemcpyAsync failed");
-  };
   if (ctx->gpu_build) {
     // ---- BVH construction on the GPU (bvh_build.hip): upload the spheres, build in place ----
     // (a multi-device prepare_scene uploads from one host thread per device: the lock covers the look-up and the
@@ -1377,24 +1413,7 @@ extern "C" int rt_prepare_scene(rt_context *ctx, rt_prepared **out, int64_t h, i
       pool_free(ctx, tmp, tmp_bytes);
     }
   } else {
-    const rt::Lbvh bvh = rt::build_lbvh(scene->desc.spheres);
-    const rt::TravLayout tl = rt::make_trav_layout(bvh, ctx->treelet);
-    ps->height = tl.height;
-    ps->tl_depth = tl.treelet_depth;
-    put(ps->L7, bvh.L.data(), n * sizeof(rt::Sphere));
-    put(ps->bmin, bvh.bmin.data(), ni * 3 * sizeof(float));
-    put(ps->bmax, bvh.bmax.data(), ni * 3 * sizeof(float));
-    put(ps->left, bvh.left.data(), ni * sizeof(int32_t));
-    put(ps->right, bvh.right.data(), ni * sizeof(int32_t));
-    put(ps->parent, bvh.parent.data(), ni * sizeof(int32_t));
-    put(ps->nodes, tl.nodes.data(), ni * sizeof(rt::TravNode));
-    put(ps->nodes64, tl.nodes64.data(), ni * 64);
-    std::copy(tl.root_lo, tl.root_lo + 3, ps->root_lo);
-    std::copy(tl.root_hi, tl.root_hi + 3, ps->root_hi);
-    put(ps->sph, tl.sph.data(), n * 16);
-    put(ps->col, tl.col.data(), n * 16);
-    // the host staging vectors die at scope exit: drain the copies first
-    e = hipStreamSynchronize(ctx->stream);
+    rc = host_build_upload(ctx, ps.get(), scene->desc.spheres, &e);
   }
   if (!rc && e == hipSuccess) {
     // culling by the best hit (lane_core.h: cull_limit): the scene's guards and constants; the spheres' side once per scene
@@ -1439,6 +1458,130 @@ extern "C" int rt_prepared_free(rt_context *ctx, rt_prepared *ps) {
   if (ps->classes_pinned && ps->classes_chunk < 0) (void)hipHostFree(ps->classes_pinned);
   if (ps->classes_chunk >= 0 && ps->classes_owner) ps->classes_owner->class_chunks_used &= ~(1ull << ps->classes_chunk);
   delete ps;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------ scenes from device spheres
+namespace {
+// ps's arrays built from its ps->n spheres at spheres7_dev (device memory of ctx), with the culling guards computed from the same
+// spheres: what rt_prepare_scene computes from a host scene of the same bytes.  gpu_build: the statistics reduction (launch_cull_stats)
+// goes ahead of the build on the context's stream and lands in the pinned block, read after the build's one synchronisation;
+// gpu_build = 0: the spheres copied back and the host builder, as rt_prepare_scene.  Returns with the stream drained; *e: a HIP failure.
+int build_from_device(rt_context *ctx, rt_prepared *ps, const float *spheres7_dev, hipError_t *e) {
+  const size_t n = static_cast<size_t>(ps->n);
+  *e = hipSuccess;
+  if (ctx->gpu_build) {
+    const size_t build_bytes = (rtk::gpu_build_scratch_bytes(static_cast<int>(n)) + 255) & ~size_t(255);
+    size_t tmp_bytes = build_bytes + rtk::cull_stats_scratch_bytes();
+    char *tmp = nullptr;
+    *e = pool_alloc(ctx, &tmp, &tmp_bytes);
+    if (*e != hipSuccess) return 0;
+    auto *slot = reinterpret_cast<const rtk::CullStatsDev *>(ctx->pinned + rtk::kCullStatsPinnedOffset);
+    *e = rtk::launch_cull_stats(spheres7_dev, static_cast<int>(n), reinterpret_cast<rtk::CullStatsDev *>(tmp + build_bytes),
+                                const_cast<rtk::CullStatsDev *>(slot), ctx->stream);
+    if (*e == hipSuccess) {
+      rtk::GpuBvhOut o{ps->L7, ps->bmin, ps->bmax, ps->left, ps->right, ps->parent, ps->nodes, ps->nodes64, ps->sph, ps->col};
+      *e = rtk::gpu_build_bvh(spheres7_dev, static_cast<int>(n), o, tmp, ctx->pinned, ctx->stream, &ps->height, ps->root_lo, ps->root_hi);
+      ps->tl_depth = rtk::kTreeletDepth;
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    pool_free(ctx, tmp, tmp_bytes);
+    if (*e != hipSuccess) return 0;
+    rt::CullStats st;
+    for (int a = 0; a < 3; ++a) {
+      st.lo[a] = slot->lo[a];
+      st.hi[a] = slot->hi[a];
+    }
+    st.r_min = slot->r_min;
+    st.r_max = slot->r_max;
+    st.c_max = slot->c_max;
+    st.bad = slot->bad != 0;
+    ps->cull = rt::cull_finish(st, n, 0);
+  } else {
+    std::vector<rt::Sphere> host(n);
+    *e = hipMemcpyAsync(host.data(), spheres7_dev, n * sizeof(rt::Sphere), hipMemcpyDeviceToHost, ctx->stream);
+    if (*e == hipSuccess) *e = hipStreamSynchronize(ctx->stream);
+    if (*e != hipSuccess) return 0;
+    if (int rc = host_build_upload(ctx, ps, host, e)) return rc;
+    if (*e != hipSuccess) return 0;
+    ps->cull = rt::cull_scene_constants(host, 0);
+  }
+  // (as rt_prepare_scene: every box contains its subtree, bvh.fut:47; a tree taller than 15 levels gets the spill regions here)
+  ps->cull.ok = ps->cull.ok && ps->height <= static_cast<int>(log2f(static_cast<float>(n))) + 2;
+  if (ctx->wide_waves != 0 && ps->height > 15 && n < (size_t(1) << 22)) return ensure_spill(ctx, 64 * (ps->height + 2));
+  return 0;
+}
+
+// The checks both device-sphere entries share (a refusal changes nothing)
+int device_spheres_ok(rt_context *ctx, const float *spheres7_dev, int64_t n) {
+  if (!spheres7_dev) return fail(ctx, "null argument");
+  if (n < 2 || n > (int64_t(1) << rtk::kMaxSpheresLog2)) return fail(ctx, "scene needs 2 .. 2^26 spheres");
+  if (ctx->group) return fail(ctx, "device spheres: a multi-device context is not supported (use a context on one device)");
+  return 0;
+}
+
+// Every view of ps back to the state of a view never rendered.  The work that may still read the scene's arrays or the views' buffers is
+// drained first: the context's streams, then each view's events (its sorts and its class table's copy).  The views' blocks go back to
+// where they came from -- this context's arena / pool (block_owner == ps->home == ctx), or a plain allocation -- so no other context's
+// lock is taken (find_view: a block's owner is the scene's home context or nobody).
+void reset_views(rt_context *ctx, rt_prepared *ps) {
+  drain_streams(ctx);
+  for (auto &o : ps->orders) {
+    for (hipEvent_t ev : {o.sort_event, o.sort_event_px, o.classes_event})
+      if (ev) (void)hipEventSynchronize(ev);
+    if (o.block) {
+      if (o.block_owner == ctx) pool_free(ctx, o.block, o.block_bytes);
+      else if (!o.block_owner) (void)hipFree(o.block);
+      o.block = nullptr;
+    }
+    for (hipEvent_t ev : {o.sort_event, o.sort_event_px, o.classes_event})
+      if (ev) (void)hipEventDestroy(ev);
+  }
+  ps->orders.clear();
+}
+}  // namespace
+
+extern "C" int rt_prepare_scene_device(rt_context *ctx, rt_prepared **out, int64_t h, int64_t w, const float *spheres7_dev, int64_t n,
+                                       const float look_from[3], const float look_at[3], float fov) {
+  RT_LOCK(ctx);
+  if (!ctx || !out || !look_from || !look_at) return fail(ctx, "null argument");
+  if (int rc = device_spheres_ok(ctx, spheres7_dev, n)) return rc;
+  if (h <= 0 || w <= 0) return fail(ctx, "image size must be positive");
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();   // (as in enqueue_render)
+  auto ps = std::make_unique<rt_prepared>();
+  ps->n = n;
+  ps->home = ctx;
+  ps->h = h; ps->w = w;
+  rt::SceneDesc d;   // (the camera of a scene with these settings: rt_scene_from_spheres + rt_prepare_scene)
+  std::copy(look_from, look_from + 3, d.look_from);
+  std::copy(look_at, look_at + 3, d.look_at);
+  d.fov = fov;
+  ps->cam = rt::scene_camera(d, h, w);
+  RT_HIP(ctx, alloc_prepared_block(ctx, ps.get()));
+  hipError_t e = hipSuccess;
+  const int rc = build_from_device(ctx, ps.get(), spheres7_dev, &e);
+  if (rc || e != hipSuccess) {
+    rt_prepared_free(ctx, ps.release());
+    return rc ? rc : hip_fail(ctx, e, "rt_prepare_scene_device");
+  }
+  *out = ps.release();
+  return 0;
+}
+
+extern "C" int rt_prepared_update_spheres(rt_context *ctx, rt_prepared *ps, const float *spheres7_dev, int64_t n) {
+  RT_LOCK(ctx);
+  if (!ctx || !ps) return fail(ctx, "null argument");
+  if (int rc = device_spheres_ok(ctx, spheres7_dev, n)) return rc;
+  if (ps->home != ctx) return fail(ctx, "rt_prepared_update_spheres: only through the context that prepared the scene");
+  if (n != ps->n) return fail(ctx, "rt_prepared_update_spheres: n must equal rt_prepared_num_spheres (" + std::to_string(ps->n) + ")");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  reset_views(ctx, ps);
+  hipError_t e = hipSuccess;
+  if (int rc = build_from_device(ctx, ps, spheres7_dev, &e)) return rc;
+  if (e != hipSuccess) return hip_fail(ctx, e, "rt_prepared_update_spheres");
   return 0;
 }
 

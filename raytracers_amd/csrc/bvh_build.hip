@@ -1399,8 +1399,10 @@ void warm_build_kernels() {   // see warm_render_kernels; with the context's dev
                             (int)sizeof(unsigned) * 4 * kNumNT * ((kRankMaxN + 4 * kNumNT - 1) / (4 * kNumNT)));
 }
 // host-pinned block the kernels report through: [0] max depth, [1] "depth changed" flag,
-// [4..11] the root's traversal record, [16..] phase timestamps of the small-scene kernel
-size_t gpu_build_pinned_bytes() { return 64 * sizeof(int); }
+// [4..11] the root's traversal record, [16..35] phase timestamps of the small-scene kernel,
+// bytes [kCullStatsPinnedOffset, + 48) the spheres' statistics (launch_cull_stats)
+size_t gpu_build_pinned_bytes() { return kCullStatsPinnedOffset + 256; }
+static_assert(kCullStatsPinnedOffset >= 64 * sizeof(int), "the statistics' slot follows the build's report");
 
 namespace {
 __global__ __launch_bounds__(kBT) void copy_words_kernel(const uint4 *src, uint4 *dst, size_t n16) {
@@ -1588,6 +1590,129 @@ hipError_t gpu_build_bvh(const float *sph7_dev, int n, const GpuBvhOut &o, char 
     root_hi[k] = root[4 + k];
   }
   return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------
+// The spheres' statistics behind the culling guards (rt_device.hpp: launch_cull_stats; the host's rt::cull_stats).  The pattern of
+// centres_minmax_kernel / minmax_final_kernel: grid-stride loads, a shuffle reduction across each wave and one through LDS per block into
+// the block's partial record, then one block over the partials -- no counter to zero, and min / max / or are exact, so the record does not
+// depend on the order in which blocks finish.  fminf / fmaxf drop a NaN, the host's std::min / std::max keep either operand: they differ
+// only where `bad` is set, and the guards then ignore the rest.  +-0 may come out of a min / max in either sign: the host uses lo / hi only
+// through hi - lo and the centre, and the centre only through squared differences (rt::cull_origin_ok).
+// ---------------------------------------------------------------------------------
+namespace {
+struct CullAcc {
+  float lo[3], hi[3], r_min, r_max;
+  double c_max;
+  int bad;
+};
+__device__ __forceinline__ void cull_acc_init(CullAcc &a) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    a.lo[k] = INFINITY;
+    a.hi[k] = -INFINITY;
+  }
+  a.r_min = INFINITY;
+  a.r_max = 0.0f;
+  a.c_max = 0.0;
+  a.bad = 0;
+}
+__device__ __forceinline__ void cull_acc_merge(CullAcc &a, const CullAcc &b) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    a.lo[k] = fminf(a.lo[k], b.lo[k]);
+    a.hi[k] = fmaxf(a.hi[k], b.hi[k]);
+  }
+  a.r_min = fminf(a.r_min, b.r_min);
+  a.r_max = fmaxf(a.r_max, b.r_max);
+  a.c_max = fmax(a.c_max, b.c_max);
+  a.bad |= b.bad;
+}
+__device__ __forceinline__ void cull_acc_load(CullAcc &a, const CullStatsDev &s) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    a.lo[k] = s.lo[k];
+    a.hi[k] = s.hi[k];
+  }
+  a.r_min = s.r_min;
+  a.r_max = s.r_max;
+  a.c_max = s.c_max;
+  a.bad = s.bad;
+}
+__device__ __forceinline__ void cull_acc_store(CullStatsDev &s, const CullAcc &a) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    s.lo[k] = a.lo[k];
+    s.hi[k] = a.hi[k];
+  }
+  s.r_min = a.r_min;
+  s.r_max = a.r_max;
+  s.c_max = a.c_max;
+  s.bad = a.bad;
+  s.pad = 0;
+}
+// the block's threads' accumulators -> thread 0's: across each wave by shuffles, then the waves' results through LDS
+__device__ __forceinline__ void cull_acc_block(CullAcc &a) {
+  constexpr int kWave = 64, kWaves = kBT / kWave;   // (gfx950: wave64)
+  __shared__ CullAcc waves[kWaves];
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+    CullAcc b;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      b.lo[k] = __shfl_xor(a.lo[k], off, kWave);
+      b.hi[k] = __shfl_xor(a.hi[k], off, kWave);
+    }
+    b.r_min = __shfl_xor(a.r_min, off, kWave);
+    b.r_max = __shfl_xor(a.r_max, off, kWave);
+    b.c_max = __shfl_xor(a.c_max, off, kWave);
+    b.bad = __shfl_xor(a.bad, off, kWave);
+    cull_acc_merge(a, b);
+  }
+  const int wave = (int)threadIdx.x / kWave, lane = (int)threadIdx.x % kWave;
+  if (lane == 0) waves[wave] = a;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < kWaves; ++w) cull_acc_merge(a, waves[w]);
+}
+__global__ __launch_bounds__(kBT) void cull_stats_kernel(const float *__restrict__ sph7, int n, CullStatsDev *__restrict__ partial) {
+  CullAcc a;
+  cull_acc_init(a);
+  for (int i = blockIdx.x * kBT + threadIdx.x; i < n; i += gridDim.x * kBT) {
+    const float *s = sph7 + 7 * (size_t)i;
+    const float p[3] = {s[0], s[1], s[2]}, r = s[6];
+    if (!(r >= 0x1p-20f) || !isfinite(r)) a.bad = 1;
+    a.r_min = fminf(a.r_min, r);
+    a.r_max = fmaxf(a.r_max, r);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (!isfinite(p[k])) a.bad = 1;
+      a.lo[k] = fminf(a.lo[k], p[k]);
+      a.hi[k] = fmaxf(a.hi[k], p[k]);
+      a.c_max = fmax(a.c_max, fabs((double)p[k]) + (double)r);   // fp64, as the host (an add of two doubles: no contraction to fear)
+    }
+  }
+  cull_acc_block(a);
+  if (threadIdx.x == 0) cull_acc_store(partial[blockIdx.x], a);
+}
+__global__ __launch_bounds__(kBT) void cull_stats_final_kernel(const CullStatsDev *__restrict__ partial, int nblocks, CullStatsDev *out) {
+  CullAcc a;
+  cull_acc_init(a);
+  for (int b = threadIdx.x; b < nblocks; b += kBT) {
+    CullAcc p;
+    cull_acc_load(p, partial[b]);
+    cull_acc_merge(a, p);
+  }
+  cull_acc_block(a);
+  if (threadIdx.x == 0) cull_acc_store(*out, a);
+}
+}  // namespace
+
+hipError_t launch_cull_stats(const float *sph7_dev, int n, CullStatsDev *partial, CullStatsDev *out, hipStream_t st) {
+  const int nb = cdiv(n, kBT), blocks = nb < kCullStatsBlocks ? nb : kCullStatsBlocks;
+  if (blocks < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cull_stats_kernel, dim3(blocks), dim3(kBT), 0, st, sph7_dev, n, partial);
+  hipLaunchKernelGGL(cull_stats_final_kernel, dim3(1), dim3(kBT), 0, st, (const CullStatsDev *)partial, blocks, out);
+  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------

@@ -372,30 +372,53 @@ int64_t part_rows(int64_t h, int32_t rows_per_tile, int32_t part, int32_t nparts
 
 // ---- culling constants (rt_host.hpp; the derivation is DESIGN.md 3.4) ----
 CullConst cull_scene_constants(const std::vector<Sphere> &ts, int height) {
+  return cull_finish(cull_stats(ts.data(), ts.size()), ts.size(), height);
+}
+
+CullStats cull_stats(const Sphere *ts, size_t n) {
+  CullStats s;
+  for (size_t i = 0; i < n; ++i) {
+    const double p[3] = {ts[i].px, ts[i].py, ts[i].pz}, r = ts[i].radius;
+    if (!(r >= 0x1p-20) || !std::isfinite(r)) s.bad = true;
+    s.r_min = std::min(s.r_min, r);
+    s.r_max = std::max(s.r_max, r);
+    for (int a = 0; a < 3; ++a) {
+      if (!std::isfinite(p[a])) s.bad = true;
+      s.lo[a] = std::min(s.lo[a], p[a]);
+      s.hi[a] = std::max(s.hi[a], p[a]);
+      s.c_max = std::max(s.c_max, std::fabs(p[a]) + r);
+    }
+  }
+  return s;
+}
+
+// min / max are exact, so any partition of the spheres merged in any order gives the same statistics (up to the sign of a zero lo / hi,
+// which cull_finish only uses through hi - lo and the centre -- and the centre only through squared differences)
+CullStats cull_stats_merge(const CullStats &a, const CullStats &b) {
+  CullStats s;
+  for (int k = 0; k < 3; ++k) {
+    s.lo[k] = std::min(a.lo[k], b.lo[k]);
+    s.hi[k] = std::max(a.hi[k], b.hi[k]);
+  }
+  s.r_min = std::min(a.r_min, b.r_min);
+  s.r_max = std::max(a.r_max, b.r_max);
+  s.c_max = std::max(a.c_max, b.c_max);
+  s.bad = a.bad || b.bad;
+  return s;
+}
+
+CullConst cull_finish(const CullStats &s, size_t n, int height) {
   CullConst c;
-  const size_t n = ts.size();
   if (n < 2) return c;
   const int sweeps = static_cast<int>(log2f(static_cast<float>(n))) + 2;   // bvh.fut:47
   if (height > sweeps) return c;
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  double r_min = INFINITY, r_max = 0.0, c_max = 0.0;
-  for (const Sphere &s : ts) {
-    const double p[3] = {s.px, s.py, s.pz}, r = s.radius;
-    if (!(r >= 0x1p-20) || !std::isfinite(r)) return c;
-    r_min = std::min(r_min, r);
-    r_max = std::max(r_max, r);
-    for (int a = 0; a < 3; ++a) {
-      if (!std::isfinite(p[a])) return c;
-      lo[a] = std::min(lo[a], p[a]);
-      hi[a] = std::max(hi[a], p[a]);
-      c_max = std::max(c_max, std::fabs(p[a]) + r);
-    }
-  }
+  if (s.bad) return c;
+  const double r_min = s.r_min, r_max = s.r_max, c_max = s.c_max;
   if (c_max > 0x1p40) return c;
   double diag2 = 0.0;
   for (int a = 0; a < 3; ++a) {
-    c.centre[a] = 0.5 * (lo[a] + hi[a]);
-    diag2 += (hi[a] - lo[a]) * (hi[a] - lo[a]);
+    c.centre[a] = 0.5 * (s.lo[a] + s.hi[a]);
+    diag2 += (s.hi[a] - s.lo[a]) * (s.hi[a] - s.lo[a]);
   }
   c.reach = 0.5 * std::sqrt(diag2) * (1.0 + 0x1p-20) + r_max;
   c.r_min = r_min;

@@ -431,6 +431,23 @@ size_t gpu_build_pinned_bytes();         // host-pinned block the build kernels 
 // Synchronises the stream; returns the tree height and the root's box.
 hipError_t gpu_build_bvh(const float *sph7_dev, int n, const GpuBvhOut &out, char *scratch, char *pinned, hipStream_t stream,
                          int *height_out, float root_lo[3], float root_hi[3]);
+// The spheres' statistics behind the culling guards (rt_host.hpp: CullStats, the host's cull_stats), reduced on the device from spheres
+// in device memory: min / max of the positions, r_min, r_max in fp32 (exact), c_max = max |p_a| + r in fp64 (the host's arithmetic), and
+// `bad`: a non-finite component or a radius failing r >= 2^-20.  Two launches (per-block partials, one block over them) on `stream`;
+// the second writes the record into `out` -- the slot of the build's pinned block at kCullStatsPinnedOffset, read by the host after
+// gpu_build_bvh's synchronisation.  `partial`: cull_stats_scratch_bytes() of device memory.
+struct CullStatsDev {
+  double c_max;
+  float lo[3], hi[3];
+  float r_min, r_max;
+  int bad;
+  int pad;
+};
+static_assert(sizeof(CullStatsDev) == 48, "CullStatsDev: 48 bytes");
+constexpr size_t kCullStatsPinnedOffset = 256;   // bytes into the pinned block (gpu_build_pinned_bytes)
+constexpr int kCullStatsBlocks = 1024;           // partials: at most this many
+constexpr size_t cull_stats_scratch_bytes() { return sizeof(CullStatsDev) * kCullStatsBlocks; }
+hipError_t launch_cull_stats(const float *sph7_dev, int n, CullStatsDev *partial, CullStatsDev *out, hipStream_t stream);
 
 constexpr int kOrderBlocksMax = 64;                                   // workgroups per shard of the tile-order sort
 constexpr int kOrderScratchInts = kMaxShards * 64 * kOrderBlocksMax;   // its scratch: [shard][bin][workgroup] counts

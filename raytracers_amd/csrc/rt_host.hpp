@@ -5,6 +5,7 @@
 // The traversal copy (TravLayout) is DERIVED from it for the kernels; the canonical
 // arrays are what parity checks dump (rt_prepared_get_bvh).
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -103,7 +104,18 @@ struct CullConst {
   float c2 = 0.0f, kappa = 0.0f;
   double centre[3] = {0, 0, 0}, reach = 0.0, r_min = 0.0;   // centre of the centres' box; R + r_max
 };
-CullConst cull_scene_constants(const std::vector<Sphere> &ts, int height);
+CullConst cull_scene_constants(const std::vector<Sphere> &ts, int height);   // == cull_finish(cull_stats(ts), n, height)
+// ... in two stages: the spheres' statistics, a reduction (any partition, any order: cull_stats_merge), and the constants derived from
+// them.  The device computes the same statistics from spheres in device memory (bvh_build.hip: launch_cull_stats).
+struct CullStats {
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};   // of the centres (+-0 either way: see cull_finish)
+  double r_min = INFINITY, r_max = 0.0;
+  double c_max = 0.0;   // max over spheres and axes of |p_a| + r, in double
+  bool bad = false;     // some component is not finite, or some radius fails r >= 2^-20 (the other fields are then unspecified)
+};
+CullStats cull_stats(const Sphere *ts, size_t n);
+CullStats cull_stats_merge(const CullStats &a, const CullStats &b);
+CullConst cull_finish(const CullStats &s, size_t n, int height);
 bool cull_origin_ok(const CullConst &c, const float origin[3]);   // |origin - centre| + R + r_max <= 2^15 r_min
 
 // rows owned by part p of nparts under the cyclic row-tile partition
