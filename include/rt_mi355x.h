@@ -74,6 +74,7 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *   "family=pixel (rays)" | "family=intersect" | "family=occluded" | "family=camera-rays"   the caller-ray entries (below)
  *   "family=intersect (per-ray)" | "family=occluded (per-ray)"   their lane kernels with per-ray intervals (rt_*_rays_ranged)
  *   "family=multi-hit k=K" | "family=multi-hit k=K (per-ray)"   rt_multi_hit_rays / rt_multi_hit_rays_ranged (K: the caller's k)
+ *   "family=nearest k=K[ pruned][ (per-point)]" | "family=none (no points)"   rt_nearest_spheres / rt_nearest_spheres_ranged (below)
  *   "family=none (no rows)"       the part owns no row of the image
  *   "family=pixel" | "family=pixel (instrumented)" | "family=persistent"
  *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2"
@@ -294,6 +295,36 @@ int rt_multi_hit_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const f
 int rt_multi_hit_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev,
                              const float *t_min_dev, const float *t_max_dev, int32_t k,
                              int32_t *count_dev, int32_t *index_dev, uint8_t *root_dev, float *hit7_dev);
+/* ---- proximity: the spheres nearest to caller-supplied points ------------------------------------------------------------------
+ * For a point p and sphere j of the prepared scene's L (centre c, radius r) the gap is the signed distance from p to the sphere's surface,
+ * negative inside, as exactly this float32 arithmetic (no contraction, correctly rounded sqrtf):
+ *     dx = p.x - c.x; dy = p.y - c.y; dz = p.z - c.z;   gap = sqrtf((dx*dx + dy*dy) + dz*dz) - r
+ * Sphere j is selected for p iff gap <= max_dist; the selected spheres are ordered by (gap, j), both ascending.  This is brute force over ALL
+ * spheres: it depends on no tree, builder or variant (the BVH walk only prunes boxes proven to hold no selected sphere).
+ * points3_dev: n x 3 float32 in the context's device memory.  count_dev: n int32, the number of selected spheres (not capped at k).
+ * index_dev: n x k int32, the first min(count, k) selected j, then -1; gap_dev: n x k float32, their gaps, then 0.0f (64-bit offsets).
+ * Any output may be NULL, not all three.  The answer for k = a is a prefix of the answer for k = b > a.  count_dev == NULL is the k-nearest
+ * mode: the walk also prunes by the k-th gap found so far; its slots are bit-identical to the same call's with count_dev set.  A point with a
+ * non-finite component gets count 0 and every slot padded.  Exact, bit for bit, for scenes whose spheres are all finite with radius >= 0
+ * (radius 0: plain k-nearest-neighbour search of the centres); for other scenes the result is unspecified, but nothing is read or written out
+ * of range.  j is an index into L (Morton order): rt_prepared_get_sphere_ids maps it back to the caller's order.
+ * Contacts: the spheres a query sphere (c_q, r_q) overlaps or touches are those selected for p = c_q, max_dist = r_q (gap <= r_q); the
+ * self-contacts of a scene pass its own centres and radii (rt_nearest_spheres_ranged), and every sphere then finds itself at gap -r.
+ * Refused (non-zero, rt_last_error set, nothing launched): n < 0 or n >= 2^31, NULL points3_dev, all outputs NULL, k < 1 or k > 32, a
+ * multi-device context, max_dist outside [0, 1e9] or not finite (rt_nearest_spheres), NULL max_dist_dev (rt_nearest_spheres_ranged).  n == 0
+ * succeeds without a launch ("family=none (no points)").  Enqueued on the context's stream (completion: rt_context_sync).  One lane per point
+ * under every variant: rt_context_last_launch "family=nearest k=<k>", with " pruned" appended in k-nearest mode and " (per-point)" for
+ * rt_nearest_spheres_ranged, whose point i has its own bound max_dist_dev[i] (n float32): an invalid one (NaN, +-inf, negative, above 1e9)
+ * makes point i a miss; -0.0 behaves as 0.0. */
+int rt_nearest_spheres(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
+                       int32_t k, int32_t *count_dev, int32_t *index_dev, float *gap_dev);
+int rt_nearest_spheres_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev,
+                              const float *max_dist_dev, int32_t k, int32_t *count_dev, int32_t *index_dev, float *gap_dev);
+/* ids_dev: n int32 in the context's device memory; ids_dev[i] = the caller's index of L[i]: the position in spheres7 given to
+ * rt_scene_from_spheres / rt_prepare_scene_device / the last rt_prepared_update_spheres, or in the generator's output for rt_scene_rgbbox /
+ * _irreg / _floor.  The Morton sort is stable, so both builders (option gpu_build) give the same ids, ascending within a run of equal keys.
+ * Enqueued on the context's stream (completion: rt_context_sync). */
+int rt_prepared_get_sphere_ids(rt_context *ctx, const rt_prepared *ps, int32_t *ids_dev);
 /* The primary rays rt_render_image would trace (get_ray at pixel_u / pixel_v), row-major from the top row: h * w x 6
  * float32 at rays_dev.  cam12 == NULL: the prepared camera.  rt_context_last_launch: "family=camera-rays". */
 int rt_camera_rays(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, const float cam12[12], float *rays_dev);

@@ -8,4 +8,5 @@ from .api import (Context, Prepared, RtError, Scene, MAX_DEPTH, ROWS_PER_TILE, V
                   VARIANT_PIXEL, part_rows, place_part, place_parts, place_parts_batch, prepare_scene, prepare_scene_from_spheres, render, render_batch_into, render_image, render_inplace_into, render_into, render_timed,
                   ipc_export, ipc_import, ipc_close, trace_rays, trace_rays_into, intersect_rays, intersect_rays_into, camera_rays,
                   camera_rays_into, occluded_rays, occluded_rays_into, intersect_rays_ranged_into, occluded_rays_ranged_into,
-                  multi_hit_rays, multi_hit_rays_into, multi_hit_rays_ranged_into)
+                  multi_hit_rays, multi_hit_rays_into, multi_hit_rays_ranged_into,
+                  nearest_spheres, nearest_spheres_into, nearest_spheres_ranged_into)

@@ -218,6 +218,21 @@ class Prepared:
                                                                        ("L", "bmin", "bmax", "left", "right", "parent")]))
         return A
 
+    def sphere_ids(self):
+        """(n,) int32 numpy array: ids[i] = the caller's index of L[i] (rt_prepared_get_sphere_ids) -- L, the order every query's sphere
+        index refers to, is Morton order; ids maps it back to the order of the spheres the scene was prepared (or last updated) from."""
+        n = self.num_spheres
+        buf = DeviceBuffer(self.ctx, max(4 * n, 4))
+        try:
+            self.sphere_ids_into(buf.ptr)
+            return buf.to_host((n,))
+        finally:
+            buf.free()
+
+    def sphere_ids_into(self, ids_ptr):
+        """Enqueue the copy of the n sphere ids (int32) to the device pointer ids_ptr.  Asynchronous: ctx.sync() completes it."""
+        self.ctx._check(lib.rt_prepared_get_sphere_ids(self.ctx._h, self._h, C.c_void_p(ids_ptr)))
+
     def update_spheres(self, spheres):
         """Rebuild this prepared scene in place from new spheres (rt_prepared_update_spheres): the same count, camera and handle;
         every view's tile order / pixel list starts afresh.  `spheres` as for prepare_scene_from_spheres.  Returns after the build:
@@ -480,6 +495,25 @@ def multi_hit_rays_ranged_into(rays_ptr, n, prepared, t_min_ptr, t_max_ptr, k, c
                                             int(k), C.c_void_p(count_ptr), C.c_void_p(index_ptr), C.c_void_p(root_ptr), C.c_void_p(hit_ptr)))
 
 
+def nearest_spheres_into(points_ptr, n, prepared, k, count_ptr, index_ptr, gap_ptr=None, max_dist=1e9):
+    """Enqueue the proximity query of `n` points (n x 3 float32 at points_ptr; rt_nearest_spheres): per point, the spheres whose gap
+    (signed distance from the point to the surface, negative inside) is <= max_dist, ordered by (gap, sphere index): their count
+    (n int32, not capped at k) to count_ptr, the first k indices into L (n x k int32, -1 past the count) to index_ptr and their gaps
+    (n x k float32, 0 past the count) to gap_ptr.  count_ptr None: k-nearest mode (the walk prunes by the k-th gap; the same slots).
+    Any pointer may be None, not all three."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_nearest_spheres(ctx._h, prepared._h, int(n), C.c_void_p(points_ptr), float(max_dist), int(k), C.c_void_p(count_ptr),
+                                      C.c_void_p(index_ptr), C.c_void_p(gap_ptr)))
+
+
+def nearest_spheres_ranged_into(points_ptr, n, prepared, max_dist_ptr, k, count_ptr, index_ptr, gap_ptr=None):
+    """nearest_spheres_into with point i's own bound max_dist_ptr[i] (n float32 on the device; rt_nearest_spheres_ranged); a bound outside
+    [0, 1e9] (NaN, +-inf included) makes its point a miss."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_nearest_spheres_ranged(ctx._h, prepared._h, int(n), C.c_void_p(points_ptr), C.c_void_p(max_dist_ptr), int(k),
+                                             C.c_void_p(count_ptr), C.c_void_p(index_ptr), C.c_void_p(gap_ptr)))
+
+
 def camera_rays_into(rays_ptr, h, w, prepared, cam=None):
     """Enqueue the h * w primary rays rt_render_image would trace (rt_camera_rays) into rays_ptr (h * w x 6 float32)."""
     ctx = prepared.ctx
@@ -509,8 +543,53 @@ def _device_rays(ctx, rays):
     return buf.ptr, a.shape[0], buf
 
 
+def _device_points(ctx, points):
+    """(pointer, n, keep-alive) for `points` (n x 3 float32), as _device_rays does for rays."""
+    if hasattr(points, "data_ptr"):
+        dev = ctx.device_info()["device"]
+        if str(points.dtype) != "torch.float32" or not points.is_contiguous() or points.device.type != "cuda" or points.device.index != dev:
+            raise ValueError(f"points: a contiguous float32 tensor on cuda:{dev} is required")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must be (n, 3)")
+        return points.data_ptr(), int(points.shape[0]), None
+    a = np.ascontiguousarray(points, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError("points must be (n, 3)")
+    buf = DeviceBuffer(ctx, max(a.nbytes, 4))
+    if a.nbytes:
+        ctx._check(lib.rt_copy_to_device(ctx._h, C.c_void_p(buf.ptr), a.ctypes.data, a.nbytes))
+    return buf.ptr, a.shape[0], buf
+
+
 def _is_bound_array(b):
     return hasattr(b, "data_ptr") or np.ndim(b) > 0
+
+
+def _device_bound(ctx, dev, n, name, b, keep, per="ray"):
+    """The device pointer of one bound of the ranged entries (see _device_bounds); a buffer it uploads is appended to `keep`."""
+    if hasattr(b, "data_ptr"):
+        if str(b.dtype) != "torch.float32" or not b.is_contiguous() or b.device.type != "cuda" or b.device.index != dev:
+            raise ValueError(f"{name}: a contiguous float32 tensor on cuda:{dev} is required")
+        if b.dim() != 1 or b.shape[0] != n:
+            raise ValueError(f"{name} must be ({n},), one bound per {per}; got {tuple(b.shape)}")
+        return b.data_ptr()
+    if np.ndim(b) > 0:
+        a = np.asarray(b)
+        if not np.issubdtype(a.dtype, np.floating):
+            raise ValueError(f"{name}: a floating-point array is required; got {a.dtype}")
+        if a.shape != (n,):
+            raise ValueError(f"{name} must be ({n},), one bound per {per}; got {a.shape}")
+        a = np.ascontiguousarray(a, dtype=np.float32)
+    else:
+        v = np.float32(b)
+        if not (np.isfinite(v) and 0.0 <= v <= 1e9):
+            raise RtError(f"{name} = {b!r}: a scalar bound must be finite and in [0, 1e9]")
+        a = np.full(n, v, dtype=np.float32)
+    buf = DeviceBuffer(ctx, max(a.nbytes, 4))
+    keep.append(buf)
+    if a.nbytes:
+        ctx._check(lib.rt_copy_to_device(ctx._h, C.c_void_p(buf.ptr), a.ctypes.data, a.nbytes))
+    return buf.ptr
 
 
 def _device_bounds(ctx, n, t_min, t_max):
@@ -521,30 +600,7 @@ def _device_bounds(ctx, n, t_min, t_max):
     ptrs, keep = [], []
     try:
         for name, b in (("t_min", t_min), ("t_max", t_max)):
-            if hasattr(b, "data_ptr"):
-                if str(b.dtype) != "torch.float32" or not b.is_contiguous() or b.device.type != "cuda" or b.device.index != dev:
-                    raise ValueError(f"{name}: a contiguous float32 tensor on cuda:{dev} is required")
-                if b.dim() != 1 or b.shape[0] != n:
-                    raise ValueError(f"{name} must be ({n},), one bound per ray; got {tuple(b.shape)}")
-                ptrs.append(b.data_ptr())
-                continue
-            if np.ndim(b) > 0:
-                a = np.asarray(b)
-                if not np.issubdtype(a.dtype, np.floating):
-                    raise ValueError(f"{name}: a floating-point array is required; got {a.dtype}")
-                if a.shape != (n,):
-                    raise ValueError(f"{name} must be ({n},), one bound per ray; got {a.shape}")
-                a = np.ascontiguousarray(a, dtype=np.float32)
-            else:
-                v = np.float32(b)
-                if not (np.isfinite(v) and 0.0 <= v <= 1e9):
-                    raise RtError(f"{name} = {b!r}: a scalar bound must be finite and in [0, 1e9]")
-                a = np.full(n, v, dtype=np.float32)
-            buf = DeviceBuffer(ctx, max(a.nbytes, 4))
-            keep.append(buf)
-            if a.nbytes:
-                ctx._check(lib.rt_copy_to_device(ctx._h, C.c_void_p(buf.ptr), a.ctypes.data, a.nbytes))
-            ptrs.append(buf.ptr)
+            ptrs.append(_device_bound(ctx, dev, n, name, b, keep))
     except BaseException:
         for buf in keep:
             buf.free()
@@ -644,6 +700,43 @@ def multi_hit_rays(prepared, rays, k, t_min=0.0, t_max=1e9):
         return (cnt.to_host((n,)), idx.to_host((n, k)), root.to_host((n, k), np.uint8), hit.to_host((n, k, 7), np.float32))
     finally:
         for buf in [cnt, idx, root, hit] + bounds:
+            if buf is not None:
+                buf.free()
+        if keep is not None:
+            keep.free()
+
+
+def nearest_spheres(prepared, points, k, max_dist=1e9, count=True):
+    """The k nearest spheres of every point (rt_nearest_spheres) -> (count (n,) int32 or None, index (n, k) int32, gap (n, k) float32)
+    numpy arrays.  A sphere is selected for point p iff its gap -- sqrtf(|p - c|^2) - r in float32, the signed distance to its surface,
+    negative inside -- is <= max_dist; the selected ones are ordered by (gap, index), index being the sphere's place in L (Morton order:
+    prepared.sphere_ids() maps it to the caller's order).  `count` is the number selected, not capped at k; slots past it are -1 / 0.0.
+    max_dist: a scalar in [0, 1e9], or an (n,) array / device tensor, one bound per point (rt_nearest_spheres_ranged; an invalid bound makes
+    its point a miss).  count=False: k-nearest mode -- the walk also prunes by the k-th gap found so far, no count is returned, the slots are
+    the same.  `points`: (n, 3) float32, a numpy array or a device tensor.  A point with a non-finite component selects nothing.
+    Contacts: the spheres a sphere (c, r) overlaps or touches are those selected at p = c with max_dist = r; for a scene's self-contacts pass
+    its own centres and radii -- every sphere finds itself at gap -r."""
+    ctx = prepared.ctx
+    k = int(k)
+    ranged = _is_bound_array(max_dist)
+    ptr, n, keep = _device_points(ctx, points)
+    bounds = []
+    cnt = idx = gap = None
+    try:
+        if ranged:
+            md_ptr = _device_bound(ctx, ctx.device_info()["device"], n, "max_dist", max_dist, bounds, per="point")
+        nk = n * max(k, 0)
+        cnt = DeviceBuffer(ctx, max(4 * n, 4)) if count else None
+        idx = DeviceBuffer(ctx, max(4 * nk, 4))
+        gap = DeviceBuffer(ctx, max(4 * nk, 4))
+        cptr = cnt.ptr if cnt is not None else None
+        if ranged:
+            nearest_spheres_ranged_into(ptr, n, prepared, md_ptr, k, cptr, idx.ptr, gap.ptr)
+        else:
+            nearest_spheres_into(ptr, n, prepared, k, cptr, idx.ptr, gap.ptr, max_dist)
+        return (cnt.to_host((n,)) if cnt is not None else None, idx.to_host((n, k)), gap.to_host((n, k), np.float32))
+    finally:
+        for buf in [cnt, idx, gap] + bounds:
             if buf is not None:
                 buf.free()
         if keep is not None:

@@ -1297,7 +1297,7 @@ hipError_t alloc_prepared_block(rt_context *ctx, rt_prepared *ps) {
   auto carve = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~size_t(255); return at; };
   const size_t o_L7 = carve(n * 28), o_bmin = carve(ni * 12), o_bmax = carve(ni * 12), o_left = carve(ni * 4),
                o_right = carve(ni * 4), o_parent = carve(ni * 4), o_nodes = carve(ni * 32), o_nodes64 = carve(ni * 64),
-               o_sph = carve(n * 16), o_col = carve(n * 16);
+               o_sph = carve(n * 16), o_col = carve(n * 16), o_ids = carve(n * 4);
   ps->block_bytes = off;
   const hipError_t e = pool_alloc(ctx, &ps->block, &ps->block_bytes);
   if (e != hipSuccess) {
@@ -1310,6 +1310,7 @@ hipError_t alloc_prepared_block(rt_context *ctx, rt_prepared *ps) {
   ps->right = reinterpret_cast<int32_t *>(b + o_right); ps->parent = reinterpret_cast<int32_t *>(b + o_parent);
   ps->nodes = reinterpret_cast<float4 *>(b + o_nodes); ps->nodes64 = reinterpret_cast<float4 *>(b + o_nodes64);
   ps->sph = reinterpret_cast<float4 *>(b + o_sph); ps->col = reinterpret_cast<float4 *>(b + o_col);
+  ps->ids = reinterpret_cast<int32_t *>(b + o_ids);
   return hipSuccess;
 }
 
@@ -1337,6 +1338,7 @@ int host_build_upload(rt_context *ctx, rt_prepared *ps, const std::vector<rt::Sp
   std::copy(tl.root_hi, tl.root_hi + 3, ps->root_hi);
   put(ps->sph, tl.sph.data(), n * 16);
   put(ps->col, tl.col.data(), n * 16);
+  put(ps->ids, bvh.ids.data(), n * sizeof(int32_t));
   // the host staging vectors die at scope exit: drain the copies first
   *e = hipStreamSynchronize(ctx->stream);
   return rc;
@@ -1403,7 +1405,7 @@ extern "C" int rt_prepare_scene(rt_context *ctx, rt_prepared **out, int64_t h, i
     char *tmp = nullptr;
     if (e == hipSuccess) e = pool_alloc(ctx, &tmp, &tmp_bytes);
     if (e == hipSuccess) {
-      rtk::GpuBvhOut o{ps->L7, ps->bmin, ps->bmax, ps->left, ps->right, ps->parent, ps->nodes, ps->nodes64, ps->sph, ps->col};
+      rtk::GpuBvhOut o{ps->L7, ps->bmin, ps->bmax, ps->left, ps->right, ps->parent, ps->nodes, ps->nodes64, ps->sph, ps->col, ps->ids};
       e = rtk::gpu_build_bvh(scene_dev, static_cast<int>(n), o, tmp, ctx->pinned, ctx->stream, &ps->height, ps->root_lo,
                              ps->root_hi);
       ps->tl_depth = rtk::kTreeletDepth;
@@ -1480,7 +1482,7 @@ int build_from_device(rt_context *ctx, rt_prepared *ps, const float *spheres7_de
     *e = rtk::launch_cull_stats(spheres7_dev, static_cast<int>(n), reinterpret_cast<rtk::CullStatsDev *>(tmp + build_bytes),
                                 const_cast<rtk::CullStatsDev *>(slot), ctx->stream);
     if (*e == hipSuccess) {
-      rtk::GpuBvhOut o{ps->L7, ps->bmin, ps->bmax, ps->left, ps->right, ps->parent, ps->nodes, ps->nodes64, ps->sph, ps->col};
+      rtk::GpuBvhOut o{ps->L7, ps->bmin, ps->bmax, ps->left, ps->right, ps->parent, ps->nodes, ps->nodes64, ps->sph, ps->col, ps->ids};
       *e = rtk::gpu_build_bvh(spheres7_dev, static_cast<int>(n), o, tmp, ctx->pinned, ctx->stream, &ps->height, ps->root_lo, ps->root_hi);
       ps->tl_depth = rtk::kTreeletDepth;
     }
@@ -2241,6 +2243,67 @@ extern "C" int rt_multi_hit_rays_ranged(rt_context *ctx, const rt_prepared *ps, 
   p.ray_tlo_dev = t_min_dev;
   p.ray_thi_dev = t_max_dev;
   return multi_hit_launch(ctx, ps, n, p, k, count_dev, index_dev, root_dev, hit7_dev, true);
+}
+
+// The proximity entries: checks, then the lane kernel under every variant (count_dev NULL: its pruned walk).  max_dist_dev != nullptr: the
+// per-point form, whose bounds are device data -- an invalid one makes its point a miss in the kernel (lane_core.h: max_dist_ok).
+static int nearest_entry(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist, const float *max_dist_dev,
+                         bool ranged, int32_t k, int32_t *count_dev, int32_t *index_dev, float *gap_dev) {
+  const char *const what = ranged ? "rt_nearest_spheres_ranged" : "rt_nearest_spheres";
+  if (!ps) return fail(ctx, "null prepared scene");
+  if (ctx->group) return fail(ctx, std::string(what) + ": a multi-device context is not supported (use a context on one device)");
+  if (n < 0 || n >= (int64_t(1) << 31)) return fail(ctx, std::string(what) + ": point count out of range: 0 <= n < 2^31");
+  if (!points3_dev) return fail(ctx, std::string(what) + ": null points pointer");
+  if (!count_dev && !index_dev && !gap_dev) return fail(ctx, std::string(what) + ": all three outputs are NULL");
+  if (k < 1 || k > rtk::kNearestMaxK) return fail(ctx, std::string(what) + ": need 1 <= k <= 32");
+  if (ranged && !max_dist_dev) return fail(ctx, std::string(what) + ": null max_dist pointer");
+  if (!ranged && !(std::isfinite(max_dist) && max_dist >= 0.0f && max_dist <= rtk::kTMax))
+    return fail(ctx, std::string(what) + ": need 0 <= max_dist <= 1e9, finite");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  if (n == 0) {
+    ctx->last_launch = "family=none (no points)";
+    return 0;
+  }
+  rtk::KParams p{};
+  scene_params(ps, &p);
+  p.nrays = static_cast<int>(n);
+  // the boxes that contain their subtrees: those of the nodes whose subtree is at most `sweeps` levels tall (the AABB propagation's
+  // floor(log2 n) + 2 Jacobi sweeps from zero boxes, bvh.fut:44-58), which every node at depth >= height - sweeps is
+  const int sweeps = static_cast<int>(log2f(static_cast<float>(ps->n))) + 2;
+  const int exact_depth = std::max(0, ps->height - sweeps);
+  RT_HIP(ctx, rtk::launch_nearest_spheres(p, points3_dev, ranged ? max_dist_dev : nullptr, max_dist, k, exact_depth, count_dev, index_dev, gap_dev,
+                                          ctx->stream));
+  ctx->last_launch = "family=nearest k=" + std::to_string(k) + (count_dev ? "" : " pruned") + (ranged ? " (per-point)" : "");
+  return 0;
+}
+
+extern "C" int rt_nearest_spheres(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist, int32_t k,
+                                  int32_t *count_dev, int32_t *index_dev, float *gap_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return nearest_entry(ctx, ps, n, points3_dev, max_dist, nullptr, false, k, count_dev, index_dev, gap_dev);
+}
+
+extern "C" int rt_nearest_spheres_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, const float *max_dist_dev,
+                                         int32_t k, int32_t *count_dev, int32_t *index_dev, float *gap_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return nearest_entry(ctx, ps, n, points3_dev, 0.0f, max_dist_dev, true, k, count_dev, index_dev, gap_dev);
+}
+
+extern "C" int rt_prepared_get_sphere_ids(rt_context *ctx, const rt_prepared *ps, int32_t *ids_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  if (!ps || !ids_dev) return fail(ctx, "null argument");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  RT_HIP(ctx, hipMemcpyAsync(ids_dev, ps->ids, static_cast<size_t>(ps->n) * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+  return 0;
 }
 
 extern "C" int rt_camera_rays(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, const float cam12[12], float *rays_dev) {

@@ -377,10 +377,13 @@ __global__ __launch_bounds__(kBT) void sort_scatter_kernel(const unsigned *keys_
 
 // ---- gather sorted spheres ----------------------------------------------------------------
 // (... and the traversal copy's sphere tables {pos, radius} {colour, 1 / radius} in the same launch: they are a function of L alone)
-__global__ __launch_bounds__(kBT) void gather_spheres_kernel(const float *sph7, const int *order, int n, float *L7, float4 *sph, float4 *col) {
+// (... and the permutation itself, ids[i] = order[i]: the caller's index of L[i])
+__global__ __launch_bounds__(kBT) void gather_spheres_kernel(const float *sph7, const int *order, int n, float *L7, float4 *sph, float4 *col, int *ids) {
   const int i = blockIdx.x * kBT + threadIdx.x;
   if (i >= n) return;
-  const float *s = sph7 + 7 * (size_t)order[i];
+  const int src = order[i];
+  ids[i] = src;
+  const float *s = sph7 + 7 * (size_t)src;
   float *d = L7 + 7 * (size_t)i;
   float v[7];
 #pragma unroll
@@ -447,11 +450,12 @@ __global__ __launch_bounds__(kBT) void build_fills_kernel(int *parent, float *pm
 template <bool LDSKEYS>
 __global__ __launch_bounds__(kBT) void tree_kernel(const unsigned *__restrict__ L, const int *__restrict__ order, const float *__restrict__ sph7,
                                                    int n, float *__restrict__ L7, float4 *__restrict__ sph, float4 *__restrict__ col,
-                                                   int *left, int *right, int *parent) {
+                                                   int *left, int *right, int *parent, int *__restrict__ ids) {
   extern __shared__ unsigned s_L[];
   const int i = blockIdx.x * kBT + threadIdx.x;
   float v[7];
   if (i < n) {
+    ids[i] = order[i];
     const float *src = sph7 + 7 * (size_t)order[i];
 #pragma unroll
     for (int k = 0; k < 7; ++k) v[k] = src[k];
@@ -1089,8 +1093,9 @@ __global__ __launch_bounds__(kSmallNT) void bvh_small_kernel(SmallArgs a) {
   // 3. stable sort by the 30-bit key
   small_sort(lk, lv, n, 30);
   STAMP(3);
-  // 4. sorted spheres (canonical L, and the traversal copies of the same data)
+  // 4. sorted spheres (canonical L, the traversal copies of the same data, and the permutation: ids)
   for (int i = tid; i < n; i += kSmallNT) {
+    a.o.ids[i] = (int)lv[i];
     const float *s = a.sph7 + 7 * (size_t)lv[i];
     float *d = a.o.L7 + 7 * (size_t)i;
     float f[7];
@@ -1509,12 +1514,12 @@ hipError_t gpu_build_bvh(const float *sph7_dev, int n, const GpuBvhOut &o, char 
   if (fused) {
     if (ranked)
       hipLaunchKernelGGL(tree_kernel<true>, dim3(nb_n), dim3(kBT), sizeof(unsigned) * (size_t)n, st, keys[cur], vals[cur], sph7_dev, n, o.L7, o.sph,
-                         o.col, o.left, o.right, o.parent);
+                         o.col, o.left, o.right, o.parent, o.ids);
     else
       hipLaunchKernelGGL(tree_kernel<false>, dim3(nb_n), dim3(kBT), 0, st, keys[cur], vals[cur], sph7_dev, n, o.L7, o.sph, o.col, o.left, o.right,
-                         o.parent);
+                         o.parent, o.ids);
   } else {
-    hipLaunchKernelGGL(gather_spheres_kernel, dim3(nb_n), dim3(kBT), 0, st, sph7_dev, vals[cur], n, o.L7, o.sph, o.col);
+    hipLaunchKernelGGL(gather_spheres_kernel, dim3(nb_n), dim3(kBT), 0, st, sph7_dev, vals[cur], n, o.L7, o.sph, o.col, o.ids);
     hipLaunchKernelGGL(build_fills_kernel, dim3(nb_ni), dim3(kBT), 0, st, o.parent, pmin, pmax, depth, ni);   // (fin[] borrows depth[], which is set later)
     hipLaunchKernelGGL(radix_tree_kernel, dim3(nb_ni), dim3(kBT), 0, st, keys[cur], n, o.left, o.right, o.parent);
   }

@@ -180,6 +180,7 @@ Lbvh build_lbvh(const std::vector<Sphere> &ts) {
     out.L[i] = ts[order[i]];
     out.morton[i] = key[order[i]];
   }
+  out.ids = order;
 
   // radix tree (radixtree.fut:23-72)
   out.left.assign(ni, 0);

@@ -2181,6 +2181,135 @@ hipError_t launch_multi_hit_rays(const KParams &p, int k, int32_t *count, int32_
                                   : launch_multi_hit_cap<false>(p, k, count, index, root, hit7, stream);
 }
 
+// rt_nearest_spheres: one lane per point.  The walk of multi_hit_lane with the box test replaced by box_may_hold (lane_core.h: the
+// point-to-box distance against the threshold plus a proven slack) and the crossing list by the same sorted list of CAP 64-bit keys,
+// gap_key(gap, j): every sphere with gap <= max_dist is counted and inserted.  A box is tested only at depth >= exact_depth: the reference's
+// AABB propagation runs floor(log2 n) + 2 sweeps from zero boxes (bvh.fut:44-58), so in a taller tree the boxes of the nodes nearer the root
+// than height - sweeps levels need not contain their subtrees -- the walk descends through them untested.  A stack entry is the node and its
+// depth (capped at 63) in bits 26..31 (node < 2^26).
+// PRUNED (no count output): once the list holds k keys the threshold is min(max_dist, the k-th gap) -- read with an unrolled select, a
+// runtime index would put the list in scratch -- and the children of a node are pushed farther first, so the nearer one is walked first (one
+// extra 32-byte read per inner child).  Neither changes the first k keys: a skipped box holds only spheres whose gap exceeds the threshold.
+// Outputs at 64-bit offsets; any may be nullptr.
+template <int CAP>
+__device__ __forceinline__ float kth_gap(const unsigned long long (&list)[CAP], int k) {
+  unsigned long long x = ~0ull;
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) x = s == k - 1 ? list[s] : x;
+  return x == ~0ull ? kNoHit : gap_of_key(x);
+}
+__device__ __forceinline__ int nearest_stack_entry(int node, int depth) { return (int)((unsigned)node | ((unsigned)(depth < 63 ? depth : 63) << 26)); }
+
+template <bool RANGED, bool PRUNED, int CAP>
+__device__ __forceinline__ void nearest_lane(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, int k, int exact_depth,
+                                             int32_t *count, int32_t *index, float *gap) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const float px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
+  if constexpr (RANGED) max_dist = max_dist_dev[i] + 0.0f;   // (-0.0 -> +0.0)
+  const bool valid = point_ok(px, py, pz) && (!RANGED || max_dist_ok(max_dist));
+  const float pmag = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
+  unsigned long long list[CAP];
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) list[s] = ~0ull;
+  int cnt = 0;
+  float T = max_dist;
+  int sp = 0;
+  if (valid) stack[sp++][lane] = nearest_stack_entry(0, 0);
+  while (sp > 0) {
+    const unsigned e = (unsigned)stack[--sp][lane];
+    const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
+    const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+    if (depth >= exact_depth && !box_may_hold(px, py, pz, pmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, T)) continue;
+    const int kids[2] = {f2i(lo.w), f2i(hi.w)};
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      const int c = kids[c2];
+      if (c < 0) {
+        const int j = ~c;
+        const float4 s = buf_load16(rs_sph, j * 16);
+        const float g = point_gap(px, py, pz, s.x, s.y, s.z, s.w);
+        if (g <= max_dist) {
+          ++cnt;
+          crossing_insert<CAP>(list, gap_key(g, j));
+          if constexpr (PRUNED) T = fminf(max_dist, kth_gap<CAP>(list, k));
+        }
+      }
+    }
+    if constexpr (PRUNED) {
+      // the inner children, farther first; one that already fails the test is not pushed
+      float b[2] = {0.0f, 0.0f};
+      bool push[2] = {false, false};
+#pragma unroll
+      for (int c2 = 0; c2 < 2; ++c2) {
+        const int c = kids[c2];
+        if (c >= 0) {
+          const float4 clo = buf_load16(rs_nodes, c * 32), chi = buf_load16(rs_nodes, c * 32 + 16);
+          push[c2] = depth + 1 < exact_depth || box_may_hold(px, py, pz, pmag, clo.x, clo.y, clo.z, chi.x, chi.y, chi.z, T);
+          b[c2] = box_gap_bound(px, py, pz, clo.x, clo.y, clo.z, chi.x, chi.y, chi.z);
+        }
+      }
+      const int first = b[0] >= b[1] ? 0 : 1;   // (the farther one goes below the nearer one)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int c2 = q == 0 ? first : 1 - first;
+        if (push[c2]) stack[sp++][lane] = nearest_stack_entry(kids[c2], depth + 1);   // (one pending sibling per level: sp <= height + 1 <= kStackPixel)
+      }
+    } else {
+#pragma unroll
+      for (int c2 = 0; c2 < 2; ++c2)
+        if (kids[c2] >= 0) stack[sp++][lane] = nearest_stack_entry(kids[c2], depth + 1);
+    }
+  }
+  if (count != nullptr) count[i] = cnt;
+  const size_t base = (size_t)i * (size_t)k;
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) {
+    if (s < k) {
+      const bool have = list[s] != ~0ull;
+      if (index != nullptr) index[base + s] = have ? (int)(unsigned)list[s] : -1;
+      if (gap != nullptr) gap[base + s] = have ? gap_of_key(list[s]) : 0.0f;
+    }
+  }
+}
+template <bool RANGED, bool PRUNED, int CAP>
+__global__ __launch_bounds__(64) void nearest_kernel(KParams p, const float *pts, const float *max_dist_dev, float max_dist, int k, int exact_depth,
+                                                     int32_t *count, int32_t *index, float *gap) {
+  nearest_lane<RANGED, PRUNED, CAP>(p, pts, max_dist_dev, max_dist, k, exact_depth, count, index, gap);
+}
+
+template <bool RANGED, bool PRUNED>
+static hipError_t launch_nearest_cap(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, int k, int exact_depth,
+                                     int32_t *count, int32_t *index, float *gap, hipStream_t stream) {
+  const dim3 grid((unsigned)((p.nrays + 63) / 64)), block(64);
+#define RT_NEAREST(CAP) \
+  hipLaunchKernelGGL((nearest_kernel<RANGED, PRUNED, CAP>), grid, block, 0, stream, p, pts, max_dist_dev, max_dist, k, exact_depth, count, index, gap)
+  if (k <= 4) RT_NEAREST(4);
+  else if (k <= 8) RT_NEAREST(8);
+  else if (k <= 16) RT_NEAREST(16);
+  else RT_NEAREST(32);
+#undef RT_NEAREST
+  return hipGetLastError();
+}
+
+hipError_t launch_nearest_spheres(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, int k, int exact_depth,
+                                  int32_t *count, int32_t *index, float *gap, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (pts == nullptr || k < 1 || k > kNearestMaxK || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (count == nullptr && index == nullptr && gap == nullptr) return hipErrorInvalidValue;
+  const bool ranged = max_dist_dev != nullptr, pruned = count == nullptr;
+  if (!ranged && !max_dist_ok(max_dist)) return hipErrorInvalidValue;
+  max_dist += 0.0f;   // (-0.0 -> +0.0)
+  if (ranged) return pruned ? launch_nearest_cap<true, true>(p, pts, max_dist_dev, 0.0f, k, exact_depth, count, index, gap, stream)
+                            : launch_nearest_cap<true, false>(p, pts, max_dist_dev, 0.0f, k, exact_depth, count, index, gap, stream);
+  return pruned ? launch_nearest_cap<false, true>(p, pts, nullptr, max_dist, k, exact_depth, count, index, gap, stream)
+                : launch_nearest_cap<false, false>(p, pts, nullptr, max_dist, k, exact_depth, count, index, gap, stream);
+}
+
 __global__ __launch_bounds__(256) void camera_rays_kernel(Cam cam, int h, int w, float *rays) {
   const int64_t n = (int64_t)h * w;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {

@@ -403,6 +403,13 @@ hipError_t launch_occluded_rays_ranged(const KParams &p, hipStream_t stream);
 // ray i's own with p.ray_tlo_dev / p.ray_thi_dev (both set, or neither)
 constexpr int kMultiHitMaxK = 32;
 hipError_t launch_multi_hit_rays(const KParams &p, int k, int32_t *count, int32_t *index, uint8_t *root, float *hit7, hipStream_t stream);
+// rt_nearest_spheres[_ranged]: for p.nrays points (pts: n x 3 float32) the first k (1 <= k <= kNearestMaxK) spheres of L by (gap, j) with
+// gap <= max_dist -- or point i's own max_dist_dev[i] when max_dist_dev is set -- and their count: count[i], index / gap [i * k + s] (any may
+// be nullptr, not all).  count == nullptr: the pruned walk (the k-th gap so far narrows the threshold).  Boxes are tested at depth >=
+// exact_depth only: the nodes whose boxes provably contain their subtrees (api.cpp: nearest_entry)
+constexpr int kNearestMaxK = 32;
+hipError_t launch_nearest_spheres(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, int k, int exact_depth,
+                                  int32_t *count, int32_t *index, float *gap, hipStream_t stream);
 // the primary rays of an h x w frame through p.cam (get_ray at pixel_u / pixel_v), row-major from the top row: rays[6 (row w + col) ..]
 hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStream_t stream);
 // block = 64 * waves_per_wg threads (4, 8 or 16 waves); grid = persistent workgroups
@@ -420,6 +427,7 @@ struct GpuBvhOut {
   float4 *nodes32;           // [2*(n-1)]
   float4 *nodes64;           // [4*(n-1)]
   float4 *sph, *col;         // [n]
+  int *ids;                  // [n]  the input's index of L[i] (rt_prepared_get_sphere_ids)
 };
 void warm_render_kernels();
 hipError_t warm_scratch(hipStream_t stream, int *sink_dev);   // the queue's scratch allocated now, not inside the first frame

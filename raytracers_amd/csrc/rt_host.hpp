@@ -46,6 +46,7 @@ struct Lbvh {
   int64_t n = 0;                 // leaves
   std::vector<Sphere> L;         // [n]   sorted by Morton key (stable)
   std::vector<uint32_t> morton;  // [n]   sorted keys
+  std::vector<int32_t> ids;      // [n]   L[i] == the input's sphere ids[i] (the stable sort's permutation)
   std::vector<float> bmin, bmax; // [n-1][3]
   std::vector<int32_t> left, right, parent;  // [n-1]
   int sweeps = 0;                // AABB propagation sweeps run (bvh.fut:47)

@@ -190,6 +190,7 @@ struct rt_prepared {
   int32_t *left = nullptr, *right = nullptr, *parent = nullptr;
   // traversal copy
   float4 *nodes = nullptr, *nodes64 = nullptr, *sph = nullptr, *col = nullptr;
+  int32_t *ids = nullptr;   // [n] the caller's index of L[i] (rt_prepared_get_sphere_ids); read by no render path
   char *block = nullptr;   // one device allocation behind all of the arrays above
   size_t block_bytes = 0;
   float root_lo[3] = {0, 0, 0}, root_hi[3] = {0, 0, 0};
