@@ -75,6 +75,7 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *   "family=intersect (per-ray)" | "family=occluded (per-ray)"   their lane kernels with per-ray intervals (rt_*_rays_ranged)
  *   "family=multi-hit k=K" | "family=multi-hit k=K (per-ray)"   rt_multi_hit_rays / rt_multi_hit_rays_ranged (K: the caller's k)
  *   "family=nearest k=K[ pruned][ (per-point)]" | "family=none (no points)"   rt_nearest_spheres / rt_nearest_spheres_ranged (below)
+ *   "family=within count|fill[ (per-point)][ first][ self]"   rt_spheres_within_count / _fill, rt_contact_pairs_count / _fill (" self"; below)
  *   "family=none (no rows)"       the part owns no row of the image
  *   "family=pixel" | "family=pixel (instrumented)" | "family=persistent"
  *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2"
@@ -320,6 +321,45 @@ int rt_nearest_spheres(rt_context *ctx, const rt_prepared *ps, int64_t n, const 
                        int32_t k, int32_t *count_dev, int32_t *index_dev, float *gap_dev);
 int rt_nearest_spheres_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev,
                               const float *max_dist_dev, int32_t k, int32_t *count_dev, int32_t *index_dev, float *gap_dev);
+/* ---- range queries: EVERY sphere within a distance of caller-supplied points, and a scene's contact pairs, with no cap -----------------
+ * The selection rule is rt_nearest_spheres's: sphere j of L is selected for point i iff gap <= the point's bound, gap being exactly the
+ * float32 arithmetic above -- and, where first_dev is given, j >= first_dev[i].  Brute force over all spheres defines the answer; it is exact,
+ * bit for bit.  A row has no length limit, so the answer comes in CSR form and in two phases, because its size is not known in advance:
+ *   offsets : n + 1 int64.  offsets[0] = 0, offsets[i + 1] - offsets[i] = the number of spheres selected for point i, offsets[n] = the total.
+ *             Without first_dev a row's length is rt_nearest_spheres's count_dev[i] for the same point and bound.
+ *   index   : total int32.  Row i at [offsets[i], offsets[i + 1]): the selected j in ASCENDING j -- not in (gap, j) order: the walk meets the
+ *             leaves of the tree in ascending j, and a row of any length cannot be sorted in registers.  Sort rows yourself if you need
+ *             them by gap.
+ *   gap     : total float32, the gap of each entry.         point : total int32, the row number i of each entry (the COO form: (point,
+ *             index) is the list of pairs).  Any of the three may be NULL, not all.
+ * rt_spheres_within_count enqueues the count pass and the scan that writes offsets_dev[0 .. n] on the context's stream and returns without
+ * synchronising.  The caller reads offsets_dev[n] (rt_copy_to_host), allocates that many entries and calls rt_spheres_within_fill with the
+ * SAME points, bounds, first_dev and scene, and capacity = the entries it allocated.  _fill recomputes the selection and writes entry
+ * offsets[i] + (rank of j in row i) only while it is below offsets[i + 1] and below capacity: offsets that belong to another query (or a
+ * scene updated between the two calls) give an unspecified result, but never a write outside [0, capacity).
+ * max_dist_dev == NULL: the scalar max_dist for every point; otherwise n float32, one bound per point, and the scalar is ignored.
+ * first_dev == NULL: no lower index bound; otherwise n int32: first_dev[i] <= 0 selects from 0, first_dev[i] >= the sphere count gives an empty
+ * row (the filter is a compare at the leaf; it prunes no subtree).  A point with a non-finite component, or a per-point bound that is NaN,
+ * +-inf, negative or above 1e9, has an empty row; -0.0 behaves as 0.0.  Exact for scenes whose spheres are finite with radius >= 0; for other
+ * scenes unspecified, but nothing is read or written out of range.
+ * Contact pairs are the scene's self-query: point i is the centre of L[i], its bound fl(radius_i + margin), first = i + 1.  Pair (i, j), i < j,
+ * is reported iff gap(centre_i, L[j]) <= fl(radius_i + margin) -- once, without (i, i).  The predicate is evaluated from the LOWER index only:
+ * in float32 it need not be symmetric in the last bit, and (j, i) is never consulted.  offsets: n + 1 int64 for the scene's n spheres;
+ * pair_dev: total x 2 int32, rows {i, j} in ascending (i, j); gap_dev: total float32, that gap (centre i to the surface of j; subtract radius_i
+ * for the surface-to-surface distance); either may be NULL, not both.  A sphere whose bound is not in [0, 1e9] or whose centre is not finite
+ * reports no pair as i.  i and j are indices into L: rt_prepared_get_sphere_ids maps them to the caller's order.
+ * Refused (non-zero, rt_last_error set, nothing launched or written): a null scene, a multi-device context, n < 0 or n >= 2^31, NULL
+ * points3_dev, NULL offsets_dev, a negative capacity, every output NULL, a scalar max_dist (when it is used) or a margin outside [0, 1e9] or
+ * not finite.  n == 0 succeeds and _count still writes offsets_dev[0] = 0.  One lane per point under every variant; rt_context_last_launch:
+ * "family=within count" / "family=within fill", then " (per-point)" with max_dist_dev, " first" with first_dev, " self" for the contact pairs. */
+int rt_spheres_within_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
+                            const float *max_dist_dev, const int32_t *first_dev, int64_t *offsets_dev);
+int rt_spheres_within_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
+                           const float *max_dist_dev, const int32_t *first_dev, const int64_t *offsets_dev, int64_t capacity,
+                           int32_t *index_dev, float *gap_dev, int32_t *point_dev);
+int rt_contact_pairs_count(rt_context *ctx, const rt_prepared *ps, float margin, int64_t *offsets_dev);
+int rt_contact_pairs_fill(rt_context *ctx, const rt_prepared *ps, float margin, const int64_t *offsets_dev, int64_t capacity,
+                          int32_t *pair_dev, float *gap_dev);
 /* ids_dev: n int32 in the context's device memory; ids_dev[i] = the caller's index of L[i]: the position in spheres7 given to
  * rt_scene_from_spheres / rt_prepare_scene_device / the last rt_prepared_update_spheres, or in the generator's output for rt_scene_rgbbox /
  * _irreg / _floor.  The Morton sort is stable, so both builders (option gpu_build) give the same ids, ascending within a run of equal keys.

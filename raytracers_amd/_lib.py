@@ -22,6 +22,7 @@ RT_SYMBOLS = [
     "rt_render_timed",
     "rt_trace_rays", "rt_intersect_rays", "rt_occluded_rays", "rt_intersect_rays_ranged", "rt_occluded_rays_ranged",
     "rt_multi_hit_rays", "rt_multi_hit_rays_ranged", "rt_nearest_spheres", "rt_nearest_spheres_ranged", "rt_prepared_get_sphere_ids",
+    "rt_spheres_within_count", "rt_spheres_within_fill", "rt_contact_pairs_count", "rt_contact_pairs_fill",
     "rt_camera_rays",
     "rt_device_alloc", "rt_device_free", "rt_copy_to_host", "rt_copy_to_device",
 ]
@@ -112,6 +113,10 @@ def _load():
         "rt_nearest_spheres": (C.c_int, [vp, vp, i64, vp, C.c_float, i32, vp, vp, vp]),
         "rt_nearest_spheres_ranged": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, vp, vp]),
         "rt_prepared_get_sphere_ids": (C.c_int, [vp, vp, vp]),
+        "rt_spheres_within_count": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, vp, vp]),
+        "rt_spheres_within_fill": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, vp, vp, i64, vp, vp, vp]),
+        "rt_contact_pairs_count": (C.c_int, [vp, vp, C.c_float, vp]),
+        "rt_contact_pairs_fill": (C.c_int, [vp, vp, C.c_float, vp, i64, vp, vp]),
         "rt_camera_rays": (C.c_int, [vp, vp, i64, i64, vp, vp]),
     }
     for name, (res, args) in sig.items():

@@ -514,6 +514,42 @@ def nearest_spheres_ranged_into(points_ptr, n, prepared, max_dist_ptr, k, count_
                                              C.c_void_p(count_ptr), C.c_void_p(index_ptr), C.c_void_p(gap_ptr)))
 
 
+def spheres_within_count_into(points_ptr, n, prepared, offsets_ptr, max_dist=1e9, max_dist_ptr=None, first_ptr=None):
+    """Enqueue the count pass of the range query of `n` points (n x 3 float32 at points_ptr; rt_spheres_within_count): offsets_ptr receives
+    n + 1 int64, offsets[i + 1] - offsets[i] = the number of spheres with gap <= the point's bound -- the scalar max_dist, or max_dist_ptr[i]
+    (n float32 on the device) -- and index >= first_ptr[i] (n int32 on the device; None: no lower bound).  Asynchronous: read offsets[n] (the
+    total) after ctx.sync() or with a copy on the context's stream, then call spheres_within_fill_into with the same arguments."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_spheres_within_count(ctx._h, prepared._h, int(n), C.c_void_p(points_ptr), float(max_dist), C.c_void_p(max_dist_ptr),
+                                           C.c_void_p(first_ptr), C.c_void_p(offsets_ptr)))
+
+
+def spheres_within_fill_into(points_ptr, n, prepared, offsets_ptr, capacity, index_ptr, gap_ptr=None, point_ptr=None, max_dist=1e9,
+                             max_dist_ptr=None, first_ptr=None):
+    """Enqueue the fill pass (rt_spheres_within_fill) for the offsets of spheres_within_count_into on the same points, bounds and scene: row i
+    at [offsets[i], offsets[i + 1]) of index_ptr (int32, ascending sphere index into L), gap_ptr (float32) and point_ptr (int32, the row number
+    of each entry); `capacity` = the entries each array holds: nothing is written at or past it.  Any pointer may be None, not all three."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_spheres_within_fill(ctx._h, prepared._h, int(n), C.c_void_p(points_ptr), float(max_dist), C.c_void_p(max_dist_ptr),
+                                          C.c_void_p(first_ptr), C.c_void_p(offsets_ptr), int(capacity), C.c_void_p(index_ptr),
+                                          C.c_void_p(gap_ptr), C.c_void_p(point_ptr)))
+
+
+def contact_pairs_count_into(prepared, offsets_ptr, margin=0.0):
+    """Enqueue the count pass of the scene's contact pairs (rt_contact_pairs_count): offsets_ptr receives num_spheres + 1 int64, row i counting
+    the j > i with gap(centre_i, L[j]) <= radius_i + margin.  Asynchronous, as spheres_within_count_into."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_contact_pairs_count(ctx._h, prepared._h, float(margin), C.c_void_p(offsets_ptr)))
+
+
+def contact_pairs_fill_into(prepared, offsets_ptr, capacity, pair_ptr, gap_ptr=None, margin=0.0):
+    """Enqueue the fill pass of the contact pairs (rt_contact_pairs_fill): pair_ptr receives total x 2 int32, rows (i, j) with i < j in
+    ascending (i, j), indices into L; gap_ptr total float32, the gap from centre i to the surface of j.  Either may be None, not both."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_contact_pairs_fill(ctx._h, prepared._h, float(margin), C.c_void_p(offsets_ptr), int(capacity), C.c_void_p(pair_ptr),
+                                         C.c_void_p(gap_ptr)))
+
+
 def camera_rays_into(rays_ptr, h, w, prepared, cam=None):
     """Enqueue the h * w primary rays rt_render_image would trace (rt_camera_rays) into rays_ptr (h * w x 6 float32)."""
     ctx = prepared.ctx
@@ -741,6 +777,96 @@ def nearest_spheres(prepared, points, k, max_dist=1e9, count=True):
                 buf.free()
         if keep is not None:
             keep.free()
+
+
+def _device_first(ctx, dev, n, first, keep):
+    """The device pointer of the per-point lower index bounds `first`: an (n,) integer numpy array (uploaded as int32, clipped to int32's range
+    first) or a contiguous int32 torch tensor on the context's device (used in place); a buffer it uploads is appended to `keep`."""
+    if hasattr(first, "data_ptr"):
+        if str(first.dtype) != "torch.int32" or not first.is_contiguous() or first.device.type != "cuda" or first.device.index != dev:
+            raise ValueError(f"first: a contiguous int32 tensor on cuda:{dev} is required")
+        if first.dim() != 1 or first.shape[0] != n:
+            raise ValueError(f"first must be ({n},), one index per point; got {tuple(first.shape)}")
+        return first.data_ptr()
+    a = np.asarray(first)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"first: an integer array is required; got {a.dtype}")
+    if a.shape != (n,):
+        raise ValueError(f"first must be ({n},), one index per point; got {a.shape}")
+    a = np.ascontiguousarray(np.clip(a, -2 ** 31, 2 ** 31 - 1), dtype=np.int32)
+    buf = DeviceBuffer(ctx, max(a.nbytes, 4))
+    keep.append(buf)
+    if a.nbytes:
+        ctx._check(lib.rt_copy_to_device(ctx._h, C.c_void_p(buf.ptr), a.ctypes.data, a.nbytes))
+    return buf.ptr
+
+
+def spheres_within(prepared, points, max_dist, first=None, gaps=True, rows=False):
+    """EVERY sphere within max_dist of every point (rt_spheres_within_count / _fill), with no cap, in CSR form -> (offsets (n + 1,) int64,
+    index (total,) int32, gap (total,) float32 or None[, point (total,) int32]) numpy arrays.  The selection rule is nearest_spheres's: sphere
+    j is selected for point i iff its gap -- sqrtf(|p - c|^2) - r in float32 -- is <= the point's bound.  Row i is
+    index[offsets[i]:offsets[i + 1]], in ASCENDING sphere index (an index into L, Morton order: prepared.sphere_ids() maps it to the caller's
+    order), not by gap: sort a row by (gap, index) to get nearest_spheres's order.  max_dist: a scalar in [0, 1e9], or an (n,) array / device
+    tensor, one bound per point (an invalid bound gives an empty row).  first: None, or an (n,) integer array / int32 device tensor: only
+    spheres with index >= first[i] are selected for point i.  gaps=False: no gap array (None is returned in its place).  rows=True: also
+    `point`, the row number of every entry, so that (point, index) is the list of pairs.  `points`: (n, 3) float32, a numpy array or a device
+    tensor.  A point with a non-finite component has an empty row."""
+    ctx = prepared.ctx
+    ranged = _is_bound_array(max_dist)
+    ptr, n, keep = _device_points(ctx, points)
+    bufs = []
+    try:
+        dev = ctx.device_info()["device"]
+        md_ptr = _device_bound(ctx, dev, n, "max_dist", max_dist, bufs, per="point") if ranged else None
+        md = 0.0 if ranged else max_dist
+        first_ptr = _device_first(ctx, dev, n, first, bufs) if first is not None else None
+        off = DeviceBuffer(ctx, 8 * (n + 1))
+        bufs.append(off)
+        spheres_within_count_into(ptr, n, prepared, off.ptr, md, md_ptr, first_ptr)
+        offsets = off.to_host((n + 1,), np.int64)
+        total = int(offsets[n])
+        out = []
+        for want in (True, gaps, rows):
+            out.append(DeviceBuffer(ctx, max(4 * total, 4)) if want else None)
+            if want:
+                bufs.append(out[-1])
+        idx, gap, row = out
+        if total:
+            spheres_within_fill_into(ptr, n, prepared, off.ptr, total, idx.ptr, gap.ptr if gap else None, row.ptr if row else None, md,
+                                     md_ptr, first_ptr)
+        res = (offsets, idx.to_host((total,)), gap.to_host((total,), np.float32) if gap else None)
+        return res + (row.to_host((total,)),) if rows else res
+    finally:
+        for buf in bufs:
+            buf.free()
+        if keep is not None:
+            keep.free()
+
+
+def contact_pairs(prepared, margin=0.0, gaps=True):
+    """The scene's contact pairs (rt_contact_pairs_count / _fill), with no cap -> (pairs (m, 2) int32, gap (m,) float32 or None) numpy arrays.
+    Pair (i, j), i < j, is reported once iff gap(centre_i, L[j]) = sqrtf(|c_i - c_j|^2) - r_j <= r_i + margin, all in float32 and evaluated
+    from the lower index only; rows in ascending (i, j).  `gap` is that gap (subtract r_i for the surface-to-surface distance).  i and j are
+    indices into L (Morton order): prepared.sphere_ids() maps them to the caller's order.  margin: a scalar in [0, 1e9]."""
+    ctx = prepared.ctx
+    n = prepared.num_spheres
+    bufs = []
+    try:
+        off = DeviceBuffer(ctx, 8 * (n + 1))
+        bufs.append(off)
+        contact_pairs_count_into(prepared, off.ptr, margin)
+        total = int(off.to_host((n + 1,), np.int64)[n])
+        pair = DeviceBuffer(ctx, max(8 * total, 4))
+        bufs.append(pair)
+        gap = DeviceBuffer(ctx, max(4 * total, 4)) if gaps else None
+        if gap:
+            bufs.append(gap)
+        if total:
+            contact_pairs_fill_into(prepared, off.ptr, total, pair.ptr, gap.ptr if gap else None, margin)
+        return pair.to_host((total, 2)), gap.to_host((total,), np.float32) if gap else None
+    finally:
+        for buf in bufs:
+            buf.free()
 
 
 def camera_rays(prepared, h, w, cam=None):

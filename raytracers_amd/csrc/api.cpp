@@ -1062,6 +1062,7 @@ extern "C" void rt_context_destroy(rt_context *ctx) {
   if (ctx->spill_dev) (void)hipFree(ctx->spill_dev);
   if (ctx->order_scratch) (void)hipFree(ctx->order_scratch);
   if (ctx->px_scratch) (void)hipFree(ctx->px_scratch);
+  if (ctx->within_scratch) (void)hipFree(ctx->within_scratch);
   if (ctx->stats_dev) (void)hipFree(ctx->stats_dev);
   for (auto &b : ctx->pool) (void)hipFree(b.p);
   if (ctx->arena) (void)hipFree(ctx->arena);
@@ -2292,6 +2293,93 @@ extern "C" int rt_nearest_spheres_ranged(rt_context *ctx, const rt_prepared *ps,
   if (!ctx) return 1;
   RT_LOCK(ctx);
   return nearest_entry(ctx, ps, n, points3_dev, 0.0f, max_dist_dev, true, k, count_dev, index_dev, gap_dev);
+}
+
+// The range entries (rt_spheres_within_*, rt_contact_pairs_*): checks, then within_lane under every variant.  self: the contact pairs (the
+// points are the scene's own centres, `max_dist` is the margin).  The count pass keeps its int32 counts and the scan's block sums in a buffer
+// cached on the context, grown when a call needs more (the steady path allocates nothing).
+static int within_scratch(rt_context *ctx, int64_t n, char **out) {
+  const size_t want = rtk::within_scratch_bytes(n);
+  if (want > ctx->within_bytes) {
+    if (ctx->within_scratch) {
+      RT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (an earlier count pass may still be reading it)
+      RT_HIP(ctx, hipFree(ctx->within_scratch));
+      ctx->within_scratch = nullptr;
+      ctx->within_bytes = 0;
+    }
+    const size_t bytes = std::max(want + want / 2, size_t(1) << 20);
+    RT_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->within_scratch), bytes));
+    ctx->within_bytes = bytes;
+  }
+  *out = ctx->within_scratch;
+  return 0;
+}
+static int within_entry(rt_context *ctx, const rt_prepared *ps, const char *what, bool fill, bool self, int64_t n, const float *points3_dev,
+                        float max_dist, const float *max_dist_dev, const int32_t *first_dev, int64_t *offsets_dev, int64_t capacity,
+                        int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
+  if (!ps) return fail(ctx, "null prepared scene");
+  if (ctx->group) return fail(ctx, std::string(what) + ": a multi-device context is not supported (use a context on one device)");
+  if (self) n = ps->n;
+  if (n < 0 || n >= (int64_t(1) << 31)) return fail(ctx, std::string(what) + ": point count out of range: 0 <= n < 2^31");
+  if (!self && !points3_dev) return fail(ctx, std::string(what) + ": null points pointer");
+  if (!offsets_dev) return fail(ctx, std::string(what) + ": null offsets pointer");
+  if (fill && capacity < 0) return fail(ctx, std::string(what) + ": negative capacity");
+  if (fill && !index_dev && !gap_dev && !point_dev) return fail(ctx, std::string(what) + ": every output is NULL");
+  if ((self || !max_dist_dev) && !(std::isfinite(max_dist) && max_dist >= 0.0f && max_dist <= rtk::kTMax))
+    return fail(ctx, std::string(what) + (self ? ": need 0 <= margin <= 1e9, finite" : ": need 0 <= max_dist <= 1e9, finite"));
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  rtk::KParams p{};
+  scene_params(ps, &p);
+  p.nrays = static_cast<int>(n);
+  // (the boxes that contain their subtrees: nearest_entry)
+  const int sweeps = static_cast<int>(log2f(static_cast<float>(ps->n))) + 2;
+  const int exact_depth = std::max(0, ps->height - sweeps);
+  if (fill) {
+    ctx->synced_since_render = false;
+    RT_HIP(ctx, rtk::launch_within_fill(p, points3_dev, max_dist_dev, max_dist, first_dev, self, exact_depth, offsets_dev, capacity, index_dev,
+                                        gap_dev, point_dev, ctx->stream));
+  } else {
+    char *scratch = nullptr;
+    if (n > 0 && within_scratch(ctx, n, &scratch) != 0) return 1;
+    ctx->synced_since_render = false;
+    RT_HIP(ctx, rtk::launch_within_count(p, points3_dev, max_dist_dev, max_dist, first_dev, self, exact_depth, scratch, offsets_dev, ctx->stream));
+  }
+  ctx->last_launch = std::string(fill ? "family=within fill" : "family=within count") + (!self && max_dist_dev ? " (per-point)" : "") +
+                     (!self && first_dev ? " first" : "") + (self ? " self" : "");
+  return 0;
+}
+
+extern "C" int rt_spheres_within_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
+                                       const float *max_dist_dev, const int32_t *first_dev, int64_t *offsets_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return within_entry(ctx, ps, "rt_spheres_within_count", false, false, n, points3_dev, max_dist, max_dist_dev, first_dev, offsets_dev, 0, nullptr,
+                      nullptr, nullptr);
+}
+
+extern "C" int rt_spheres_within_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
+                                      const float *max_dist_dev, const int32_t *first_dev, const int64_t *offsets_dev, int64_t capacity,
+                                      int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return within_entry(ctx, ps, "rt_spheres_within_fill", true, false, n, points3_dev, max_dist, max_dist_dev, first_dev,
+                      const_cast<int64_t *>(offsets_dev), capacity, index_dev, gap_dev, point_dev);
+}
+
+extern "C" int rt_contact_pairs_count(rt_context *ctx, const rt_prepared *ps, float margin, int64_t *offsets_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return within_entry(ctx, ps, "rt_contact_pairs_count", false, true, 0, nullptr, margin, nullptr, nullptr, offsets_dev, 0, nullptr, nullptr, nullptr);
+}
+
+extern "C" int rt_contact_pairs_fill(rt_context *ctx, const rt_prepared *ps, float margin, const int64_t *offsets_dev, int64_t capacity,
+                                     int32_t *pair_dev, float *gap_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return within_entry(ctx, ps, "rt_contact_pairs_fill", true, true, 0, nullptr, margin, nullptr, nullptr, const_cast<int64_t *>(offsets_dev), capacity,
+                      nullptr, gap_dev, pair_dev);
 }
 
 extern "C" int rt_prepared_get_sphere_ids(rt_context *ctx, const rt_prepared *ps, int32_t *ids_dev) {

@@ -2310,6 +2310,234 @@ hipError_t launch_nearest_spheres(const KParams &p, const float *pts, const floa
                 : launch_nearest_cap<false, false>(p, pts, nullptr, max_dist, k, exact_depth, count, index, gap, stream);
 }
 
+// rt_spheres_within_* / rt_contact_pairs_*: EVERY sphere with gap <= the point's bound, in CSR form.  One lane per point,
+// nearest_lane's count-mode walk (the same stack, loads and box_may_hold with T = the point's bound, the untested descent through the partial
+// boxes above exact_depth) without a key list: a row has no length limit.  Rows come out in ASCENDING j with no sort: the leaves below a node
+// are a contiguous run of L and the left child holds the lower part, so a depth-first walk that takes the left child first meets the leaves in
+// ascending j.  The children are therefore pushed right then left, and a right child that is a leaf waits on the stack behind an inner left
+// sibling (a stack entry with depth field 63 is a leaf; a node's depth is capped at 62, above any exact_depth: height <= 63 and at least 3
+// sweeps).  The count pass (FILL false) and the fill pass evaluate the same predicate, so they select the same set; the fill pass writes
+// entry offsets[i] + rank, and only below offsets[i + 1] and below `capacity` -- offsets from another query can misplace entries, never put
+// one outside the caller's arrays.  `first`: sphere j is selected only if j >= first[i], a compare at the leaf (no subtree is pruned by it).
+// SELF (contact pairs): point i is the centre of L[i], its bound fl(radius_i + max_dist), first = i + 1; `point` then is the pair array,
+// rows {i, j}.
+constexpr int kWithinLeaf = 63, kWithinMaxDepth = 62;
+__device__ __forceinline__ int within_node_entry(int node, int depth) {
+  return (int)((unsigned)node | ((unsigned)(depth < kWithinMaxDepth ? depth : kWithinMaxDepth) << 26));
+}
+__device__ __forceinline__ int within_leaf_entry(int j) { return (int)((unsigned)j | ((unsigned)kWithinLeaf << 26)); }
+
+template <bool FILL, bool SELF>
+__device__ __forceinline__ void within_lane(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev,
+                                            int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap,
+                                            int32_t *point) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  float px, py, pz;
+  int first = 0;
+  bool valid;
+  if constexpr (SELF) {
+    const float4 me = p.sph[i];
+    px = me.x, py = me.y, pz = me.z;
+    max_dist = (me.w + max_dist) + 0.0f;
+    first = i + 1;
+    valid = point_ok(px, py, pz) && max_dist_ok(max_dist);
+  } else {
+    px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
+    if (max_dist_dev != nullptr) max_dist = max_dist_dev[i] + 0.0f;   // (-0.0 -> +0.0)
+    if (first_dev != nullptr) first = first_dev[i] > 0 ? first_dev[i] : 0;
+    valid = point_ok(px, py, pz) && max_dist_ok(max_dist);
+  }
+  const float pmag = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
+  int cnt = 0;
+  int64_t at = 0, end = 0;
+  if constexpr (FILL) {
+    at = offsets[i];
+    end = offsets[i + 1] < capacity ? offsets[i + 1] : capacity;
+    if (at < 0) at = end;   // (offsets that are not a scan of counts: nothing is written)
+  }
+  int sp = 0;
+  if (valid) stack[sp++][lane] = within_node_entry(0, 0);
+  while (sp > 0) {
+    const unsigned e = (unsigned)stack[--sp][lane];
+    const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
+    int leaf[2] = {-1, -1};
+    if (depth == kWithinLeaf) {
+      leaf[0] = ni;
+    } else {
+      const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+      if (depth >= exact_depth && !box_may_hold(px, py, pz, pmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, max_dist)) continue;
+      const int l = f2i(lo.w), r = f2i(hi.w);
+      // (one pending sibling per level: sp <= height + 1 <= kStackPixel)
+      if (l < 0) {
+        leaf[0] = ~l;
+        if (r < 0) leaf[1] = ~r;
+        else stack[sp++][lane] = within_node_entry(r, depth + 1);
+      } else {
+        stack[sp++][lane] = r < 0 ? within_leaf_entry(~r) : within_node_entry(r, depth + 1);
+        stack[sp++][lane] = within_node_entry(l, depth + 1);
+      }
+    }
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      const int j = leaf[c2];
+      if (j >= first) {   // (first >= 0: an empty leaf slot, -1, never passes)
+        const float4 s = buf_load16(rs_sph, j * 16);
+        const float g = point_gap(px, py, pz, s.x, s.y, s.z, s.w);
+        if (g <= max_dist) {
+          if constexpr (FILL) {
+            if (at < end) {
+              if constexpr (SELF) {
+                if (point != nullptr) *reinterpret_cast<int2 *>(point + 2 * at) = make_int2(i, j);
+              } else {
+                if (index != nullptr) index[at] = j;
+                if (point != nullptr) point[at] = i;
+              }
+              if (gap != nullptr) gap[at] = g;
+            }
+            ++at;
+          } else {
+            ++cnt;
+          }
+        }
+      }
+    }
+  }
+  if constexpr (!FILL) count[i] = cnt;
+}
+template <bool FILL, bool SELF>
+__global__ __launch_bounds__(64) void within_kernel(KParams p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev,
+                                                    int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index,
+                                                    float *gap, int32_t *point) {
+  within_lane<FILL, SELF>(p, pts, max_dist_dev, max_dist, first_dev, exact_depth, count, offsets, capacity, index, gap, point);
+}
+
+// The scan between the two passes: n int32 counts -> n + 1 int64 offsets (offsets[0] = 0, offsets[i + 1] = counts[0] + .. + counts[i]), in
+// three plain launches.  No workgroup waits on another: 1. every workgroup sums its kWithinScanItems counts; 2. ONE workgroup turns the block
+// sums into their exclusive prefix, kWithinScanThreads at a time with a running carry; 3. every workgroup scans its own counts again on top
+// of its prefix.  All sums are 64-bit: a row may hold 2^26 entries, the total of 2^31 rows does not fit 32 bits.
+constexpr int kWithinScanThreads = 256, kWithinScanPer = 4, kWithinScanItems = kWithinScanThreads * kWithinScanPer;
+__device__ __forceinline__ long long wave_scan_incl(long long v, int lane) {
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long u = __shfl_up(v, o);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+// inclusive scan of v over the workgroup's kWithinScanThreads threads; *total = the workgroup's sum (wsum: one slot per wave, reusable after return)
+__device__ __forceinline__ long long block_scan_incl(long long v, long long *wsum, long long *total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long incl = wave_scan_incl(v, lane);
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  long long before = 0, all = 0;
+#pragma unroll
+  for (int k = 0; k < kWithinScanThreads / 64; ++k) {
+    const long long w = wsum[k];
+    if (k < wave) before += w;
+    all += w;
+  }
+  __syncthreads();
+  *total = all;
+  return before + incl;
+}
+__device__ __forceinline__ void within_load_counts(const int32_t *counts, int n, int (&c)[kWithinScanPer]) {
+  const long long at = ((long long)blockIdx.x * kWithinScanThreads + threadIdx.x) * kWithinScanPer;
+#pragma unroll
+  for (int q = 0; q < kWithinScanPer; ++q) c[q] = at + q < n ? counts[at + q] : 0;
+}
+__global__ __launch_bounds__(kWithinScanThreads) void within_scan_sums_kernel(const int32_t *counts, int n, long long *sums) {
+  __shared__ long long wsum[kWithinScanThreads / 64];
+  int c[kWithinScanPer];
+  within_load_counts(counts, n, c);
+  long long v = 0, total;
+#pragma unroll
+  for (int q = 0; q < kWithinScanPer; ++q) v += c[q];
+  (void)block_scan_incl(v, wsum, &total);
+  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(kWithinScanThreads) void within_scan_carry_kernel(long long *sums, int nblocks) {
+  __shared__ long long wsum[kWithinScanThreads / 64];
+  long long carry = 0;   // (the same value in every thread)
+  for (int base = 0; base < nblocks; base += kWithinScanThreads) {
+    const int b = base + (int)threadIdx.x;
+    const long long v = b < nblocks ? sums[b] : 0;
+    long long total;
+    const long long incl = block_scan_incl(v, wsum, &total);
+    if (b < nblocks) sums[b] = carry + incl - v;
+    carry += total;
+  }
+}
+__global__ __launch_bounds__(kWithinScanThreads) void within_scan_apply_kernel(const int32_t *counts, int n, const long long *sums, int64_t *offsets) {
+  __shared__ long long wsum[kWithinScanThreads / 64];
+  int c[kWithinScanPer];
+  within_load_counts(counts, n, c);
+  long long v = 0, total;
+#pragma unroll
+  for (int q = 0; q < kWithinScanPer; ++q) v += c[q];
+  long long run = sums[blockIdx.x] + block_scan_incl(v, wsum, &total) - v;
+  const long long at = ((long long)blockIdx.x * kWithinScanThreads + threadIdx.x) * kWithinScanPer;
+  if (at == 0) offsets[0] = 0;
+#pragma unroll
+  for (int q = 0; q < kWithinScanPer; ++q) {
+    run += c[q];
+    if (at + q < n) offsets[at + q + 1] = run;
+  }
+}
+
+size_t within_scratch_bytes(int64_t n) {
+  const size_t nblocks = ((size_t)n + kWithinScanItems - 1) / kWithinScanItems;
+  return (((size_t)n * 4 + 255) & ~(size_t)255) + nblocks * 8;
+}
+
+hipError_t launch_within_count(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
+                               int exact_depth, char *scratch, int64_t *offsets, hipStream_t stream) {
+  if (offsets == nullptr) return hipErrorInvalidValue;
+  if (p.nrays <= 0) return hipMemsetAsync(offsets, 0, sizeof(int64_t), stream);
+  if ((!self && pts == nullptr) || scratch == nullptr || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (self && p.nrays != p.n_sph) return hipErrorInvalidValue;
+  if ((self || max_dist_dev == nullptr) && !max_dist_ok(max_dist)) return hipErrorInvalidValue;
+  max_dist += 0.0f;   // (-0.0 -> +0.0)
+  const int n = p.nrays;
+  int32_t *const counts = reinterpret_cast<int32_t *>(scratch);
+  long long *const sums = reinterpret_cast<long long *>(scratch + (((size_t)n * 4 + 255) & ~(size_t)255));
+  const dim3 grid(((unsigned)n + 63u) / 64u), block(64);
+  if (self)
+    hipLaunchKernelGGL((within_kernel<false, true>), grid, block, 0, stream, p, nullptr, nullptr, max_dist, nullptr, exact_depth, counts, nullptr,
+                       (int64_t)0, nullptr, nullptr, nullptr);
+  else
+    hipLaunchKernelGGL((within_kernel<false, false>), grid, block, 0, stream, p, pts, max_dist_dev, max_dist, first_dev, exact_depth, counts, nullptr,
+                       (int64_t)0, nullptr, nullptr, nullptr);
+  const int nblocks = (int)(((int64_t)n + kWithinScanItems - 1) / kWithinScanItems);
+  hipLaunchKernelGGL(within_scan_sums_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums);
+  hipLaunchKernelGGL(within_scan_carry_kernel, dim3(1), dim3(kWithinScanThreads), 0, stream, sums, nblocks);
+  hipLaunchKernelGGL(within_scan_apply_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums, offsets);
+  return hipGetLastError();
+}
+
+hipError_t launch_within_fill(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
+                              int exact_depth, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point,
+                              hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if ((!self && pts == nullptr) || offsets == nullptr || capacity < 0 || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (self && (p.nrays != p.n_sph || index != nullptr)) return hipErrorInvalidValue;
+  if (index == nullptr && gap == nullptr && point == nullptr) return hipErrorInvalidValue;
+  if ((self || max_dist_dev == nullptr) && !max_dist_ok(max_dist)) return hipErrorInvalidValue;
+  max_dist += 0.0f;   // (-0.0 -> +0.0)
+  const dim3 grid(((unsigned)p.nrays + 63u) / 64u), block(64);
+  if (self)
+    hipLaunchKernelGGL((within_kernel<true, true>), grid, block, 0, stream, p, nullptr, nullptr, max_dist, nullptr, exact_depth, nullptr, offsets,
+                       capacity, nullptr, gap, point);
+  else
+    hipLaunchKernelGGL((within_kernel<true, false>), grid, block, 0, stream, p, pts, max_dist_dev, max_dist, first_dev, exact_depth, nullptr, offsets,
+                       capacity, index, gap, point);
+  return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void camera_rays_kernel(Cam cam, int h, int w, float *rays) {
   const int64_t n = (int64_t)h * w;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {

@@ -410,6 +410,18 @@ hipError_t launch_multi_hit_rays(const KParams &p, int k, int32_t *count, int32_
 constexpr int kNearestMaxK = 32;
 hipError_t launch_nearest_spheres(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, int k, int exact_depth,
                                   int32_t *count, int32_t *index, float *gap, hipStream_t stream);
+// rt_spheres_within_* / rt_contact_pairs_*: for p.nrays points EVERY sphere of L with gap <= the point's bound and j >= first_dev[i] (nullptr: no
+// lower index bound), as n + 1 int64 offsets and rows in ascending j.  launch_within_count: the count kernel (n int32 counts at `scratch`,
+// within_scratch_bytes(n) bytes of device memory) and the three launches of the scan, offsets[0 .. n]; p.nrays == 0 writes offsets[0] = 0.
+// launch_within_fill: entry offsets[i] + rank -> index / gap / point (any may be nullptr, not all), only below offsets[i + 1] and `capacity`.
+// self: the contact pairs -- point i is the centre of L[i] (p.nrays == p.n_sph), its bound fl(radius_i + max_dist), first = i + 1, and `point` is
+// the pair array, rows {i, j} (index must be nullptr).  Boxes are tested at depth >= exact_depth only, as launch_nearest_spheres.
+size_t within_scratch_bytes(int64_t n);
+hipError_t launch_within_count(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
+                               int exact_depth, char *scratch, int64_t *offsets, hipStream_t stream);
+hipError_t launch_within_fill(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
+                              int exact_depth, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point,
+                              hipStream_t stream);
 // the primary rays of an h x w frame through p.cam (get_ray at pixel_u / pixel_v), row-major from the top row: rays[6 (row w + col) ..]
 hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStream_t stream);
 // block = 64 * waves_per_wg threads (4, 8 or 16 waves); grid = persistent workgroups

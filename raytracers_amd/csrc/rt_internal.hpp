@@ -85,6 +85,8 @@ struct rt_context {
   size_t spill_bytes = 0;
   int *order_scratch = nullptr;   // the tile-order sort's chunk counts (rtk::kOrderScratchInts), allocated with the first record
   int *px_scratch = nullptr;      // the pixel-list sort's counts (rtk::px_scratch_ints()), likewise
+  char *within_scratch = nullptr;   // the range queries' count pass: its int32 counts and the scan's block sums (rtk::within_scratch_bytes), grown on demand
+  size_t within_bytes = 0;
   unsigned long long *stats_dev = nullptr;
   // per-(w, h) tables of the primary-ray parameters u = i / w and v = (h - row) / h
   struct UvTable {
