@@ -78,12 +78,13 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *   "family=within count|fill[ (per-point)][ first][ self]"   rt_spheres_within_count / _fill, rt_contact_pairs_count / _fill (" self"; below)
  *   "family=none (no rows)"       the part owns no row of the image
  *   "family=pixel" | "family=pixel (instrumented)" | "family=persistent"
- *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2"
+ *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2[ nodes=sign-ordered|planes]"
  *     T = rays (rt_trace_rays: blocks of 64 caller rays, instantiation plain[+SPILL]; rt_occluded_rays: instantiation any[+SPILL]; rt_occluded_rays_ranged:
  *         the same, with " intervals=per-ray" appended to the string) | pixel-list | tiles-ordered | tiles-bit-reversed (a view's first frame with nothing to borrow, first_order = 1) | tiles-raster,
  *         followed by "(borrowed)" when the order / list is another view's (a new view of a prepared scene that has rendered a view of the same shape)
  *     I = plain | SOLO | COLD | COLD+SOLO | DONATE | DONATE+SOLO | ORD | ORD+SOLO | ORD+DONATE | ORD+SOLO+DONATE;  +CULL: boxes tested against the best hit so far; +SPILL: a box stack that may overflow into device memory (twenty waves per CU, trees taller than 15 levels)
- *     recording: 0 nothing, 1 the tiles' longest chains, 2 also every pixel's chain length */
+ *     recording: 0 nothing, 1 the tiles' longest chains, 2 also every pixel's chain length
+ *     nodes (render launches): the layout of the node records staged in LDS -- sign-ordered: the plain instantiations on a scene that is in LDS whole; planes: every other launch */
 const char *rt_context_last_launch(const rt_context *ctx);
 int rt_context_sync(rt_context *ctx);
 /* Threads: every entry that takes a context holds that context's lock for the duration of the call (as a Futhark context does:

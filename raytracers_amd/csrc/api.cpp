@@ -528,6 +528,11 @@ std::string pooled_launch_name(const rtk::KParams &p, int waves, int rays = 0) {
   rtk::PooledKey k{};
   return rtk::choose_pooled(p, false, waves, rays, &k) ? rtk::pooled_name(k) : "none";
 }
+// ... and its node layout in LDS: "sign-ordered" (the PRESORT instantiations) or "planes"
+const char *pooled_launch_nodes(const rtk::KParams &p, int waves) {
+  rtk::PooledKey k{};
+  return rtk::choose_pooled(p, false, waves, 0, &k) && rtk::pooled_presort(k) ? "sign-ordered" : "planes";
+}
 
 // p's scene fields: the prepared scene's traversal copy
 void scene_params(const rt_prepared *ps, rtk::KParams *p) {
@@ -951,10 +956,10 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
   RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream));
   tick("launch_pooled");
   char buf[256];
-  std::snprintf(buf, sizeof buf, "family=pooled tickets=%s%s instantiation=%s frames=%d tiles=%d grid=%d waves=%d counters=%d%s deep_class=%d deep_split=%d recording=%d",
+  std::snprintf(buf, sizeof buf, "family=pooled tickets=%s%s instantiation=%s frames=%d tiles=%d grid=%d waves=%d counters=%d%s deep_class=%d deep_split=%d recording=%d nodes=%s",
                 p.px_hdr ? "pixel-list" : t.first_order ? "tiles-bit-reversed" : (p.order ? "tiles-ordered" : "tiles-raster"), t.borrowed ? "(borrowed)" : "",
                 pooled_launch_name(p, pl.waves).c_str(), p.nframes, p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "", p.px_hdr ? 0 : p.deep_class,
-                p.px_hdr ? 0 : p.deep_split, p.cost ? (p.cost_px ? 2 : 1) : 0);
+                p.px_hdr ? 0 : p.deep_split, p.cost ? (p.cost_px ? 2 : 1) : 0, pooled_launch_nodes(p, pl.waves));
   ctx->last_launch = buf;
   if (to && p.cost) {
     // This frame recorded the view's bounce chains.  The sorts that turn the record into the view's tile order and pixel list are

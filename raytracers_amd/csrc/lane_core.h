@@ -107,6 +107,50 @@ RT_HD bool box_hit_interval(const Ray &r, float lox, float loy, float loz, float
   tmax = fminf(nz ? t0z : t1z, tmax);
   return !(tmax <= tmin);
 }
+// box_hit_interval for a caller that holds the bounds already ORDERED by the ray's signs: near_k = (r.i_k < 0 ? hi_k : lo_k), far_k the
+// other one.  Bit-equal to box_hit_interval on the same box in every case: `nx ? t1 : t0` picks between two products, each of which is a
+// function of its own operands alone -- (lo - o) * i or (hi - o) * i, one IEEE subtraction and one IEEE multiplication (no contraction) --
+// so computing only the picked product from the picked operand, ((nx ? hi : lo) - o) * i, gives the same bits, NaN products (0 * inf:
+// the origin on a slab of a zero direction component) and their payloads included.  The select still happens on `i_k < 0` (sign_offsets
+// below), never through min / max, and the fmaxf / fminf chain is box_hit_interval's in its order.  What moves is WHERE the select is
+// made: once per ray, as a choice of addresses, instead of six v_cndmask per box (the pooled kernel's LDS-resident instantiation).
+RT_HD bool box_hit_presorted(const Ray &r, float nx, float fx, float ny, float fy, float nz, float fz, float tlo, float thi) {
+  float tmin = fmaxf((nx - r.ox) * r.ix, tlo);
+  float tmax = fminf((fx - r.ox) * r.ix, thi);
+  tmin = fmaxf((ny - r.oy) * r.iy, tmin);
+  tmax = fminf((fy - r.oy) * r.iy, tmax);
+  tmin = fmaxf((nz - r.oz) * r.iz, tmin);
+  tmax = fminf((fz - r.oz) * r.iz, tmax);
+  return !(tmax <= tmin);
+}
+// The ray's three selects as one word: bit 3 / 4 / 5 set iff i_x / i_y / i_z < 0.0f (true for -inf and every negative finite value; false
+// for +-0, +inf and NaN -- box_hit_interval's own condition).  The bits are the BYTE distances between a record's lo and hi entries of
+// that axis in the sign-ordered node layout (render_kernels.hip, PRESORT): near_k is read at `entry_k + (w & d_k)`, far_k at
+// `entry_k + d_k - (w & d_k)` (= `entry_k + ((w ^ kSignAll) & d_k)`).
+constexpr uint32_t kSignX = 8u, kSignY = 16u, kSignZ = 32u, kSignAll = kSignX | kSignY | kSignZ;
+RT_HD uint32_t sign_offsets(const Ray &r) {
+  return (r.ix < 0.0f ? kSignX : 0u) | (r.iy < 0.0f ? kSignY : 0u) | (r.iz < 0.0f ? kSignZ : 0u);
+}
+// The sign-ordered node record: 14 dwords in seven 8-byte entries {left child's value, right child's value}; the lo and hi entries of an
+// axis lie d_k = 8 / 16 / 32 bytes apart (x / y / z), the child references take the entry that is left over:
+//   byte  0 z lo | 8 y lo | 16 refs | 24 y hi | 32 z hi | 40 x lo | 48 x hi
+// Seven entries make the record's stride an ODD number of 8-byte bank pairs: the ds_read_b64 of 32 lanes on 32 different records are
+// conflict-free whichever records they are consecutive in, and random records spread over all 32 pairs (a 64-byte stride: over four).
+constexpr int kPsNodeBytes = 56, kPsX = 40, kPsY = 8, kPsZ = 0, kPsRefs = 16;
+// (the work items of the instantiations that use it: the record's byte offset -- a multiple of 8 -- from bit 11, the ray's sign_offsets << 5 in
+// bits 8 .. 10, the slot * 4 below)
+constexpr int kPsItemShift = 11;
+constexpr uint32_t kPsItemLow = 0x7fcu;
+RT_HD void presort_pack(uint32_t *cell, const float *lo_l, const float *hi_l, const float *lo_r, const float *hi_r, uint32_t ref_l, uint32_t ref_r) {
+  auto put = [&](int byte, float l, float r) {
+    __builtin_memcpy(cell + byte / 4, &l, 4);
+    __builtin_memcpy(cell + byte / 4 + 1, &r, 4);
+  };
+  put(kPsX, lo_l[0], lo_r[0]); put(kPsX + (int)kSignX, hi_l[0], hi_r[0]);
+  put(kPsY, lo_l[1], lo_r[1]); put(kPsY + (int)kSignY, hi_l[1], hi_r[1]);
+  put(kPsZ, lo_l[2], lo_r[2]); put(kPsZ + (int)kSignZ, hi_l[2], hi_r[2]);
+  cell[kPsRefs / 4] = ref_l; cell[kPsRefs / 4 + 1] = ref_r;
+}
 RT_HD bool box_hit_clamped(const Ray &r, float lox, float loy, float loz, float hix, float hiy, float hiz, float tclamp) {
   return box_hit_interval(r, lox, loy, loz, hix, hiy, hiz, 0.0f, tclamp);
 }

@@ -435,6 +435,16 @@ __device__ __forceinline__ float4 lds_load16(unsigned a) {
   const v4f v = *reinterpret_cast<const __attribute__((address_space(3))) v4f *>(a);
   return make_float4(v.x, v.y, v.z, v.w);
 }
+// (PRESORT) reads of a sign-ordered node record through LDS pointers: the constant part of an address ends up in the instruction's offset
+typedef float v2f __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(3))) char *lds_cp;
+__device__ __forceinline__ lds_cp lds_ptr(unsigned a) { return reinterpret_cast<lds_cp>(a); }
+__device__ __forceinline__ v2f lds_load8(lds_cp a) { return *reinterpret_cast<const __attribute__((address_space(3))) v2f *>(a); }   // (8-byte aligned: ds_read_b64)
+__device__ __forceinline__ float lds_load4f(lds_cp a) { return *reinterpret_cast<const __attribute__((address_space(3))) float *>(a); }
+// the near / far entries of axis k: `t` = the ray's sign offsets & d_k (0, or the distance d_k from the lo entry to the hi entry): near at
+// entry + t, far at entry + d_k - t -- an and, an add and a sub per axis, all of the cheap issue class
+#define RT_PS_NEAR(cell, t, entry) ((cell) + (t) + (entry))
+#define RT_PS_FAR(cell, t, entry, dist) ((cell) - (t) + ((entry) + (int)(dist)))
 __device__ __forceinline__ unsigned lds_load4(unsigned a) { return *reinterpret_cast<const __attribute__((address_space(3))) unsigned *>(a); }
 
 // (CULL exists here and is NOT used, kSoloCull: a lone ray's box items are all expanded before its first sphere test -- the leaves sit at
@@ -663,6 +673,10 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
   static_assert(!RAYS || (!STATS && !SOLO && TAIL == 0 && !ORD && !CULL), "RAYS: the plain instantiations only");
   static_assert(!ORD || TAIL != 1, "ORD: no COLD variant");   // (ORD + DONATE: a frame rendered through a pixel list BORROWED from a neighbouring view, round 6)
   static_assert(!CULL || !ALL_LDS, "CULL: instantiated for the general scene path only");
+  // PRESORT: the plain instantiations on a scene wholly in LDS stage the node records SIGN-ORDERED (lane_core.h: presort_pack, 56 bytes in the
+  // place of the 64-byte record) and every box item carries its ray's sign offsets: BOX and BOX2 read near / far bounds at selected addresses
+  // instead of selecting among products (box_hit_presorted).  The instantiations that call solo_trace keep the four planes its treelet reads use.
+  constexpr bool PRESORT = pooled_presort(ALL_LDS, SOLO, TAIL, ORD, RAYS);
   extern __shared__ float4 smem[];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -682,7 +696,18 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
   const __amdgpu_buffer_rsrc_t rs_col = make_rsrc(p.col, (unsigned)p.n_sph * 16u);
 
   // stage the node prefix as four planes of quarters, then the sphere prefix
-  for (int i = threadIdx.x; i < 4 * plane; i += THREADS) smem[(i & 3) * plane + (i >> 2)] = p.nodes64[i];
+  if constexpr (PRESORT) {
+    // (PRESORT items: bits 2 .. 7 the slot * 4 as everywhere, bits 8 .. 10 the ray's signs -- sign_offsets << 5, set with the root item and
+    // handed down from an item to its children, so that a record's addresses need the item alone and its reads go out next to the ray's --
+    // and from bit 11 the byte offset of the node's record, or ~leaf.  The staged child references are stored in that form)
+    auto ref_of = [](float w) { const int c = f2i(w) >> 8; return (unsigned)(c < 0 ? c : c * kPsNodeBytes) << kPsItemShift; };
+    for (int i = threadIdx.x; i < plane; i += THREADS) {
+      const float4 ll = p.nodes64[4 * i], lh = p.nodes64[4 * i + 1], rl = p.nodes64[4 * i + 2], rh = p.nodes64[4 * i + 3];
+      presort_pack(reinterpret_cast<unsigned *>(smem) + (kPsNodeBytes / 4) * i, &ll.x, &lh.x, &rl.x, &rh.x, ref_of(ll.w), ref_of(lh.w));
+    }
+  } else {
+    for (int i = threadIdx.x; i < 4 * plane; i += THREADS) smem[(i & 3) * plane + (i >> 2)] = p.nodes64[i];
+  }
   for (int i = threadIdx.x; i < p.lds_sph; i += THREADS) smem[sph_base + i] = p.sph[i];
   // Zero the wave's region: lanes without an item read a stale entry and compute on it with
   // their results masked off, so every stale entry must decode to valid indices.
@@ -1178,7 +1203,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
             if (STATS) { n_rays++; n_box++; }
           }
           const unsigned long long m_root = bal(root_hit);
-          if (root_hit) wbox[nbox + lane_rank(m_root)] = (unsigned)lane << 2;   // (node 0, slot = lane)
+          if (root_hit) wbox[nbox + lane_rank(m_root)] = (unsigned)lane << 2 | (PRESORT ? sign_offsets(r) << 5 : 0u);   // (node 0, slot = lane; PRESORT: + the ray's signs)
           nbox = uni(nbox + __popcll(m_root));
           // Issue priority follows the deepest bounce chain this wave carries: the frame cannot
           // end before its longest chain (up to 50 dependent folds) does, and a wave that shares
@@ -1208,7 +1233,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
       const bool act = top >= 0;
       nleaf = uni(nleaf > 64 ? nleaf - 64 : 0);
       const int sl = (int)(item & 0xfcu) >> 2;
-      const int j = ~((int)item >> 8);        // stale zero entry -> ~0 = -1: masked below
+      const int j = ~((int)item >> (PRESORT ? kPsItemShift : 8));        // stale zero entry -> ~0 = -1: masked below
       const float4 ra = wray[sl];
       Ray q;
       q.ox = ra.x; q.oy = ra.y; q.oz = ra.z; q.a = ra.w;
@@ -1262,6 +1287,22 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         Ray q;
         q.ox = ra.x; q.oy = ra.y; q.oz = ra.z;
         q.ix = ri.x; q.iy = ri.y; q.iz = ri.z;
+        int cl8, cr8;                                 // child references, stored pre-shifted by 8 (sign = leaf)
+        unsigned long long m_hl, m_hr;                // lane masks straight from the compares; the rest is 64-bit scalar logic
+        if constexpr (PRESORT) {
+          // the record's seven entries, the near / far ones at the addresses the ray's signs pick: an and, an add and a sub per axis, the
+          // rest is the instruction's own offset
+          const lds_cp cell = lds_ptr((unsigned)(size_t)smem + (item >> kPsItemShift));
+          const int sn = (int)(item >> 5), tx = sn & (int)kSignX, ty = sn & (int)kSignY, tz = sn & (int)kSignZ;
+          const v2f nx = lds_load8(RT_PS_NEAR(cell, tx, kPsX)), fx = lds_load8(RT_PS_FAR(cell, tx, kPsX, kSignX));
+          const v2f ny = lds_load8(RT_PS_NEAR(cell, ty, kPsY)), fy = lds_load8(RT_PS_FAR(cell, ty, kPsY, kSignY));
+          const v2f nz = lds_load8(RT_PS_NEAR(cell, tz, kPsZ)), fz = lds_load8(RT_PS_FAR(cell, tz, kPsZ, kSignZ));
+          const v2f refs = lds_load8(cell + kPsRefs);
+          asm volatile("" ::"v"(ra.w), "v"(ri.w));    // 16-byte reads of the ray
+          cl8 = f2i(refs.x); cr8 = f2i(refs.y);
+          m_hl = bal(box_hit_presorted(q, nx.x, fx.x, ny.x, fy.x, nz.x, fz.x, 0.0f, kTMax));
+          m_hr = bal(box_hit_presorted(q, nx.y, fx.y, ny.y, fy.y, nz.y, fz.y, 0.0f, kTMax));
+        } else {
         float4 q0, q1, q2, q3;
         {
           const int lo16 = ALL_LDS ? ni16 : (ni16 < 16 * plane ? ni16 : 0);
@@ -1275,7 +1316,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           }
         }
         asm volatile("" ::"v"(q2.w), "v"(q3.w), "v"(ra.w), "v"(ri.w));   // 16-byte reads throughout
-        const int cl8 = f2i(q0.w), cr8 = f2i(q1.w);   // child references, stored pre-shifted by 8 (sign = leaf)
+        cl8 = f2i(q0.w); cr8 = f2i(q1.w);
         // (CULL: the interval's upper end is the slot's best root so far -- the high word of its hit key, one ds_read_b32 -- widened by
         // the proven margin; the ray's weight W2 travels in the spare dword of the {1/d} entry.  Two v_fma + one v_min per item.)
         float limc = kTMax, limlo = 0.0f;
@@ -1285,9 +1326,9 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           limlo = ri.w;
           limc = __uint_as_float(*reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(wkey) + 2 * sl4 + 4));
         }
-        // lane masks straight from the compares; the rest is 64-bit scalar logic
-        const unsigned long long m_hl = bal(box_hit_interval(q, q0.x, q0.y, q0.z, q1.x, q1.y, q1.z, limlo, limc));
-        const unsigned long long m_hr = bal(box_hit_interval(q, q2.x, q2.y, q2.z, q3.x, q3.y, q3.z, limlo, limc));
+        m_hl = bal(box_hit_interval(q, q0.x, q0.y, q0.z, q1.x, q1.y, q1.z, limlo, limc));
+        m_hr = bal(box_hit_interval(q, q2.x, q2.y, q2.z, q3.x, q3.y, q3.z, limlo, limc));
+        }
         const unsigned long long m_ln = bal(cl8 < 0), m_rn = bal(cr8 < 0);
         // an inner child continues iff its box passes; a leaf child is tested because this node passed
         const unsigned long long m_inl = m_act & ~m_ln & m_hl, m_inr = m_act & ~m_rn & m_hr;
@@ -1302,8 +1343,9 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         const int a_l = sel_mask(m_lfl, sel_mask(m_inl, dump, b_box + 4 * lane_rank(m_inl)), b_leaf + 4 * lane_rank(m_lfl));
         const int a_r = sel_mask(m_lfr, sel_mask(m_inr, dump, b_box + 4 * lane_rank_from(m_inr, c_inl)),
                                  b_leaf + 4 * lane_rank_from(m_lfr, c_lfl));
-        lds_store(a_l, (unsigned)cl8 | (unsigned)sl4);
-        lds_store(a_r, (unsigned)cr8 | (unsigned)sl4);
+        const unsigned low = PRESORT ? item & kPsItemLow : (unsigned)sl4;   // what a child's item inherits: the slot (PRESORT: and the ray's signs)
+        lds_store(a_l, (unsigned)cl8 | low);
+        lds_store(a_r, (unsigned)cr8 | low);
         nbox = uni(nbox + c_inl + __popcll(m_inr));
         nleaf = uni(nleaf + c_lfl + __popcll(m_lfr));
         // outstanding inner-node items of the slot: one consumed, k in {0, 1, 2} appended.  Only items with k != 1
@@ -1333,9 +1375,32 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         Ray q;
         q.ox = ra.x; q.oy = ra.y; q.oz = ra.z;
         q.ix = ri.x; q.iy = ri.y; q.iz = ri.z;
+        int ref, cl8, cr8;
+        bool pass, child_leaf;
+        unsigned long long m_pass, m_cleaf, m_hl, m_hr;
+        if constexpr (PRESORT) {
+          // this lane's child: dword `role` of the entries of the item's record; then the child's own record as in BOX
+          const int sn = (int)(item >> 5), tx = sn & (int)kSignX, ty = sn & (int)kSignY, tz = sn & (int)kSignZ;
+          const lds_cp cell = lds_ptr((unsigned)(size_t)smem + (item >> kPsItemShift) + 4u * (unsigned)role);
+          const float cnx = lds_load4f(RT_PS_NEAR(cell, tx, kPsX)), cfx = lds_load4f(RT_PS_FAR(cell, tx, kPsX, kSignX));
+          const float cny = lds_load4f(RT_PS_NEAR(cell, ty, kPsY)), cfy = lds_load4f(RT_PS_FAR(cell, ty, kPsY, kSignY));
+          const float cnz = lds_load4f(RT_PS_NEAR(cell, tz, kPsZ)), cfz = lds_load4f(RT_PS_FAR(cell, tz, kPsZ, kSignZ));
+          ref = f2i(lds_load4f(cell + kPsRefs));
+          child_leaf = act & (ref < 0);
+          pass = act & (ref >= 0) && box_hit_presorted(q, cnx, cfx, cny, cfy, cnz, cfz, 0.0f, kTMax);
+          const lds_cp cell2 = lds_ptr((unsigned)(size_t)smem + (pass ? (unsigned)ref >> kPsItemShift : 0u));
+          const v2f nx = lds_load8(RT_PS_NEAR(cell2, tx, kPsX)), fx = lds_load8(RT_PS_FAR(cell2, tx, kPsX, kSignX));
+          const v2f ny = lds_load8(RT_PS_NEAR(cell2, ty, kPsY)), fy = lds_load8(RT_PS_FAR(cell2, ty, kPsY, kSignY));
+          const v2f nz = lds_load8(RT_PS_NEAR(cell2, tz, kPsZ)), fz = lds_load8(RT_PS_FAR(cell2, tz, kPsZ, kSignZ));
+          const v2f refs = lds_load8(cell2 + kPsRefs);
+          asm volatile("" ::"v"(ra.w), "v"(ri.w));
+          cl8 = f2i(refs.x); cr8 = f2i(refs.y);
+          m_pass = bal(pass); m_cleaf = bal(child_leaf);
+          m_hl = bal(box_hit_presorted(q, nx.x, fx.x, ny.x, fy.x, nz.x, fz.x, 0.0f, kTMax));
+          m_hr = bal(box_hit_presorted(q, nx.y, fx.y, ny.y, fy.y, nz.y, fz.y, 0.0f, kTMax));
+        } else {
         // this lane's child: its box is quarters (2 role, 2 role + 1) of the item's record, its reference the .w of quarter `role`
         float4 lo, hi;
-        int ref;
         {
           const bool res = ALL_LDS || ni16 < 16 * plane;
           const int lo16 = res ? ni16 : 0;
@@ -1355,8 +1420,8 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           limlo = ri.w;
           limc = __uint_as_float(*reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(wkey) + 2 * sl4 + 4));
         }
-        const bool child_leaf = act & (ref < 0);
-        const bool pass = act & (ref >= 0) && box_hit_interval(q, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, limlo, limc);
+        child_leaf = act & (ref < 0);
+        pass = act & (ref >= 0) && box_hit_interval(q, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, limlo, limc);
         if (STATS) n_box += (act & (ref >= 0)) ? 1 : 0;
         // second level: the child's own record (a virtual item `ref | sl4`)
         const int ci16 = pass ? (int)(((unsigned)ref >> 4) & 0xfffffff0u) : 0;
@@ -1373,10 +1438,11 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           }
         }
         asm volatile("" ::"v"(q2.w), "v"(q3.w), "v"(ra.w), "v"(ri.w), "v"(lo.w), "v"(hi.w));
-        const int cl8 = f2i(q0.w), cr8 = f2i(q1.w);
-        const unsigned long long m_pass = bal(pass), m_cleaf = bal(child_leaf);
-        const unsigned long long m_hl = bal(box_hit_interval(q, q0.x, q0.y, q0.z, q1.x, q1.y, q1.z, limlo, limc));
-        const unsigned long long m_hr = bal(box_hit_interval(q, q2.x, q2.y, q2.z, q3.x, q3.y, q3.z, limlo, limc));
+        cl8 = f2i(q0.w); cr8 = f2i(q1.w);
+        m_pass = bal(pass); m_cleaf = bal(child_leaf);
+        m_hl = bal(box_hit_interval(q, q0.x, q0.y, q0.z, q1.x, q1.y, q1.z, limlo, limc));
+        m_hr = bal(box_hit_interval(q, q2.x, q2.y, q2.z, q3.x, q3.y, q3.z, limlo, limc));
+        }
         const unsigned long long m_ln = bal(cl8 < 0), m_rn = bal(cr8 < 0);
         const unsigned long long m_inl = m_pass & ~m_ln & m_hl, m_inr = m_pass & ~m_rn & m_hr;
         // leaf appends: the child itself (lanes whose child is a leaf), or its leaf children -- never both for one lane
@@ -1388,8 +1454,9 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         const int a_l = sel_mask(m_lfl, sel_mask(m_inl, dump, b_box + 4 * lane_rank(m_inl)), b_leaf + 4 * lane_rank(m_lfl));
         const int a_r = sel_mask(m_lfr, sel_mask(m_inr, dump, b_box + 4 * lane_rank_from(m_inr, c_inl)),
                                  b_leaf + 4 * lane_rank_from(m_lfr, c_lfl));
-        lds_store(a_l, (unsigned)sel_mask(m_cleaf, cl8, ref) | (unsigned)sl4);
-        lds_store(a_r, (unsigned)cr8 | (unsigned)sl4);
+        const unsigned low = PRESORT ? item & kPsItemLow : (unsigned)sl4;
+        lds_store(a_l, (unsigned)sel_mask(m_cleaf, cl8, ref) | low);
+        lds_store(a_r, (unsigned)cr8 | low);
         nbox = uni(c_inl + __popcll(m_inr));
         nleaf = uni(nleaf + c_lfl + __popcll(m_lfr));
         // the slot's counter of outstanding inner-node items: this lane's appended inner grandchildren, minus the item

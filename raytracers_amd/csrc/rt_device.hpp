@@ -376,6 +376,12 @@ inline bool choose_pooled(const KParams &p, bool stats, int waves_per_wg, int ra
   return true;
 }
 
+// PRESORT: the instantiations that stage the node records sign-ordered (lane_core.h: presort_pack) and read near / far bounds at addresses the
+// ray's signs pick -- the plain render kernels on a scene wholly in LDS.  The kernels that call solo_trace (SOLO, COLD, DONATE, ORD: its treelet
+// reads want the four planes of quarters), the caller-ray loops and everything that reads nodes from L2 keep the 64-byte records.
+constexpr bool pooled_presort(bool all_lds, bool solo, int tail, bool ord, int rays) { return all_lds && !solo && tail == 0 && !ord && rays == 0; }
+constexpr bool pooled_presort(const PooledKey &k) { return pooled_presort(k.all_lds, k.solo, k.tail, k.ord, k.rays); }
+
 // The instantiation's name in rt_context_last_launch: plain, SOLO, COLD, COLD+SOLO, DONATE, DONATE+SOLO, ORD, ORD+SOLO, ORD+DONATE, ORD+SOLO+DONATE,
 // any (the occlusion loop); then +CULL, +SPILL
 inline std::string pooled_name(const PooledKey &k) {

@@ -9,6 +9,8 @@
 //     voting policy, and the SIMT lane efficiency of each phase.
 //
 //   build/wavesim <rgbbox|irreg|floor:n:k> <h> <w> [thr_shade thr_leaf lmax nwaves policy]
+//   (policy 10 / 11: the pooled design with 64 / 128 items per operation; 12: policy 10 plus the LDS cost of every BOX operation's node
+//   reads under the four-plane layout and the candidate sign-ordered layouts -- e.g. wavesim rgbbox 1000 1000 32 0 64 4096 12)
 #include <omp.h>
 
 #include <algorithm>
@@ -267,6 +269,97 @@ struct PCounters {
 static inline unsigned f2u(float f) { unsigned u; std::memcpy(&u, &f, 4); return u; }
 static inline float u2f(unsigned u) { float f; std::memcpy(&f, &u, 4); return f; }
 
+// ---- LDS cost of a BOX operation's node reads under candidate layouts of the staged records (policy 12) ------------------------------
+// Every BOX operation hands its lanes' (record, ray signs) to each layout, which issues the wave-instructions the kernel would and counts
+// LDS-array cycles by the rules of the LDS table: an instruction is served in fixed lane groups, a group takes one cycle plus one for
+// every further DISTINCT address on its busiest bank (equal addresses broadcast).  ds_read_b32: two groups of 32 lanes, bank = dword
+// address mod 32; ds_read_b64: two groups of 32, mod 64; ds_read_b128: four groups of 16 (the table's lane sets), mod 64; ds_read2_b32: two
+// ds_read_b32.  Lanes without an item read the record of the stack's bottom item, as the kernel's do.  The simulator's BOX items are
+// nodes whose OWN box is about to be tested (the kernel's: nodes whose box passed, read for their children's boxes) and it has no BOX2:
+// the batches' composition -- which records meet in one instruction -- is what the model takes from it.
+struct LdsLayout {
+  const char *name;
+  int node_bytes;
+  unsigned long long insts = 0, cycles = 0, conflicts = 0;
+};
+enum { L_PLANES, L_DWORD, L_TRIPLE, L_BOTH, L_PAIRS, L_COUNT };
+static LdsLayout g_lds[L_COUNT] = {{"today: four planes of 16-byte quarters, 4 ds_read_b128", 64},
+                                   {"(A) 14 dword planes, 14 ds_read_b32", 56},
+                                   {"(B) {lo, hi, lo} triples, 6 ds_read2_b32 + ds_read_b64", 80},
+                                   {"(C) both orders, 7 ds_read_b64", 104},
+                                   {"(D) pairs {left, right} per entry, lo / hi picked by address, 7 ds_read_b64", 56}};
+static bool g_lds_model = false;
+static unsigned long long g_lds_ops = 0;
+
+// one wave-instruction: lane l reads `dwords` consecutive dwords at byte address addr[l]
+static void lds_inst(LdsLayout &L, const unsigned *addr, int dwords, int ngroups, int nbanks, bool count_inst = true) {
+  static const int g128[32] = {0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1};
+  if (count_inst) L.insts++;
+  for (int g = 0; g < ngroups; ++g) {
+    unsigned seen[64][32];
+    int nseen[64] = {0};
+    int worst = 1;
+    for (int l = 0; l < 64; ++l) {
+      const int gl = ngroups == 4 ? g128[l & 31] + 2 * (l >> 5) : (l >> 5);
+      if (gl != g) continue;
+      for (int d = 0; d < dwords; ++d) {
+        const int b = (int)((addr[l] / 4 + d) % (unsigned)nbanks);
+        bool dup = false;
+        for (int k = 0; k < nseen[b]; ++k) dup |= seen[b][k] == addr[l];
+        if (!dup) {
+          seen[b][nseen[b]++] = addr[l];
+          worst = std::max(worst, nseen[b]);
+        }
+      }
+    }
+    L.cycles += worst;
+    L.conflicts += worst - 1;
+  }
+}
+
+// rec[l]: the record lane l reads; sg[l][k]: 1 / d_k < 0 for the lane's ray; n: records staged
+static void lds_model_box(const int *rec, const bool (*sg)[3], int n) {
+  unsigned a[64];
+  g_lds_ops++;
+  for (int q = 0; q < 4; ++q) {                                    // today
+    for (int l = 0; l < 64; ++l) a[l] = (unsigned)(q * 16 * n + 16 * rec[l]);
+    lds_inst(g_lds[L_PLANES], a, 4, 4, 64);
+  }
+  for (int child = 0; child < 2; ++child)
+    for (int k = 0; k < 3; ++k)
+      for (int far = 0; far < 2; ++far) {
+        // (A) plane = child * 6 + axis * 2 + (0: lo, 1: hi)
+        for (int l = 0; l < 64; ++l) a[l] = (unsigned)((child * 6 + k * 2 + ((int)sg[l][k] ^ far)) * 4 * n + 4 * rec[l]);
+        lds_inst(g_lds[L_DWORD], a, 1, 2, 32);
+      }
+  for (int c = 12; c < 14; ++c) {
+    for (int l = 0; l < 64; ++l) a[l] = (unsigned)(c * 4 * n + 4 * rec[l]);
+    lds_inst(g_lds[L_DWORD], a, 1, 2, 32);
+  }
+  for (int t = 0; t < 6; ++t) {
+    // (B) 80-byte records: triple t at 12 t, read2 at + 4 s: (near, far); (C) 104-byte records: {lo, hi, hi, lo} at 16 t, read at + 8 s
+    for (int l = 0; l < 64; ++l) a[l] = (unsigned)(80 * rec[l] + 12 * t + 4 * (int)sg[l][t % 3]);
+    lds_inst(g_lds[L_TRIPLE], a, 1, 2, 32);
+    for (int l = 0; l < 64; ++l) a[l] += 4u;
+    lds_inst(g_lds[L_TRIPLE], a, 1, 2, 32, false);
+    for (int l = 0; l < 64; ++l) a[l] = (unsigned)(104 * rec[l] + 16 * t + 8 * (int)sg[l][t % 3]);
+    lds_inst(g_lds[L_BOTH], a, 2, 2, 64);
+  }
+  for (int l = 0; l < 64; ++l) a[l] = (unsigned)(80 * rec[l] + 72);
+  lds_inst(g_lds[L_TRIPLE], a, 2, 2, 64);
+  for (int l = 0; l < 64; ++l) a[l] = (unsigned)(104 * rec[l] + 96);
+  lds_inst(g_lds[L_BOTH], a, 2, 2, 64);
+  // (D) lane_core.h: presort_pack
+  const int entry[3] = {kPsX, kPsY, kPsZ}, dist[3] = {(int)kSignX, (int)kSignY, (int)kSignZ};
+  for (int k = 0; k < 3; ++k)
+    for (int far = 0; far < 2; ++far) {
+      for (int l = 0; l < 64; ++l) a[l] = (unsigned)(kPsNodeBytes * rec[l] + entry[k] + (((int)sg[l][k] ^ far) ? dist[k] : 0));
+      lds_inst(g_lds[L_PAIRS], a, 2, 2, 64);
+    }
+  for (int l = 0; l < 64; ++l) a[l] = (unsigned)(kPsNodeBytes * rec[l] + kPsRefs);
+  lds_inst(g_lds[L_PAIRS], a, 2, 2, 64);
+}
+
 static bool pwave_step(PWave &W, const SceneData &S, int width, int thr_shade, unsigned &next_ticket,
                        std::vector<int32_t> &out, PCounters &C) {
   const size_t nbox = W.box.size(), nleaf = W.leaf.size();
@@ -292,6 +385,17 @@ static bool pwave_step(PWave &W, const SceneData &S, int width, int thr_shade, u
     std::vector<unsigned> items(W.box.end() - n, W.box.end());
     W.box.resize(nbox - n);
     C.lanes[0] += n;
+    if (g_lds_model && width == 64) {
+      int rec[64];
+      bool sg[64][3];
+      for (int l = 0; l < 64; ++l) {
+        const unsigned it = items[(size_t)l < n ? n - 1 - (size_t)l : 0];
+        const Ray &r = W.slot[it >> 24].r;
+        rec[l] = (int)(it & 0xffffff);
+        sg[l][0] = r.ix < 0.0f; sg[l][1] = r.iy < 0.0f; sg[l][2] = r.iz < 0.0f;
+      }
+      lds_model_box(rec, sg, (int)S.nodes.size());
+    }
     for (size_t k = 0; k < n; ++k) {
       const unsigned it = items[n - 1 - k];
       const int sl = it >> 24, ni = it & 0xffffff;
@@ -398,6 +502,13 @@ static int run_pooled(const SceneData &S, const std::vector<int32_t> &ref, int n
     std::printf("  %-5s wave-ops %10llu lanes %12llu efficiency %.3f\n", names[i], C.ops[i], C.lanes[i],
                 C.ops[i] ? (double)C.lanes[i] / ((i == 2 ? (double)g_nslots : (double)width) * C.ops[i]) : 0.0);
   std::printf("  rounds (longest wave, in phases) %llu  max box stack %zu  max leaf list %zu\n", rounds, C.max_box, C.max_leaf);
+  if (g_lds_model) {
+    std::printf("LDS model of the node reads, %llu BOX operations (%zu records):\n", g_lds_ops, S.nodes.size());
+    std::printf("  %-84s %5s %12s %14s %14s %9s %9s\n", "layout", "bytes", "wave-insts", "array cycles", "of them confl.", "cyc / op", "x free");
+    for (const LdsLayout &L : g_lds)
+      std::printf("  %-84s %5d %12llu %14llu %14llu %9.1f %9.2f\n", L.name, L.node_bytes, L.insts, L.cycles, L.conflicts,
+                  g_lds_ops ? (double)L.cycles / (double)g_lds_ops : 0.0, L.cycles > L.conflicts ? (double)L.cycles / (double)(L.cycles - L.conflicts) : 0.0);
+  }
   return diff ? 1 : 0;
 }
 
@@ -450,7 +561,8 @@ int main(int argc, char **argv) {
   std::printf("simple: checksum %08x rays %llu box %llu sphere %llu\n", checksum(ref), C0.rays, C0.box, C0.sphere);
 
   if (P.kind >= 10) {
-    // pooled design: kind 10 -> 64 items per op, kind 11 -> 128 items per op
+    // pooled design: kind 10 -> 64 items per op, kind 11 -> 128 items per op, kind 12 -> 10 with the LDS model of the node reads
+    g_lds_model = P.kind == 12;
     if (P.lmax >= 64) g_nslots = P.lmax;   // reuse the lmax argument: slots per wave
     return run_pooled(S, ref, nwaves, P.kind == 11 ? 128 : 64, P.thr_shade);
   }
