@@ -74,6 +74,7 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *   "family=pixel (rays)" | "family=intersect" | "family=occluded" | "family=camera-rays"   the caller-ray entries (below)
  *   "family=intersect (per-ray)" | "family=occluded (per-ray)"   their lane kernels with per-ray intervals (rt_*_rays_ranged)
  *   "family=multi-hit k=K" | "family=multi-hit k=K (per-ray)"   rt_multi_hit_rays / rt_multi_hit_rays_ranged (K: the caller's k)
+ *   "family=sweep k=K" [" (per-query)"] [" exclude"]   rt_sweep_spheres / rt_sweep_spheres_ranged (K: the caller's k)
  *   "family=nearest k=K[ pruned][ (per-point)]" | "family=none (no points)"   rt_nearest_spheres / rt_nearest_spheres_ranged (below)
  *   "family=within count|fill[ (per-point)][ first][ self]"   rt_spheres_within_count / _fill, rt_contact_pairs_count / _fill (" self"; below)
  *   "family=none (no rows)"       the part owns no row of the image
@@ -297,6 +298,42 @@ int rt_multi_hit_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const f
 int rt_multi_hit_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev,
                              const float *t_min_dev, const float *t_max_dev, int32_t k,
                              int32_t *count_dev, int32_t *index_dev, uint8_t *root_dev, float *hit7_dev);
+/* Sphere casts (sweeps): the first k contacts of a MOVING sphere -- continuous collision detection, a character or probe volume, a thick
+ * ray.  A query is a ray {o, d} (the n x 6 float32 layout of the ray queries), a radius rq and an interval (t_min, t_max): o is the moving
+ * sphere's centre at t = 0, d its displacement per unit t.  It meets sphere j of L (centre c, radius r) exactly where the ray of its
+ * centre meets the sphere (c, r + rq), so, in binary32 without contraction:
+ *     R = r + rq;  t1 = (-b - sq) / a, t2 = (-b + sq) / a: the two roots of sphere_hit (ray.fut:32-51) of the ray against (c, R), the
+ *     arithmetic of rt_multi_hit_rays with R in place of the radius; a discriminant <= 0 gives no contact, NaN roots pass no compare below.
+ *     Entry contact:         if t1 > t_min, the contact is tau = t1, start = 0, accepted iff t1 < t_max.
+ *     Overlap at the start:  otherwise, if t2 > t_min and t_min < t_max, the contact is tau = t_min (-0.0 reported as +0.0), start = 1: the
+ *                            moving sphere already overlaps j where the interval begins (the physics engines' convention: an initial
+ *                            overlap is a hit at distance zero).
+ *     Otherwise none (touching only at the exit, t2 == t_min, is none).  A sphere gives at most one contact.
+ * Sphere j is consulted iff every inner node on its root path passes aabb_hit (ray.fut:53-70) over (t_min, t_max) on the node's box WIDENED
+ * by rq per component, fl(lo_k - rq) and fl(hi_k + rq).  With rq = 0 (or -0.0) these are exactly the leaves rt_multi_hit_rays visits.  Like
+ * every ray query here this inherits the reference's partial boxes: on a tree taller than the AABB propagation's floor(log2 n) + 2 sweeps
+ * the nodes nearest the root do not contain their subtrees, and a sphere under a box the widened test fails is not consulted.
+ * The contacts of a query are ordered by (tau, j), ascending: several start overlaps come first, in ascending j (rt_spheres_within_* at
+ * p = o + t_min d with bound rq enumerates them all).  count_dev: n int32, all contacts (not capped at k).  The first min(count, k),
+ * row-major per query: index_dev n x k int32 (j), start_dev n x k uint8 (0 entry contact, 1 overlap at the start), hit7_dev n x k x 7
+ * float32 {tau, p.xyz, normal.xyz}: p = o + tau d is the moving sphere's CENTRE at contact, normal = (1.0f / R) * (p - c), one division per
+ * written slot (the touching point on the scene sphere is c + r * normal: left to the caller).  The slots past min(count, k) are -1, 0 and
+ * seven zero floats.  Any output may be NULL, not all four.  Exact, bit for bit, for every k: the answer for k = a is a prefix of the answer
+ * for k = b > a; k = 1 is the classic sphere cast.  The interval is never narrowed by the contacts found.
+ * Refused (non-zero, rt_last_error set, nothing launched): as rt_multi_hit_rays (n out of range, NULL rays, a multi-device context, the
+ * scalar interval rule, k < 1 or k > 32), and a radius that is not finite or outside [0, 1e9].  n == 0 succeeds without a launch.  One lane
+ * per query under every variant (rt_context_last_launch: "family=sweep k=<k>").
+ * rt_sweep_spheres_ranged: query i has its own radius_dev[i], t_min_dev[i], t_max_dev[i] (n float32 each; a NULL one is refused).  A query
+ * whose interval fails 0 <= t_min <= t_max <= 1e9 or whose radius fails 0 <= radius <= 1e9 (NaN, +-inf included) is a miss: count 0, every
+ * slot padded, its walk does not start; -0.0 behaves as 0.0.  exclude_dev: NULL, or n int32 -- sphere exclude_dev[i] is skipped at the leaf
+ * (one compare: neither counted nor listed); a value outside [0, num_spheres) excludes nothing.  This lets a scene sweep its own spheres:
+ * query i is the centre and radius of L[i], d its velocity times the time step, exclude = i.  rt_context_last_launch: "family=sweep k=<k>
+ * (per-query)", then " exclude" when exclude_dev is given. */
+int rt_sweep_spheres(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float radius, float t_min, float t_max,
+                     int32_t k, int32_t *count_dev, int32_t *index_dev, uint8_t *start_dev, float *hit7_dev);
+int rt_sweep_spheres_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *radius_dev,
+                            const float *t_min_dev, const float *t_max_dev, const int32_t *exclude_dev, int32_t k,
+                            int32_t *count_dev, int32_t *index_dev, uint8_t *start_dev, float *hit7_dev);
 /* ---- proximity: the spheres nearest to caller-supplied points ------------------------------------------------------------------
  * For a point p and sphere j of the prepared scene's L (centre c, radius r) the gap is the signed distance from p to the sphere's surface,
  * negative inside, as exactly this float32 arithmetic (no contraction, correctly rounded sqrtf):

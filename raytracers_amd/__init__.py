@@ -9,6 +9,7 @@ from .api import (Context, Prepared, RtError, Scene, MAX_DEPTH, ROWS_PER_TILE, V
                   ipc_export, ipc_import, ipc_close, trace_rays, trace_rays_into, intersect_rays, intersect_rays_into, camera_rays,
                   camera_rays_into, occluded_rays, occluded_rays_into, intersect_rays_ranged_into, occluded_rays_ranged_into,
                   multi_hit_rays, multi_hit_rays_into, multi_hit_rays_ranged_into,
+                  sweep_spheres, sweep_spheres_into, sweep_spheres_ranged_into,
                   nearest_spheres, nearest_spheres_into, nearest_spheres_ranged_into,
                   spheres_within, spheres_within_count_into, spheres_within_fill_into,
                   contact_pairs, contact_pairs_count_into, contact_pairs_fill_into)

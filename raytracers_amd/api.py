@@ -550,6 +550,28 @@ def contact_pairs_fill_into(prepared, offsets_ptr, capacity, pair_ptr, gap_ptr=N
                                          C.c_void_p(gap_ptr)))
 
 
+def sweep_spheres_into(rays_ptr, n, prepared, radius, k, count_ptr, index_ptr, start_ptr=None, hit_ptr=None, t_min=0.0, t_max=1.0):
+    """Enqueue the first k (1 <= k <= 32) contacts of `n` moving spheres of radius `radius` (rt_sweep_spheres): ray i is the centre's
+    origin and its displacement per unit t, the contacts over (t_min, t_max) are ordered by (tau, sphere).  Their count (n int32, not capped
+    at k) to count_ptr, sphere indices (n x k int32, -1 past the count) to index_ptr, start flags (n x k uint8: 1 for an overlap where the
+    interval begins, tau = t_min) to start_ptr and {tau, centre at contact xyz, normal xyz} (n x k x 7 float32) to hit_ptr.  Any pointer may
+    be None, not all four."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_sweep_spheres(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), float(radius), float(t_min), float(t_max), int(k),
+                                    C.c_void_p(count_ptr), C.c_void_p(index_ptr), C.c_void_p(start_ptr), C.c_void_p(hit_ptr)))
+
+
+def sweep_spheres_ranged_into(rays_ptr, n, prepared, radius_ptr, t_min_ptr, t_max_ptr, k, count_ptr, index_ptr, start_ptr=None, hit_ptr=None,
+                              exclude_ptr=None):
+    """sweep_spheres_into with query i's own radius_ptr[i] and interval (t_min_ptr[i], t_max_ptr[i]) (rt_sweep_spheres_ranged; n float32
+    each): a query whose interval fails 0 <= t_min <= t_max <= 1e9 or whose radius fails 0 <= radius <= 1e9 (NaN included) has no contact.
+    exclude_ptr: None, or n int32 on the device -- sphere exclude_ptr[i] is skipped for query i (a scene sweeping its own spheres)."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_sweep_spheres_ranged(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), C.c_void_p(radius_ptr), C.c_void_p(t_min_ptr),
+                                           C.c_void_p(t_max_ptr), C.c_void_p(exclude_ptr), int(k), C.c_void_p(count_ptr),
+                                           C.c_void_p(index_ptr), C.c_void_p(start_ptr), C.c_void_p(hit_ptr)))
+
+
 def camera_rays_into(rays_ptr, h, w, prepared, cam=None):
     """Enqueue the h * w primary rays rt_render_image would trace (rt_camera_rays) into rays_ptr (h * w x 6 float32)."""
     ctx = prepared.ctx
@@ -742,6 +764,50 @@ def multi_hit_rays(prepared, rays, k, t_min=0.0, t_max=1e9):
             keep.free()
 
 
+def sweep_spheres(prepared, rays, radius, k=1, t_min=0.0, t_max=1.0, exclude=None):
+    """The first k contacts of a sphere of radius `radius` whose centre moves from rays[i, :3] by rays[i, 3:] per unit t, over (t_min, t_max)
+    (rt_sweep_spheres) -> (count (n,) int32, index (n, k) int32, start (n, k) uint8, hit (n, k, 7) float32) numpy arrays.  With the default
+    t_max = 1.0 the direction is the displacement of one step.  A contact is the first touch of a scene sphere (start 0, tau = the time of
+    touch) or an overlap that already exists where the interval begins (start 1, tau = t_min); they are ordered by (tau, index).  hit =
+    {tau, the moving centre at contact, the normal from the scene sphere's centre towards it}.  k = 1 is the classic sphere cast.
+    radius, t_min or t_max may be an (n,) array / device tensor, one per query (rt_sweep_spheres_ranged; a scalar next to it is broadcast;
+    an invalid array value makes its query a miss; an invalid scalar, or a scalar pair with t_min > t_max, is an RtError).  exclude: None,
+    or an (n,) integer array / int32 device tensor -- sphere exclude[i] of L is skipped for query i, so a scene can sweep its own spheres
+    (also the ranged entry)."""
+    ctx = prepared.ctx
+    k = int(k)
+    ranged = _is_bound_array(radius) or _is_bound_array(t_min) or _is_bound_array(t_max) or exclude is not None
+    ptr, n, keep = _device_rays(ctx, rays)
+    bounds = []
+    cnt = idx = start = hit = None
+    try:
+        if ranged:
+            dev = ctx.device_info()["device"]
+            # (a scalar pair is held to the scalar entry's rule as a pair: each scalar alone passes _device_bound with t_min > t_max)
+            if not _is_bound_array(t_min) and not _is_bound_array(t_max) and not np.float32(t_min) <= np.float32(t_max):
+                raise RtError(f"t_min = {t_min!r}, t_max = {t_max!r}: scalar bounds must satisfy t_min <= t_max")
+            rad_ptr = _device_bound(ctx, dev, n, "radius", radius, bounds, per="query")
+            lo_ptr = _device_bound(ctx, dev, n, "t_min", t_min, bounds, per="query")
+            hi_ptr = _device_bound(ctx, dev, n, "t_max", t_max, bounds, per="query")
+            ex_ptr = _device_first(ctx, dev, n, exclude, bounds, name="exclude", per="query") if exclude is not None else None
+        nk = n * max(k, 0)
+        cnt = DeviceBuffer(ctx, max(4 * n, 4))
+        idx = DeviceBuffer(ctx, max(4 * nk, 4))
+        start = DeviceBuffer(ctx, max(nk, 4))
+        hit = DeviceBuffer(ctx, max(28 * nk, 4))
+        if ranged:
+            sweep_spheres_ranged_into(ptr, n, prepared, rad_ptr, lo_ptr, hi_ptr, k, cnt.ptr, idx.ptr, start.ptr, hit.ptr, ex_ptr)
+        else:
+            sweep_spheres_into(ptr, n, prepared, radius, k, cnt.ptr, idx.ptr, start.ptr, hit.ptr, t_min, t_max)
+        return (cnt.to_host((n,)), idx.to_host((n, k)), start.to_host((n, k), np.uint8), hit.to_host((n, k, 7), np.float32))
+    finally:
+        for buf in [cnt, idx, start, hit] + bounds:
+            if buf is not None:
+                buf.free()
+        if keep is not None:
+            keep.free()
+
+
 def nearest_spheres(prepared, points, k, max_dist=1e9, count=True):
     """The k nearest spheres of every point (rt_nearest_spheres) -> (count (n,) int32 or None, index (n, k) int32, gap (n, k) float32)
     numpy arrays.  A sphere is selected for point p iff its gap -- sqrtf(|p - c|^2) - r in float32, the signed distance to its surface,
@@ -779,20 +845,21 @@ def nearest_spheres(prepared, points, k, max_dist=1e9, count=True):
             keep.free()
 
 
-def _device_first(ctx, dev, n, first, keep):
-    """The device pointer of the per-point lower index bounds `first`: an (n,) integer numpy array (uploaded as int32, clipped to int32's range
-    first) or a contiguous int32 torch tensor on the context's device (used in place); a buffer it uploads is appended to `keep`."""
+def _device_first(ctx, dev, n, first, keep, name="first", per="point"):
+    """The device pointer of the per-point lower index bounds `first` (or, as `name`, the sweep queries' excluded indices): an (n,) integer
+    numpy array (uploaded as int32, clipped to int32's range first) or a contiguous int32 torch tensor on the context's device (used in
+    place); a buffer it uploads is appended to `keep`."""
     if hasattr(first, "data_ptr"):
         if str(first.dtype) != "torch.int32" or not first.is_contiguous() or first.device.type != "cuda" or first.device.index != dev:
-            raise ValueError(f"first: a contiguous int32 tensor on cuda:{dev} is required")
+            raise ValueError(f"{name}: a contiguous int32 tensor on cuda:{dev} is required")
         if first.dim() != 1 or first.shape[0] != n:
-            raise ValueError(f"first must be ({n},), one index per point; got {tuple(first.shape)}")
+            raise ValueError(f"{name} must be ({n},), one index per {per}; got {tuple(first.shape)}")
         return first.data_ptr()
     a = np.asarray(first)
     if not np.issubdtype(a.dtype, np.integer):
-        raise ValueError(f"first: an integer array is required; got {a.dtype}")
+        raise ValueError(f"{name}: an integer array is required; got {a.dtype}")
     if a.shape != (n,):
-        raise ValueError(f"first must be ({n},), one index per point; got {a.shape}")
+        raise ValueError(f"{name} must be ({n},), one index per {per}; got {a.shape}")
     a = np.ascontiguousarray(np.clip(a, -2 ** 31, 2 ** 31 - 1), dtype=np.int32)
     buf = DeviceBuffer(ctx, max(a.nbytes, 4))
     keep.append(buf)

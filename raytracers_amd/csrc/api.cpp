@@ -2251,6 +2251,54 @@ extern "C" int rt_multi_hit_rays_ranged(rt_context *ctx, const rt_prepared *ps, 
   return multi_hit_launch(ctx, ps, n, p, k, count_dev, index_dev, root_dev, hit7_dev, true);
 }
 
+// The sweep entries' checks past ray_entry_params and their launch: the lane kernel under every variant, k contacts per query.  The caller holds
+// the context lock and has set p's interval (scalar, or per-query next to radius_dev).
+static int sweep_launch(rt_context *ctx, const rt_prepared *ps, int64_t n, rtk::KParams &p, const float *radius_dev, float radius,
+                        const int32_t *exclude_dev, int32_t k, int32_t *count_dev, int32_t *index_dev, uint8_t *start_dev, float *hit7_dev) {
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  if (n == 0) {
+    ctx->last_launch = "family=none (no rays)";
+    return 0;
+  }
+  RT_HIP(ctx, rtk::launch_sweep_spheres(p, radius_dev, radius, exclude_dev, k, count_dev, index_dev, start_dev, hit7_dev, ctx->stream));
+  ctx->last_launch = "family=sweep k=" + std::to_string(k) + (radius_dev ? " (per-query)" : "") + (exclude_dev ? " exclude" : "");
+  return 0;
+}
+
+extern "C" int rt_sweep_spheres(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float radius, float t_min, float t_max,
+                                int32_t k, int32_t *count_dev, int32_t *index_dev, uint8_t *start_dev, float *hit7_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!count_dev && !index_dev && !start_dev && !hit7_dev) return fail(ctx, "rt_sweep_spheres: all four outputs are NULL");
+  if (k < 1 || k > rtk::kSweepMaxK) return fail(ctx, "rt_sweep_spheres: need 1 <= k <= 32");
+  if (!ray_interval_ok(t_min, t_max)) return fail(ctx, "rt_sweep_spheres: need 0 <= t_min <= t_max <= 1e9, both finite");
+  if (!(std::isfinite(radius) && radius >= 0.0f && radius <= rtk::kTMax)) return fail(ctx, "rt_sweep_spheres: need 0 <= radius <= 1e9, finite");
+  p.ray_tlo = t_min;
+  p.ray_thi = t_max;
+  return sweep_launch(ctx, ps, n, p, nullptr, radius, nullptr, k, count_dev, index_dev, start_dev, hit7_dev);
+}
+
+// The per-query form: a query whose interval or radius fails its rule is a miss in the kernel (count 0, every slot padded).
+extern "C" int rt_sweep_spheres_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *radius_dev,
+                                       const float *t_min_dev, const float *t_max_dev, const int32_t *exclude_dev, int32_t k,
+                                       int32_t *count_dev, int32_t *index_dev, uint8_t *start_dev, float *hit7_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!count_dev && !index_dev && !start_dev && !hit7_dev) return fail(ctx, "rt_sweep_spheres_ranged: all four outputs are NULL");
+  if (k < 1 || k > rtk::kSweepMaxK) return fail(ctx, "rt_sweep_spheres_ranged: need 1 <= k <= 32");
+  if (!radius_dev || !t_min_dev || !t_max_dev) return fail(ctx, "rt_sweep_spheres_ranged: null radius, t_min or t_max pointer");
+  p.ray_tlo_dev = t_min_dev;
+  p.ray_thi_dev = t_max_dev;
+  return sweep_launch(ctx, ps, n, p, radius_dev, 0.0f, exclude_dev, k, count_dev, index_dev, start_dev, hit7_dev);
+}
+
 // The proximity entries: checks, then the lane kernel under every variant (count_dev NULL: its pruned walk).  max_dist_dev != nullptr: the
 // per-point form, whose bounds are device data -- an invalid one makes its point a miss in the kernel (lane_core.h: max_dist_ok).
 static int nearest_entry(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist, const float *max_dist_dev,

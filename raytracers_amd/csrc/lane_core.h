@@ -293,6 +293,29 @@ RT_HD bool sphere_roots(const Ray &r, float spx, float spy, float spz, float sra
   return true;
 }
 
+// The contact of a sphere of radius rq moving along r with scene sphere (sp, srad) over (tlo, thi) (rt_sweep_spheres): the
+// ray of its centre against the sphere (sp, R = srad + rq), sphere_roots' arithmetic with R for the radius.  kSweepEntry: root 1 lies past
+// tlo and the contact is there, accepted iff it is below thi.  kSweepStart: root 1 is at or before tlo and root 2 past it -- the two
+// spheres already overlap where the interval begins -- and the contact is at tlo itself (-0.0 reported as +0.0), provided the interval is
+// not empty.  kSweepNone otherwise: touching only at the exit (t2 == tlo) is none, and NaN roots pass no compare.  *tau is written for a
+// contact only.
+constexpr int kSweepNone = 0, kSweepEntry = 1, kSweepStart = 2;
+RT_HD int sweep_contact(const Ray &r, float spx, float spy, float spz, float srad, float rq, float tlo, float thi, float *tau) {
+  const float R = srad + rq;
+  float t1, t2;
+  if (!sphere_roots(r, spx, spy, spz, R, &t1, &t2)) return kSweepNone;
+  if (t1 > tlo) {
+    if (!(t1 < thi)) return kSweepNone;
+    *tau = t1;
+    return kSweepEntry;
+  }
+  if ((t2 > tlo) && (tlo < thi)) {
+    *tau = tlo + 0.0f;
+    return kSweepStart;
+  }
+  return kSweepNone;
+}
+
 // The interval rule of the queries that take one: 0 <= tlo <= thi <= 1e9.  Three compares, each false on a NaN operand, so NaN and +-inf fail
 // too (+inf exceeds 1e9, -inf is below 0).  A per-ray interval is checked with it once, where the ray is loaded: box_hit_interval's
 // fmaxf / fminf drop a NaN bound rather than empty the box interval.

@@ -2248,6 +2248,118 @@ hipError_t launch_multi_hit_rays(const KParams &p, int k, int32_t *count, int32_
                                   : launch_multi_hit_cap<false>(p, k, count, index, root, hit7, stream);
 }
 
+// rt_sweep_spheres: one lane per query -- a sphere of radius rq whose centre moves along the lane's ray.  multi_hit_lane's walk with every
+// node's box widened by rq per component (fl(lo - rq), fl(hi + rq): six additions per box test, rq being the query's own) and, at a
+// leaf, sweep_contact (lane_core.h) in place of the two roots: a sphere gives at most one contact, counted and inserted into the same
+// sorted list as the key bits(tau) << 32 | j << 1 | start.  tau is t1 inside (t_min, t_max), or t_min + 0.0f for an overlap at the start:
+// never negative, finite, so its bits order as it does, and the key order is (tau, j).  The interval is never narrowed by the contacts
+// found: the visited leaves are part of the contract.  RANGED: the query's own radius and interval (a failing interval_ok or max_dist_ok
+// is a miss, its walk does not start).  exclude != nullptr: sphere exclude[i] is skipped at the leaf, one compare (a value no leaf has
+// excludes nothing).  At write-out slot s < min(count, k) gets j, start and {tau, p, (1.0f / R) * (p - centre)} with R = radius_j + rq;
+// slots up to k are padded with -1, 0 and seven zeros.  64-bit output offsets; any output may be nullptr.
+template <bool RANGED, int CAP>
+__device__ __forceinline__ void sweep_lane(const KParams &p, const float *radius_dev, float rq, const int32_t *exclude, int k, int32_t *count,
+                                           int32_t *index, uint8_t *start, float *hit7) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const Ray r = load_ray(p.rays, i);
+  float t_min = p.ray_tlo, t_max = p.ray_thi;
+  bool valid = lane_interval<RANGED>(p, i, t_min, t_max);
+  if constexpr (RANGED) {
+    rq = radius_dev[i] + 0.0f;   // (-0.0 -> +0.0)
+    valid = valid && max_dist_ok(rq);
+  }
+  const int skip = exclude != nullptr ? exclude[i] : -1;
+  unsigned long long list[CAP];
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) list[s] = ~0ull;
+  int cnt = 0;
+  int sp = 0;
+  if (valid) stack[sp++][lane] = 0;
+  while (sp > 0) {
+    const int ni = stack[--sp][lane];
+    const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+    if (!box_hit_interval(r, lo.x - rq, lo.y - rq, lo.z - rq, hi.x + rq, hi.y + rq, hi.z + rq, t_min, t_max)) continue;
+    const int kids[2] = {f2i(lo.w), f2i(hi.w)};
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      const int c = kids[c2];
+      if (c < 0) {
+        const int j = ~c;
+        if (j != skip) {
+          const float4 s = buf_load16(rs_sph, j * 16);
+          float tau;
+          const int what = sweep_contact(r, s.x, s.y, s.z, s.w, rq, t_min, t_max, &tau);
+          if (what != kSweepNone) {
+            cnt += 1;
+            crossing_insert<CAP>(list, crossing_key(tau, j, what == kSweepStart ? 1 : 0));
+          }
+        }
+      } else {
+        stack[sp++][lane] = c;   // (at most one pending sibling per level: sp <= tree height + 1 <= kStackPixel)
+      }
+    }
+  }
+  if (count != nullptr) count[i] = cnt;
+  const size_t base = (size_t)i * (size_t)k;
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) {
+    if (s < k) {
+      const bool have = s < cnt;
+      const int j = have ? (int)((unsigned)list[s] >> 1) : -1;
+      if (index != nullptr) index[base + s] = j;
+      if (start != nullptr) start[base + s] = have ? (uint8_t)((unsigned)list[s] & 1u) : (uint8_t)0;
+      if (hit7 != nullptr) {
+        float h[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (have) {
+          const float tau = __uint_as_float((unsigned)(list[s] >> 32));
+          const float4 ce = p.sph[j];
+          const float inv_rad = 1.0f / (ce.w + rq);   // 1 / R: the one division of the slot
+          h[0] = tau;
+          h[1] = r.ox + tau * r.dx; h[2] = r.oy + tau * r.dy; h[3] = r.oz + tau * r.dz;   // point_at_param: the moving centre at contact
+          h[4] = inv_rad * (h[1] - ce.x); h[5] = inv_rad * (h[2] - ce.y); h[6] = inv_rad * (h[3] - ce.z);
+        }
+        float *const o = hit7 + (base + s) * 7;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) o[q] = h[q];
+      }
+    }
+  }
+}
+template <bool RANGED, int CAP>
+__global__ __launch_bounds__(64) void sweep_kernel(KParams p, const float *radius_dev, float rq, const int32_t *exclude, int k, int32_t *count,
+                                                   int32_t *index, uint8_t *start, float *hit7) {
+  sweep_lane<RANGED, CAP>(p, radius_dev, rq, exclude, k, count, index, start, hit7);
+}
+
+template <bool RANGED>
+static hipError_t launch_sweep_cap(const KParams &p, const float *radius_dev, float rq, const int32_t *exclude, int k, int32_t *count,
+                                   int32_t *index, uint8_t *start, float *hit7, hipStream_t stream) {
+  const dim3 grid((unsigned)((p.nrays + 63) / 64)), block(64);
+  if (k <= 4) hipLaunchKernelGGL((sweep_kernel<RANGED, 4>), grid, block, 0, stream, p, radius_dev, rq, exclude, k, count, index, start, hit7);
+  else if (k <= 8) hipLaunchKernelGGL((sweep_kernel<RANGED, 8>), grid, block, 0, stream, p, radius_dev, rq, exclude, k, count, index, start, hit7);
+  else if (k <= 16) hipLaunchKernelGGL((sweep_kernel<RANGED, 16>), grid, block, 0, stream, p, radius_dev, rq, exclude, k, count, index, start, hit7);
+  else hipLaunchKernelGGL((sweep_kernel<RANGED, 32>), grid, block, 0, stream, p, radius_dev, rq, exclude, k, count, index, start, hit7);
+  return hipGetLastError();
+}
+
+hipError_t launch_sweep_spheres(const KParams &p, const float *radius_dev, float radius, const int32_t *exclude, int k, int32_t *count,
+                                int32_t *index, uint8_t *start, float *hit7, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (k < 1 || k > kSweepMaxK) return hipErrorInvalidValue;
+  if (count == nullptr && index == nullptr && start == nullptr && hit7 == nullptr) return hipErrorInvalidValue;
+  const bool ranged = radius_dev != nullptr;
+  if (ranged != (p.ray_tlo_dev != nullptr) || ranged != (p.ray_thi_dev != nullptr)) return hipErrorInvalidValue;
+  if (!ranged && !max_dist_ok(radius)) return hipErrorInvalidValue;
+  radius += 0.0f;   // (-0.0 -> +0.0)
+  return ranged ? launch_sweep_cap<true>(p, radius_dev, 0.0f, exclude, k, count, index, start, hit7, stream)
+                : launch_sweep_cap<false>(p, nullptr, radius, exclude, k, count, index, start, hit7, stream);
+}
+
 // rt_nearest_spheres: one lane per point.  The walk of multi_hit_lane with the box test replaced by box_may_hold (lane_core.h: the
 // point-to-box distance against the threshold plus a proven slack) and the crossing list by the same sorted list of CAP 64-bit keys,
 // gap_key(gap, j): every sphere with gap <= max_dist is counted and inserted.  A box is tested only at depth >= exact_depth: the reference's

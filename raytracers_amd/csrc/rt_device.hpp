@@ -428,6 +428,13 @@ hipError_t launch_within_count(const KParams &p, const float *pts, const float *
 hipError_t launch_within_fill(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
                               int exact_depth, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point,
                               hipStream_t stream);
+// rt_sweep_spheres[_ranged]: the first k (1 <= k <= kSweepMaxK) contacts of a sphere moving along each ray, in (tau, j) order, and their count,
+// one lane per query: count[i], index / start [i * k + s], hit7 [(i * k + s) * 7 ..] (any may be nullptr, not all).  radius_dev == nullptr:
+// the radius `radius` (0 <= radius <= 1e9) and the interval (p.ray_tlo, p.ray_thi) for every query; otherwise query i's own radius_dev[i]
+// and (p.ray_tlo_dev[i], p.ray_thi_dev[i]) (all three set, or none).  exclude: nullptr, or n sphere indices skipped at the leaf
+constexpr int kSweepMaxK = 32;
+hipError_t launch_sweep_spheres(const KParams &p, const float *radius_dev, float radius, const int32_t *exclude, int k, int32_t *count,
+                                int32_t *index, uint8_t *start, float *hit7, hipStream_t stream);
 // the primary rays of an h x w frame through p.cam (get_ray at pixel_u / pixel_v), row-major from the top row: rays[6 (row w + col) ..]
 hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStream_t stream);
 // block = 64 * waves_per_wg threads (4, 8 or 16 waves); grid = persistent workgroups

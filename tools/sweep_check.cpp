@@ -1,0 +1,53 @@
+// The per-sphere rule of the sphere casts (lane_core.h: sweep_contact, what sweep_lane runs at a leaf) on the host, over cases read from a
+// file: the CPU suite holds the numpy restatement (tests/sweep_ref.py: rule_cases) equal to this arithmetic bit for bit, without a GPU.
+// A case is 13 float32: ray origin xyz, direction xyz, sphere centre xyz, sphere radius, query radius, t_min, t_max.  For each case two
+// uint32 are written: the kind (0 none, 1 entry contact, 2 overlap at the start) and tau's bits (0 for none).
+// usage: sweep_check <cases.bin> <out.bin>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "lane_core.h"
+
+using namespace rtk;
+
+int main(int argc, char **argv) {
+  if (argc != 3) {
+    fprintf(stderr, "usage: sweep_check <cases.bin> <out.bin>\n");
+    return 2;
+  }
+  FILE *in = fopen(argv[1], "rb");
+  if (!in) {
+    fprintf(stderr, "sweep_check: cannot read %s\n", argv[1]);
+    return 2;
+  }
+  std::vector<float> cases;
+  float row[13];
+  while (fread(row, sizeof(float), 13, in) == 13) cases.insert(cases.end(), row, row + 13);
+  fclose(in);
+  const size_t n = cases.size() / 13;
+  std::vector<uint32_t> out(2 * n);
+  size_t kinds[3] = {0, 0, 0};
+  for (size_t i = 0; i < n; ++i) {
+    const float *c = &cases[13 * i];
+    Ray r;
+    r.ox = c[0]; r.oy = c[1]; r.oz = c[2];
+    r.dx = c[3]; r.dy = c[4]; r.dz = c[5];
+    ray_derive(r);
+    float tau = 0.0f;
+    const int kind = sweep_contact(r, c[6], c[7], c[8], c[9], c[10], c[11], c[12], &tau);
+    if (kind == kSweepNone) tau = 0.0f;
+    out[2 * i] = static_cast<uint32_t>(kind);
+    memcpy(&out[2 * i + 1], &tau, 4);
+    kinds[kind] += 1;
+  }
+  FILE *o = fopen(argv[2], "wb");
+  if (!o || fwrite(out.data(), sizeof(uint32_t), out.size(), o) != out.size()) {
+    fprintf(stderr, "sweep_check: cannot write %s\n", argv[2]);
+    return 2;
+  }
+  fclose(o);
+  printf("%zu cases: %zu none, %zu entry contacts, %zu overlaps at the start\n", n, kinds[0], kinds[1], kinds[2]);
+  return 0;
+}
