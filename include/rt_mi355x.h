@@ -309,6 +309,8 @@ int rt_multi_hit_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, 
  *                            moving sphere already overlaps j where the interval begins (the physics engines' convention: an initial
  *                            overlap is a hit at distance zero).
  *     Otherwise none (touching only at the exit, t2 == t_min, is none).  A sphere gives at most one contact.
+ *     A STATIONARY query, d = (+-0, +-0, +-0), has no contact at all, not even with a sphere it rests inside: a = b = 0, so the discriminant
+ *     is 0 - 0 * c = 0 (NaN where c overflows), which is not positive.  Ask rt_spheres_within_* at p = o with bound rq for those overlaps.
  * Sphere j is consulted iff every inner node on its root path passes aabb_hit (ray.fut:53-70) over (t_min, t_max) on the node's box WIDENED
  * by rq per component, fl(lo_k - rq) and fl(hi_k + rq).  With rq = 0 (or -0.0) these are exactly the leaves rt_multi_hit_rays visits.  Like
  * every ray query here this inherits the reference's partial boxes: on a tree taller than the AABB propagation's floor(log2 n) + 2 sweeps

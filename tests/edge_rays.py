@@ -147,15 +147,15 @@ def _axis_signed_zero_dirs():
     return np.array(out, F)
 
 
-def _search_root(pos, rad, axis, target, sign=1.0, steps=8, scales=96):
-    """Rays along +-axis toward a sphere whose root 1 or root 2 equals `target` exactly, searched in sphere_hit's float32 arithmetic
+def _search_root(pos, rad, axis, target, sign=1.0, steps=8, scales=96, which=(1, 2)):
+    """Rays along +-axis toward a sphere whose root 1 or root 2 (`which`) equals `target` exactly, searched in sphere_hit's float32 arithmetic
     (multi_hit_ref._pair_roots): direction lengths from 0.5 to 3 and origins stepped a float32 ulp at a time from the nominal one.
-    [m, 6] (m may be 0)."""
+    `rad` is the radius the roots are taken against (the sphere casts pass R = fl(r + rq)).  [m, 6] (m may be 0)."""
     e = np.zeros(3, F)
     e[axis] = F(sign)
     s = np.linspace(0.5, 3.0, scales).astype(F)
     found = []
-    for which in (1, 2):
+    for which in which:
         dist = (F(rad) + F(target) * s) if which == 1 else (F(target) * s - F(rad))   # centre - origin along the ray
         o = (pos[None, :] - e[None, :] * dist[:, None]).astype(F)
         o = np.repeat(o, 2 * steps + 1, axis=0)
@@ -168,7 +168,7 @@ def _search_root(pos, rad, axis, target, sign=1.0, steps=8, scales=96):
         r1, r2, ok = _pair_roots(np.broadcast_to(pos, o.shape).astype(F), np.full(o.shape[0], rad, F), o, d)
         hit = ok & ((r1 if which == 1 else r2) == F(target))
         found.append(_rays(o[hit], d[hit]))
-    return np.concatenate(found)
+    return np.concatenate(found) if found else np.zeros((0, 6), F)
 
 
 def ray_families(arrays, seed=0, per=48):
