@@ -79,6 +79,12 @@ build/cull_bound_check: tools/cull_bound_check.cpp $(CSRC)/lane_core.h $(CSRC)/r
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -fopenmp -I$(CSRC) -o $@ tools/cull_bound_check.cpp $(OBJ)/host_build.o -lquadmath
 
+# whole renders at the limits of the culling guards: the host's decision and constants, and every ray chain walked un-culled and under the
+# strongest limit any traversal order could apply (cases: tests/edge_cull.py); in the CPU test suite
+build/cull_guard_check: tools/cull_guard_check.cpp $(CSRC)/lane_core.h $(CSRC)/rt_host.hpp $(OBJ)/host_build.o
+	@mkdir -p build
+	$(CXX) $(HOSTFLAGS) -I$(CSRC) -o $@ tools/cull_guard_check.cpp $(OBJ)/host_build.o
+
 # the box test of the proximity queries (lane_core.h: box_may_hold) hammered with host-built boxes and __float128; in the CPU test suite
 build/proximity_bound_check: tools/proximity_bound_check.cpp $(CSRC)/lane_core.h $(CSRC)/rt_host.hpp $(OBJ)/host_build.o
 	@mkdir -p build
@@ -133,7 +139,7 @@ build/first_call_probe: tools/first_call_probe.c include/ray.h $(LIB)
 	@mkdir -p build
 	$(CC) -O2 -std=gnu99 -Wall -Iinclude -o $@ tools/first_call_probe.c -Lraytracers_amd -lray_mi355x -Wl,-rpath,'$$ORIGIN/../raytracers_amd'
 
-tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_presorted_check build/sweep_check
+tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_presorted_check build/sweep_check
 
 oracle:
 	$(MAKE) -s -C oracle

@@ -1693,8 +1693,11 @@ extern "C" int rt_render_batch(rt_context *ctx, const rt_prepared *ps, int64_t h
   if (ctx->group) {   // every device renders its rows of ALL the frames in one launch; one gather, one assembly launch
     if (part != 0 || nparts != 1) return fail(ctx, "a multi-device context renders whole frames: it partitions them itself");
     if (max_depth < 0) return fail(ctx, "negative max_depth");
-    return rti::group_render(ctx, ps, h, w, max_depth, out_dev, nullptr, nframes, frame_stride, cams12);
+    // (one frame: its camera travels in the kernel arguments -- the kernels read a batch's camera array only where nframes > 1)
+    return rti::group_render(ctx, ps, h, w, max_depth, out_dev, nframes == 1 ? cams12 : nullptr, nframes, frame_stride, nframes == 1 ? nullptr : cams12);
   }
+  if (nframes == 1)   // (as above, and as rt_render_part_inplace: a staged camera would be ignored and the frame traced through the prepared one)
+    return enqueue_render(ctx, ps, h, w, max_depth, rows_per_tile, part, nparts, out_dev, false, cams12, 1, frame_stride, nullptr);
   const float *cams_dev = nullptr;
   if (int rc = rti::stage_cams(ctx, cams12, nframes, &cams_dev)) return rc;
   return enqueue_render(ctx, ps, h, w, max_depth, rows_per_tile, part, nparts, out_dev, false, nullptr, nframes, frame_stride, cams_dev);
