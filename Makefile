@@ -135,11 +135,17 @@ build/tsan_nolock/ctx_threads: tools/ctx_threads.cpp $(CSRC)/api.cpp $(CSRC)/mul
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(TSAN) -o build/tsan_nolock/libray_mi355x.so $(OBJ)/render_kernels.o $(OBJ)/bvh_build.o build/tsan_nolock/api.o build/tsan_nolock/multi_gpu.o build/tsan/host_build.o -ldl
 	/opt/rocm/lib/llvm/bin/clang++ -O1 -std=c++17 $(TSAN) -Iinclude -pthread -o $@ tools/ctx_threads.cpp -Lbuild/tsan_nolock -lray_mi355x -Wl,-rpath,'$$ORIGIN'
 
+# the view-order sorts (tile order, pixel list + header, first order: launch_tile_order / launch_px_order / launch_first_order of the library) on
+# cases from a file, every buffer between guards, and a view's arrays after rendered frames (white box); in the GPU test suite (tests/test_view_order_gpu.py)
+build/view_order_check: tools/view_order_check.cpp $(CSRC)/rt_internal.hpp $(CSRC)/rt_device.hpp $(CSRC)/rt_host.hpp $(CSRC)/lane_core.h $(CSRC)/treelet.h include/rt_mi355x.h $(LIB)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -Iinclude -o $@ tools/view_order_check.cpp -Lraytracers_amd -lray_mi355x -Wl,-rpath,'$$ORIGIN/../raytracers_amd'
+
 build/first_call_probe: tools/first_call_probe.c include/ray.h $(LIB)
 	@mkdir -p build
 	$(CC) -O2 -std=gnu99 -Wall -Iinclude -o $@ tools/first_call_probe.c -Lraytracers_amd -lray_mi355x -Wl,-rpath,'$$ORIGIN/../raytracers_amd'
 
-tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_presorted_check build/sweep_check
+tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_presorted_check build/sweep_check build/view_order_check
 
 oracle:
 	$(MAKE) -s -C oracle

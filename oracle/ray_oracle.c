@@ -576,6 +576,30 @@ int orc_render(const orc_bvh *objs, const orc_camera *cam, int64_t width, int64_
   return orc_render_rows(objs, cam, width, height, 0, height, max_depth, threads, out, counters);
 }
 
+/* The length of every pixel's bounce chain: the number of objs_hit calls ray_colour makes for it (ray.fut:130), for the
+ * rows [row_begin, row_end) as orc_render_rows walks them; out is the packed band (row_end-row_begin) x width.  The
+ * band's sum is orc_render_rows' `rays` counter. */
+int orc_chain_rows(const orc_bvh *objs, const orc_camera *cam, int64_t width, int64_t height,
+                   int64_t row_begin, int64_t row_end, int32_t max_depth, int threads, int32_t *out) {
+#ifdef _OPENMP
+  if (threads > 0) omp_set_num_threads(threads);
+  else omp_set_num_threads(omp_get_num_procs());
+#else
+  (void)threads;
+#endif
+#pragma omp parallel for schedule(dynamic, 1)
+  for (int64_t j = row_begin; j < row_end; j++)
+    for (int64_t i = 0; i < width; i++) {
+      orc_counters c;
+      memset(&c, 0, sizeof c);
+      float u = (float)i / (float)width;
+      float v = (float)(height - j) / (float)height;
+      (void)ray_colour(objs, get_ray(cam, u, v), max_depth, &c);
+      out[(j - row_begin) * width + i] = (int32_t)c.rays;
+    }
+  return 0;
+}
+
 /* ------------------------------------------------------------------ caller rays
  *
  * Thin loops over caller-supplied rays for the ray-query tests: rays are n x 6 float32

@@ -68,6 +68,8 @@ def lib():
         L.orc_scene_camera.argtypes = [C.POINTER(Scene), C.c_int64, C.c_int64, C.POINTER(Camera)]
         L.orc_render_rows.argtypes = [C.POINTER(Bvh), C.POINTER(Camera), C.c_int64, C.c_int64, C.c_int64,
                                       C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.POINTER(Counters)]
+        L.orc_chain_rows.argtypes = [C.POINTER(Bvh), C.POINTER(Camera), C.c_int64, C.c_int64, C.c_int64,
+                                     C.c_int64, C.c_int32, C.c_int, C.c_void_p]
         L.orc_checksum.argtypes = [C.c_void_p, C.c_int64]
         L.orc_checksum.restype = C.c_uint32
         L.orc_num_threads.restype = C.c_int
@@ -139,6 +141,16 @@ class OracleScene:
                                    out.ctypes.data, C.byref(cnt))
         assert rc == 0
         return out, cnt.as_dict()
+
+    def chain_lengths(self, h, w, max_depth=50, threads=0, rows=None, cam=None):
+        """Per pixel the number of objs_hit calls ray_colour makes (ray.fut:130): int32 [h_band, w], same camera, rows and max_depth
+        arguments as render(); its sum is render()'s `rays` counter."""
+        r0, r1 = (0, h) if rows is None else rows
+        out = np.empty((r1 - r0, w), dtype=np.int32)
+        cam = self.camera(h, w) if cam is None else Camera.from_buffer_copy(np.ascontiguousarray(cam, dtype=np.float32).tobytes())
+        rc = lib().orc_chain_rows(C.byref(self.bvh), C.byref(cam), w, h, r0, r1, max_depth, threads, out.ctypes.data)
+        assert rc == 0
+        return out
 
     # --- caller rays: the literal walk over n x 6 float32 rays, one (t_min, t_max) per ray (scalars are broadcast); an interval that fails
     # 0 <= t_min <= t_max <= 1e9 is a miss (the library's rule)
