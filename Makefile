@@ -55,6 +55,8 @@ build/hip_touch: tools/hip_touch.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -o $@ $<
 
 # the pooled kernel's tile-queue protocol (rt_device.hpp) played on the CPU; in the CPU test suite
+# (`queue_check extreme`: the tile grids of strip images, 1 x 8192 ... 131072 x 1; `queue_check span NTILES NFRAMES DS TPT N_DEEP N_SPLIT`: every ticket's
+# 32-bit span against the formula in 64 bits, no per-slot memory -- the bound tiles x frames < 2^26; tests/test_frame_edges_cpu.py)
 build/queue_check: tools/queue_check.cpp $(CSRC)/rt_device.hpp $(CSRC)/lane_core.h $(CSRC)/treelet.h
 	@mkdir -p build
 	$(HIPCC) -O2 -std=c++17 -Wall -I$(CSRC) -o $@ $<

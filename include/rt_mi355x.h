@@ -164,6 +164,9 @@ int rt_render_image(rt_context *ctx, const rt_prepared *objs, int64_t width, int
  * the prepared camera for every frame) into out_dev + f * frame_stride (int32 elements, >= rows * w).  The persistent
  * waves run straight across frame boundaries, so a launch's fill and drain are paid once per batch instead of once
  * per frame.  Partition arguments as rt_render_part.  The array at cams12 is copied before the call returns.
+ * Limits (refused, nothing launched): 1 <= nframes <= 4096; nframes * frame_stride < 2^31; and tiles per frame x nframes < 2^26, where
+ * a frame (a part: its rows) has ceil(rows / 8) x ceil(w / 8) tiles of 8 x 8 pixels -- the second limit implies the third for frames whose
+ * sides are multiples of 8, but not for thin ones: 512 frames of 1 x 2^20 are refused by the third alone.  rt_render_part_inplace: the same.
  * On a multi-device context (part 0 of 1 only): every device renders its row tiles of ALL the frames in one launch, the
  * framebuffer gather moves nframes x part per device, one assembly launch writes the nframes images. */
 int rt_render_batch(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, int32_t max_depth, int32_t rows_per_tile,

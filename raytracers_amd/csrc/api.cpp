@@ -877,6 +877,12 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
   const int64_t frame_elems = inplace ? h * w : static_cast<int64_t>(p.rows_local) * p.w;
   if (nframes < 1 || (nframes > 1 && (frame_stride < frame_elems || frame_stride * nframes >= (int64_t(1) << 31))))
     return fail(ctx, "bad batch: nframes >= 1, frame_stride >= rows * w (in place: h * w), nframes * frame_stride < 2^31");
+  // The pooled kernel counts in positions (tile x frame) of 64 pixel slots each, in 32 bits (rt_device.hpp: ticket_span): all of a launch's positions
+  // must stay below 2^26.  The limit above counts pixels, and a frame whose sides are no multiples of 8 has up to 64 slots per pixel: 512 frames of
+  // 1 x 2^20 pass it with 2^26 positions.  One frame within the size limits never gets there (at most 2^24 + 2^18 + 1 tiles).  (The ray-buffer entries
+  // cannot either: their positions are blocks of 64 rays, one frame of n < 2^31 rays -- fewer than 2^25 of them.)
+  if (rti::tiles_of(p.rows_local, w) * nframes >= rti::kMaxPositions)
+    return fail(ctx, "bad batch: tiles per frame x frames < 2^26 (a frame has ceil(rows / 8) x ceil(w / 8) tiles of 8 x 8 pixels)");
   if (inplace) {
     // the part's row tile k (rows_per_tile rows) starts at image row (k * nparts + part) * rows_per_tile: k * rows_per_tile
     // of that is the packed position the kernels compute anyway, `part * rows_per_tile` goes into the base pointer, the rest

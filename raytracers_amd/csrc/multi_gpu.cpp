@@ -295,9 +295,12 @@ int rti::group_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t
   const int n = static_cast<int>(g->kids.size());
   if (ps->replicas.size() != static_cast<size_t>(n)) return fail(ctx, "prepared scene does not belong to this multi-device context");
   if (!out_dev) return fail(ctx, "null output pointer");
-  if (h <= 0 || w <= 0 || h * w > (int64_t(1) << 30)) return fail(ctx, "image size out of range");
+  if (h <= 0 || w <= 0 || h > (1 << 20) || w > (1 << 20) || h * w > (int64_t(1) << 30)) return fail(ctx, "image size out of range");
   if (nframes < 1 || (nframes > 1 && (frame_stride < h * w || frame_stride * nframes >= (int64_t(1) << 31))))
     return fail(ctx, "bad batch: nframes >= 1, frame_stride >= h * w, nframes * frame_stride < 2^31");
+  // (enqueue_render's limit, on the whole frame -- no device's rows have more tiles -- so that no device has launched when another one refuses)
+  if (rti::tiles_of(h, w) * nframes >= rti::kMaxPositions)
+    return fail(ctx, "bad batch: tiles per frame x frames < 2^26 (a frame has ceil(rows / 8) x ceil(w / 8) tiles of 8 x 8 pixels)");
   constexpr int32_t kRows = 8;
   // Auto mode takes the direct path only for an image the other devices can certainly reach: a device allocation on the first
   // device, which hipDeviceEnablePeerAccess covers (memory from a virtual-memory mapping or another device's pool is not, and

@@ -220,6 +220,9 @@ int hip_fail(rt_context *ctx, hipError_t e, const char *what);
 int enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, int32_t max_depth, int32_t rows_per_tile,
                    int32_t part, int32_t nparts, int32_t *out_dev, bool stats, const float *cam12 = nullptr, int32_t nframes = 1,
                    int64_t frame_stride = 0, const float *cams_dev = nullptr, bool inplace = false);
+// A launch's positions (tiles of 8 x 8 pixels, times frames) are counted in 32 bits, 64 slots each (rt_device.hpp: ticket_span): fewer than 2^26
+constexpr int64_t kMaxPositions = int64_t(1) << 26;
+inline int64_t tiles_of(int64_t rows, int64_t w) { return ((rows + 7) / 8) * ((w + 7) / 8); }
 // multi_gpu.cpp
 // (nframes > 1: a batch -- frame f to out_dev + f * frame_stride, through cams12 + 12 f when cams12 is given)
 int group_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, int32_t max_depth, int32_t *out_dev,

@@ -8,8 +8,19 @@
 //   * every wave ends with all shards seen dry, having failed at most once per counter,
 //   * no counter is touched for a shard whose tickets are all static.
 // Host-only (no GPU needed); part of the CPU test suite (tests/test_host_logic.py).
+//
+//   queue_check [cases [seed]]   the production shapes, then `cases` random launch shapes and as many pixel-ticket lists
+//   queue_check extreme          the tile grids of strip images and of the first order's limits (1 x 8192 ... 131072 x 1), each under one counter,
+//                                eight strips and eight counters taking turns, with 4096 and with 5120 waves, and as a batch; same checks, and the
+//                                strips of a grid narrower than eight tiles must be empty with their counters untouched
+//   queue_check span NTILES NFRAMES DS TPT N_DEEP N_SPLIT
+//                                no per-slot memory: every ticket of one shard of NTILES x NFRAMES positions once, ticket_span's 32-bit q_next / q_end
+//                                against the same formula in uint64_t (the bound of a pooled launch: tiles x frames < 2^26); prints the number of tickets that differ
+// (tests/test_frame_edges_cpu.py runs the last two)
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <vector>
 
@@ -22,7 +33,7 @@ struct Cfg {
   int cap_log2 = 5;
 };
 
-static int run(const Cfg &c, std::mt19937 &rng, bool verbose) {
+static int run(const Cfg &c, std::mt19937 &rng, bool verbose, int *empty_untouched = nullptr) {
   const int ns = 1 << c.ns_log2;                 // counters
   const int gl2 = c.interleave ? 0 : c.ns_log2;  // log2 of the shards of the GEOMETRY (strips, order table)
   const int gs = 1 << gl2;
@@ -114,6 +125,7 @@ static int run(const Cfg &c, std::mt19937 &rng, bool verbose) {
     if (c.interleave) tk = (tk + static_cast<unsigned>(ns) - 1u - static_cast<unsigned>(s)) >> c.ns_log2;
     const unsigned dyn = tk > qc.q_static ? tk - qc.q_static : 0u;
     if (dyn == 0 && draws[static_cast<size_t>(s)] != 0) { std::printf("counter of an all-static shard was drawn from\n"); return 1; }
+    if (empty_untouched && sh.ntiles == 0 && draws[static_cast<size_t>(s)] == 0 && counter[static_cast<size_t>(s)] == 0) ++*empty_untouched;
     if (dyn != 0 && (draws[static_cast<size_t>(s)] < dyn || draws[static_cast<size_t>(s)] > dyn + static_cast<unsigned>(c.waves))) {
       std::printf("shard %d: %u draws for %u dynamic tickets and %d waves\n", s, draws[static_cast<size_t>(s)], dyn, c.waves);
       return 1;
@@ -189,7 +201,84 @@ static int run_px(std::mt19937 &rng, bool verbose) {
   return 0;
 }
 
+// The grids of strip images and of the first order's limits (tiles_x x tiles_y), as the launch shapes take them: 16 waves per CU (4096) and twenty (5120)
+static int run_extreme() {
+  std::mt19937 rng(1u);
+  const int grids[][2] = {{1, 8192}, {8192, 1}, {1, 131072}, {131072, 1}, {32768, 2}, {2, 4096}};
+  int n = 0;
+  for (const auto &g : grids) {
+    for (int waves : {4096, 5120}) {
+      for (int mode = 0; mode < 3; ++mode) {   // one counter; eight strips; eight counters taking turns
+        Cfg c{g[0], g[1], mode ? 3 : 0, 1, 2, 0, 3, waves, 1, mode == 2 ? 1 : 0};
+        int empty = 0;
+        if (run(c, rng, true, &empty)) return 1;
+        // (strips: shard s holds the tile columns [s tiles_x / 8, (s + 1) tiles_x / 8): a grid of fewer than eight columns leaves 8 - tiles_x of them empty)
+        const int want = mode == 1 && g[0] < 8 ? 8 - g[0] : 0;
+        if (empty != want) { std::printf("%d x %d tiles, mode %d: %d empty untouched shards, expected %d\n", g[0], g[1], mode, empty, want); return 1; }
+        ++n;
+      }
+      // a batch (one counter, two tiles per ticket; no deep tiles: they are a single frame's)
+      Cfg b{g[0], g[1], 0, 3, 2, 1, 3, waves, 1, 0};
+      if (run(b, rng, true)) return 1;
+      ++n;
+    }
+  }
+  std::printf("queue_check: %d extreme cases passed\n", n);
+  return 0;
+}
+
+// ticket_span in 64 bits: the same three kinds of ticket, no wrap
+static void ticket_span64(uint64_t t, uint64_t seg, uint64_t npos, uint64_t n_split, uint64_t n_deep, int ds, int tpt, uint64_t *q_next, uint64_t *q_end) {
+  if (t < (n_split << ds)) {
+    const uint64_t piece = 64u >> ds;
+    *q_next = (seg + (t >> ds)) * 64u + (t & ((uint64_t(1) << ds) - 1u)) * piece;
+    *q_end = *q_next + piece;
+    return;
+  }
+  t -= n_split << ds;
+  if (t < n_deep - n_split) {
+    *q_next = (seg + n_split + t) * 64u;
+    *q_end = *q_next + 64u;
+    return;
+  }
+  const uint64_t k0 = n_deep + ((t - (n_deep - n_split)) << tpt);
+  const uint64_t k1 = k0 + (uint64_t(1) << tpt) < npos ? k0 + (uint64_t(1) << tpt) : npos;
+  *q_next = (seg + k0) * 64u;
+  *q_end = (seg + k1) * 64u;
+}
+
+static int run_span(int argc, char **argv) {
+  if (argc != 8) { std::printf("usage: queue_check span NTILES NFRAMES DS TPT N_DEEP N_SPLIT\n"); return 2; }
+  const uint64_t ntiles = std::strtoull(argv[2], nullptr, 10), nframes = std::strtoull(argv[3], nullptr, 10);
+  const int ds = std::atoi(argv[4]), tpt = std::atoi(argv[5]);
+  const uint64_t n_deep = std::strtoull(argv[6], nullptr, 10), n_split = std::strtoull(argv[7], nullptr, 10);
+  const uint64_t npos = ntiles * nframes;
+  if (npos == 0 || npos >= (uint64_t(1) << 32) || ds < 0 || ds > 6 || tpt < 0 || tpt > 4 || n_split > n_deep || n_deep > npos) { std::printf("span: bad arguments\n"); return 2; }
+  const uint64_t tickets = (n_split << ds) + (n_deep - n_split) + ((npos - n_deep + (uint64_t(1) << tpt) - 1u) >> tpt);
+  const unsigned tickets32 = shard_tickets(static_cast<unsigned>(npos), static_cast<unsigned>(n_split), static_cast<unsigned>(n_deep), ds, tpt);
+  uint64_t differ = 0, first = 0, covered = 0;
+  unsigned got_next = 0, got_end = 0;
+  uint64_t want_next = 0, want_end = 0;
+  for (uint64_t t = 0; t < tickets; ++t) {
+    const TicketSpan sp = ticket_span(static_cast<unsigned>(t), 0u, static_cast<unsigned>(npos), static_cast<unsigned>(n_split), static_cast<unsigned>(n_deep), ds, tpt);
+    uint64_t qn, qe;
+    ticket_span64(t, 0, npos, n_split, n_deep, ds, tpt, &qn, &qe);
+    covered += qe - qn;
+    if (sp.q_next != qn || sp.q_end != qe) {
+      if (!differ) { first = t; got_next = sp.q_next; got_end = sp.q_end; want_next = qn; want_end = qe; }
+      ++differ;
+    }
+  }
+  if (covered != npos * 64u) { std::printf("span: the 64-bit formula covers %llu slots of %llu\n", (unsigned long long)covered, (unsigned long long)(npos * 64u)); return 1; }
+  std::printf("span: positions=%llu tickets=%llu tickets32=%u differ=%llu", (unsigned long long)npos, (unsigned long long)tickets, tickets32, (unsigned long long)differ);
+  if (differ) std::printf(" first=%llu got=[%u,%u) want=[%llu,%llu)", (unsigned long long)first, got_next, got_end, (unsigned long long)want_next, (unsigned long long)want_end);
+  std::printf("\n");
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 1 && std::strcmp(argv[1], "extreme") == 0) return run_extreme();
+  if (argc > 1 && std::strcmp(argv[1], "span") == 0) return run_span(argc, argv);
   const int cases = argc > 1 ? std::atoi(argv[1]) : 2000;
   const unsigned seed = argc > 2 ? static_cast<unsigned>(std::atoi(argv[2])) : 1u;
   std::mt19937 rng(seed);
