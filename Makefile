@@ -16,11 +16,23 @@ $(OBJ)/render_kernels.o: $(CSRC)/render_kernels.hip $(CSRC)/lane_core.h $(CSRC)/
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+$(OBJ)/query_kernels.o: $(CSRC)/query_kernels.hip $(CSRC)/query_core.h $(CSRC)/query_device.hpp $(CSRC)/lane_core.h $(CSRC)/rt_device.hpp $(CSRC)/treelet.h
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(OBJ)/bvh_build.o: $(CSRC)/bvh_build.hip $(CSRC)/rt_device.hpp $(CSRC)/lane_core.h $(CSRC)/treelet.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(OBJ)/api.o: $(CSRC)/api.cpp $(CSRC)/rt_internal.hpp $(CSRC)/rt_device.hpp $(CSRC)/rt_host.hpp $(CSRC)/lane_core.h include/ray.h include/rt_mi355x.h $(CSRC)/treelet.h
+$(OBJ)/api.o: $(CSRC)/api.cpp $(CSRC)/rt_internal.hpp $(CSRC)/rt_device.hpp $(CSRC)/rt_host.hpp $(CSRC)/lane_core.h include/rt_mi355x.h $(CSRC)/treelet.h
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(OBJ)/api_queries.o: $(CSRC)/api_queries.cpp $(CSRC)/rt_internal.hpp $(CSRC)/query_device.hpp $(CSRC)/rt_device.hpp $(CSRC)/rt_host.hpp $(CSRC)/lane_core.h include/rt_mi355x.h $(CSRC)/treelet.h
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(OBJ)/futhark_shim.o: $(CSRC)/futhark_shim.cpp $(CSRC)/rt_internal.hpp $(CSRC)/rt_device.hpp $(CSRC)/rt_host.hpp $(CSRC)/lane_core.h include/ray.h include/rt_mi355x.h $(CSRC)/treelet.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -33,7 +45,7 @@ $(OBJ)/host_build.o: $(CSRC)/host_build.cpp $(CSRC)/rt_host.hpp $(CSRC)/treelet.
 	$(CXX) $(HOSTFLAGS) -c $< -o $@
 
 # (librccl is NOT linked: multi_gpu.cpp loads it on demand, so a single-GPU host needs no RCCL)
-$(LIB): $(OBJ)/render_kernels.o $(OBJ)/bvh_build.o $(OBJ)/api.o $(OBJ)/multi_gpu.o $(OBJ)/host_build.o
+$(LIB): $(OBJ)/render_kernels.o $(OBJ)/query_kernels.o $(OBJ)/bvh_build.o $(OBJ)/api.o $(OBJ)/api_queries.o $(OBJ)/futhark_shim.o $(OBJ)/multi_gpu.o $(OBJ)/host_build.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -ldl
 
 # native harness (our own bench front-end; the reference's futhark/main.c links the same way)
@@ -87,8 +99,8 @@ build/cull_guard_check: tools/cull_guard_check.cpp $(CSRC)/lane_core.h $(CSRC)/r
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -I$(CSRC) -o $@ tools/cull_guard_check.cpp $(OBJ)/host_build.o
 
-# the box test of the proximity queries (lane_core.h: box_may_hold) hammered with host-built boxes and __float128; in the CPU test suite
-build/proximity_bound_check: tools/proximity_bound_check.cpp $(CSRC)/lane_core.h $(CSRC)/rt_host.hpp $(OBJ)/host_build.o
+# the box test of the proximity queries (query_core.h: box_may_hold) hammered with host-built boxes and __float128; in the CPU test suite
+build/proximity_bound_check: tools/proximity_bound_check.cpp $(CSRC)/query_core.h $(CSRC)/lane_core.h $(CSRC)/rt_host.hpp $(OBJ)/host_build.o
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -fopenmp -I$(CSRC) -o $@ tools/proximity_bound_check.cpp $(OBJ)/host_build.o -lquadmath
 
@@ -103,8 +115,8 @@ build/box_presorted_check: tools/box_presorted_check.cpp $(CSRC)/lane_core.h
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -I$(CSRC) -o $@ tools/box_presorted_check.cpp
 
-# the sphere casts' per-sphere rule (lane_core.h: sweep_contact) over cases read from a file, tau and kind written as bits; in the CPU test suite
-build/sweep_check: tools/sweep_check.cpp $(CSRC)/lane_core.h
+# the sphere casts' per-sphere rule (query_core.h: sweep_contact) over cases read from a file, tau and kind written as bits; in the CPU test suite
+build/sweep_check: tools/sweep_check.cpp $(CSRC)/query_core.h $(CSRC)/lane_core.h
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -I$(CSRC) -o $@ tools/sweep_check.cpp
 
@@ -121,20 +133,24 @@ build/ctx_threads: tools/ctx_threads.cpp include/ray.h include/rt_mi355x.h $(LIB
 # ... and the same program over the library's HOST code built with -fsanitize=thread (device code and the HIP runtime are not
 # instrumented): build/tsan/libray_mi355x.so + build/tsan/ctx_threads, run on a GPU box by tools/gpu.sh tsan
 TSAN := -fsanitize=thread -g
-build/tsan/ctx_threads: tools/ctx_threads.cpp $(CSRC)/api.cpp $(CSRC)/multi_gpu.cpp $(CSRC)/host_build.cpp $(OBJ)/render_kernels.o $(OBJ)/bvh_build.o
+build/tsan/ctx_threads: tools/ctx_threads.cpp $(CSRC)/api.cpp $(CSRC)/api_queries.cpp $(CSRC)/futhark_shim.cpp $(CSRC)/multi_gpu.cpp $(CSRC)/host_build.cpp $(OBJ)/render_kernels.o $(OBJ)/query_kernels.o $(OBJ)/bvh_build.o
 	@mkdir -p build/tsan
 	$(HIPCC) $(HIPFLAGS) $(TSAN) -c $(CSRC)/api.cpp -o build/tsan/api.o
+	$(HIPCC) $(HIPFLAGS) $(TSAN) -c $(CSRC)/api_queries.cpp -o build/tsan/api_queries.o
+	$(HIPCC) $(HIPFLAGS) $(TSAN) -c $(CSRC)/futhark_shim.cpp -o build/tsan/futhark_shim.o
 	$(HIPCC) $(HIPFLAGS) $(TSAN) -c $(CSRC)/multi_gpu.cpp -o build/tsan/multi_gpu.o
 	/opt/rocm/lib/llvm/bin/clang++ $(HOSTFLAGS) $(TSAN) -c $(CSRC)/host_build.cpp -o build/tsan/host_build.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(TSAN) -o build/tsan/libray_mi355x.so $(OBJ)/render_kernels.o $(OBJ)/bvh_build.o build/tsan/api.o build/tsan/multi_gpu.o build/tsan/host_build.o -ldl
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(TSAN) -o build/tsan/libray_mi355x.so $(OBJ)/render_kernels.o $(OBJ)/query_kernels.o $(OBJ)/bvh_build.o build/tsan/api.o build/tsan/api_queries.o build/tsan/futhark_shim.o build/tsan/multi_gpu.o build/tsan/host_build.o -ldl
 	/opt/rocm/lib/llvm/bin/clang++ -O1 -std=c++17 $(TSAN) -Iinclude -pthread -o $@ tools/ctx_threads.cpp -Lbuild/tsan -lray_mi355x -Wl,-rpath,'$$ORIGIN'
 
 # ... and once more with the locks compiled out (-DRT_NO_CONTEXT_LOCK): what the sanitizer says about the library WITHOUT them (the control run)
-build/tsan_nolock/ctx_threads: tools/ctx_threads.cpp $(CSRC)/api.cpp $(CSRC)/multi_gpu.cpp $(CSRC)/host_build.cpp $(OBJ)/render_kernels.o $(OBJ)/bvh_build.o
+build/tsan_nolock/ctx_threads: tools/ctx_threads.cpp $(CSRC)/api.cpp $(CSRC)/api_queries.cpp $(CSRC)/futhark_shim.cpp $(CSRC)/multi_gpu.cpp $(CSRC)/host_build.cpp $(OBJ)/render_kernels.o $(OBJ)/query_kernels.o $(OBJ)/bvh_build.o
 	@mkdir -p build/tsan_nolock
 	$(HIPCC) $(HIPFLAGS) $(TSAN) -DRT_NO_CONTEXT_LOCK -c $(CSRC)/api.cpp -o build/tsan_nolock/api.o
+	$(HIPCC) $(HIPFLAGS) $(TSAN) -DRT_NO_CONTEXT_LOCK -c $(CSRC)/api_queries.cpp -o build/tsan_nolock/api_queries.o
+	$(HIPCC) $(HIPFLAGS) $(TSAN) -DRT_NO_CONTEXT_LOCK -c $(CSRC)/futhark_shim.cpp -o build/tsan_nolock/futhark_shim.o
 	$(HIPCC) $(HIPFLAGS) $(TSAN) -DRT_NO_CONTEXT_LOCK -c $(CSRC)/multi_gpu.cpp -o build/tsan_nolock/multi_gpu.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(TSAN) -o build/tsan_nolock/libray_mi355x.so $(OBJ)/render_kernels.o $(OBJ)/bvh_build.o build/tsan_nolock/api.o build/tsan_nolock/multi_gpu.o build/tsan/host_build.o -ldl
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(TSAN) -o build/tsan_nolock/libray_mi355x.so $(OBJ)/render_kernels.o $(OBJ)/query_kernels.o $(OBJ)/bvh_build.o build/tsan_nolock/api.o build/tsan_nolock/api_queries.o build/tsan_nolock/futhark_shim.o build/tsan_nolock/multi_gpu.o build/tsan/host_build.o -ldl
 	/opt/rocm/lib/llvm/bin/clang++ -O1 -std=c++17 $(TSAN) -Iinclude -pthread -o $@ tools/ctx_threads.cpp -Lbuild/tsan_nolock -lray_mi355x -Wl,-rpath,'$$ORIGIN'
 
 # the view-order sorts (tile order, pixel list + header, first order: launch_tile_order / launch_px_order / launch_first_order of the library) on

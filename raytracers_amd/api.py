@@ -582,186 +582,159 @@ def camera_rays_into(rays_ptr, h, w, prepared, cam=None):
     ctx._check(lib.rt_camera_rays(ctx._h, prepared._h, int(h), int(w), None if c is None else c.ctypes.data, C.c_void_p(rays_ptr)))
 
 
-def _device_rays(ctx, rays):
-    """(pointer, n, keep-alive) for `rays`: a numpy array is uploaded to a fresh device buffer; a contiguous float32 torch
-    tensor on the context's device is used in place."""
-    if hasattr(rays, "data_ptr"):
-        dev = ctx.device_info()["device"]
-        if str(rays.dtype) != "torch.float32" or not rays.is_contiguous() or rays.device.type != "cuda" or rays.device.index != dev:
-            raise ValueError(f"rays: a contiguous float32 tensor on cuda:{dev} is required")
-        if rays.dim() != 2 or rays.shape[1] != 6:
-            raise ValueError("rays must be (n, 6): origin.xyz, dir.xyz")
-        return rays.data_ptr(), int(rays.shape[0]), None
-    a = np.ascontiguousarray(rays, dtype=np.float32)
-    if a.ndim != 2 or a.shape[1] != 6:
-        raise ValueError("rays must be (n, 6): origin.xyz, dir.xyz")
-    buf = DeviceBuffer(ctx, max(a.nbytes, 4))
-    if a.nbytes:
-        ctx._check(lib.rt_copy_to_device(ctx._h, C.c_void_p(buf.ptr), a.ctypes.data, a.nbytes))
-    return buf.ptr, a.shape[0], buf
+class _Scope:
+    """The device buffers of one query call: whatever alloc() and upload() hand out is freed when the `with` block is left, on every path."""
+
+    def __init__(self, ctx):
+        self.ctx, self._bufs = ctx, []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for buf in self._bufs:
+            buf.free()
+        return False
+
+    def alloc(self, nbytes):
+        buf = DeviceBuffer(self.ctx, max(nbytes, 4))
+        self._bufs.append(buf)
+        return buf
+
+    def upload(self, a):
+        """The device pointer of a copy of the contiguous numpy array `a`."""
+        buf = self.alloc(a.nbytes)
+        if a.nbytes:
+            self.ctx._check(lib.rt_copy_to_device(self.ctx._h, C.c_void_p(buf.ptr), a.ctypes.data, a.nbytes))
+        return buf.ptr
 
 
-def _device_points(ctx, points):
-    """(pointer, n, keep-alive) for `points` (n x 3 float32), as _device_rays does for rays."""
-    if hasattr(points, "data_ptr"):
-        dev = ctx.device_info()["device"]
-        if str(points.dtype) != "torch.float32" or not points.is_contiguous() or points.device.type != "cuda" or points.device.index != dev:
-            raise ValueError(f"points: a contiguous float32 tensor on cuda:{dev} is required")
-        if points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError("points must be (n, 3)")
-        return points.data_ptr(), int(points.shape[0]), None
-    a = np.ascontiguousarray(points, dtype=np.float32)
-    if a.ndim != 2 or a.shape[1] != 3:
-        raise ValueError("points must be (n, 3)")
-    buf = DeviceBuffer(ctx, max(a.nbytes, 4))
-    if a.nbytes:
-        ctx._check(lib.rt_copy_to_device(ctx._h, C.c_void_p(buf.ptr), a.ctypes.data, a.nbytes))
-    return buf.ptr, a.shape[0], buf
+def _check_tensor(t, dev, dtype, name):
+    if str(t.dtype) != f"torch.{dtype}" or not t.is_contiguous() or t.device.type != "cuda" or t.device.index != dev:
+        raise ValueError(f"{name}: a contiguous {dtype} tensor on cuda:{dev} is required")
+
+
+_RAYS = ("rays", 6, "rays must be (n, 6): origin.xyz, dir.xyz")
+_POINTS = ("points", 3, "points must be (n, 3)")
+
+
+def _device_rows(scope, rows, name, cols, shape_error):
+    """(pointer, n) for `rows` (n x cols float32; _RAYS, _POINTS): a numpy array is uploaded to a buffer of the scope; a contiguous float32
+    torch tensor on the context's device is used in place."""
+    if hasattr(rows, "data_ptr"):
+        _check_tensor(rows, scope.ctx.device_info()["device"], "float32", name)
+        if rows.dim() != 2 or rows.shape[1] != cols:
+            raise ValueError(shape_error)
+        return rows.data_ptr(), int(rows.shape[0])
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != cols:
+        raise ValueError(shape_error)
+    return scope.upload(a), a.shape[0]
 
 
 def _is_bound_array(b):
     return hasattr(b, "data_ptr") or np.ndim(b) > 0
 
 
-def _device_bound(ctx, dev, n, name, b, keep, per="ray"):
-    """The device pointer of one bound of the ranged entries (see _device_bounds); a buffer it uploads is appended to `keep`."""
-    if hasattr(b, "data_ptr"):
-        if str(b.dtype) != "torch.float32" or not b.is_contiguous() or b.device.type != "cuda" or b.device.index != dev:
-            raise ValueError(f"{name}: a contiguous float32 tensor on cuda:{dev} is required")
-        if b.dim() != 1 or b.shape[0] != n:
-            raise ValueError(f"{name} must be ({n},), one bound per {per}; got {tuple(b.shape)}")
-        return b.data_ptr()
-    if np.ndim(b) > 0:
-        a = np.asarray(b)
-        if not np.issubdtype(a.dtype, np.floating):
-            raise ValueError(f"{name}: a floating-point array is required; got {a.dtype}")
-        if a.shape != (n,):
-            raise ValueError(f"{name} must be ({n},), one bound per {per}; got {a.shape}")
-        a = np.ascontiguousarray(a, dtype=np.float32)
-    else:
-        v = np.float32(b)
-        if not (np.isfinite(v) and 0.0 <= v <= 1e9):
-            raise RtError(f"{name} = {b!r}: a scalar bound must be finite and in [0, 1e9]")
-        a = np.full(n, v, dtype=np.float32)
-    buf = DeviceBuffer(ctx, max(a.nbytes, 4))
-    keep.append(buf)
-    if a.nbytes:
-        ctx._check(lib.rt_copy_to_device(ctx._h, C.c_void_p(buf.ptr), a.ctypes.data, a.nbytes))
-    return buf.ptr
+def _device_values(scope, dev, n, name, v, dtype, kind, what, per, convert):
+    """The device pointer of the (n,) per-query values `v`: a contiguous `dtype` torch tensor on the context's device is used in place; a numpy
+    array of dtype kind `kind` is passed through convert() and uploaded to a buffer of the scope."""
+    if hasattr(v, "data_ptr"):
+        _check_tensor(v, dev, dtype, name)
+        if v.dim() != 1 or v.shape[0] != n:
+            raise ValueError(f"{name} must be ({n},), one {what} per {per}; got {tuple(v.shape)}")
+        return v.data_ptr()
+    a = np.asarray(v)
+    if not np.issubdtype(a.dtype, kind):
+        raise ValueError(f"{name}: {'a floating-point' if kind is np.floating else 'an integer'} array is required; got {a.dtype}")
+    if a.shape != (n,):
+        raise ValueError(f"{name} must be ({n},), one {what} per {per}; got {a.shape}")
+    return scope.upload(convert(a))
 
 
-def _device_bounds(ctx, n, t_min, t_max):
-    """(t_min pointer, t_max pointer, keep-alive buffers) for the ranged entries: each bound an (n,) array -- numpy (a floating dtype,
-    uploaded as float32) or a contiguous float32 torch tensor on the context's device (used in place) -- or a scalar, checked by the
-    scalar entries' rule and broadcast."""
-    dev = ctx.device_info()["device"]
-    ptrs, keep = [], []
-    try:
-        for name, b in (("t_min", t_min), ("t_max", t_max)):
-            ptrs.append(_device_bound(ctx, dev, n, name, b, keep))
-    except BaseException:
-        for buf in keep:
-            buf.free()
-        raise
-    return ptrs[0], ptrs[1], keep
+def _device_bound(scope, dev, n, name, b, per="ray"):
+    """The device pointer of one bound of the ranged entries: an (n,) array -- numpy (a floating dtype, uploaded as float32) or a contiguous
+    float32 torch tensor on the context's device (used in place) -- or a scalar, checked by the scalar entries' rule and broadcast."""
+    if _is_bound_array(b):
+        return _device_values(scope, dev, n, name, b, "float32", np.floating, "bound", per, lambda a: np.ascontiguousarray(a, dtype=np.float32))
+    v = np.float32(b)
+    if not (np.isfinite(v) and 0.0 <= v <= 1e9):
+        raise RtError(f"{name} = {b!r}: a scalar bound must be finite and in [0, 1e9]")
+    return scope.upload(np.full(n, v, dtype=np.float32))
+
+
+def _device_bounds(scope, n, t_min, t_max):
+    """(t_min pointer, t_max pointer) of the ranged ray entries (_device_bound)."""
+    dev = scope.ctx.device_info()["device"]
+    return _device_bound(scope, dev, n, "t_min", t_min), _device_bound(scope, dev, n, "t_max", t_max)
+
+
+def _device_first(scope, dev, n, first, name="first", per="point"):
+    """The device pointer of the per-point lower index bounds `first` (or, as `name`, the sweep queries' excluded indices): an (n,) integer
+    numpy array (uploaded as int32, clipped to int32's range first) or a contiguous int32 torch tensor on the context's device (used in
+    place)."""
+    return _device_values(scope, dev, n, name, first, "int32", np.integer, "index", per,
+                          lambda a: np.ascontiguousarray(np.clip(a, -2 ** 31, 2 ** 31 - 1), dtype=np.int32))
 
 
 def trace_rays(prepared, rays, max_depth=MAX_DEPTH):
     """ray_colour of every ray (ray.fut:126-148) -> (colour (n, 3) float32, pixel (n,) int32) numpy arrays."""
-    ctx = prepared.ctx
-    ptr, n, keep = _device_rays(ctx, rays)
-    col = DeviceBuffer(ctx, max(12 * n, 4))
-    px = DeviceBuffer(ctx, max(4 * n, 4))
-    try:
+    with _Scope(prepared.ctx) as s:
+        ptr, n = _device_rows(s, rays, *_RAYS)
+        col, px = s.alloc(12 * n), s.alloc(4 * n)
         trace_rays_into(ptr, n, prepared, col.ptr, px.ptr, max_depth)
         return col.to_host((n, 3), np.float32), px.to_host((n,))
-    finally:
-        col.free()
-        px.free()
-        if keep is not None:
-            keep.free()
 
 
 def intersect_rays(prepared, rays, t_min=0.0, t_max=1e9):
     """objs_hit bvh r t_min t_max of every ray (ray.fut:76-86) -> (index (n,) int32, hit (n, 7) float32) numpy arrays.
     Either bound may be an (n,) array, one per ray (rt_intersect_rays_ranged; a scalar next to it is broadcast)."""
-    ctx = prepared.ctx
     ranged = _is_bound_array(t_min) or _is_bound_array(t_max)
-    ptr, n, keep = _device_rays(ctx, rays)
-    bounds = []
-    idx = hit = None
-    try:
+    with _Scope(prepared.ctx) as s:
+        ptr, n = _device_rows(s, rays, *_RAYS)
         if ranged:
-            lo_ptr, hi_ptr, bounds = _device_bounds(ctx, n, t_min, t_max)
-        idx = DeviceBuffer(ctx, max(4 * n, 4))
-        hit = DeviceBuffer(ctx, max(28 * n, 4))
+            lo_ptr, hi_ptr = _device_bounds(s, n, t_min, t_max)
+        idx, hit = s.alloc(4 * n), s.alloc(28 * n)
         if ranged:
             intersect_rays_ranged_into(ptr, n, prepared, lo_ptr, hi_ptr, idx.ptr, hit.ptr)
         else:
             intersect_rays_into(ptr, n, prepared, idx.ptr, hit.ptr, t_min, t_max)
         return idx.to_host((n,)), hit.to_host((n, 7), np.float32)
-    finally:
-        for buf in [idx, hit] + bounds:
-            if buf is not None:
-                buf.free()
-        if keep is not None:
-            keep.free()
 
 
 def occluded_rays(prepared, rays, t_min=0.0, t_max=1e9):
     """Occlusion of every ray over (t_min, t_max) (rt_occluded_rays) -> (n,) bool numpy array.  Either bound may be an (n,)
     array, one per ray (rt_occluded_rays_ranged; a scalar next to it is broadcast)."""
-    ctx = prepared.ctx
     ranged = _is_bound_array(t_min) or _is_bound_array(t_max)
-    ptr, n, keep = _device_rays(ctx, rays)
-    bounds = []
-    out = None
-    try:
+    with _Scope(prepared.ctx) as s:
+        ptr, n = _device_rows(s, rays, *_RAYS)
         if ranged:
-            lo_ptr, hi_ptr, bounds = _device_bounds(ctx, n, t_min, t_max)
-        out = DeviceBuffer(ctx, max(n, 4))
+            lo_ptr, hi_ptr = _device_bounds(s, n, t_min, t_max)
+        out = s.alloc(n)
         if ranged:
             occluded_rays_ranged_into(ptr, n, prepared, lo_ptr, hi_ptr, out.ptr)
         else:
             occluded_rays_into(ptr, n, prepared, out.ptr, t_min, t_max)
         return out.to_host((n,), np.uint8).astype(bool)
-    finally:
-        for buf in [out] + bounds:
-            if buf is not None:
-                buf.free()
-        if keep is not None:
-            keep.free()
 
 
 def multi_hit_rays(prepared, rays, k, t_min=0.0, t_max=1e9):
     """The first k sphere crossings of every ray over (t_min, t_max) (rt_multi_hit_rays) -> (count (n,) int32, index (n, k) int32,
     root (n, k) uint8, hit (n, k, 7) float32) numpy arrays.  Either bound may be an (n,) array, one per ray (rt_multi_hit_rays_ranged;
     a scalar next to it is broadcast)."""
-    ctx = prepared.ctx
     k = int(k)
     ranged = _is_bound_array(t_min) or _is_bound_array(t_max)
-    ptr, n, keep = _device_rays(ctx, rays)
-    bounds = []
-    cnt = idx = root = hit = None
-    try:
+    with _Scope(prepared.ctx) as s:
+        ptr, n = _device_rows(s, rays, *_RAYS)
         if ranged:
-            lo_ptr, hi_ptr, bounds = _device_bounds(ctx, n, t_min, t_max)
+            lo_ptr, hi_ptr = _device_bounds(s, n, t_min, t_max)
         nk = n * max(k, 0)
-        cnt = DeviceBuffer(ctx, max(4 * n, 4))
-        idx = DeviceBuffer(ctx, max(4 * nk, 4))
-        root = DeviceBuffer(ctx, max(nk, 4))
-        hit = DeviceBuffer(ctx, max(28 * nk, 4))
+        cnt, idx, root, hit = s.alloc(4 * n), s.alloc(4 * nk), s.alloc(nk), s.alloc(28 * nk)
         if ranged:
             multi_hit_rays_ranged_into(ptr, n, prepared, lo_ptr, hi_ptr, k, cnt.ptr, idx.ptr, root.ptr, hit.ptr)
         else:
             multi_hit_rays_into(ptr, n, prepared, k, cnt.ptr, idx.ptr, root.ptr, hit.ptr, t_min, t_max)
         return (cnt.to_host((n,)), idx.to_host((n, k)), root.to_host((n, k), np.uint8), hit.to_host((n, k, 7), np.float32))
-    finally:
-        for buf in [cnt, idx, root, hit] + bounds:
-            if buf is not None:
-                buf.free()
-        if keep is not None:
-            keep.free()
 
 
 def sweep_spheres(prepared, rays, radius, k=1, t_min=0.0, t_max=1.0, exclude=None):
@@ -774,38 +747,26 @@ def sweep_spheres(prepared, rays, radius, k=1, t_min=0.0, t_max=1.0, exclude=Non
     an invalid array value makes its query a miss; an invalid scalar, or a scalar pair with t_min > t_max, is an RtError).  exclude: None,
     or an (n,) integer array / int32 device tensor -- sphere exclude[i] of L is skipped for query i, so a scene can sweep its own spheres
     (also the ranged entry)."""
-    ctx = prepared.ctx
     k = int(k)
     ranged = _is_bound_array(radius) or _is_bound_array(t_min) or _is_bound_array(t_max) or exclude is not None
-    ptr, n, keep = _device_rays(ctx, rays)
-    bounds = []
-    cnt = idx = start = hit = None
-    try:
+    with _Scope(prepared.ctx) as s:
+        ptr, n = _device_rows(s, rays, *_RAYS)
         if ranged:
-            dev = ctx.device_info()["device"]
+            dev = s.ctx.device_info()["device"]
             # (a scalar pair is held to the scalar entry's rule as a pair: each scalar alone passes _device_bound with t_min > t_max)
             if not _is_bound_array(t_min) and not _is_bound_array(t_max) and not np.float32(t_min) <= np.float32(t_max):
                 raise RtError(f"t_min = {t_min!r}, t_max = {t_max!r}: scalar bounds must satisfy t_min <= t_max")
-            rad_ptr = _device_bound(ctx, dev, n, "radius", radius, bounds, per="query")
-            lo_ptr = _device_bound(ctx, dev, n, "t_min", t_min, bounds, per="query")
-            hi_ptr = _device_bound(ctx, dev, n, "t_max", t_max, bounds, per="query")
-            ex_ptr = _device_first(ctx, dev, n, exclude, bounds, name="exclude", per="query") if exclude is not None else None
+            rad_ptr = _device_bound(s, dev, n, "radius", radius, per="query")
+            lo_ptr = _device_bound(s, dev, n, "t_min", t_min, per="query")
+            hi_ptr = _device_bound(s, dev, n, "t_max", t_max, per="query")
+            ex_ptr = _device_first(s, dev, n, exclude, name="exclude", per="query") if exclude is not None else None
         nk = n * max(k, 0)
-        cnt = DeviceBuffer(ctx, max(4 * n, 4))
-        idx = DeviceBuffer(ctx, max(4 * nk, 4))
-        start = DeviceBuffer(ctx, max(nk, 4))
-        hit = DeviceBuffer(ctx, max(28 * nk, 4))
+        cnt, idx, start, hit = s.alloc(4 * n), s.alloc(4 * nk), s.alloc(nk), s.alloc(28 * nk)
         if ranged:
             sweep_spheres_ranged_into(ptr, n, prepared, rad_ptr, lo_ptr, hi_ptr, k, cnt.ptr, idx.ptr, start.ptr, hit.ptr, ex_ptr)
         else:
             sweep_spheres_into(ptr, n, prepared, radius, k, cnt.ptr, idx.ptr, start.ptr, hit.ptr, t_min, t_max)
         return (cnt.to_host((n,)), idx.to_host((n, k)), start.to_host((n, k), np.uint8), hit.to_host((n, k, 7), np.float32))
-    finally:
-        for buf in [cnt, idx, start, hit] + bounds:
-            if buf is not None:
-                buf.free()
-        if keep is not None:
-            keep.free()
 
 
 def nearest_spheres(prepared, points, k, max_dist=1e9, count=True):
@@ -818,54 +779,21 @@ def nearest_spheres(prepared, points, k, max_dist=1e9, count=True):
     the same.  `points`: (n, 3) float32, a numpy array or a device tensor.  A point with a non-finite component selects nothing.
     Contacts: the spheres a sphere (c, r) overlaps or touches are those selected at p = c with max_dist = r; for a scene's self-contacts pass
     its own centres and radii -- every sphere finds itself at gap -r."""
-    ctx = prepared.ctx
     k = int(k)
     ranged = _is_bound_array(max_dist)
-    ptr, n, keep = _device_points(ctx, points)
-    bounds = []
-    cnt = idx = gap = None
-    try:
+    with _Scope(prepared.ctx) as s:
+        ptr, n = _device_rows(s, points, *_POINTS)
         if ranged:
-            md_ptr = _device_bound(ctx, ctx.device_info()["device"], n, "max_dist", max_dist, bounds, per="point")
+            md_ptr = _device_bound(s, s.ctx.device_info()["device"], n, "max_dist", max_dist, per="point")
         nk = n * max(k, 0)
-        cnt = DeviceBuffer(ctx, max(4 * n, 4)) if count else None
-        idx = DeviceBuffer(ctx, max(4 * nk, 4))
-        gap = DeviceBuffer(ctx, max(4 * nk, 4))
+        cnt = s.alloc(4 * n) if count else None
+        idx, gap = s.alloc(4 * nk), s.alloc(4 * nk)
         cptr = cnt.ptr if cnt is not None else None
         if ranged:
             nearest_spheres_ranged_into(ptr, n, prepared, md_ptr, k, cptr, idx.ptr, gap.ptr)
         else:
             nearest_spheres_into(ptr, n, prepared, k, cptr, idx.ptr, gap.ptr, max_dist)
         return (cnt.to_host((n,)) if cnt is not None else None, idx.to_host((n, k)), gap.to_host((n, k), np.float32))
-    finally:
-        for buf in [cnt, idx, gap] + bounds:
-            if buf is not None:
-                buf.free()
-        if keep is not None:
-            keep.free()
-
-
-def _device_first(ctx, dev, n, first, keep, name="first", per="point"):
-    """The device pointer of the per-point lower index bounds `first` (or, as `name`, the sweep queries' excluded indices): an (n,) integer
-    numpy array (uploaded as int32, clipped to int32's range first) or a contiguous int32 torch tensor on the context's device (used in
-    place); a buffer it uploads is appended to `keep`."""
-    if hasattr(first, "data_ptr"):
-        if str(first.dtype) != "torch.int32" or not first.is_contiguous() or first.device.type != "cuda" or first.device.index != dev:
-            raise ValueError(f"{name}: a contiguous int32 tensor on cuda:{dev} is required")
-        if first.dim() != 1 or first.shape[0] != n:
-            raise ValueError(f"{name} must be ({n},), one index per {per}; got {tuple(first.shape)}")
-        return first.data_ptr()
-    a = np.asarray(first)
-    if not np.issubdtype(a.dtype, np.integer):
-        raise ValueError(f"{name}: an integer array is required; got {a.dtype}")
-    if a.shape != (n,):
-        raise ValueError(f"{name} must be ({n},), one index per {per}; got {a.shape}")
-    a = np.ascontiguousarray(np.clip(a, -2 ** 31, 2 ** 31 - 1), dtype=np.int32)
-    buf = DeviceBuffer(ctx, max(a.nbytes, 4))
-    keep.append(buf)
-    if a.nbytes:
-        ctx._check(lib.rt_copy_to_device(ctx._h, C.c_void_p(buf.ptr), a.ctypes.data, a.nbytes))
-    return buf.ptr
 
 
 def spheres_within(prepared, points, max_dist, first=None, gaps=True, rows=False):
@@ -878,36 +806,23 @@ def spheres_within(prepared, points, max_dist, first=None, gaps=True, rows=False
     spheres with index >= first[i] are selected for point i.  gaps=False: no gap array (None is returned in its place).  rows=True: also
     `point`, the row number of every entry, so that (point, index) is the list of pairs.  `points`: (n, 3) float32, a numpy array or a device
     tensor.  A point with a non-finite component has an empty row."""
-    ctx = prepared.ctx
     ranged = _is_bound_array(max_dist)
-    ptr, n, keep = _device_points(ctx, points)
-    bufs = []
-    try:
-        dev = ctx.device_info()["device"]
-        md_ptr = _device_bound(ctx, dev, n, "max_dist", max_dist, bufs, per="point") if ranged else None
+    with _Scope(prepared.ctx) as s:
+        ptr, n = _device_rows(s, points, *_POINTS)
+        dev = s.ctx.device_info()["device"]
+        md_ptr = _device_bound(s, dev, n, "max_dist", max_dist, per="point") if ranged else None
         md = 0.0 if ranged else max_dist
-        first_ptr = _device_first(ctx, dev, n, first, bufs) if first is not None else None
-        off = DeviceBuffer(ctx, 8 * (n + 1))
-        bufs.append(off)
+        first_ptr = _device_first(s, dev, n, first) if first is not None else None
+        off = s.alloc(8 * (n + 1))
         spheres_within_count_into(ptr, n, prepared, off.ptr, md, md_ptr, first_ptr)
         offsets = off.to_host((n + 1,), np.int64)
         total = int(offsets[n])
-        out = []
-        for want in (True, gaps, rows):
-            out.append(DeviceBuffer(ctx, max(4 * total, 4)) if want else None)
-            if want:
-                bufs.append(out[-1])
-        idx, gap, row = out
+        idx, gap, row = (s.alloc(4 * total) if want else None for want in (True, gaps, rows))
         if total:
             spheres_within_fill_into(ptr, n, prepared, off.ptr, total, idx.ptr, gap.ptr if gap else None, row.ptr if row else None, md,
                                      md_ptr, first_ptr)
         res = (offsets, idx.to_host((total,)), gap.to_host((total,), np.float32) if gap else None)
         return res + (row.to_host((total,)),) if rows else res
-    finally:
-        for buf in bufs:
-            buf.free()
-        if keep is not None:
-            keep.free()
 
 
 def contact_pairs(prepared, margin=0.0, gaps=True):
@@ -915,25 +830,16 @@ def contact_pairs(prepared, margin=0.0, gaps=True):
     Pair (i, j), i < j, is reported once iff gap(centre_i, L[j]) = sqrtf(|c_i - c_j|^2) - r_j <= r_i + margin, all in float32 and evaluated
     from the lower index only; rows in ascending (i, j).  `gap` is that gap (subtract r_i for the surface-to-surface distance).  i and j are
     indices into L (Morton order): prepared.sphere_ids() maps them to the caller's order.  margin: a scalar in [0, 1e9]."""
-    ctx = prepared.ctx
     n = prepared.num_spheres
-    bufs = []
-    try:
-        off = DeviceBuffer(ctx, 8 * (n + 1))
-        bufs.append(off)
+    with _Scope(prepared.ctx) as s:
+        off = s.alloc(8 * (n + 1))
         contact_pairs_count_into(prepared, off.ptr, margin)
         total = int(off.to_host((n + 1,), np.int64)[n])
-        pair = DeviceBuffer(ctx, max(8 * total, 4))
-        bufs.append(pair)
-        gap = DeviceBuffer(ctx, max(4 * total, 4)) if gaps else None
-        if gap:
-            bufs.append(gap)
+        pair = s.alloc(8 * total)
+        gap = s.alloc(4 * total) if gaps else None
         if total:
             contact_pairs_fill_into(prepared, off.ptr, total, pair.ptr, gap.ptr if gap else None, margin)
         return pair.to_host((total, 2)), gap.to_host((total,), np.float32) if gap else None
-    finally:
-        for buf in bufs:
-            buf.free()
 
 
 def camera_rays(prepared, h, w, cam=None):

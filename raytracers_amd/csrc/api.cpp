@@ -1,6 +1,6 @@
-// api.cpp -- the C ABI of libray_mi355x.so: the rt_* surface (include/rt_mi355x.h) and,
-// on top of it, the Futhark-shaped drop-in boundary (include/ray.h) that the reference's
-// futhark/main.c is written against.
+// api.cpp -- the C ABI of libray_mi355x.so: contexts, scenes, prepared scenes and the render entries of the rt_* surface
+// (include/rt_mi355x.h), with the policy that plans and launches the render kernels.  The caller queries are api_queries.cpp; the
+// Futhark-shaped drop-in boundary (include/ray.h) that the reference's futhark/main.c is written against is futhark_shim.cpp.
 //
 // There is no CPU fallback anywhere in this library: every render entry launches HIP
 // kernels, and context creation fails loudly when no HIP device is usable.
@@ -16,7 +16,6 @@
 #include <string>
 #include <vector>
 
-#include "../../include/ray.h"
 #include "../../include/rt_mi355x.h"
 #include "rt_device.hpp"
 #include "rt_host.hpp"
@@ -33,6 +32,10 @@ int hip_fail(rt_context *ctx, hipError_t e, const char *what) {
 }  // namespace rti
 using rti::fail;
 using rti::hip_fail;
+using rti::Plan;
+using rti::pool_alloc;
+using rti::pool_free;
+using rti::scene_params;
 
 namespace {
 
@@ -52,7 +55,9 @@ struct Ticks {
 constexpr size_t kGranule = size_t(64) << 10, kArenaGranules = 2048;   // 128 MiB arena per context (views' blocks, tables, the Futhark ABI's images)
 constexpr size_t kStageBytes = size_t(1) << 20;
 
-hipError_t pool_alloc(rt_context *ctx, char **out, size_t *bytes_io) {
+}  // namespace
+
+hipError_t rti::pool_alloc(rt_context *ctx, char **out, size_t *bytes_io) {
   const size_t want = (*bytes_io + kGranule - 1) & ~(kGranule - 1);   // granules make repeats hit
   // 1. the arena (small scenes)
   const size_t g = want / kGranule;
@@ -85,7 +90,7 @@ hipError_t pool_alloc(rt_context *ctx, char **out, size_t *bytes_io) {
   return hipMalloc(reinterpret_cast<void **>(out), want);
 }
 // (the caller has drained every stream that used the block)
-void pool_free(rt_context *ctx, char *p, size_t bytes) {
+void rti::pool_free(rt_context *ctx, char *p, size_t bytes) {
   if (!p) return;
   if (ctx && ctx->arena && p >= ctx->arena && p < ctx->arena + kArenaGranules * kGranule) {
     const size_t first = static_cast<size_t>(p - ctx->arena) / kGranule, g = bytes / kGranule;
@@ -102,6 +107,8 @@ void pool_free(rt_context *ctx, char *p, size_t bytes) {
   }
   ctx->pool.push_back({p, bytes});
 }
+
+namespace {
 
 template <class T>
 int upload(rt_context *ctx, T **dev, const void *host, size_t bytes) {
@@ -163,14 +170,6 @@ int get_first_order(rt_context *ctx, int tiles_x, int tiles_y, const int **out) 
   return 0;
 }
 
-struct Plan {
-  int variant;
-  int lds_nodes, lds_sph, smax, lmax, waves, grid;
-  int grid_full;   // every persistent workgroup (grid == grid_full unless grid_div says otherwise)
-  int capb, capl, ray_planes;
-  int spill_stride;   // > 0: capb is below the box stack's bound -- the launch needs a spill region of this many dwords per wave (the twenty-wave shape, tall trees)
-  size_t lds_bytes;
-};
 
 // Decide the launch shape of the persistent family for one prepared scene.
 // `ntiles`: 8x8 tiles of the launch (grid_div == 0 picks the launch size from it: up to ~1000x1000 a
@@ -534,14 +533,7 @@ const char *pooled_launch_nodes(const rtk::KParams &p, int waves) {
   return rtk::choose_pooled(p, false, waves, 0, &k) && rtk::pooled_presort(k) ? "sign-ordered" : "planes";
 }
 
-// p's scene fields: the prepared scene's traversal copy
-void scene_params(const rt_prepared *ps, rtk::KParams *p) {
-  p->nodes = ps->nodes; p->nodes64 = ps->nodes64; p->sph = ps->sph; p->col = ps->col;
-  std::copy(ps->root_lo, ps->root_lo + 3, p->root_lo);
-  std::copy(ps->root_hi, ps->root_hi + 3, p->root_hi);
-  p->n_nodes = static_cast<int>(ps->n - 1); p->n_sph = static_cast<int>(ps->n);
-}
-// ... and those of one frame: part `part` of `nparts` of an h x w image through camera cam12 (nullptr: the prepared scene's)
+// p's scene fields (rti::scene_params, below) and those of one frame: part `part` of `nparts` of an h x w image through camera cam12 (nullptr: the prepared scene's)
 void frame_params(const rt_prepared *ps, int64_t h, int64_t w, int rows_per_tile, int part, int nparts, int max_depth, const float *cam12, rtk::KParams *p) {
   scene_params(ps, p);
   std::memcpy(&p->cam, cam12 ? static_cast<const void *>(cam12) : static_cast<const void *>(&ps->cam), sizeof(p->cam));
@@ -840,6 +832,69 @@ int clear_frames(rt_context *ctx, const rtk::KParams &p, int32_t *out_dev, int n
 }
 
 }  // namespace
+
+// ---- what the caller-ray entries (api_queries.cpp) take from the render policy above ---------------
+// p's scene fields: the prepared scene's traversal copy
+void rti::scene_params(const rt_prepared *ps, rtk::KParams *p) {
+  p->nodes = ps->nodes; p->nodes64 = ps->nodes64; p->sph = ps->sph; p->col = ps->col;
+  std::copy(ps->root_lo, ps->root_lo + 3, p->root_lo);
+  std::copy(ps->root_hi, ps->root_hi + 3, p->root_hi);
+  p->n_nodes = static_cast<int>(ps->n - 1); p->n_sph = static_cast<int>(ps->n);
+}
+
+// The pooled family's plan for a frame of as many 64-ray blocks as there are rays (its LDS staging, the wide shape), under RT_VARIANT_AUTO /
+// RT_VARIANT_POOLED; pl->variant is RT_VARIANT_PIXEL under the other variants, and AUTO's beyond the family's limits (make_plan).
+int rti::pooled_rays_plan(rt_context *ctx, const rt_prepared *ps, int64_t n, Plan *pl) {
+  *pl = Plan{};
+  pl->variant = RT_VARIANT_PIXEL;
+  const int64_t nblocks = (n + 63) / 64;
+  if (ctx->variant == RT_VARIANT_AUTO || ctx->variant == RT_VARIANT_POOLED) {
+    const bool huge = rt_scene_exceeds_l2(ps);
+    const bool wide = ctx->wide_waves == 2 || (ctx->wide_waves == 1 && nblocks >= (huge ? 40000 : 100000) && nblocks > ctx->px_max_tiles);
+    if (int rc = make_plan(ctx, ps, pl, nblocks, 0, wide)) return rc;
+    // The caller-ray loops exist for workgroups of 16 and 4 waves only (choose_pooled).  A scene that fits in LDS whole beside 12 or 8 waves
+    // but not beside 16 (about 600 spheres) made the plan pick one of those, and the launch failed: plan 16 waves instead, else 4.
+    if (pl->variant == RT_VARIANT_POOLED && pl->waves != 16 && pl->waves != 4) {
+      Plan p16{};
+      if (make_plan(ctx, ps, &p16, nblocks, 16, wide) == 0) {
+        *pl = p16;
+      } else {
+        *pl = Plan{};
+        if (int rc = make_plan(ctx, ps, pl, nblocks, 4, wide)) return rc;
+      }
+    }
+  }
+  return 0;
+}
+
+// p's fields for the plain pooled loop over those blocks: the raster queue, the plan's shape and staging, the spill region.
+int rti::pooled_rays_params(rt_context *ctx, const rt_prepared *ps, const Plan &pl, rtk::KParams *pp) {
+  rtk::KParams &p = *pp;
+  if (ps->n >= (int64_t(1) << 22)) return fail(ctx, "pooled kernel: at most 2^22 spheres (work items and hit keys carry the leaf index in 22 bits)");
+  const int64_t nblocks = (static_cast<int64_t>(p.nrays) + 63) / 64;
+  p.nframes = 1;
+  p.queue = ctx->queue_dev;
+  p.w = 64; p.h = 1;
+  p.rows_local = 1; p.rows_per_tile = 1; p.part = 0; p.nparts = 1; p.rpt_log2 = 0;
+  p.tiles_x = static_cast<int>(nblocks); p.tiles_y = 1;
+  p.nchunks = static_cast<int>(nblocks);
+  p.tpt_log2 = 0;
+  // the eight counters take turns over the one raster queue (strips of tile columns are a 2D layout; the rays have none)
+  set_counters(&p, ctx->xcd_queues != 0 ? 2 : 0, pl.grid);
+  return pooled_shape_params(ctx, ps, pl, &p);
+}
+
+// The launch of the pooled family's loop on caller rays (`rays`: kRaysColour, kRaysAny), and its rt_context_last_launch (" intervals=per-ray"
+// appended when each ray carries its own interval)
+int rti::launch_pooled_rays(rt_context *ctx, const rtk::KParams &p, const Plan &pl, int rays) {
+  RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream, rays));
+  char buf[256];
+  std::snprintf(buf, sizeof buf, "family=pooled tickets=rays instantiation=%s frames=1 tiles=%d grid=%d waves=%d counters=%d%s deep_class=0 deep_split=0 recording=0%s",
+                pooled_launch_name(p, pl.waves, rays).c_str(), p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "",
+                p.ray_tlo_dev != nullptr ? " intervals=per-ray" : "");
+  ctx->last_launch = buf;
+  return 0;
+}
 
 int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, int32_t max_depth, int32_t rows_per_tile,
                         int32_t part, int32_t nparts, int32_t *out_dev, bool stats, const float *cam12, int32_t nframes,
@@ -1978,760 +2033,5 @@ extern "C" int rt_copy_to_device(rt_context *ctx, void *dst_dev, const void *src
   RT_HIP(ctx, hipMemcpyAsync(dst_dev, src_host, static_cast<size_t>(bytes), hipMemcpyHostToDevice, ctx->stream));
   RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->synced_since_render = true;
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------ caller rays
-namespace {
-// The checks every caller-ray entry shares; on success p holds the prepared scene's traversal copy and the ray count.
-int ray_entry_params(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, rtk::KParams *p) {
-  if (!ps) return fail(ctx, "null prepared scene");
-  if (ctx->group) return fail(ctx, "caller rays: a multi-device context is not supported (use a context on one device)");
-  if (n < 0 || n >= (int64_t(1) << 31)) return fail(ctx, "ray count out of range: 0 <= n < 2^31");
-  if (!rays_dev) return fail(ctx, "null rays pointer");
-  *p = rtk::KParams{};
-  scene_params(ps, p);
-  p->rays = rays_dev;
-  p->nrays = static_cast<int>(n);
-  return 0;
-}
-
-// The interval rule of the entries that take one (aabb_hit's NaN argument in lane_core.h -- the last slab test decides -- needs a
-// finite interval; its one-test form needs a finite start).
-bool ray_interval_ok(float t_min, float t_max) {
-  return std::isfinite(t_min) && std::isfinite(t_max) && t_min >= 0.0f && t_min <= t_max && t_max <= rtk::kTMax;
-}
-
-// The pooled family's plan for a frame of as many 64-ray blocks as there are rays (its LDS staging, the wide shape), under RT_VARIANT_AUTO /
-// RT_VARIANT_POOLED; pl->variant is RT_VARIANT_PIXEL under the other variants, and AUTO's beyond the family's limits (make_plan).
-int pooled_rays_plan(rt_context *ctx, const rt_prepared *ps, int64_t n, Plan *pl) {
-  *pl = Plan{};
-  pl->variant = RT_VARIANT_PIXEL;
-  const int64_t nblocks = (n + 63) / 64;
-  if (ctx->variant == RT_VARIANT_AUTO || ctx->variant == RT_VARIANT_POOLED) {
-    const bool huge = rt_scene_exceeds_l2(ps);
-    const bool wide = ctx->wide_waves == 2 || (ctx->wide_waves == 1 && nblocks >= (huge ? 40000 : 100000) && nblocks > ctx->px_max_tiles);
-    if (int rc = make_plan(ctx, ps, pl, nblocks, 0, wide)) return rc;
-    // The caller-ray loops exist for workgroups of 16 and 4 waves only (choose_pooled).  A scene that fits in LDS whole beside 12 or 8 waves
-    // but not beside 16 (about 600 spheres) made the plan pick one of those, and the launch failed: plan 16 waves instead, else 4.
-    if (pl->variant == RT_VARIANT_POOLED && pl->waves != 16 && pl->waves != 4) {
-      Plan p16{};
-      if (make_plan(ctx, ps, &p16, nblocks, 16, wide) == 0) {
-        *pl = p16;
-      } else {
-        *pl = Plan{};
-        if (int rc = make_plan(ctx, ps, pl, nblocks, 4, wide)) return rc;
-      }
-    }
-  }
-  return 0;
-}
-
-// p's fields for the plain pooled loop over those blocks: the raster queue, the plan's shape and staging, the spill region.
-int pooled_rays_params(rt_context *ctx, const rt_prepared *ps, const Plan &pl, rtk::KParams *pp) {
-  rtk::KParams &p = *pp;
-  if (ps->n >= (int64_t(1) << 22)) return fail(ctx, "pooled kernel: at most 2^22 spheres (work items and hit keys carry the leaf index in 22 bits)");
-  const int64_t nblocks = (static_cast<int64_t>(p.nrays) + 63) / 64;
-  p.nframes = 1;
-  p.queue = ctx->queue_dev;
-  p.w = 64; p.h = 1;
-  p.rows_local = 1; p.rows_per_tile = 1; p.part = 0; p.nparts = 1; p.rpt_log2 = 0;
-  p.tiles_x = static_cast<int>(nblocks); p.tiles_y = 1;
-  p.nchunks = static_cast<int>(nblocks);
-  p.tpt_log2 = 0;
-  // the eight counters take turns over the one raster queue (strips of tile columns are a 2D layout; the rays have none)
-  set_counters(&p, ctx->xcd_queues != 0 ? 2 : 0, pl.grid);
-  return pooled_shape_params(ctx, ps, pl, &p);
-}
-
-// The launch of the pooled family's loop on caller rays (`rays`: kRaysColour, kRaysAny), and its rt_context_last_launch (" intervals=per-ray"
-// appended when each ray carries its own interval)
-int launch_pooled_rays(rt_context *ctx, const rtk::KParams &p, const Plan &pl, int rays) {
-  RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream, rays));
-  char buf[256];
-  std::snprintf(buf, sizeof buf, "family=pooled tickets=rays instantiation=%s frames=1 tiles=%d grid=%d waves=%d counters=%d%s deep_class=0 deep_split=0 recording=0%s",
-                pooled_launch_name(p, pl.waves, rays).c_str(), p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "",
-                p.ray_tlo_dev != nullptr ? " intervals=per-ray" : "");
-  ctx->last_launch = buf;
-  return 0;
-}
-}  // namespace
-
-extern "C" int rt_trace_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, int32_t max_depth,
-                             float *colour3_dev, int32_t *pixel_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  rtk::KParams p;
-  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
-  if (!colour3_dev && !pixel_dev) return fail(ctx, "rt_trace_rays: both outputs are NULL");
-  if (max_depth < 0) return fail(ctx, "negative max_depth");
-  RT_LOCK_PS(ps);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  ctx->synced_since_render = false;
-  if (n == 0) {
-    ctx->last_launch = "family=none (no rays)";
-    return 0;
-  }
-  if (max_depth == 0) {
-    // `while depth < 0`: every ray's colour is the initial (0,0,0)
-    if (colour3_dev) RT_HIP(ctx, hipMemsetAsync(colour3_dev, 0, sizeof(float) * 3 * static_cast<size_t>(n), ctx->stream));
-    if (pixel_dev) RT_HIP(ctx, hipMemsetAsync(pixel_dev, 0, sizeof(int32_t) * static_cast<size_t>(n), ctx->stream));
-    ctx->last_launch = "family=none (memset)";
-    return 0;
-  }
-  p.max_depth = max_depth;
-  p.out = pixel_dev;
-  p.colour3 = colour3_dev;
-  p.nframes = 1;
-  // the pooled family's plan; the pixel family beyond its limits (AUTO), or under RT_VARIANT_PIXEL / RT_VARIANT_PERSISTENT
-  Plan pl;
-  if (int rc = pooled_rays_plan(ctx, ps, n, &pl)) return rc;
-  if (pl.variant != RT_VARIANT_POOLED) {
-    RT_HIP(ctx, rtk::launch_pixel_rays(p, ctx->stream));
-    ctx->last_launch = "family=pixel (rays)";
-    return 0;
-  }
-  if (int rc = pooled_rays_params(ctx, ps, pl, &p)) return rc;
-  return launch_pooled_rays(ctx, p, pl, rtk::kRaysColour);
-}
-
-extern "C" int rt_intersect_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
-                                 int32_t *index_dev, float *hit7_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  rtk::KParams p;
-  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
-  if (!index_dev) return fail(ctx, "rt_intersect_rays: null index pointer");
-  if (!ray_interval_ok(t_min, t_max)) return fail(ctx, "rt_intersect_rays: need 0 <= t_min <= t_max <= 1e9, both finite");
-  RT_LOCK_PS(ps);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  ctx->synced_since_render = false;
-  if (n == 0) {
-    ctx->last_launch = "family=none (no rays)";
-    return 0;
-  }
-  RT_HIP(ctx, rtk::launch_intersect_rays(p, t_min, t_max, index_dev, hit7_dev, ctx->stream));
-  ctx->last_launch = "family=intersect";
-  return 0;
-}
-
-// The per-ray form: the intervals are device data, so they are not checked here -- the kernel answers a ray whose interval fails the rule
-// above (NaN included) as a miss (lane_core.h: interval_ok).
-extern "C" int rt_intersect_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *t_min_dev,
-                                        const float *t_max_dev, int32_t *index_dev, float *hit7_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  rtk::KParams p;
-  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
-  if (!index_dev) return fail(ctx, "rt_intersect_rays_ranged: null index pointer");
-  if (!t_min_dev || !t_max_dev) return fail(ctx, "rt_intersect_rays_ranged: null t_min or t_max pointer");
-  RT_LOCK_PS(ps);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  ctx->synced_since_render = false;
-  if (n == 0) {
-    ctx->last_launch = "family=none (no rays)";
-    return 0;
-  }
-  p.ray_tlo_dev = t_min_dev;
-  p.ray_thi_dev = t_max_dev;
-  RT_HIP(ctx, rtk::launch_intersect_rays_ranged(p, index_dev, hit7_dev, ctx->stream));
-  ctx->last_launch = "family=intersect (per-ray)";
-  return 0;
-}
-
-extern "C" int rt_occluded_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
-                                uint8_t *occluded_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  rtk::KParams p;
-  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
-  if (!occluded_dev) return fail(ctx, "rt_occluded_rays: null output pointer");
-  if (!ray_interval_ok(t_min, t_max)) return fail(ctx, "rt_occluded_rays: need 0 <= t_min <= t_max <= 1e9, both finite");
-  RT_LOCK_PS(ps);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  ctx->synced_since_render = false;
-  if (n == 0) {
-    ctx->last_launch = "family=none (no rays)";
-    return 0;
-  }
-  p.occluded = occluded_dev;
-  p.ray_tlo = t_min;
-  p.ray_thi = t_max;
-  // the pooled family's any-hit loop under RT_VARIANT_POOLED; the lane kernel under RT_VARIANT_PIXEL / RT_VARIANT_PERSISTENT.  AUTO takes the
-  // pooled loop only where it was measured faster: the whole scene staged in LDS, and rays rather than segments (t_max > 1;
-  // a shadow ray's (eps, 1) is a segment) -- elsewhere, and beyond the pooled family's limits, the lane kernel
-  Plan pl;
-  if (int rc = pooled_rays_plan(ctx, ps, n, &pl)) return rc;
-  if (ctx->variant == RT_VARIANT_AUTO && pl.variant == RT_VARIANT_POOLED &&
-      !(pl.lds_nodes == static_cast<int>(ps->n - 1) && pl.lds_sph == static_cast<int>(ps->n) && t_max > 1.0f))
-    pl.variant = RT_VARIANT_PIXEL;
-  if (pl.variant != RT_VARIANT_POOLED) {
-    RT_HIP(ctx, rtk::launch_occluded_rays(p, ctx->stream));
-    ctx->last_launch = "family=occluded";
-    return 0;
-  }
-  if (int rc = pooled_rays_params(ctx, ps, pl, &p)) return rc;
-  return launch_pooled_rays(ctx, p, pl, rtk::kRaysAny);
-}
-
-extern "C" int rt_occluded_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *t_min_dev,
-                                       const float *t_max_dev, uint8_t *occluded_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  rtk::KParams p;
-  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
-  if (!occluded_dev) return fail(ctx, "rt_occluded_rays_ranged: null output pointer");
-  if (!t_min_dev || !t_max_dev) return fail(ctx, "rt_occluded_rays_ranged: null t_min or t_max pointer");
-  RT_LOCK_PS(ps);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  ctx->synced_since_render = false;
-  if (n == 0) {
-    ctx->last_launch = "family=none (no rays)";
-    return 0;
-  }
-  p.occluded = occluded_dev;
-  p.ray_tlo_dev = t_min_dev;
-  p.ray_thi_dev = t_max_dev;
-  // the pooled family's any-hit loop in its per-ray mode under RT_VARIANT_POOLED; the lane kernel under RT_VARIANT_PIXEL / RT_VARIANT_PERSISTENT.
-  // AUTO: the host cannot see the rays' t_max, so the scalar rule's t_max > 1 clause cannot be asked.  Measured, the pooled
-  // loop won only long random rays on a scene staged in LDS (1.3x) and lost normalised shadow rays on the same scene (1.8x): AUTO takes the
-  // lane kernel
-  Plan pl;
-  if (int rc = pooled_rays_plan(ctx, ps, n, &pl)) return rc;
-  if (ctx->variant == RT_VARIANT_AUTO) pl.variant = RT_VARIANT_PIXEL;
-  if (pl.variant != RT_VARIANT_POOLED) {
-    RT_HIP(ctx, rtk::launch_occluded_rays_ranged(p, ctx->stream));
-    ctx->last_launch = "family=occluded (per-ray)";
-    return 0;
-  }
-  if (int rc = pooled_rays_params(ctx, ps, pl, &p)) return rc;
-  return launch_pooled_rays(ctx, p, pl, rtk::kRaysAny);
-}
-
-// The multi-hit entries' checks past ray_entry_params and their launch: the lane kernel under every variant, k crossings per ray.  The caller
-// holds the context lock and has set p's interval (scalar, or per-ray).
-static int multi_hit_launch(rt_context *ctx, const rt_prepared *ps, int64_t n, rtk::KParams &p, int32_t k, int32_t *count_dev,
-                            int32_t *index_dev, uint8_t *root_dev, float *hit7_dev, bool ranged) {
-  RT_LOCK_PS(ps);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  ctx->synced_since_render = false;
-  if (n == 0) {
-    ctx->last_launch = "family=none (no rays)";
-    return 0;
-  }
-  RT_HIP(ctx, rtk::launch_multi_hit_rays(p, k, count_dev, index_dev, root_dev, hit7_dev, ctx->stream));
-  ctx->last_launch = "family=multi-hit k=" + std::to_string(k) + (ranged ? " (per-ray)" : "");
-  return 0;
-}
-
-extern "C" int rt_multi_hit_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max, int32_t k,
-                                 int32_t *count_dev, int32_t *index_dev, uint8_t *root_dev, float *hit7_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  rtk::KParams p;
-  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
-  if (!count_dev && !index_dev && !root_dev && !hit7_dev) return fail(ctx, "rt_multi_hit_rays: all four outputs are NULL");
-  if (k < 1 || k > rtk::kMultiHitMaxK) return fail(ctx, "rt_multi_hit_rays: need 1 <= k <= 32");
-  if (!ray_interval_ok(t_min, t_max)) return fail(ctx, "rt_multi_hit_rays: need 0 <= t_min <= t_max <= 1e9, both finite");
-  p.ray_tlo = t_min;
-  p.ray_thi = t_max;
-  return multi_hit_launch(ctx, ps, n, p, k, count_dev, index_dev, root_dev, hit7_dev, false);
-}
-
-// The per-ray form: as rt_intersect_rays_ranged, a ray whose interval fails the rule is a miss in the kernel (count 0, every slot padded).
-extern "C" int rt_multi_hit_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *t_min_dev,
-                                        const float *t_max_dev, int32_t k, int32_t *count_dev, int32_t *index_dev, uint8_t *root_dev,
-                                        float *hit7_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  rtk::KParams p;
-  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
-  if (!count_dev && !index_dev && !root_dev && !hit7_dev) return fail(ctx, "rt_multi_hit_rays_ranged: all four outputs are NULL");
-  if (k < 1 || k > rtk::kMultiHitMaxK) return fail(ctx, "rt_multi_hit_rays_ranged: need 1 <= k <= 32");
-  if (!t_min_dev || !t_max_dev) return fail(ctx, "rt_multi_hit_rays_ranged: null t_min or t_max pointer");
-  p.ray_tlo_dev = t_min_dev;
-  p.ray_thi_dev = t_max_dev;
-  return multi_hit_launch(ctx, ps, n, p, k, count_dev, index_dev, root_dev, hit7_dev, true);
-}
-
-// The sweep entries' checks past ray_entry_params and their launch: the lane kernel under every variant, k contacts per query.  The caller holds
-// the context lock and has set p's interval (scalar, or per-query next to radius_dev).
-static int sweep_launch(rt_context *ctx, const rt_prepared *ps, int64_t n, rtk::KParams &p, const float *radius_dev, float radius,
-                        const int32_t *exclude_dev, int32_t k, int32_t *count_dev, int32_t *index_dev, uint8_t *start_dev, float *hit7_dev) {
-  RT_LOCK_PS(ps);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  ctx->synced_since_render = false;
-  if (n == 0) {
-    ctx->last_launch = "family=none (no rays)";
-    return 0;
-  }
-  RT_HIP(ctx, rtk::launch_sweep_spheres(p, radius_dev, radius, exclude_dev, k, count_dev, index_dev, start_dev, hit7_dev, ctx->stream));
-  ctx->last_launch = "family=sweep k=" + std::to_string(k) + (radius_dev ? " (per-query)" : "") + (exclude_dev ? " exclude" : "");
-  return 0;
-}
-
-extern "C" int rt_sweep_spheres(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float radius, float t_min, float t_max,
-                                int32_t k, int32_t *count_dev, int32_t *index_dev, uint8_t *start_dev, float *hit7_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  rtk::KParams p;
-  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
-  if (!count_dev && !index_dev && !start_dev && !hit7_dev) return fail(ctx, "rt_sweep_spheres: all four outputs are NULL");
-  if (k < 1 || k > rtk::kSweepMaxK) return fail(ctx, "rt_sweep_spheres: need 1 <= k <= 32");
-  if (!ray_interval_ok(t_min, t_max)) return fail(ctx, "rt_sweep_spheres: need 0 <= t_min <= t_max <= 1e9, both finite");
-  if (!(std::isfinite(radius) && radius >= 0.0f && radius <= rtk::kTMax)) return fail(ctx, "rt_sweep_spheres: need 0 <= radius <= 1e9, finite");
-  p.ray_tlo = t_min;
-  p.ray_thi = t_max;
-  return sweep_launch(ctx, ps, n, p, nullptr, radius, nullptr, k, count_dev, index_dev, start_dev, hit7_dev);
-}
-
-// The per-query form: a query whose interval or radius fails its rule is a miss in the kernel (count 0, every slot padded).
-extern "C" int rt_sweep_spheres_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *radius_dev,
-                                       const float *t_min_dev, const float *t_max_dev, const int32_t *exclude_dev, int32_t k,
-                                       int32_t *count_dev, int32_t *index_dev, uint8_t *start_dev, float *hit7_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  rtk::KParams p;
-  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
-  if (!count_dev && !index_dev && !start_dev && !hit7_dev) return fail(ctx, "rt_sweep_spheres_ranged: all four outputs are NULL");
-  if (k < 1 || k > rtk::kSweepMaxK) return fail(ctx, "rt_sweep_spheres_ranged: need 1 <= k <= 32");
-  if (!radius_dev || !t_min_dev || !t_max_dev) return fail(ctx, "rt_sweep_spheres_ranged: null radius, t_min or t_max pointer");
-  p.ray_tlo_dev = t_min_dev;
-  p.ray_thi_dev = t_max_dev;
-  return sweep_launch(ctx, ps, n, p, radius_dev, 0.0f, exclude_dev, k, count_dev, index_dev, start_dev, hit7_dev);
-}
-
-// The proximity entries: checks, then the lane kernel under every variant (count_dev NULL: its pruned walk).  max_dist_dev != nullptr: the
-// per-point form, whose bounds are device data -- an invalid one makes its point a miss in the kernel (lane_core.h: max_dist_ok).
-static int nearest_entry(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist, const float *max_dist_dev,
-                         bool ranged, int32_t k, int32_t *count_dev, int32_t *index_dev, float *gap_dev) {
-  const char *const what = ranged ? "rt_nearest_spheres_ranged" : "rt_nearest_spheres";
-  if (!ps) return fail(ctx, "null prepared scene");
-  if (ctx->group) return fail(ctx, std::string(what) + ": a multi-device context is not supported (use a context on one device)");
-  if (n < 0 || n >= (int64_t(1) << 31)) return fail(ctx, std::string(what) + ": point count out of range: 0 <= n < 2^31");
-  if (!points3_dev) return fail(ctx, std::string(what) + ": null points pointer");
-  if (!count_dev && !index_dev && !gap_dev) return fail(ctx, std::string(what) + ": all three outputs are NULL");
-  if (k < 1 || k > rtk::kNearestMaxK) return fail(ctx, std::string(what) + ": need 1 <= k <= 32");
-  if (ranged && !max_dist_dev) return fail(ctx, std::string(what) + ": null max_dist pointer");
-  if (!ranged && !(std::isfinite(max_dist) && max_dist >= 0.0f && max_dist <= rtk::kTMax))
-    return fail(ctx, std::string(what) + ": need 0 <= max_dist <= 1e9, finite");
-  RT_LOCK_PS(ps);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  ctx->synced_since_render = false;
-  if (n == 0) {
-    ctx->last_launch = "family=none (no points)";
-    return 0;
-  }
-  rtk::KParams p{};
-  scene_params(ps, &p);
-  p.nrays = static_cast<int>(n);
-  // the boxes that contain their subtrees: those of the nodes whose subtree is at most `sweeps` levels tall (the AABB propagation's
-  // floor(log2 n) + 2 Jacobi sweeps from zero boxes, bvh.fut:44-58), which every node at depth >= height - sweeps is
-  const int sweeps = static_cast<int>(log2f(static_cast<float>(ps->n))) + 2;
-  const int exact_depth = std::max(0, ps->height - sweeps);
-  RT_HIP(ctx, rtk::launch_nearest_spheres(p, points3_dev, ranged ? max_dist_dev : nullptr, max_dist, k, exact_depth, count_dev, index_dev, gap_dev,
-                                          ctx->stream));
-  ctx->last_launch = "family=nearest k=" + std::to_string(k) + (count_dev ? "" : " pruned") + (ranged ? " (per-point)" : "");
-  return 0;
-}
-
-extern "C" int rt_nearest_spheres(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist, int32_t k,
-                                  int32_t *count_dev, int32_t *index_dev, float *gap_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  return nearest_entry(ctx, ps, n, points3_dev, max_dist, nullptr, false, k, count_dev, index_dev, gap_dev);
-}
-
-extern "C" int rt_nearest_spheres_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, const float *max_dist_dev,
-                                         int32_t k, int32_t *count_dev, int32_t *index_dev, float *gap_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  return nearest_entry(ctx, ps, n, points3_dev, 0.0f, max_dist_dev, true, k, count_dev, index_dev, gap_dev);
-}
-
-// The range entries (rt_spheres_within_*, rt_contact_pairs_*): checks, then within_lane under every variant.  self: the contact pairs (the
-// points are the scene's own centres, `max_dist` is the margin).  The count pass keeps its int32 counts and the scan's block sums in a buffer
-// cached on the context, grown when a call needs more (the steady path allocates nothing).
-static int within_scratch(rt_context *ctx, int64_t n, char **out) {
-  const size_t want = rtk::within_scratch_bytes(n);
-  if (want > ctx->within_bytes) {
-    if (ctx->within_scratch) {
-      RT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (an earlier count pass may still be reading it)
-      RT_HIP(ctx, hipFree(ctx->within_scratch));
-      ctx->within_scratch = nullptr;
-      ctx->within_bytes = 0;
-    }
-    const size_t bytes = std::max(want + want / 2, size_t(1) << 20);
-    RT_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->within_scratch), bytes));
-    ctx->within_bytes = bytes;
-  }
-  *out = ctx->within_scratch;
-  return 0;
-}
-static int within_entry(rt_context *ctx, const rt_prepared *ps, const char *what, bool fill, bool self, int64_t n, const float *points3_dev,
-                        float max_dist, const float *max_dist_dev, const int32_t *first_dev, int64_t *offsets_dev, int64_t capacity,
-                        int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
-  if (!ps) return fail(ctx, "null prepared scene");
-  if (ctx->group) return fail(ctx, std::string(what) + ": a multi-device context is not supported (use a context on one device)");
-  if (self) n = ps->n;
-  if (n < 0 || n >= (int64_t(1) << 31)) return fail(ctx, std::string(what) + ": point count out of range: 0 <= n < 2^31");
-  if (!self && !points3_dev) return fail(ctx, std::string(what) + ": null points pointer");
-  if (!offsets_dev) return fail(ctx, std::string(what) + ": null offsets pointer");
-  if (fill && capacity < 0) return fail(ctx, std::string(what) + ": negative capacity");
-  if (fill && !index_dev && !gap_dev && !point_dev) return fail(ctx, std::string(what) + ": every output is NULL");
-  if ((self || !max_dist_dev) && !(std::isfinite(max_dist) && max_dist >= 0.0f && max_dist <= rtk::kTMax))
-    return fail(ctx, std::string(what) + (self ? ": need 0 <= margin <= 1e9, finite" : ": need 0 <= max_dist <= 1e9, finite"));
-  RT_LOCK_PS(ps);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  rtk::KParams p{};
-  scene_params(ps, &p);
-  p.nrays = static_cast<int>(n);
-  // (the boxes that contain their subtrees: nearest_entry)
-  const int sweeps = static_cast<int>(log2f(static_cast<float>(ps->n))) + 2;
-  const int exact_depth = std::max(0, ps->height - sweeps);
-  if (fill) {
-    ctx->synced_since_render = false;
-    RT_HIP(ctx, rtk::launch_within_fill(p, points3_dev, max_dist_dev, max_dist, first_dev, self, exact_depth, offsets_dev, capacity, index_dev,
-                                        gap_dev, point_dev, ctx->stream));
-  } else {
-    char *scratch = nullptr;
-    if (n > 0 && within_scratch(ctx, n, &scratch) != 0) return 1;
-    ctx->synced_since_render = false;
-    RT_HIP(ctx, rtk::launch_within_count(p, points3_dev, max_dist_dev, max_dist, first_dev, self, exact_depth, scratch, offsets_dev, ctx->stream));
-  }
-  ctx->last_launch = std::string(fill ? "family=within fill" : "family=within count") + (!self && max_dist_dev ? " (per-point)" : "") +
-                     (!self && first_dev ? " first" : "") + (self ? " self" : "");
-  return 0;
-}
-
-extern "C" int rt_spheres_within_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
-                                       const float *max_dist_dev, const int32_t *first_dev, int64_t *offsets_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  return within_entry(ctx, ps, "rt_spheres_within_count", false, false, n, points3_dev, max_dist, max_dist_dev, first_dev, offsets_dev, 0, nullptr,
-                      nullptr, nullptr);
-}
-
-extern "C" int rt_spheres_within_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
-                                      const float *max_dist_dev, const int32_t *first_dev, const int64_t *offsets_dev, int64_t capacity,
-                                      int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  return within_entry(ctx, ps, "rt_spheres_within_fill", true, false, n, points3_dev, max_dist, max_dist_dev, first_dev,
-                      const_cast<int64_t *>(offsets_dev), capacity, index_dev, gap_dev, point_dev);
-}
-
-extern "C" int rt_contact_pairs_count(rt_context *ctx, const rt_prepared *ps, float margin, int64_t *offsets_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  return within_entry(ctx, ps, "rt_contact_pairs_count", false, true, 0, nullptr, margin, nullptr, nullptr, offsets_dev, 0, nullptr, nullptr, nullptr);
-}
-
-extern "C" int rt_contact_pairs_fill(rt_context *ctx, const rt_prepared *ps, float margin, const int64_t *offsets_dev, int64_t capacity,
-                                     int32_t *pair_dev, float *gap_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  return within_entry(ctx, ps, "rt_contact_pairs_fill", true, true, 0, nullptr, margin, nullptr, nullptr, const_cast<int64_t *>(offsets_dev), capacity,
-                      nullptr, gap_dev, pair_dev);
-}
-
-extern "C" int rt_prepared_get_sphere_ids(rt_context *ctx, const rt_prepared *ps, int32_t *ids_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  if (!ps || !ids_dev) return fail(ctx, "null argument");
-  RT_LOCK_PS(ps);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  ctx->synced_since_render = false;
-  RT_HIP(ctx, hipMemcpyAsync(ids_dev, ps->ids, static_cast<size_t>(ps->n) * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
-  return 0;
-}
-
-extern "C" int rt_camera_rays(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, const float cam12[12], float *rays_dev) {
-  if (!ctx) return 1;
-  RT_LOCK(ctx);
-  if (!ps) return fail(ctx, "null prepared scene");
-  if (ctx->group) return fail(ctx, "caller rays: a multi-device context is not supported (use a context on one device)");
-  if (!rays_dev) return fail(ctx, "null rays pointer");
-  if (h <= 0 || w <= 0 || h > (1 << 20) || w > (1 << 20) || h * w > (int64_t(1) << 30)) return fail(ctx, "image size out of range");
-  rtk::Cam cam;
-  std::memcpy(&cam, cam12 ? static_cast<const void *>(cam12) : static_cast<const void *>(&ps->cam), sizeof(cam));
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  ctx->synced_since_render = false;
-  RT_HIP(ctx, rtk::launch_camera_rays(cam, static_cast<int>(h), static_cast<int>(w), rays_dev, ctx->stream));
-  ctx->last_launch = "family=camera-rays";
-  return 0;
-}
-
-// ====================================================================================
-// The Futhark-shaped boundary (include/ray.h) -- thin wrappers over the rt_* surface.
-// ====================================================================================
-struct futhark_context_config {
-  int device = -1;
-  std::vector<int> devices;   // more than one entry: a multi-device context (set_device("0-7") / "0,2,4"; env RT_DEVICES)
-  int debugging = 0, logging = 0, profiling = 0;
-};
-struct futhark_context {
-  std::recursive_mutex mu;   // Futhark's context lock: every futhark_* entry holds it (the image pool, the pending error, the counters)
-  rt_context *rt = nullptr;
-  // freed images are kept for reuse: main.c frees and re-renders every run, and a
-  // hipFree/hipMalloc pair per frame costs more than the frame itself
-  struct PooledImage { int64_t elems; int32_t *dev; size_t block_bytes; };
-  std::vector<PooledImage> image_pool;
-  std::string pending;   // error not yet collected by futhark_context_get_error
-  int logging = 0;
-  uint64_t renders = 0, prepares = 0;
-};
-struct futhark_opaque_scene {
-  rt_scene *s = nullptr;
-};
-struct futhark_opaque_prepared_scene {
-  rt_prepared *p = nullptr;
-};
-struct futhark_i32_2d {
-  int32_t *dev = nullptr;
-  int64_t shape[2] = {0, 0};
-  size_t block_bytes = 0;   // != 0: a block of the context's arena / block pool (image_alloc); 0: rt_device_alloc's
-};
-namespace {
-// An entry point's result array from the context's arena (pool_alloc): a hipMalloc of 4 MB inside the harness's first render call was ~0.1 ms
-// of its first frame.  Freed (image_release) behind a drained stream, like rt_device_free.
-int image_alloc(rt_context *ctx, void **dev, size_t *block_bytes, int64_t bytes) {
-  RT_LOCK(ctx);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  char *blk = nullptr;
-  *block_bytes = static_cast<size_t>(std::max<int64_t>(bytes, 16));
-  RT_HIP(ctx, pool_alloc(ctx, &blk, block_bytes));
-  *dev = blk;
-  return 0;
-}
-int image_release(rt_context *ctx, void *dev, size_t block_bytes) {
-  if (!block_bytes) return rt_device_free(ctx, dev);
-  RT_LOCK(ctx);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  pool_free(ctx, static_cast<char *>(dev), block_bytes);
-  return 0;
-}
-}  // namespace
-
-#ifndef RT_NO_CONTEXT_LOCK
-#define FUT_LOCK(ctx) std::unique_lock<std::recursive_mutex> fut_lock_ = (ctx) ? std::unique_lock<std::recursive_mutex>((ctx)->mu) : std::unique_lock<std::recursive_mutex>()
-#else
-#define FUT_LOCK(ctx) (void)(ctx)
-#endif
-
-namespace {
-int fut_fail(futhark_context *ctx, int rc) {
-  if (rc && ctx) ctx->pending = rt_last_error(ctx->rt);
-  return rc;
-}
-}  // namespace
-
-extern "C" struct futhark_context_config *futhark_context_config_new(void) { return new futhark_context_config(); }
-extern "C" void futhark_context_config_free(struct futhark_context_config *cfg) { delete cfg; }
-extern "C" void futhark_context_config_set_debugging(struct futhark_context_config *cfg, int flag) { if (cfg) cfg->debugging = flag; }
-extern "C" void futhark_context_config_set_logging(struct futhark_context_config *cfg, int flag) { if (cfg) cfg->logging = flag; }
-extern "C" void futhark_context_config_set_profiling(struct futhark_context_config *cfg, int flag) { if (cfg) cfg->profiling = flag; }
-// "k" / "#k": HIP device k (the Futhark convention); "a-b" or "a,b,c": several devices = one multi-device
-// context (the frame is partitioned over them, include/rt_mi355x.h: rt_context_create_multi)
-static std::vector<int> parse_device_list(const char *s) {
-  std::vector<int> out;
-  while (*s) {
-    while (*s == ' ' || *s == ',' || *s == '#') ++s;
-    if (!*s) break;
-    char *end = nullptr;
-    const long a = std::strtol(s, &end, 10);
-    if (end == s || a < 0) return {};
-    s = end;
-    long b = a;
-    if (*s == '-') {
-      b = std::strtol(s + 1, &end, 10);
-      if (end == s + 1 || b < a) return {};
-      s = end;
-    }
-    for (long d = a; d <= b && out.size() < 64; ++d) out.push_back(static_cast<int>(d));
-  }
-  return out;
-}
-extern "C" void futhark_context_config_set_device(struct futhark_context_config *cfg, const char *s) {
-  if (!cfg || !s) return;
-  cfg->devices = parse_device_list(s);
-  cfg->device = cfg->devices.empty() ? std::atoi(*s == '#' ? s + 1 : s) : cfg->devices[0];
-}
-
-extern "C" void futhark_context_config_set_num_threads(struct futhark_context_config *, int) {}
-extern "C" void futhark_context_config_set_cache_file(struct futhark_context_config *, const char *) {}
-
-extern "C" struct futhark_context *futhark_context_new(struct futhark_context_config *cfg) {
-  auto ctx = std::make_unique<futhark_context>();
-  ctx->logging = cfg ? (cfg->logging | cfg->debugging) : 0;
-  // RT_DEVICES lets a harness that never calls set_device (futhark/main.c does not) use several GPUs
-  // (an explicit futhark_context_config_set_device wins over the environment)
-  std::vector<int> devs = cfg ? cfg->devices : std::vector<int>();
-  if (const char *env = std::getenv("RT_DEVICES"); env && devs.empty() && !(cfg && cfg->device >= 0)) devs = parse_device_list(env);
-  const int rc = devs.size() > 1 ? rt_context_create_multi(&ctx->rt, devs.data(), static_cast<int>(devs.size()))
-                                 : rt_context_create(&ctx->rt, !devs.empty() ? devs[0] : (cfg ? cfg->device : -1), nullptr, 0);
-  if (rc) {
-    // Futhark returns a context whose error is set; main.c asserts it is NULL.
-    ctx->pending = "libray_mi355x: cannot create a HIP context (code " + std::to_string(rc) + "); no CPU path exists";
-  }
-  return ctx.release();
-}
-extern "C" void futhark_context_free(struct futhark_context *ctx) {
-  if (!ctx) return;
-  for (auto &e : ctx->image_pool) (void)image_release(ctx->rt, e.dev, e.block_bytes);
-  rt_context_destroy(ctx->rt);
-  delete ctx;
-}
-extern "C" char *futhark_context_get_error(struct futhark_context *ctx) {
-  FUT_LOCK(ctx);
-  if (!ctx || ctx->pending.empty()) return nullptr;
-  char *s = static_cast<char *>(std::malloc(ctx->pending.size() + 1));
-  if (s) std::memcpy(s, ctx->pending.c_str(), ctx->pending.size() + 1);
-  ctx->pending.clear();
-  return s;
-}
-extern "C" int futhark_context_sync(struct futhark_context *ctx) {
-  FUT_LOCK(ctx);
-  if (!ctx || !ctx->rt) return 1;
-  return fut_fail(ctx, rt_context_sync(ctx->rt));
-}
-extern "C" char *futhark_context_report(struct futhark_context *ctx) {
-  FUT_LOCK(ctx);
-  char buf[512];
-  int dev = -1, cus = 0, lds = 0;
-  char name[64] = "";
-  if (ctx && ctx->rt) rt_context_device_info(ctx->rt, &dev, &cus, &lds, name, sizeof name);
-  std::snprintf(buf, sizeof buf, "libray_mi355x: device %d (%s), %d CUs, %d B LDS/CU; %d device(s), framebuffer gather: %s; %llu prepare_scene, %llu render calls\n",
-                dev, name, cus, lds, ctx && ctx->rt ? rt_context_num_devices(ctx->rt) : 0,
-                ctx && ctx->rt ? rt_context_gather_mode(ctx->rt) : "none", ctx ? (unsigned long long)ctx->prepares : 0ull,
-                ctx ? (unsigned long long)ctx->renders : 0ull);
-  char *s = static_cast<char *>(std::malloc(std::strlen(buf) + 1));
-  if (s) std::strcpy(s, buf);
-  return s;
-}
-
-extern "C" int futhark_entry_rgbbox(struct futhark_context *ctx, struct futhark_opaque_scene **out0) {
-  FUT_LOCK(ctx);
-  if (!ctx || !ctx->rt || !out0) return 1;
-  auto o = std::make_unique<futhark_opaque_scene>();
-  if (int rc = rt_scene_rgbbox(ctx->rt, &o->s)) return fut_fail(ctx, rc);
-  *out0 = o.release();
-  return 0;
-}
-extern "C" int futhark_entry_irreg(struct futhark_context *ctx, struct futhark_opaque_scene **out0) {
-  FUT_LOCK(ctx);
-  if (!ctx || !ctx->rt || !out0) return 1;
-  auto o = std::make_unique<futhark_opaque_scene>();
-  if (int rc = rt_scene_irreg(ctx->rt, &o->s)) return fut_fail(ctx, rc);
-  *out0 = o.release();
-  return 0;
-}
-extern "C" int futhark_entry_prepare_scene(struct futhark_context *ctx, struct futhark_opaque_prepared_scene **out0,
-                                           const int64_t in0, const int64_t in1, const struct futhark_opaque_scene *in2) {
-  FUT_LOCK(ctx);
-  if (!ctx || !ctx->rt || !out0 || !in2) return 1;
-  auto o = std::make_unique<futhark_opaque_prepared_scene>();
-  if (int rc = rt_prepare_scene(ctx->rt, &o->p, in0, in1, in2->s)) return fut_fail(ctx, rc);
-  ctx->prepares++;
-  *out0 = o.release();
-  return 0;
-}
-extern "C" int futhark_entry_render(struct futhark_context *ctx, struct futhark_i32_2d **out0, const int64_t in0,
-                                    const int64_t in1, const struct futhark_opaque_prepared_scene *in2) {
-  FUT_LOCK(ctx);
-  if (!ctx || !ctx->rt || !out0 || !in2) return 1;
-  auto img = std::make_unique<futhark_i32_2d>();
-  void *dev = nullptr;
-  for (size_t i = 0; i < ctx->image_pool.size(); ++i)
-    if (ctx->image_pool[i].elems == in0 * in1) {
-      dev = ctx->image_pool[i].dev;   // same stream => the new frame orders after any pending use
-      img->block_bytes = ctx->image_pool[i].block_bytes;
-      ctx->image_pool.erase(ctx->image_pool.begin() + static_cast<long>(i));
-      break;
-    }
-  if (!dev)
-    if (int rc = image_alloc(ctx->rt, &dev, &img->block_bytes, static_cast<int64_t>(sizeof(int32_t)) * in0 * in1)) return fut_fail(ctx, rc);
-  img->dev = static_cast<int32_t *>(dev);
-  img->shape[0] = in0;
-  img->shape[1] = in1;
-  if (int rc = rt_render(ctx->rt, in2->p, in0, in1, img->dev)) {
-    (void)image_release(ctx->rt, dev, img->block_bytes);
-    return fut_fail(ctx, rc);
-  }
-  ctx->renders++;
-  *out0 = img.release();
-  return 0;
-}
-extern "C" int futhark_values_i32_2d(struct futhark_context *ctx, struct futhark_i32_2d *arr, int32_t *data) {
-  FUT_LOCK(ctx);
-  if (!ctx || !ctx->rt || !arr || !data) return 1;
-  return fut_fail(ctx, rt_copy_to_host(ctx->rt, data, arr->dev, static_cast<int64_t>(sizeof(int32_t)) * arr->shape[0] * arr->shape[1]));
-}
-extern "C" int futhark_free_i32_2d(struct futhark_context *ctx, struct futhark_i32_2d *arr) {
-  FUT_LOCK(ctx);
-  if (!arr) return 0;
-  int rc = 0;
-  if (ctx && ctx->rt && arr->dev) {
-    if (ctx->image_pool.size() < 4) ctx->image_pool.push_back({arr->shape[0] * arr->shape[1], arr->dev, arr->block_bytes});
-    else rc = image_release(ctx->rt, arr->dev, arr->block_bytes);
-  }
-  delete arr;
-  return fut_fail(ctx, rc);
-}
-extern "C" struct futhark_i32_2d *futhark_new_i32_2d(struct futhark_context *ctx, const int32_t *data, int64_t dim0, int64_t dim1) {
-  FUT_LOCK(ctx);
-  if (!ctx || !ctx->rt || !data || dim0 < 0 || dim1 < 0) return nullptr;
-  auto arr = std::make_unique<futhark_i32_2d>();
-  arr->shape[0] = dim0; arr->shape[1] = dim1;
-  const int64_t bytes = static_cast<int64_t>(sizeof(int32_t)) * dim0 * dim1;
-  if (rt_device_alloc(ctx->rt, reinterpret_cast<void **>(&arr->dev), std::max<int64_t>(bytes, 4)) != 0) { fut_fail(ctx, 1); return nullptr; }
-  if (bytes > 0 && hipMemcpy(arr->dev, data, static_cast<size_t>(bytes), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)rt_device_free(ctx->rt, arr->dev);
-    ctx->pending = "futhark_new_i32_2d: host to device copy failed";
-    return nullptr;
-  }
-  return arr.release();
-}
-extern "C" int32_t *futhark_values_raw_i32_2d(struct futhark_context *, struct futhark_i32_2d *arr) { return arr ? arr->dev : nullptr; }
-extern "C" int futhark_context_clear_caches(struct futhark_context *ctx) {
-  FUT_LOCK(ctx);
-  if (!ctx || !ctx->rt) return 1;
-  if (rt_context_sync(ctx->rt)) return fut_fail(ctx, 1);
-  for (auto &im : ctx->image_pool) (void)image_release(ctx->rt, im.dev, im.block_bytes);
-  ctx->image_pool.clear();
-  for (auto &b : ctx->rt->pool) (void)hipFree(b.p);
-  ctx->rt->pool.clear();
-  return 0;
-}
-extern "C" void futhark_context_pause_profiling(struct futhark_context *) {}
-extern "C" void futhark_context_unpause_profiling(struct futhark_context *) {}
-
-extern "C" const int64_t *futhark_shape_i32_2d(struct futhark_context *, struct futhark_i32_2d *arr) {
-  return arr ? arr->shape : nullptr;
-}
-extern "C" int futhark_free_opaque_prepared_scene(struct futhark_context *ctx, struct futhark_opaque_prepared_scene *obj) {
-  FUT_LOCK(ctx);
-  if (!obj) return 0;
-  if (ctx && ctx->rt) rt_prepared_free(ctx->rt, obj->p);
-  delete obj;
-  return 0;
-}
-extern "C" int futhark_free_opaque_scene(struct futhark_context *ctx, struct futhark_opaque_scene *obj) {
-  FUT_LOCK(ctx);
-  if (!obj) return 0;
-  rt_scene_free(ctx ? ctx->rt : nullptr, obj->s);
-  delete obj;
   return 0;
 }

@@ -1,0 +1,431 @@
+// api_queries.cpp -- the caller queries of the rt_* surface (include/rt_mi355x.h): rays traced, intersected, tested for occlusion, multi-hit,
+// sphere casts, the proximity and range queries, contact pairs, a frame's primary rays.  Checks and launches only: the lane kernels are
+// query_kernels.hip, and where an entry runs the pooled family (rt_trace_rays, rt_occluded_rays[_ranged]) its plan, parameters and launch
+// are the render policy's (api.cpp, through rt_internal.hpp).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "../../include/rt_mi355x.h"
+#include "query_device.hpp"
+#include "rt_internal.hpp"
+
+using rti::fail;
+using rti::Plan;
+
+// ------------------------------------------------------------------------------------ caller rays
+namespace {
+// The checks every caller-ray entry shares; on success p holds the prepared scene's traversal copy and the ray count.
+int ray_entry_params(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, rtk::KParams *p) {
+  if (!ps) return fail(ctx, "null prepared scene");
+  if (ctx->group) return fail(ctx, "caller rays: a multi-device context is not supported (use a context on one device)");
+  if (n < 0 || n >= (int64_t(1) << 31)) return fail(ctx, "ray count out of range: 0 <= n < 2^31");
+  if (!rays_dev) return fail(ctx, "null rays pointer");
+  *p = rtk::KParams{};
+  rti::scene_params(ps, p);
+  p->rays = rays_dev;
+  p->nrays = static_cast<int>(n);
+  return 0;
+}
+
+// The interval rule of the entries that take one (aabb_hit's NaN argument in lane_core.h -- the last slab test decides -- needs a
+// finite interval; its one-test form needs a finite start).
+bool ray_interval_ok(float t_min, float t_max) {
+  return std::isfinite(t_min) && std::isfinite(t_max) && t_min >= 0.0f && t_min <= t_max && t_max <= rtk::kTMax;
+}
+// ... and the rule of a scalar distance (a cast's radius, a proximity bound, a margin)
+bool distance_ok(float d) { return std::isfinite(d) && d >= 0.0f && d <= rtk::kTMax; }
+
+// What a query entry does between its argument checks and its launch: the prepared scene's lock, the context's device, the thread's last
+// error cleared (the launchers read it right behind their launches), and n == 0 answered with `empty` in rt_context_last_launch.
+// launch() enqueues, names the launch and returns the entry's code.  The caller holds the context lock.
+const char *const kNoRays = "family=none (no rays)", *const kNoPoints = "family=none (no points)";
+template <class Launch>
+int locked_launch(rt_context *ctx, const rt_prepared *ps, int64_t n, const char *empty, Launch &&launch) {
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  if (n == 0) {
+    ctx->last_launch = empty;
+    return 0;
+  }
+  return launch();
+}
+}  // namespace
+
+extern "C" int rt_trace_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, int32_t max_depth,
+                             float *colour3_dev, int32_t *pixel_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!colour3_dev && !pixel_dev) return fail(ctx, "rt_trace_rays: both outputs are NULL");
+  if (max_depth < 0) return fail(ctx, "negative max_depth");
+  return locked_launch(ctx, ps, n, kNoRays, [&] {
+    if (max_depth == 0) {
+      // `while depth < 0`: every ray's colour is the initial (0,0,0)
+      if (colour3_dev) RT_HIP(ctx, hipMemsetAsync(colour3_dev, 0, sizeof(float) * 3 * static_cast<size_t>(n), ctx->stream));
+      if (pixel_dev) RT_HIP(ctx, hipMemsetAsync(pixel_dev, 0, sizeof(int32_t) * static_cast<size_t>(n), ctx->stream));
+      ctx->last_launch = "family=none (memset)";
+      return 0;
+    }
+    p.max_depth = max_depth;
+    p.out = pixel_dev;
+    p.colour3 = colour3_dev;
+    p.nframes = 1;
+    // the pooled family's plan; the pixel family beyond its limits (AUTO), or under RT_VARIANT_PIXEL / RT_VARIANT_PERSISTENT
+    Plan pl;
+    if (int rc = rti::pooled_rays_plan(ctx, ps, n, &pl)) return rc;
+    if (pl.variant != RT_VARIANT_POOLED) {
+      RT_HIP(ctx, rtk::launch_pixel_rays(p, ctx->stream));
+      ctx->last_launch = "family=pixel (rays)";
+      return 0;
+    }
+    if (int rc = rti::pooled_rays_params(ctx, ps, pl, &p)) return rc;
+    return rti::launch_pooled_rays(ctx, p, pl, rtk::kRaysColour);
+  });
+}
+
+// The closest-hit entries past their checks: the lane kernel under every variant, with the scalar interval or (p.ray_tlo_dev set) each
+// ray's own.  The caller holds the context lock.
+static int intersect_launch(rt_context *ctx, const rt_prepared *ps, int64_t n, const rtk::KParams &p, float t_min, float t_max,
+                            int32_t *index_dev, float *hit7_dev) {
+  return locked_launch(ctx, ps, n, kNoRays, [&] {
+    const bool ranged = p.ray_tlo_dev != nullptr;
+    RT_HIP(ctx, ranged ? rtk::launch_intersect_rays_ranged(p, index_dev, hit7_dev, ctx->stream)
+                       : rtk::launch_intersect_rays(p, t_min, t_max, index_dev, hit7_dev, ctx->stream));
+    ctx->last_launch = ranged ? "family=intersect (per-ray)" : "family=intersect";
+    return 0;
+  });
+}
+
+extern "C" int rt_intersect_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
+                                 int32_t *index_dev, float *hit7_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!index_dev) return fail(ctx, "rt_intersect_rays: null index pointer");
+  if (!ray_interval_ok(t_min, t_max)) return fail(ctx, "rt_intersect_rays: need 0 <= t_min <= t_max <= 1e9, both finite");
+  return intersect_launch(ctx, ps, n, p, t_min, t_max, index_dev, hit7_dev);
+}
+
+// The per-ray form: the intervals are device data, so they are not checked here -- the kernel answers a ray whose interval fails the rule
+// above (NaN included) as a miss (lane_core.h: interval_ok).
+extern "C" int rt_intersect_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *t_min_dev,
+                                        const float *t_max_dev, int32_t *index_dev, float *hit7_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!index_dev) return fail(ctx, "rt_intersect_rays_ranged: null index pointer");
+  if (!t_min_dev || !t_max_dev) return fail(ctx, "rt_intersect_rays_ranged: null t_min or t_max pointer");
+  p.ray_tlo_dev = t_min_dev;
+  p.ray_thi_dev = t_max_dev;
+  return intersect_launch(ctx, ps, n, p, 0.0f, 0.0f, index_dev, hit7_dev);
+}
+
+// The occlusion entries past their checks (p.occluded and the interval -- scalar, or per-ray with p.ray_tlo_dev -- are set): the pooled family's
+// any-hit loop under RT_VARIANT_POOLED; the lane kernel under RT_VARIANT_PIXEL / RT_VARIANT_PERSISTENT, and beyond the pooled family's limits.
+// AUTO, scalar interval: the pooled loop only where it was measured faster: the whole scene staged in LDS, and rays rather
+// than segments (t_max > 1; a shadow ray's (eps, 1) is a segment) -- elsewhere the lane kernel.
+// AUTO, per-ray intervals: the host cannot see the rays' t_max, so the scalar rule's t_max > 1 clause cannot be asked.  Measured (DESIGN.md
+// 3.5c), the pooled loop won only long random rays on a scene staged in LDS (1.3x) and lost normalised shadow rays on the same scene (1.8x):
+// AUTO takes the lane kernel.
+static int occluded_launch(rt_context *ctx, const rt_prepared *ps, int64_t n, rtk::KParams &p) {
+  return locked_launch(ctx, ps, n, kNoRays, [&] {
+    const bool ranged = p.ray_tlo_dev != nullptr;
+    Plan pl;
+    if (int rc = rti::pooled_rays_plan(ctx, ps, n, &pl)) return rc;
+    if (ctx->variant == RT_VARIANT_AUTO &&
+        (ranged || (pl.variant == RT_VARIANT_POOLED &&
+                    !(pl.lds_nodes == static_cast<int>(ps->n - 1) && pl.lds_sph == static_cast<int>(ps->n) && p.ray_thi > 1.0f))))
+      pl.variant = RT_VARIANT_PIXEL;
+    if (pl.variant != RT_VARIANT_POOLED) {
+      RT_HIP(ctx, ranged ? rtk::launch_occluded_rays_ranged(p, ctx->stream) : rtk::launch_occluded_rays(p, ctx->stream));
+      ctx->last_launch = ranged ? "family=occluded (per-ray)" : "family=occluded";
+      return 0;
+    }
+    if (int rc = rti::pooled_rays_params(ctx, ps, pl, &p)) return rc;
+    return rti::launch_pooled_rays(ctx, p, pl, rtk::kRaysAny);
+  });
+}
+
+extern "C" int rt_occluded_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
+                                uint8_t *occluded_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!occluded_dev) return fail(ctx, "rt_occluded_rays: null output pointer");
+  if (!ray_interval_ok(t_min, t_max)) return fail(ctx, "rt_occluded_rays: need 0 <= t_min <= t_max <= 1e9, both finite");
+  p.occluded = occluded_dev;
+  p.ray_tlo = t_min;
+  p.ray_thi = t_max;
+  return occluded_launch(ctx, ps, n, p);
+}
+
+extern "C" int rt_occluded_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *t_min_dev,
+                                       const float *t_max_dev, uint8_t *occluded_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!occluded_dev) return fail(ctx, "rt_occluded_rays_ranged: null output pointer");
+  if (!t_min_dev || !t_max_dev) return fail(ctx, "rt_occluded_rays_ranged: null t_min or t_max pointer");
+  p.occluded = occluded_dev;
+  p.ray_tlo_dev = t_min_dev;
+  p.ray_thi_dev = t_max_dev;
+  return occluded_launch(ctx, ps, n, p);
+}
+
+// The multi-hit entries' checks past ray_entry_params and their launch: the lane kernel under every variant, k crossings per ray.  The caller
+// holds the context lock and has set p's interval (scalar, or per-ray).
+static int multi_hit_launch(rt_context *ctx, const rt_prepared *ps, int64_t n, rtk::KParams &p, int32_t k, int32_t *count_dev,
+                            int32_t *index_dev, uint8_t *root_dev, float *hit7_dev, bool ranged) {
+  return locked_launch(ctx, ps, n, kNoRays, [&] {
+    RT_HIP(ctx, rtk::launch_multi_hit_rays(p, k, count_dev, index_dev, root_dev, hit7_dev, ctx->stream));
+    ctx->last_launch = "family=multi-hit k=" + std::to_string(k) + (ranged ? " (per-ray)" : "");
+    return 0;
+  });
+}
+
+extern "C" int rt_multi_hit_rays(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max, int32_t k,
+                                 int32_t *count_dev, int32_t *index_dev, uint8_t *root_dev, float *hit7_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!count_dev && !index_dev && !root_dev && !hit7_dev) return fail(ctx, "rt_multi_hit_rays: all four outputs are NULL");
+  if (k < 1 || k > rtk::kMultiHitMaxK) return fail(ctx, "rt_multi_hit_rays: need 1 <= k <= 32");
+  if (!ray_interval_ok(t_min, t_max)) return fail(ctx, "rt_multi_hit_rays: need 0 <= t_min <= t_max <= 1e9, both finite");
+  p.ray_tlo = t_min;
+  p.ray_thi = t_max;
+  return multi_hit_launch(ctx, ps, n, p, k, count_dev, index_dev, root_dev, hit7_dev, false);
+}
+
+// The per-ray form: as rt_intersect_rays_ranged, a ray whose interval fails the rule is a miss in the kernel (count 0, every slot padded).
+extern "C" int rt_multi_hit_rays_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *t_min_dev,
+                                        const float *t_max_dev, int32_t k, int32_t *count_dev, int32_t *index_dev, uint8_t *root_dev,
+                                        float *hit7_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!count_dev && !index_dev && !root_dev && !hit7_dev) return fail(ctx, "rt_multi_hit_rays_ranged: all four outputs are NULL");
+  if (k < 1 || k > rtk::kMultiHitMaxK) return fail(ctx, "rt_multi_hit_rays_ranged: need 1 <= k <= 32");
+  if (!t_min_dev || !t_max_dev) return fail(ctx, "rt_multi_hit_rays_ranged: null t_min or t_max pointer");
+  p.ray_tlo_dev = t_min_dev;
+  p.ray_thi_dev = t_max_dev;
+  return multi_hit_launch(ctx, ps, n, p, k, count_dev, index_dev, root_dev, hit7_dev, true);
+}
+
+// The sweep entries' checks past ray_entry_params and their launch: the lane kernel under every variant, k contacts per query.  The caller holds
+// the context lock and has set p's interval (scalar, or per-query next to radius_dev).
+static int sweep_launch(rt_context *ctx, const rt_prepared *ps, int64_t n, rtk::KParams &p, const float *radius_dev, float radius,
+                        const int32_t *exclude_dev, int32_t k, int32_t *count_dev, int32_t *index_dev, uint8_t *start_dev, float *hit7_dev) {
+  return locked_launch(ctx, ps, n, kNoRays, [&] {
+    RT_HIP(ctx, rtk::launch_sweep_spheres(p, radius_dev, radius, exclude_dev, k, count_dev, index_dev, start_dev, hit7_dev, ctx->stream));
+    ctx->last_launch = "family=sweep k=" + std::to_string(k) + (radius_dev ? " (per-query)" : "") + (exclude_dev ? " exclude" : "");
+    return 0;
+  });
+}
+
+extern "C" int rt_sweep_spheres(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float radius, float t_min, float t_max,
+                                int32_t k, int32_t *count_dev, int32_t *index_dev, uint8_t *start_dev, float *hit7_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!count_dev && !index_dev && !start_dev && !hit7_dev) return fail(ctx, "rt_sweep_spheres: all four outputs are NULL");
+  if (k < 1 || k > rtk::kSweepMaxK) return fail(ctx, "rt_sweep_spheres: need 1 <= k <= 32");
+  if (!ray_interval_ok(t_min, t_max)) return fail(ctx, "rt_sweep_spheres: need 0 <= t_min <= t_max <= 1e9, both finite");
+  if (!distance_ok(radius)) return fail(ctx, "rt_sweep_spheres: need 0 <= radius <= 1e9, finite");
+  p.ray_tlo = t_min;
+  p.ray_thi = t_max;
+  return sweep_launch(ctx, ps, n, p, nullptr, radius, nullptr, k, count_dev, index_dev, start_dev, hit7_dev);
+}
+
+// The per-query form: a query whose interval or radius fails its rule is a miss in the kernel (count 0, every slot padded).
+extern "C" int rt_sweep_spheres_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *radius_dev,
+                                       const float *t_min_dev, const float *t_max_dev, const int32_t *exclude_dev, int32_t k,
+                                       int32_t *count_dev, int32_t *index_dev, uint8_t *start_dev, float *hit7_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!count_dev && !index_dev && !start_dev && !hit7_dev) return fail(ctx, "rt_sweep_spheres_ranged: all four outputs are NULL");
+  if (k < 1 || k > rtk::kSweepMaxK) return fail(ctx, "rt_sweep_spheres_ranged: need 1 <= k <= 32");
+  if (!radius_dev || !t_min_dev || !t_max_dev) return fail(ctx, "rt_sweep_spheres_ranged: null radius, t_min or t_max pointer");
+  p.ray_tlo_dev = t_min_dev;
+  p.ray_thi_dev = t_max_dev;
+  return sweep_launch(ctx, ps, n, p, radius_dev, 0.0f, exclude_dev, k, count_dev, index_dev, start_dev, hit7_dev);
+}
+
+// The checks the point entries share, `what` being the entry's name in their messages (self: the points are the scene's own centres, *n
+// their number), and past them the parameter block of n points with exact_depth, the depth from which the walk tests boxes: the boxes
+// that contain their subtrees are those of the nodes whose subtree is at most `sweeps` levels tall (the AABB propagation's
+// floor(log2 n) + 2 Jacobi sweeps from zero boxes, bvh.fut:44-58), which every node at depth >= height - sweeps is.
+static int fail_in(rt_context *ctx, const char *what, const char *msg) { return fail(ctx, std::string(what) + msg); }
+static int point_entry_checks(rt_context *ctx, const rt_prepared *ps, const char *what, bool self, int64_t *n, const float *points3_dev) {
+  if (!ps) return fail(ctx, "null prepared scene");
+  if (ctx->group) return fail_in(ctx, what, ": a multi-device context is not supported (use a context on one device)");
+  if (self) *n = ps->n;
+  if (*n < 0 || *n >= (int64_t(1) << 31)) return fail_in(ctx, what, ": point count out of range: 0 <= n < 2^31");
+  if (!self && !points3_dev) return fail_in(ctx, what, ": null points pointer");
+  return 0;
+}
+static rtk::KParams point_params(const rt_prepared *ps, int64_t n, int *exact_depth) {
+  rtk::KParams p{};
+  rti::scene_params(ps, &p);
+  p.nrays = static_cast<int>(n);
+  const int sweeps = static_cast<int>(log2f(static_cast<float>(ps->n))) + 2;
+  *exact_depth = std::max(0, ps->height - sweeps);
+  return p;
+}
+
+// The proximity entries: checks, then the lane kernel under every variant (count_dev NULL: its pruned walk).  max_dist_dev != nullptr: the
+// per-point form, whose bounds are device data -- an invalid one makes its point a miss in the kernel (query_core.h: max_dist_ok).
+static int nearest_entry(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist, const float *max_dist_dev,
+                         bool ranged, int32_t k, int32_t *count_dev, int32_t *index_dev, float *gap_dev) {
+  const char *const what = ranged ? "rt_nearest_spheres_ranged" : "rt_nearest_spheres";
+  if (int rc = point_entry_checks(ctx, ps, what, false, &n, points3_dev)) return rc;
+  if (!count_dev && !index_dev && !gap_dev) return fail_in(ctx, what, ": all three outputs are NULL");
+  if (k < 1 || k > rtk::kNearestMaxK) return fail_in(ctx, what, ": need 1 <= k <= 32");
+  if (ranged && !max_dist_dev) return fail_in(ctx, what, ": null max_dist pointer");
+  if (!ranged && !distance_ok(max_dist)) return fail_in(ctx, what, ": need 0 <= max_dist <= 1e9, finite");
+  return locked_launch(ctx, ps, n, kNoPoints, [&] {
+    int exact_depth;
+    const rtk::KParams p = point_params(ps, n, &exact_depth);
+    RT_HIP(ctx, rtk::launch_nearest_spheres(p, points3_dev, ranged ? max_dist_dev : nullptr, max_dist, k, exact_depth, count_dev, index_dev, gap_dev,
+                                            ctx->stream));
+    ctx->last_launch = "family=nearest k=" + std::to_string(k) + (count_dev ? "" : " pruned") + (ranged ? " (per-point)" : "");
+    return 0;
+  });
+}
+
+extern "C" int rt_nearest_spheres(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist, int32_t k,
+                                  int32_t *count_dev, int32_t *index_dev, float *gap_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return nearest_entry(ctx, ps, n, points3_dev, max_dist, nullptr, false, k, count_dev, index_dev, gap_dev);
+}
+
+extern "C" int rt_nearest_spheres_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, const float *max_dist_dev,
+                                         int32_t k, int32_t *count_dev, int32_t *index_dev, float *gap_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return nearest_entry(ctx, ps, n, points3_dev, 0.0f, max_dist_dev, true, k, count_dev, index_dev, gap_dev);
+}
+
+// The range entries (rt_spheres_within_*, rt_contact_pairs_*): checks, then within_lane under every variant.  self: the contact pairs (the
+// points are the scene's own centres, `max_dist` is the margin).  The count pass keeps its int32 counts and the scan's block sums in a buffer
+// cached on the context, grown when a call needs more (the steady path allocates nothing).
+static int within_scratch(rt_context *ctx, int64_t n, char **out) {
+  const size_t want = rtk::within_scratch_bytes(n);
+  if (want > ctx->within_bytes) {
+    if (ctx->within_scratch) {
+      RT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (an earlier count pass may still be reading it)
+      RT_HIP(ctx, hipFree(ctx->within_scratch));
+      ctx->within_scratch = nullptr;
+      ctx->within_bytes = 0;
+    }
+    const size_t bytes = std::max(want + want / 2, size_t(1) << 20);
+    RT_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->within_scratch), bytes));
+    ctx->within_bytes = bytes;
+  }
+  *out = ctx->within_scratch;
+  return 0;
+}
+static int within_entry(rt_context *ctx, const rt_prepared *ps, const char *what, bool fill, bool self, int64_t n, const float *points3_dev,
+                        float max_dist, const float *max_dist_dev, const int32_t *first_dev, int64_t *offsets_dev, int64_t capacity,
+                        int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
+  if (int rc = point_entry_checks(ctx, ps, what, self, &n, points3_dev)) return rc;
+  if (!offsets_dev) return fail_in(ctx, what, ": null offsets pointer");
+  if (fill && capacity < 0) return fail_in(ctx, what, ": negative capacity");
+  if (fill && !index_dev && !gap_dev && !point_dev) return fail_in(ctx, what, ": every output is NULL");
+  if ((self || !max_dist_dev) && !distance_ok(max_dist))
+    return fail_in(ctx, what, self ? ": need 0 <= margin <= 1e9, finite" : ": need 0 <= max_dist <= 1e9, finite");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  int exact_depth;
+  const rtk::KParams p = point_params(ps, n, &exact_depth);
+  if (fill) {
+    ctx->synced_since_render = false;
+    RT_HIP(ctx, rtk::launch_within_fill(p, points3_dev, max_dist_dev, max_dist, first_dev, self, exact_depth, offsets_dev, capacity, index_dev,
+                                        gap_dev, point_dev, ctx->stream));
+  } else {
+    char *scratch = nullptr;
+    if (n > 0 && within_scratch(ctx, n, &scratch) != 0) return 1;
+    ctx->synced_since_render = false;
+    RT_HIP(ctx, rtk::launch_within_count(p, points3_dev, max_dist_dev, max_dist, first_dev, self, exact_depth, scratch, offsets_dev, ctx->stream));
+  }
+  ctx->last_launch = std::string(fill ? "family=within fill" : "family=within count") + (!self && max_dist_dev ? " (per-point)" : "") +
+                     (!self && first_dev ? " first" : "") + (self ? " self" : "");
+  return 0;
+}
+
+extern "C" int rt_spheres_within_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
+                                       const float *max_dist_dev, const int32_t *first_dev, int64_t *offsets_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return within_entry(ctx, ps, "rt_spheres_within_count", false, false, n, points3_dev, max_dist, max_dist_dev, first_dev, offsets_dev, 0, nullptr,
+                      nullptr, nullptr);
+}
+
+extern "C" int rt_spheres_within_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
+                                      const float *max_dist_dev, const int32_t *first_dev, const int64_t *offsets_dev, int64_t capacity,
+                                      int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return within_entry(ctx, ps, "rt_spheres_within_fill", true, false, n, points3_dev, max_dist, max_dist_dev, first_dev,
+                      const_cast<int64_t *>(offsets_dev), capacity, index_dev, gap_dev, point_dev);
+}
+
+extern "C" int rt_contact_pairs_count(rt_context *ctx, const rt_prepared *ps, float margin, int64_t *offsets_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return within_entry(ctx, ps, "rt_contact_pairs_count", false, true, 0, nullptr, margin, nullptr, nullptr, offsets_dev, 0, nullptr, nullptr, nullptr);
+}
+
+extern "C" int rt_contact_pairs_fill(rt_context *ctx, const rt_prepared *ps, float margin, const int64_t *offsets_dev, int64_t capacity,
+                                     int32_t *pair_dev, float *gap_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return within_entry(ctx, ps, "rt_contact_pairs_fill", true, true, 0, nullptr, margin, nullptr, nullptr, const_cast<int64_t *>(offsets_dev), capacity,
+                      nullptr, gap_dev, pair_dev);
+}
+
+extern "C" int rt_prepared_get_sphere_ids(rt_context *ctx, const rt_prepared *ps, int32_t *ids_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  if (!ps || !ids_dev) return fail(ctx, "null argument");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  RT_HIP(ctx, hipMemcpyAsync(ids_dev, ps->ids, static_cast<size_t>(ps->n) * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+  return 0;
+}
+
+extern "C" int rt_camera_rays(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, const float cam12[12], float *rays_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  if (!ps) return fail(ctx, "null prepared scene");
+  if (ctx->group) return fail(ctx, "caller rays: a multi-device context is not supported (use a context on one device)");
+  if (!rays_dev) return fail(ctx, "null rays pointer");
+  if (h <= 0 || w <= 0 || h > (1 << 20) || w > (1 << 20) || h * w > (int64_t(1) << 30)) return fail(ctx, "image size out of range");
+  rtk::Cam cam;
+  std::memcpy(&cam, cam12 ? static_cast<const void *>(cam12) : static_cast<const void *>(&ps->cam), sizeof(cam));
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  RT_HIP(ctx, rtk::launch_camera_rays(cam, static_cast<int>(h), static_cast<int>(w), rays_dev, ctx->stream));
+  ctx->last_launch = "family=camera-rays";
+  return 0;
+}

@@ -1,0 +1,111 @@
+// query_core.h -- per-lane arithmetic of the caller queries that no render-path kernel calls: both roots of a sphere and the sphere
+// casts' contact rule, the proximity queries' gap, box bound, slack and selection key.  Shared by query_kernels.hip and the host-side
+// checks (tools/sweep_check.cpp, tools/proximity_bound_check.cpp).  Same parity contract as lane_core.h, which holds what the render
+// path shares with the queries (box_hit_interval, sphere_hit_any, interval_ok, rehit_range).
+#pragma once
+#include "lane_core.h"
+
+namespace rtk {
+
+// `sphere_hit`'s two roots (ray.fut:32-51) with sphere_hit_any's arithmetic, both kept: the crossings of rt_multi_hit_rays.  False (roots
+// not written) when the discriminant is not positive; a NaN discriminant gives two NaN roots, which lie inside no interval.
+RT_HD bool sphere_roots(const Ray &r, float spx, float spy, float spz, float srad, float *t1, float *t2) {
+  const float ocx = r.ox - spx, ocy = r.oy - spy, ocz = r.oz - spz;
+  const float b = dot3(ocx, ocy, ocz, r.dx, r.dy, r.dz);
+  const float c = dot3(ocx, ocy, ocz, ocx, ocy, ocz) - srad * srad;
+  const float disc = b * b - r.a * c;
+  if (disc <= 0.0f) return false;
+  const float sq = sqrtf(disc);
+  *t1 = (-b - sq) / r.a;
+  *t2 = (-b + sq) / r.a;
+  return true;
+}
+
+// The contact of a sphere of radius rq moving along r with scene sphere (sp, srad) over (tlo, thi) (rt_sweep_spheres): the
+// ray of its centre against the sphere (sp, R = srad + rq), sphere_roots' arithmetic with R for the radius.  kSweepEntry: root 1 lies past
+// tlo and the contact is there, accepted iff it is below thi.  kSweepStart: root 1 is at or before tlo and root 2 past it -- the two
+// spheres already overlap where the interval begins -- and the contact is at tlo itself (-0.0 reported as +0.0), provided the interval is
+// not empty.  kSweepNone otherwise: touching only at the exit (t2 == tlo) is none, and NaN roots pass no compare.  *tau is written for a
+// contact only.
+constexpr int kSweepNone = 0, kSweepEntry = 1, kSweepStart = 2;
+RT_HD int sweep_contact(const Ray &r, float spx, float spy, float spz, float srad, float rq, float tlo, float thi, float *tau) {
+  const float R = srad + rq;
+  float t1, t2;
+  if (!sphere_roots(r, spx, spy, spz, R, &t1, &t2)) return kSweepNone;
+  if (t1 > tlo) {
+    if (!(t1 < thi)) return kSweepNone;
+    *tau = t1;
+    return kSweepEntry;
+  }
+  if ((t2 > tlo) && (tlo < thi)) {
+    *tau = tlo + 0.0f;
+    return kSweepStart;
+  }
+  return kSweepNone;
+}
+
+// ---- proximity: the spheres nearest to a point (rt_nearest_spheres) ------------------------------------------------
+// The gap of point p to sphere (c, r): the signed distance to its surface, negative inside.  This exact binary32 arithmetic IS the
+// definition (with -ffp-contract=off and a correctly rounded sqrtf); it is never -0.0 (sqrtf gives +0 or more, and x - x = +0).
+RT_HD float point_gap(float px, float py, float pz, float cx, float cy, float cz, float r) {
+  const float dx = px - cx, dy = py - cy, dz = pz - cz;
+  return sqrtf(dot3(dx, dy, dz, dx, dy, dz)) - r;
+}
+// The point-to-box distance, computed in binary32: for every sphere whose binary32 box fl(c -+ r) lies inside [lo, hi] it is, up to the slack
+// below, a LOWER bound on max(gap, 0).  Those are the spheres below a node only where the node's box contains its subtree: the boxes are
+// unions of the spheres' boxes after floor(log2 n) + 2 sweeps from zero boxes, so in a taller tree the nodes nearer the root than
+// height - sweeps levels are never tested (query_kernels.hip: nearest_lane).
+RT_HD float box_gap_bound(float px, float py, float pz, float lox, float loy, float loz, float hix, float hiy, float hiz) {
+  const float ex = fmaxf(fmaxf(lox - px, px - hix), 0.0f);
+  const float ey = fmaxf(fmaxf(loy - py, py - hiy), 0.0f);
+  const float ez = fmaxf(fmaxf(loz - pz, pz - hiz), 0.0f);
+  return sqrtf(dot3(ex, ey, ez, ex, ey, ez));
+}
+// The slack of the box test.  Let u = 2^-24, g the exact gap of p to a sphere (c, r) below the node, G = point_gap (computed), B =
+// box_gap_bound (computed), P = max_k |p_k|, M = max_k max(|lo_k|, |hi_k|) of the node's box, t >= 0 the threshold.  Then
+//   (P1)  |G - g| <= 4.6 u D + u r + 2^-62,   D = |p - c| <= sqrt(3) (P + M) (1 + 3u),  r <= M (1 + 2u)
+//         (dx = (p - c)(1 + e): the sum of squares is within (1 + u)^5 of exact, sqrtf adds u, the subtraction of r adds u |G|;
+//         2^-62 covers squares that underflow, flushed or not)
+//   (P2)  the stored box misses at most u M (1 + 2u) of the exact sphere on each side (round to nearest of c -+ r, whose magnitude is
+//         at most M / (1 - u)), so the exact point-to-box distance is at most max(g, 0) + sqrt(3) u M (1 + 2u)
+//   (P3)  B <= (1 + 3.5 u) (exact point-to-box distance) + 2^-62 (the same chain as P1 on the box's per-axis excesses)
+// Hence G <= T implies, with t = max(T, 0):  B <= t + u (3.6 t + 9.8 P + 12.6 M) + 2^-61  (second-order terms folded into the decimals).
+// proximity_slack is 2^-19 = 32 u times t + P + M, plus 2^-56: at least twice every coefficient, which also absorbs the rounding of the
+// slack's own two additions and of t + slack.  A box with B > t + slack therefore holds no sphere with G <= T; t clamps T at 0 because B
+// bounds max(gap, 0), not the gap (a point inside a sphere is at distance 0 from its box).  tools/proximity_bound_check.cpp searches for
+// counterexamples with boxes from the host builder; with the slack set to 0 it finds them.  An overflowing sum (|coordinates| near 2^64
+// and beyond) gives B = +inf (the node is skipped) only where every G below it is +inf too, and a slack of +inf skips nothing.
+RT_HD float proximity_slack(float t, float pmag, float bmag) { return 0x1p-19f * ((t + pmag) + bmag) + 0x1p-56f; }
+RT_HD float box_mag(float lox, float loy, float loz, float hix, float hiy, float hiz) {
+  return fmaxf(fmaxf(fmaxf(fabsf(lox), fabsf(hix)), fmaxf(fabsf(loy), fabsf(hiy))), fmaxf(fabsf(loz), fabsf(hiz)));
+}
+// May the node with box [lo, hi] hold a sphere whose gap to p is <= T?  (pmag = max_k |p_k|; T finite.)  `slack_scale` is 1 in the
+// product; the bound check's sensitivity run passes 0.
+RT_HD bool box_may_hold(float px, float py, float pz, float pmag, float lox, float loy, float loz, float hix, float hiy, float hiz, float T,
+                        float slack_scale = 1.0f) {
+  const float t = fmaxf(T, 0.0f);
+  const float b = box_gap_bound(px, py, pz, lox, loy, loz, hix, hiy, hiz);
+  return !(b > t + slack_scale * proximity_slack(t, pmag, box_mag(lox, loy, loz, hix, hiy, hiz)));
+}
+// The selection key of sphere j at gap g: g's bits mapped to an order-preserving unsigned word (negative: all bits flipped; otherwise the
+// sign bit set) above j.  A selected gap is <= 1e9, so its high word is below 0xffffffff and the empty slot ~0 never collides with it.
+RT_HD uint64_t gap_key(float g, int j) {
+  uint32_t b;
+  __builtin_memcpy(&b, &g, 4);
+  const uint32_t hi = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return ((uint64_t)hi << 32) | (uint32_t)j;
+}
+RT_HD float gap_of_key(uint64_t key) {
+  const uint32_t hi = (uint32_t)(key >> 32);
+  const uint32_t b = (hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi;
+  float g;
+  __builtin_memcpy(&g, &b, 4);
+  return g;
+}
+// A point with a non-finite component gets no walk (count 0); so does, in rt_nearest_spheres_ranged, a bound failing 0 <= max_dist <= 1e9.
+RT_HD bool point_ok(float px, float py, float pz) {
+  return fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz)) <= 3.40282347e38f && px == px && py == py && pz == pz;
+}
+RT_HD bool max_dist_ok(float m) { return (m >= 0.0f) & (m <= kTMax); }
+
+}  // namespace rtk

@@ -1,0 +1,49 @@
+// query_device.hpp -- launcher declarations and constants of the caller queries (host <-> query_kernels.hip).  The parameter block
+// (KParams) and everything the render path launches stay in rt_device.hpp.
+#pragma once
+#include "rt_device.hpp"
+
+namespace rtk {
+
+// rt_occluded_rays's lane kernel (query_kernels.hip), each lane leaving its traversal at its first accepted sphere
+hipError_t launch_occluded_rays(const KParams &p, hipStream_t stream);
+// objs_hit bvh r t_min t_max of n rays (ray.fut:76-86): index[i] = the winning leaf or -1, hit7 (may be nullptr) = {t, p.xyz, normal.xyz}
+hipError_t launch_intersect_rays(const KParams &p, float t_min, float t_max, int32_t *index, float *hit7, hipStream_t stream);
+// ... the two lane kernels with ray i's interval from (p.ray_tlo_dev[i], p.ray_thi_dev[i]) (both non-null)
+hipError_t launch_intersect_rays_ranged(const KParams &p, int32_t *index, float *hit7, hipStream_t stream);
+hipError_t launch_occluded_rays_ranged(const KParams &p, hipStream_t stream);
+// rt_multi_hit_rays[_ranged]: the first k (1 <= k <= kMultiHitMaxK) crossings of each ray in (t, j, root) order and their count, one lane per
+// ray: count[i], index / root [i * k + s], hit7 [(i * k + s) * 7 ..] (any may be nullptr, not all).  The interval: (p.ray_tlo, p.ray_thi), or
+// ray i's own with p.ray_tlo_dev / p.ray_thi_dev (both set, or neither)
+constexpr int kMultiHitMaxK = 32;
+hipError_t launch_multi_hit_rays(const KParams &p, int k, int32_t *count, int32_t *index, uint8_t *root, float *hit7, hipStream_t stream);
+// rt_nearest_spheres[_ranged]: for p.nrays points (pts: n x 3 float32) the first k (1 <= k <= kNearestMaxK) spheres of L by (gap, j) with
+// gap <= max_dist -- or point i's own max_dist_dev[i] when max_dist_dev is set -- and their count: count[i], index / gap [i * k + s] (any may
+// be nullptr, not all).  count == nullptr: the pruned walk (the k-th gap so far narrows the threshold).  Boxes are tested at depth >=
+// exact_depth only: the nodes whose boxes provably contain their subtrees (api_queries.cpp: nearest_entry)
+constexpr int kNearestMaxK = 32;
+hipError_t launch_nearest_spheres(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, int k, int exact_depth,
+                                  int32_t *count, int32_t *index, float *gap, hipStream_t stream);
+// rt_spheres_within_* / rt_contact_pairs_*: for p.nrays points EVERY sphere of L with gap <= the point's bound and j >= first_dev[i] (nullptr: no
+// lower index bound), as n + 1 int64 offsets and rows in ascending j.  launch_within_count: the count kernel (n int32 counts at `scratch`,
+// within_scratch_bytes(n) bytes of device memory) and the three launches of the scan, offsets[0 .. n]; p.nrays == 0 writes offsets[0] = 0.
+// launch_within_fill: entry offsets[i] + rank -> index / gap / point (any may be nullptr, not all), only below offsets[i + 1] and `capacity`.
+// self: the contact pairs -- point i is the centre of L[i] (p.nrays == p.n_sph), its bound fl(radius_i + max_dist), first = i + 1, and `point` is
+// the pair array, rows {i, j} (index must be nullptr).  Boxes are tested at depth >= exact_depth only, as launch_nearest_spheres.
+size_t within_scratch_bytes(int64_t n);
+hipError_t launch_within_count(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
+                               int exact_depth, char *scratch, int64_t *offsets, hipStream_t stream);
+hipError_t launch_within_fill(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
+                              int exact_depth, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point,
+                              hipStream_t stream);
+// rt_sweep_spheres[_ranged]: the first k (1 <= k <= kSweepMaxK) contacts of a sphere moving along each ray, in (tau, j) order, and their count,
+// one lane per query: count[i], index / start [i * k + s], hit7 [(i * k + s) * 7 ..] (any may be nullptr, not all).  radius_dev == nullptr:
+// the radius `radius` (0 <= radius <= 1e9) and the interval (p.ray_tlo, p.ray_thi) for every query; otherwise query i's own radius_dev[i]
+// and (p.ray_tlo_dev[i], p.ray_thi_dev[i]) (all three set, or none).  exclude: nullptr, or n sphere indices skipped at the leaf
+constexpr int kSweepMaxK = 32;
+hipError_t launch_sweep_spheres(const KParams &p, const float *radius_dev, float radius, const int32_t *exclude, int k, int32_t *count,
+                                int32_t *index, uint8_t *start, float *hit7, hipStream_t stream);
+// the primary rays of an h x w frame through p.cam (get_ray at pixel_u / pixel_v), row-major from the top row: rays[6 (row w + col) ..]
+hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStream_t stream);
+
+}  // namespace rtk

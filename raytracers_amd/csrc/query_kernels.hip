@@ -1,0 +1,748 @@
+// query_kernels.hip -- the lane kernels of the caller queries, one lane per ray or point: closest hit (rt_intersect_rays), occlusion
+// (rt_occluded_rays), multi-hit, sphere casts, the nearest spheres, the range queries / contact pairs with their scan, and the primary
+// rays of a frame (rt_camera_rays).  The render path -- pixel_kernel, persistent_kernel, pooled_kernel and their RAYS modes -- is
+// render_kernels.hip; nothing here is launched by a render entry.  Build: as render_kernels.hip (-ffp-contract=off, bit-exact fp32).
+#include <hip/hip_runtime.h>
+
+#include "query_core.h"
+#include "query_device.hpp"
+
+namespace rtk {
+
+// A lane's interval in the lane kernels: the caller's (t_min, t_max), or with RANGED ray i's own -- two coalesced 4-byte loads next to its ray.
+// A ray whose own interval fails interval_ok does not start its walk: it is a miss.
+template <bool RANGED>
+__device__ __forceinline__ bool lane_interval(const KParams &p, int i, float &t_min, float &t_max) {
+  if constexpr (!RANGED) return true;
+  t_min = p.ray_tlo_dev[i];
+  t_max = p.ray_thi_dev[i];
+  return interval_ok(t_min, t_max);
+}
+
+// objs_hit bvh r t_min t_max (ray.fut:76-86), one lane per ray: the pixel family's stack fold with the caller's interval on every box,
+// the spheres folded over (scene_epsilon, best) from best = t_max, then one re-intersection of the winner over (t_min, best + 1).
+template <bool RANGED>
+__device__ __forceinline__ void intersect_lane(const KParams &p, float t_min, float t_max, int32_t *index, float *hit7) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const Ray r = load_ray(p.rays, i);
+  const bool valid = lane_interval<RANGED>(p, i, t_min, t_max);
+  float best = t_max;
+  int bestj = -1;
+  int sp = 0;
+  if (valid) stack[sp++][lane] = 0;
+  while (sp > 0) {
+    const int ni = stack[--sp][lane];
+    const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+    if (!box_hit_interval(r, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, t_min, t_max)) continue;
+    const int kids[2] = {f2i(lo.w), f2i(hi.w)};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int c = kids[k];
+      if (c < 0) {
+        const int j = ~c;
+        const float4 s = buf_load16(rs_sph, j * 16);
+        closest_update(sphere_root(r, s.x, s.y, s.z, s.w), j, best, bestj);
+      } else {
+        stack[sp++][lane] = c;   // (at most one pending sibling per level: sp <= tree height + 1 <= kStackPixel)
+      }
+    }
+  }
+  float t = 0.0f, h[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  bool have = false;
+  if (bestj >= 0) {
+    const float4 s = p.sph[bestj];
+    have = rehit_range(r, t_min, best, s.x, s.y, s.z, s.w, &t);
+    if (have) {
+      const float inv_rad = p.col[bestj].w;   // 1.0f / radius, the bits of scale (1.0/s.radius) (ray.fut:43)
+      h[0] = r.ox + t * r.dx; h[1] = r.oy + t * r.dy; h[2] = r.oz + t * r.dz;   // point_at_param
+      h[3] = inv_rad * (h[0] - s.x); h[4] = inv_rad * (h[1] - s.y); h[5] = inv_rad * (h[2] - s.z);
+    }
+  }
+  index[i] = have ? bestj : -1;
+  if (hit7 != nullptr) {
+    float *const o = hit7 + (size_t)i * 7;
+    o[0] = have ? t : 0.0f;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[1 + k] = h[k];
+  }
+}
+__global__ __launch_bounds__(64) void intersect_kernel(KParams p, float t_min, float t_max, int32_t *index, float *hit7) {
+  intersect_lane<false>(p, t_min, t_max, index, hit7);
+}
+__global__ __launch_bounds__(64) void intersect_ranged_kernel(KParams p, int32_t *index, float *hit7) {
+  intersect_lane<true>(p, 0.0f, 0.0f, index, hit7);
+}
+
+hipError_t launch_intersect_rays(const KParams &p, float t_min, float t_max, int32_t *index, float *hit7, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  hipLaunchKernelGGL(intersect_kernel, dim3((unsigned)((p.nrays + 63) / 64)), dim3(64), 0, stream, p, t_min, t_max, index, hit7);
+  return hipGetLastError();
+}
+hipError_t launch_intersect_rays_ranged(const KParams &p, int32_t *index, float *hit7, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (p.ray_tlo_dev == nullptr || p.ray_thi_dev == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(intersect_ranged_kernel, dim3((unsigned)((p.nrays + 63) / 64)), dim3(64), 0, stream, p, index, hit7);
+  return hipGetLastError();
+}
+
+// rt_occluded_rays, one lane per ray: intersect_kernel's stack fold with the caller's interval on every box and on every sphere
+// (sphere_hit_any); the lane leaves the walk at its first accepted sphere -- the fold is an OR, so no order can change the answer.
+template <bool RANGED>
+__device__ __forceinline__ void occluded_lane(const KParams &p) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const Ray r = load_ray(p.rays, i);
+  float t_min = p.ray_tlo, t_max = p.ray_thi;
+  const bool valid = lane_interval<RANGED>(p, i, t_min, t_max);
+  bool hit = false;
+  int sp = 0;
+  if (valid) stack[sp++][lane] = 0;
+  while (sp > 0 && !hit) {
+    const int ni = stack[--sp][lane];
+    const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+    if (!box_hit_interval(r, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, t_min, t_max)) continue;
+    const int kids[2] = {f2i(lo.w), f2i(hi.w)};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int c = kids[k];
+      if (c < 0) {
+        const float4 s = buf_load16(rs_sph, ~c * 16);
+        hit = hit || sphere_hit_any(r, t_min, t_max, s.x, s.y, s.z, s.w);
+      } else {
+        stack[sp++][lane] = c;   // (at most one pending sibling per level: sp <= tree height + 1 <= kStackPixel)
+      }
+    }
+  }
+  p.occluded[i] = hit ? 1 : 0;
+}
+__global__ __launch_bounds__(64) void occluded_kernel(KParams p) { occluded_lane<false>(p); }
+__global__ __launch_bounds__(64) void occluded_ranged_kernel(KParams p) { occluded_lane<true>(p); }
+
+hipError_t launch_occluded_rays(const KParams &p, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (p.occluded == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(occluded_kernel, dim3((unsigned)((p.nrays + 63) / 64)), dim3(64), 0, stream, p);
+  return hipGetLastError();
+}
+hipError_t launch_occluded_rays_ranged(const KParams &p, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (p.occluded == nullptr || p.ray_tlo_dev == nullptr || p.ray_thi_dev == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(occluded_ranged_kernel, dim3((unsigned)((p.nrays + 63) / 64)), dim3(64), 0, stream, p);
+  return hipGetLastError();
+}
+
+// rt_multi_hit_rays: a lane's crossings -- (t, j, root) for every root of every visited sphere strictly inside (t_min, t_max) -- kept as
+// one 64-bit key each, bits(t) << 32 | j << 1 | (root - 1).  t > t_min >= 0 (-0.0 included) and t < t_max <= 1e9, so t is positive and
+// finite and its bits order as t does; j < 2^26 (rt_scene's sphere limit; any j < 2^31 would do) fills the low word below bit 27 next to
+// the root bit.  The key carries no ray index, so the order is (t, j, root) for every ray count.  An empty slot is ~0: no crossing has a
+// high word of 0xffffffff.
+__device__ __forceinline__ unsigned long long crossing_key(float t, int j, int root2) {
+  return ((unsigned long long)__float_as_uint(t) << 32) | ((unsigned)j << 1) | (unsigned)root2;
+}
+// Insert x into the sorted list of the CAP smallest keys: x is carried down the list, each slot keeping the smaller of the two.  Every index
+// is a compile-time constant after unrolling, so the list stays in VGPRs (a runtime index would put it in scratch).  Skipped when x is
+// not below the last slot.
+template <int CAP>
+__device__ __forceinline__ void crossing_insert(unsigned long long (&list)[CAP], unsigned long long x) {
+  if (!(x < list[CAP - 1])) return;
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) {
+    const unsigned long long y = list[s];
+    list[s] = x < y ? x : y;
+    x = x < y ? y : x;
+  }
+}
+
+// One lane per ray: occluded_lane's walk (box_hit_interval over the lane's interval on every box) without its early exit and without
+// culling.  At each leaf both roots are computed once (sphere_roots); each one inside the interval is counted and inserted into the
+// lane's list of the CAP smallest crossings (k <= CAP of them are written).  At write-out slot s < min(count, k) gets j, its root and
+// {t, p.xyz, normal.xyz} with intersect_lane's arithmetic; slots up to k are padded with -1, 0 and seven zeros.  Outputs are at
+// 64-bit offsets (n * k * 7 passes 2^31); any of them may be nullptr.
+template <bool RANGED, int CAP>
+__device__ __forceinline__ void multi_hit_lane(const KParams &p, int k, int32_t *count, int32_t *index, uint8_t *root, float *hit7) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const Ray r = load_ray(p.rays, i);
+  float t_min = p.ray_tlo, t_max = p.ray_thi;
+  const bool valid = lane_interval<RANGED>(p, i, t_min, t_max);
+  unsigned long long list[CAP];
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) list[s] = ~0ull;
+  int cnt = 0;
+  int sp = 0;
+  if (valid) stack[sp++][lane] = 0;
+  while (sp > 0) {
+    const int ni = stack[--sp][lane];
+    const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+    if (!box_hit_interval(r, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, t_min, t_max)) continue;
+    const int kids[2] = {f2i(lo.w), f2i(hi.w)};
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      const int c = kids[c2];
+      if (c < 0) {
+        const int j = ~c;
+        const float4 s = buf_load16(rs_sph, j * 16);
+        float t1, t2;
+        if (sphere_roots(r, s.x, s.y, s.z, s.w, &t1, &t2)) {
+          const bool in1 = (t1 < t_max) && (t1 > t_min), in2 = (t2 < t_max) && (t2 > t_min);   // (sphere_hit_any's tests)
+          cnt += (in1 ? 1 : 0) + (in2 ? 1 : 0);
+          if (in1) crossing_insert<CAP>(list, crossing_key(t1, j, 0));
+          if (in2) crossing_insert<CAP>(list, crossing_key(t2, j, 1));
+        }
+      } else {
+        stack[sp++][lane] = c;   // (at most one pending sibling per level: sp <= tree height + 1 <= kStackPixel)
+      }
+    }
+  }
+  if (count != nullptr) count[i] = cnt;
+  const size_t base = (size_t)i * (size_t)k;
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) {
+    if (s < k) {
+      const bool have = s < cnt;
+      const int j = have ? (int)((unsigned)list[s] >> 1) : -1;
+      if (index != nullptr) index[base + s] = j;
+      if (root != nullptr) root[base + s] = have ? (uint8_t)(((unsigned)list[s] & 1u) + 1u) : (uint8_t)0;
+      if (hit7 != nullptr) {
+        float h[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (have) {
+          const float t = __uint_as_float((unsigned)(list[s] >> 32));
+          const float4 ce = p.sph[j];
+          const float inv_rad = p.col[j].w;   // 1.0f / radius, as intersect_lane
+          h[0] = t;
+          h[1] = r.ox + t * r.dx; h[2] = r.oy + t * r.dy; h[3] = r.oz + t * r.dz;   // point_at_param
+          h[4] = inv_rad * (h[1] - ce.x); h[5] = inv_rad * (h[2] - ce.y); h[6] = inv_rad * (h[3] - ce.z);
+        }
+        float *const o = hit7 + (base + s) * 7;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) o[q] = h[q];
+      }
+    }
+  }
+}
+template <bool RANGED, int CAP>
+__global__ __launch_bounds__(64) void multi_hit_kernel(KParams p, int k, int32_t *count, int32_t *index, uint8_t *root, float *hit7) {
+  multi_hit_lane<RANGED, CAP>(p, k, count, index, root, hit7);
+}
+
+template <bool RANGED>
+static hipError_t launch_multi_hit_cap(const KParams &p, int k, int32_t *count, int32_t *index, uint8_t *root, float *hit7, hipStream_t stream) {
+  const dim3 grid((unsigned)((p.nrays + 63) / 64)), block(64);
+  if (k <= 4) hipLaunchKernelGGL((multi_hit_kernel<RANGED, 4>), grid, block, 0, stream, p, k, count, index, root, hit7);
+  else if (k <= 8) hipLaunchKernelGGL((multi_hit_kernel<RANGED, 8>), grid, block, 0, stream, p, k, count, index, root, hit7);
+  else if (k <= 16) hipLaunchKernelGGL((multi_hit_kernel<RANGED, 16>), grid, block, 0, stream, p, k, count, index, root, hit7);
+  else hipLaunchKernelGGL((multi_hit_kernel<RANGED, 32>), grid, block, 0, stream, p, k, count, index, root, hit7);
+  return hipGetLastError();
+}
+
+hipError_t launch_multi_hit_rays(const KParams &p, int k, int32_t *count, int32_t *index, uint8_t *root, float *hit7, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (k < 1 || k > kMultiHitMaxK) return hipErrorInvalidValue;
+  if (count == nullptr && index == nullptr && root == nullptr && hit7 == nullptr) return hipErrorInvalidValue;
+  if ((p.ray_tlo_dev == nullptr) != (p.ray_thi_dev == nullptr)) return hipErrorInvalidValue;
+  return p.ray_tlo_dev != nullptr ? launch_multi_hit_cap<true>(p, k, count, index, root, hit7, stream)
+                                  : launch_multi_hit_cap<false>(p, k, count, index, root, hit7, stream);
+}
+
+// rt_sweep_spheres: one lane per query -- a sphere of radius rq whose centre moves along the lane's ray.  multi_hit_lane's walk with every
+// node's box widened by rq per component (fl(lo - rq), fl(hi + rq): six additions per box test, rq being the query's own) and, at a
+// leaf, sweep_contact (query_core.h) in place of the two roots: a sphere gives at most one contact, counted and inserted into the same
+// sorted list as the key bits(tau) << 32 | j << 1 | start.  tau is t1 inside (t_min, t_max), or t_min + 0.0f for an overlap at the start:
+// never negative, finite, so its bits order as it does, and the key order is (tau, j).  The interval is never narrowed by the contacts
+// found: the visited leaves are part of the contract.  RANGED: the query's own radius and interval (a failing interval_ok or max_dist_ok
+// is a miss, its walk does not start).  exclude != nullptr: sphere exclude[i] is skipped at the leaf, one compare (a value no leaf has
+// excludes nothing).  At write-out slot s < min(count, k) gets j, start and {tau, p, (1.0f / R) * (p - centre)} with R = radius_j + rq;
+// slots up to k are padded with -1, 0 and seven zeros.  64-bit output offsets; any output may be nullptr.
+template <bool RANGED, int CAP>
+__device__ __forceinline__ void sweep_lane(const KParams &p, const float *radius_dev, float rq, const int32_t *exclude, int k, int32_t *count,
+                                           int32_t *index, uint8_t *start, float *hit7) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const Ray r = load_ray(p.rays, i);
+  float t_min = p.ray_tlo, t_max = p.ray_thi;
+  bool valid = lane_interval<RANGED>(p, i, t_min, t_max);
+  if constexpr (RANGED) {
+    rq = radius_dev[i] + 0.0f;   // (-0.0 -> +0.0)
+    valid = valid && max_dist_ok(rq);
+  }
+  const int skip = exclude != nullptr ? exclude[i] : -1;
+  unsigned long long list[CAP];
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) list[s] = ~0ull;
+  int cnt = 0;
+  int sp = 0;
+  if (valid) stack[sp++][lane] = 0;
+  while (sp > 0) {
+    const int ni = stack[--sp][lane];
+    const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+    if (!box_hit_interval(r, lo.x - rq, lo.y - rq, lo.z - rq, hi.x + rq, hi.y + rq, hi.z + rq, t_min, t_max)) continue;
+    const int kids[2] = {f2i(lo.w), f2i(hi.w)};
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      const int c = kids[c2];
+      if (c < 0) {
+        const int j = ~c;
+        if (j != skip) {
+          const float4 s = buf_load16(rs_sph, j * 16);
+          float tau;
+          const int what = sweep_contact(r, s.x, s.y, s.z, s.w, rq, t_min, t_max, &tau);
+          if (what != kSweepNone) {
+            cnt += 1;
+            crossing_insert<CAP>(list, crossing_key(tau, j, what == kSweepStart ? 1 : 0));
+          }
+        }
+      } else {
+        stack[sp++][lane] = c;   // (at most one pending sibling per level: sp <= tree height + 1 <= kStackPixel)
+      }
+    }
+  }
+  if (count != nullptr) count[i] = cnt;
+  const size_t base = (size_t)i * (size_t)k;
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) {
+    if (s < k) {
+      const bool have = s < cnt;
+      const int j = have ? (int)((unsigned)list[s] >> 1) : -1;
+      if (index != nullptr) index[base + s] = j;
+      if (start != nullptr) start[base + s] = have ? (uint8_t)((unsigned)list[s] & 1u) : (uint8_t)0;
+      if (hit7 != nullptr) {
+        float h[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (have) {
+          const float tau = __uint_as_float((unsigned)(list[s] >> 32));
+          const float4 ce = p.sph[j];
+          const float inv_rad = 1.0f / (ce.w + rq);   // 1 / R: the one division of the slot
+          h[0] = tau;
+          h[1] = r.ox + tau * r.dx; h[2] = r.oy + tau * r.dy; h[3] = r.oz + tau * r.dz;   // point_at_param: the moving centre at contact
+          h[4] = inv_rad * (h[1] - ce.x); h[5] = inv_rad * (h[2] - ce.y); h[6] = inv_rad * (h[3] - ce.z);
+        }
+        float *const o = hit7 + (base + s) * 7;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) o[q] = h[q];
+      }
+    }
+  }
+}
+template <bool RANGED, int CAP>
+__global__ __launch_bounds__(64) void sweep_kernel(KParams p, const float *radius_dev, float rq, const int32_t *exclude, int k, int32_t *count,
+                                                   int32_t *index, uint8_t *start, float *hit7) {
+  sweep_lane<RANGED, CAP>(p, radius_dev, rq, exclude, k, count, index, start, hit7);
+}
+
+template <bool RANGED>
+static hipError_t launch_sweep_cap(const KParams &p, const float *radius_dev, float rq, const int32_t *exclude, int k, int32_t *count,
+                                   int32_t *index, uint8_t *start, float *hit7, hipStream_t stream) {
+  const dim3 grid((unsigned)((p.nrays + 63) / 64)), block(64);
+  if (k <= 4) hipLaunchKernelGGL((sweep_kernel<RANGED, 4>), grid, block, 0, stream, p, radius_dev, rq, exclude, k, count, index, start, hit7);
+  else if (k <= 8) hipLaunchKernelGGL((sweep_kernel<RANGED, 8>), grid, block, 0, stream, p, radius_dev, rq, exclude, k, count, index, start, hit7);
+  else if (k <= 16) hipLaunchKernelGGL((sweep_kernel<RANGED, 16>), grid, block, 0, stream, p, radius_dev, rq, exclude, k, count, index, start, hit7);
+  else hipLaunchKernelGGL((sweep_kernel<RANGED, 32>), grid, block, 0, stream, p, radius_dev, rq, exclude, k, count, index, start, hit7);
+  return hipGetLastError();
+}
+
+hipError_t launch_sweep_spheres(const KParams &p, const float *radius_dev, float radius, const int32_t *exclude, int k, int32_t *count,
+                                int32_t *index, uint8_t *start, float *hit7, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (k < 1 || k > kSweepMaxK) return hipErrorInvalidValue;
+  if (count == nullptr && index == nullptr && start == nullptr && hit7 == nullptr) return hipErrorInvalidValue;
+  const bool ranged = radius_dev != nullptr;
+  if (ranged != (p.ray_tlo_dev != nullptr) || ranged != (p.ray_thi_dev != nullptr)) return hipErrorInvalidValue;
+  if (!ranged && !max_dist_ok(radius)) return hipErrorInvalidValue;
+  radius += 0.0f;   // (-0.0 -> +0.0)
+  return ranged ? launch_sweep_cap<true>(p, radius_dev, 0.0f, exclude, k, count, index, start, hit7, stream)
+                : launch_sweep_cap<false>(p, nullptr, radius, exclude, k, count, index, start, hit7, stream);
+}
+
+// rt_nearest_spheres: one lane per point.  The walk of multi_hit_lane with the box test replaced by box_may_hold (query_core.h: the
+// point-to-box distance against the threshold plus a proven slack) and the crossing list by the same sorted list of CAP 64-bit keys,
+// gap_key(gap, j): every sphere with gap <= max_dist is counted and inserted.  A box is tested only at depth >= exact_depth: the reference's
+// AABB propagation runs floor(log2 n) + 2 sweeps from zero boxes (bvh.fut:44-58), so in a taller tree the boxes of the nodes nearer the root
+// than height - sweeps levels need not contain their subtrees -- the walk descends through them untested.  A stack entry is the node and its
+// depth (capped at 63) in bits 26..31 (node < 2^26).
+// PRUNED (no count output): once the list holds k keys the threshold is min(max_dist, the k-th gap) -- read with an unrolled select, a
+// runtime index would put the list in scratch -- and the children of a node are pushed farther first, so the nearer one is walked first (one
+// extra 32-byte read per inner child).  Neither changes the first k keys: a skipped box holds only spheres whose gap exceeds the threshold.
+// Outputs at 64-bit offsets; any may be nullptr.
+template <int CAP>
+__device__ __forceinline__ float kth_gap(const unsigned long long (&list)[CAP], int k) {
+  unsigned long long x = ~0ull;
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) x = s == k - 1 ? list[s] : x;
+  return x == ~0ull ? kNoHit : gap_of_key(x);
+}
+__device__ __forceinline__ int nearest_stack_entry(int node, int depth) { return (int)((unsigned)node | ((unsigned)(depth < 63 ? depth : 63) << 26)); }
+
+template <bool RANGED, bool PRUNED, int CAP>
+__device__ __forceinline__ void nearest_lane(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, int k, int exact_depth,
+                                             int32_t *count, int32_t *index, float *gap) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const float px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
+  if constexpr (RANGED) max_dist = max_dist_dev[i] + 0.0f;   // (-0.0 -> +0.0)
+  const bool valid = point_ok(px, py, pz) && (!RANGED || max_dist_ok(max_dist));
+  const float pmag = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
+  unsigned long long list[CAP];
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) list[s] = ~0ull;
+  int cnt = 0;
+  float T = max_dist;
+  int sp = 0;
+  if (valid) stack[sp++][lane] = nearest_stack_entry(0, 0);
+  while (sp > 0) {
+    const unsigned e = (unsigned)stack[--sp][lane];
+    const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
+    const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+    if (depth >= exact_depth && !box_may_hold(px, py, pz, pmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, T)) continue;
+    const int kids[2] = {f2i(lo.w), f2i(hi.w)};
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      const int c = kids[c2];
+      if (c < 0) {
+        const int j = ~c;
+        const float4 s = buf_load16(rs_sph, j * 16);
+        const float g = point_gap(px, py, pz, s.x, s.y, s.z, s.w);
+        if (g <= max_dist) {
+          ++cnt;
+          crossing_insert<CAP>(list, gap_key(g, j));
+          if constexpr (PRUNED) T = fminf(max_dist, kth_gap<CAP>(list, k));
+        }
+      }
+    }
+    if constexpr (PRUNED) {
+      // the inner children, farther first; one that already fails the test is not pushed
+      float b[2] = {0.0f, 0.0f};
+      bool push[2] = {false, false};
+#pragma unroll
+      for (int c2 = 0; c2 < 2; ++c2) {
+        const int c = kids[c2];
+        if (c >= 0) {
+          const float4 clo = buf_load16(rs_nodes, c * 32), chi = buf_load16(rs_nodes, c * 32 + 16);
+          push[c2] = depth + 1 < exact_depth || box_may_hold(px, py, pz, pmag, clo.x, clo.y, clo.z, chi.x, chi.y, chi.z, T);
+          b[c2] = box_gap_bound(px, py, pz, clo.x, clo.y, clo.z, chi.x, chi.y, chi.z);
+        }
+      }
+      const int first = b[0] >= b[1] ? 0 : 1;   // (the farther one goes below the nearer one)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int c2 = q == 0 ? first : 1 - first;
+        if (push[c2]) stack[sp++][lane] = nearest_stack_entry(kids[c2], depth + 1);   // (one pending sibling per level: sp <= height + 1 <= kStackPixel)
+      }
+    } else {
+#pragma unroll
+      for (int c2 = 0; c2 < 2; ++c2)
+        if (kids[c2] >= 0) stack[sp++][lane] = nearest_stack_entry(kids[c2], depth + 1);
+    }
+  }
+  if (count != nullptr) count[i] = cnt;
+  const size_t base = (size_t)i * (size_t)k;
+#pragma unroll
+  for (int s = 0; s < CAP; ++s) {
+    if (s < k) {
+      const bool have = list[s] != ~0ull;
+      if (index != nullptr) index[base + s] = have ? (int)(unsigned)list[s] : -1;
+      if (gap != nullptr) gap[base + s] = have ? gap_of_key(list[s]) : 0.0f;
+    }
+  }
+}
+template <bool RANGED, bool PRUNED, int CAP>
+__global__ __launch_bounds__(64) void nearest_kernel(KParams p, const float *pts, const float *max_dist_dev, float max_dist, int k, int exact_depth,
+                                                     int32_t *count, int32_t *index, float *gap) {
+  nearest_lane<RANGED, PRUNED, CAP>(p, pts, max_dist_dev, max_dist, k, exact_depth, count, index, gap);
+}
+
+template <bool RANGED, bool PRUNED>
+static hipError_t launch_nearest_cap(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, int k, int exact_depth,
+                                     int32_t *count, int32_t *index, float *gap, hipStream_t stream) {
+  const dim3 grid((unsigned)((p.nrays + 63) / 64)), block(64);
+#define RT_NEAREST(CAP) \
+  hipLaunchKernelGGL((nearest_kernel<RANGED, PRUNED, CAP>), grid, block, 0, stream, p, pts, max_dist_dev, max_dist, k, exact_depth, count, index, gap)
+  if (k <= 4) RT_NEAREST(4);
+  else if (k <= 8) RT_NEAREST(8);
+  else if (k <= 16) RT_NEAREST(16);
+  else RT_NEAREST(32);
+#undef RT_NEAREST
+  return hipGetLastError();
+}
+
+hipError_t launch_nearest_spheres(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, int k, int exact_depth,
+                                  int32_t *count, int32_t *index, float *gap, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (pts == nullptr || k < 1 || k > kNearestMaxK || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (count == nullptr && index == nullptr && gap == nullptr) return hipErrorInvalidValue;
+  const bool ranged = max_dist_dev != nullptr, pruned = count == nullptr;
+  if (!ranged && !max_dist_ok(max_dist)) return hipErrorInvalidValue;
+  max_dist += 0.0f;   // (-0.0 -> +0.0)
+  if (ranged) return pruned ? launch_nearest_cap<true, true>(p, pts, max_dist_dev, 0.0f, k, exact_depth, count, index, gap, stream)
+                            : launch_nearest_cap<true, false>(p, pts, max_dist_dev, 0.0f, k, exact_depth, count, index, gap, stream);
+  return pruned ? launch_nearest_cap<false, true>(p, pts, nullptr, max_dist, k, exact_depth, count, index, gap, stream)
+                : launch_nearest_cap<false, false>(p, pts, nullptr, max_dist, k, exact_depth, count, index, gap, stream);
+}
+
+// rt_spheres_within_* / rt_contact_pairs_*: EVERY sphere with gap <= the point's bound, in CSR form.  One lane per point,
+// nearest_lane's count-mode walk (the same stack, loads and box_may_hold with T = the point's bound, the untested descent through the partial
+// boxes above exact_depth) without a key list: a row has no length limit.  Rows come out in ASCENDING j with no sort: the leaves below a node
+// are a contiguous run of L and the left child holds the lower part, so a depth-first walk that takes the left child first meets the leaves in
+// ascending j.  The children are therefore pushed right then left, and a right child that is a leaf waits on the stack behind an inner left
+// sibling (a stack entry with depth field 63 is a leaf; a node's depth is capped at 62, above any exact_depth: height <= 63 and at least 3
+// sweeps).  The count pass (FILL false) and the fill pass evaluate the same predicate, so they select the same set; the fill pass writes
+// entry offsets[i] + rank, and only below offsets[i + 1] and below `capacity` -- offsets from another query can misplace entries, never put
+// one outside the caller's arrays.  `first`: sphere j is selected only if j >= first[i], a compare at the leaf (no subtree is pruned by it).
+// SELF (contact pairs): point i is the centre of L[i], its bound fl(radius_i + max_dist), first = i + 1; `point` then is the pair array,
+// rows {i, j}.
+constexpr int kWithinLeaf = 63, kWithinMaxDepth = 62;
+__device__ __forceinline__ int within_node_entry(int node, int depth) {
+  return (int)((unsigned)node | ((unsigned)(depth < kWithinMaxDepth ? depth : kWithinMaxDepth) << 26));
+}
+__device__ __forceinline__ int within_leaf_entry(int j) { return (int)((unsigned)j | ((unsigned)kWithinLeaf << 26)); }
+
+template <bool FILL, bool SELF>
+__device__ __forceinline__ void within_lane(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev,
+                                            int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap,
+                                            int32_t *point) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  float px, py, pz;
+  int first = 0;
+  bool valid;
+  if constexpr (SELF) {
+    const float4 me = p.sph[i];
+    px = me.x, py = me.y, pz = me.z;
+    max_dist = (me.w + max_dist) + 0.0f;
+    first = i + 1;
+    valid = point_ok(px, py, pz) && max_dist_ok(max_dist);
+  } else {
+    px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
+    if (max_dist_dev != nullptr) max_dist = max_dist_dev[i] + 0.0f;   // (-0.0 -> +0.0)
+    if (first_dev != nullptr) first = first_dev[i] > 0 ? first_dev[i] : 0;
+    valid = point_ok(px, py, pz) && max_dist_ok(max_dist);
+  }
+  const float pmag = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
+  int cnt = 0;
+  int64_t at = 0, end = 0;
+  if constexpr (FILL) {
+    at = offsets[i];
+    end = offsets[i + 1] < capacity ? offsets[i + 1] : capacity;
+    if (at < 0) at = end;   // (offsets that are not a scan of counts: nothing is written)
+  }
+  int sp = 0;
+  if (valid) stack[sp++][lane] = within_node_entry(0, 0);
+  while (sp > 0) {
+    const unsigned e = (unsigned)stack[--sp][lane];
+    const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
+    int leaf[2] = {-1, -1};
+    if (depth == kWithinLeaf) {
+      leaf[0] = ni;
+    } else {
+      const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+      if (depth >= exact_depth && !box_may_hold(px, py, pz, pmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, max_dist)) continue;
+      const int l = f2i(lo.w), r = f2i(hi.w);
+      // (one pending sibling per level: sp <= height + 1 <= kStackPixel)
+      if (l < 0) {
+        leaf[0] = ~l;
+        if (r < 0) leaf[1] = ~r;
+        else stack[sp++][lane] = within_node_entry(r, depth + 1);
+      } else {
+        stack[sp++][lane] = r < 0 ? within_leaf_entry(~r) : within_node_entry(r, depth + 1);
+        stack[sp++][lane] = within_node_entry(l, depth + 1);
+      }
+    }
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      const int j = leaf[c2];
+      if (j >= first) {   // (first >= 0: an empty leaf slot, -1, never passes)
+        const float4 s = buf_load16(rs_sph, j * 16);
+        const float g = point_gap(px, py, pz, s.x, s.y, s.z, s.w);
+        if (g <= max_dist) {
+          if constexpr (FILL) {
+            if (at < end) {
+              if constexpr (SELF) {
+                if (point != nullptr) *reinterpret_cast<int2 *>(point + 2 * at) = make_int2(i, j);
+              } else {
+                if (index != nullptr) index[at] = j;
+                if (point != nullptr) point[at] = i;
+              }
+              if (gap != nullptr) gap[at] = g;
+            }
+            ++at;
+          } else {
+            ++cnt;
+          }
+        }
+      }
+    }
+  }
+  if constexpr (!FILL) count[i] = cnt;
+}
+template <bool FILL, bool SELF>
+__global__ __launch_bounds__(64) void within_kernel(KParams p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev,
+                                                    int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index,
+                                                    float *gap, int32_t *point) {
+  within_lane<FILL, SELF>(p, pts, max_dist_dev, max_dist, first_dev, exact_depth, count, offsets, capacity, index, gap, point);
+}
+
+// The scan between the two passes: n int32 counts -> n + 1 int64 offsets (offsets[0] = 0, offsets[i + 1] = counts[0] + .. + counts[i]), in
+// three plain launches.  No workgroup waits on another: 1. every workgroup sums its kWithinScanItems counts; 2. ONE workgroup turns the block
+// sums into their exclusive prefix, kWithinScanThreads at a time with a running carry; 3. every workgroup scans its own counts again on top
+// of its prefix.  All sums are 64-bit: a row may hold 2^26 entries, the total of 2^31 rows does not fit 32 bits.
+constexpr int kWithinScanThreads = 256, kWithinScanPer = 4, kWithinScanItems = kWithinScanThreads * kWithinScanPer;
+__device__ __forceinline__ long long wave_scan_incl(long long v, int lane) {
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long u = __shfl_up(v, o);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+// inclusive scan of v over the workgroup's kWithinScanThreads threads; *total = the workgroup's sum (wsum: one slot per wave, reusable after return)
+__device__ __forceinline__ long long block_scan_incl(long long v, long long *wsum, long long *total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long incl = wave_scan_incl(v, lane);
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  long long before = 0, all = 0;
+#pragma unroll
+  for (int k = 0; k < kWithinScanThreads / 64; ++k) {
+    const long long w = wsum[k];
+    if (k < wave) before += w;
+    all += w;
+  }
+  __syncthreads();
+  *total = all;
+  return before + incl;
+}
+__device__ __forceinline__ void within_load_counts(const int32_t *counts, int n, int (&c)[kWithinScanPer]) {
+  const long long at = ((long long)blockIdx.x * kWithinScanThreads + threadIdx.x) * kWithinScanPer;
+#pragma unroll
+  for (int q = 0; q < kWithinScanPer; ++q) c[q] = at + q < n ? counts[at + q] : 0;
+}
+__global__ __launch_bounds__(kWithinScanThreads) void within_scan_sums_kernel(const int32_t *counts, int n, long long *sums) {
+  __shared__ long long wsum[kWithinScanThreads / 64];
+  int c[kWithinScanPer];
+  within_load_counts(counts, n, c);
+  long long v = 0, total;
+#pragma unroll
+  for (int q = 0; q < kWithinScanPer; ++q) v += c[q];
+  (void)block_scan_incl(v, wsum, &total);
+  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(kWithinScanThreads) void within_scan_carry_kernel(long long *sums, int nblocks) {
+  __shared__ long long wsum[kWithinScanThreads / 64];
+  long long carry = 0;   // (the same value in every thread)
+  for (int base = 0; base < nblocks; base += kWithinScanThreads) {
+    const int b = base + (int)threadIdx.x;
+    const long long v = b < nblocks ? sums[b] : 0;
+    long long total;
+    const long long incl = block_scan_incl(v, wsum, &total);
+    if (b < nblocks) sums[b] = carry + incl - v;
+    carry += total;
+  }
+}
+__global__ __launch_bounds__(kWithinScanThreads) void within_scan_apply_kernel(const int32_t *counts, int n, const long long *sums, int64_t *offsets) {
+  __shared__ long long wsum[kWithinScanThreads / 64];
+  int c[kWithinScanPer];
+  within_load_counts(counts, n, c);
+  long long v = 0, total;
+#pragma unroll
+  for (int q = 0; q < kWithinScanPer; ++q) v += c[q];
+  long long run = sums[blockIdx.x] + block_scan_incl(v, wsum, &total) - v;
+  const long long at = ((long long)blockIdx.x * kWithinScanThreads + threadIdx.x) * kWithinScanPer;
+  if (at == 0) offsets[0] = 0;
+#pragma unroll
+  for (int q = 0; q < kWithinScanPer; ++q) {
+    run += c[q];
+    if (at + q < n) offsets[at + q + 1] = run;
+  }
+}
+
+size_t within_scratch_bytes(int64_t n) {
+  const size_t nblocks = ((size_t)n + kWithinScanItems - 1) / kWithinScanItems;
+  return (((size_t)n * 4 + 255) & ~(size_t)255) + nblocks * 8;
+}
+
+hipError_t launch_within_count(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
+                               int exact_depth, char *scratch, int64_t *offsets, hipStream_t stream) {
+  if (offsets == nullptr) return hipErrorInvalidValue;
+  if (p.nrays <= 0) return hipMemsetAsync(offsets, 0, sizeof(int64_t), stream);
+  if ((!self && pts == nullptr) || scratch == nullptr || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (self && p.nrays != p.n_sph) return hipErrorInvalidValue;
+  if ((self || max_dist_dev == nullptr) && !max_dist_ok(max_dist)) return hipErrorInvalidValue;
+  max_dist += 0.0f;   // (-0.0 -> +0.0)
+  const int n = p.nrays;
+  int32_t *const counts = reinterpret_cast<int32_t *>(scratch);
+  long long *const sums = reinterpret_cast<long long *>(scratch + (((size_t)n * 4 + 255) & ~(size_t)255));
+  const dim3 grid(((unsigned)n + 63u) / 64u), block(64);
+  if (self)
+    hipLaunchKernelGGL((within_kernel<false, true>), grid, block, 0, stream, p, nullptr, nullptr, max_dist, nullptr, exact_depth, counts, nullptr,
+                       (int64_t)0, nullptr, nullptr, nullptr);
+  else
+    hipLaunchKernelGGL((within_kernel<false, false>), grid, block, 0, stream, p, pts, max_dist_dev, max_dist, first_dev, exact_depth, counts, nullptr,
+                       (int64_t)0, nullptr, nullptr, nullptr);
+  const int nblocks = (int)(((int64_t)n + kWithinScanItems - 1) / kWithinScanItems);
+  hipLaunchKernelGGL(within_scan_sums_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums);
+  hipLaunchKernelGGL(within_scan_carry_kernel, dim3(1), dim3(kWithinScanThreads), 0, stream, sums, nblocks);
+  hipLaunchKernelGGL(within_scan_apply_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums, offsets);
+  return hipGetLastError();
+}
+
+hipError_t launch_within_fill(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
+                              int exact_depth, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point,
+                              hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if ((!self && pts == nullptr) || offsets == nullptr || capacity < 0 || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (self && (p.nrays != p.n_sph || index != nullptr)) return hipErrorInvalidValue;
+  if (index == nullptr && gap == nullptr && point == nullptr) return hipErrorInvalidValue;
+  if ((self || max_dist_dev == nullptr) && !max_dist_ok(max_dist)) return hipErrorInvalidValue;
+  max_dist += 0.0f;   // (-0.0 -> +0.0)
+  const dim3 grid(((unsigned)p.nrays + 63u) / 64u), block(64);
+  if (self)
+    hipLaunchKernelGGL((within_kernel<true, true>), grid, block, 0, stream, p, nullptr, nullptr, max_dist, nullptr, exact_depth, nullptr, offsets,
+                       capacity, nullptr, gap, point);
+  else
+    hipLaunchKernelGGL((within_kernel<true, false>), grid, block, 0, stream, p, pts, max_dist_dev, max_dist, first_dev, exact_depth, nullptr, offsets,
+                       capacity, index, gap, point);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void camera_rays_kernel(Cam cam, int h, int w, float *rays) {
+  const int64_t n = (int64_t)h * w;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int row = (int)(i / w), col = (int)(i - (int64_t)row * w);
+    const Ray r = primary_ray(cam, col, row, w, h);
+    float *const o = rays + i * 6;
+    o[0] = r.ox; o[1] = r.oy; o[2] = r.oz;
+    o[3] = r.dx; o[4] = r.dy; o[5] = r.dz;
+  }
+}
+
+hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStream_t stream) {
+  const int64_t n = (int64_t)h * w;
+  if (n <= 0) return hipSuccess;
+  const unsigned grid = (unsigned)((n + 255) / 256 < 16384 ? (n + 255) / 256 : 16384);
+  hipLaunchKernelGGL(camera_rays_kernel, dim3(grid), dim3(256), 0, stream, cam, h, w, rays);
+  return hipGetLastError();
+}
+
+}  // namespace rtk

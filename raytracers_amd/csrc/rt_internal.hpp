@@ -1,5 +1,6 @@
-// rt_internal.hpp -- the library's internal data model, shared by api.cpp (single-device surface) and
-// multi_gpu.cpp (one process, several devices).  Not installed; the public surfaces are include/*.h.
+// rt_internal.hpp -- the library's internal data model, shared by api.cpp (single-device surface), api_queries.cpp (the caller
+// queries), futhark_shim.cpp (the Futhark boundary) and multi_gpu.cpp (one process, several devices).  Not installed; the public
+// surfaces are include/*.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -228,6 +229,28 @@ inline int64_t tiles_of(int64_t rows, int64_t w) { return ((rows + 7) / 8) * ((w
 int group_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64_t w, int32_t max_depth, int32_t *out_dev,
                  const float *cam12, int32_t nframes = 1, int64_t frame_stride = 0, const float *cams12 = nullptr);
 int stage_cams(rt_context *ctx, const float *cams12, int32_t nframes, const float **cams_dev);
+// (between the library's own sources only: kept out of its dynamic symbol list)
+#pragma GCC visibility push(hidden)
+// api.cpp: the launch shape of the persistent families for one prepared scene (make_plan) ...
+struct Plan {
+  int variant;
+  int lds_nodes, lds_sph, smax, lmax, waves, grid;
+  int grid_full;   // every persistent workgroup (grid == grid_full unless grid_div says otherwise)
+  int capb, capl, ray_planes;
+  int spill_stride;   // > 0: capb is below the box stack's bound -- the launch needs a spill region of this many dwords per wave (the twenty-wave shape, tall trees)
+  size_t lds_bytes;
+};
+// ... and what the caller-ray entries (api_queries.cpp) take from the render policy: a prepared scene's fields of a parameter block, and the
+// pooled family's plan, parameters and launch for n caller rays (rt_trace_rays, rt_occluded_rays[_ranged])
+void scene_params(const rt_prepared *ps, rtk::KParams *p);
+int pooled_rays_plan(rt_context *ctx, const rt_prepared *ps, int64_t n, Plan *pl);
+int pooled_rays_params(rt_context *ctx, const rt_prepared *ps, const Plan &pl, rtk::KParams *pp);
+int launch_pooled_rays(rt_context *ctx, const rtk::KParams &p, const Plan &pl, int rays);
+// api.cpp: the context's device-block pool (arena, then cached blocks, then hipMalloc); *bytes_io: wanted -> granted.  The Futhark
+// boundary's images come from it (futhark_shim.cpp)
+hipError_t pool_alloc(rt_context *ctx, char **out, size_t *bytes_io);
+void pool_free(rt_context *ctx, char *p, size_t bytes);
+#pragma GCC visibility pop
 void group_prepare_begin(rt_context *ctx, rt_prepared *ps, int64_t h, int64_t w, const rt_scene *scene);   // starts the replicas' builds
 int group_prepare_end(rt_context *ctx, rt_prepared *ps);                                                    // joins them
 void group_prepared_free(rt_context *ctx, rt_prepared *ps);

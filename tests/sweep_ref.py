@@ -255,7 +255,7 @@ def walk_counts(arrays, o, d, radius, t_min, t_max):
 
 def rule_cases(o, d, c, r, rq, lo, hi):
     """The per-sphere rule on one (ray, sphere, radius, interval) case per row -> (kind [m] uint8, tau [m] float32): what tools/sweep_check.cpp
-    computes with lane_core.h's sweep_contact"""
+    computes with query_core.h's sweep_contact"""
     o, d, c = (np.asarray(v, dtype=F) for v in (o, d, c))
     r, rq, lo, hi = (np.asarray(v, dtype=F) for v in (r, rq, lo, hi))
     t1, t2, good, _ = swept_roots(o[:, 0], o[:, 1], o[:, 2], d[:, 0], d[:, 1], d[:, 2], c[:, 0], c[:, 1], c[:, 2], r, rq)

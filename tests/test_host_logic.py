@@ -322,6 +322,23 @@ def test_bench_dump_outputs_writer(tmp_path):
     assert np.array_equal(vals.astype(np.int64), big[("irreg", 4000, 4000)].reshape(-1)[idx])
 
 
+def test_hashed_sources_hold_the_render_path_only():
+    """bench.py ties profiles/pmc.json to a hash over bench.KERNEL_SOURCES: those files hold the render path and nothing of
+    the caller queries, so that query work does not orphan counters measured on the pooled kernel's frame launches."""
+    B = _bench_module()
+    src = "\n".join(B.strip_comments(open(os.path.join(ROOT, rel)).read()) for rel in B.KERNEL_SOURCES)
+
+    def defined(name):   # `<type> name(parameters) {`, also as rti::name
+        return re.search(r"[\w>*&]\s+(?:rti::)?" + name + r"\s*\([^;{}]*?\)\s*\{", src) is not None
+
+    for name in ("intersect_kernel", "occluded_kernel", "multi_hit_kernel", "sweep_kernel", "nearest_kernel", "within_kernel",
+                 "camera_rays_kernel", "rt_intersect_rays", "rt_multi_hit_rays", "rt_sweep_spheres", "rt_nearest_spheres",
+                 "rt_spheres_within_count", "rt_contact_pairs_count", "futhark_entry_render"):
+        assert not defined(name), f"{name} is defined in the hashed render-path sources"
+    for name in ("pooled_kernel", "pixel_kernel", "persistent_kernel", "make_plan", "enqueue_render"):
+        assert defined(name), f"{name} is not defined in the hashed render-path sources"
+
+
 def test_reference_harness_builds_against_our_header():
     """/root/reference/futhark/main.c must compile and link unmodified (build container only)."""
     if not os.path.exists("/root/reference/futhark/main.c"):

@@ -30,7 +30,7 @@ def ctx(R):
 
 def _families(R, spec=None, t_max=None):
     # (variant, what last_launch must start with): the pooled family, the lane kernel, and AUTO -- the pooled loop only for a scene that is
-    # staged in LDS whole (rgbbox) and t_max > 1, the lane kernel otherwise (api.cpp)
+    # staged in LDS whole (rgbbox) and t_max > 1, the lane kernel otherwise (api_queries.cpp)
     auto = "family=" if spec is None else POOLED_ANY if spec == "rgbbox" and t_max > 1.0 else "family=occluded"
     return ((R.VARIANT_POOLED, POOLED_ANY), (R.VARIANT_PIXEL, "family=occluded"), (R.VARIANT_AUTO, auto))
 

@@ -38,7 +38,7 @@ def ctx(R):
 
 def _families(R):
     # (variant, check of last_launch) for the ranged occlusion entry: the pooled loop in its per-ray mode, the lane kernel, and AUTO -- which
-    # takes the lane kernel (api.cpp)
+    # takes the lane kernel (api_queries.cpp)
     pooled = lambda s: s.startswith(POOLED_ANY) and s.endswith(PER_RAY)   # noqa: E731
     lane = lambda s: s == LANE_OCC                                        # noqa: E731
     return ((R.VARIANT_POOLED, pooled), (R.VARIANT_PIXEL, lane), (R.VARIANT_AUTO, lane))

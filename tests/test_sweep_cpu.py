@@ -1,6 +1,6 @@
 """CPU checks of the sphere casts: the restatement (sweep_ref.py) against the multi-hit and range-query restatements, its dense form against its
 walk form, its tree-defined answer against the brute force over all spheres, the per-sphere rule against the C++ arithmetic
-(build/sweep_check runs lane_core.h's sweep_contact), and the loader's symbols and Python signatures."""
+(build/sweep_check runs query_core.h's sweep_contact), and the loader's symbols and Python signatures."""
 import inspect
 import os
 import subprocess

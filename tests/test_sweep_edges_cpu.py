@@ -1,5 +1,5 @@
 """CPU checks of the sphere casts on the edge inputs of edge_sweeps.py: every family provably sits on its edge, the restatement's dense form
-equals its walk form there, lane_core.h's sweep_contact (build/sweep_check) equals the restatement's per-sphere rule on every query paired
+equals its walk form there, query_core.h's sweep_contact (build/sweep_check) equals the restatement's per-sphere rule on every query paired
 with its target sphere, the tree-defined answer differs from the brute force only on unconsulted leaves, wrong variants of the restatement
 (mutants) are told apart by the inputs, and the defined answer is the geometric one: a float64 brute force of the contact rule agrees with
 it outside a thin band around the rule's boundaries.  No GPU needed."""

@@ -1,7 +1,7 @@
 """The sphere casts on the GPU against the numpy restatement (sweep_ref.py) on the edge scenes and query families of edge_sweeps.py: roots
 equal to t_min / t_max bit for bit, zero discriminants, stationary queries, lists full of equal tau, origins on widened box faces, radii
 that absorb the coordinates, inflated radii of zero, and the NaN / inf / denormal rays of edge_rays.py under edge radii and intervals.
-test_sweep_edges_cpu.py holds the restatement equal to its walk form, to lane_core.h's rule on the host and to a float64 brute force on
+test_sweep_edges_cpu.py holds the restatement equal to its walk form, to query_core.h's rule on the host and to a float64 brute force on
 these inputs.  Also here: device pointers that are not 16-byte aligned for the sweep, proximity and range-query entries, and a bounded run
 of tools/query_fuzz.py.  Every comparison is bit for bit (edge_rays.same_bits: any NaN matches any NaN)."""
 import functools

@@ -16,27 +16,33 @@ PASSES=(
 "GRBM_GUI_ACTIVE FETCH_SIZE"
 "GRBM_COUNT WRITE_SIZE"
 )
+# One profiler pass into directory $1 (log beside it).  The script ends at the first pass that fails, with that pass's exit status (a time
+# limit's 124 / 137 included): nothing more is started on the device, and no summary is written from a partial set.
+pass() {
+  local d=$1; shift
+  timeout -k 10 300 rocprofv3 "$@" > $d.log 2>&1 || { rc=$?; echo "pmc pass $(basename $d) failed: exit $rc ($d.log)"; exit $rc; }
+}
 cd /tmp
 for s in $SCENES; do for gd in $GDS; do
   np=${#PASSES[@]}
   [ "$gd" != "0" ] && np=2        # other launch sizes: instruction counts and LDS cycles only
   for ((i = 0; i < np; i++)); do
     d=$OUT/${s}_gd${gd}_p${i}
-    timeout 300 rocprofv3 --pmc ${PASSES[$i]} --kernel-trace --output-format csv -d $d -- $OLDPWD/build/rtbench -s $s -n 1000 -m 1000 -r 8 -v 3 -o sync_policy=1 $([ "$gd" = "0" ] || echo "-o grid_div=$gd -o deep_class=0") > $d.log 2>&1
+    pass $d --pmc ${PASSES[$i]} --kernel-trace --output-format csv -d $d -- $OLDPWD/build/rtbench -s $s -n 1000 -m 1000 -r 8 -v 3 -o sync_policy=1 $([ "$gd" = "0" ] || echo "-o grid_div=$gd -o deep_class=0")
   done
 done
 # batch launches (rt_render_batch, what bench.py times): 20 frames per launch, batch-only mode of rtbench
 for i in 0 1 3 4; do
   d=$OUT/${s}_batch20_p${i}
-  timeout 300 rocprofv3 --pmc ${PASSES[$i]} --kernel-trace --output-format csv -d $d -- $OLDPWD/build/rtbench -s $s -n 1000 -m 1000 -r 0 -B 20 > $d.log 2>&1
+  pass $d --pmc ${PASSES[$i]} --kernel-trace --output-format csv -d $d -- $OLDPWD/build/rtbench -s $s -n 1000 -m 1000 -r 0 -B 20
 done
 done
 # the 10^6-sphere frame (configs[4]): L2 hit rate and memory-side traffic -- the one workload whose scene exceeds the L2s
 if [ -z "$PMC_NO_BIG" ]; then
   i=0
-  for pass in "TCC_HIT_sum TCC_MISS_sum" "GRBM_GUI_ACTIVE FETCH_SIZE SQ_INSTS_VMEM" "GRBM_COUNT WRITE_SIZE SQ_INSTS_VALU"; do
+  for ctrs in "TCC_HIT_sum TCC_MISS_sum" "GRBM_GUI_ACTIVE FETCH_SIZE SQ_INSTS_VMEM" "GRBM_COUNT WRITE_SIZE SQ_INSTS_VALU"; do
     d=$OUT/big2000_p$i
-    timeout 300 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $d -- $OLDPWD/build/rtbench -s big -n 2000 -m 2000 -r 3 > $d.log 2>&1
+    pass $d --pmc $ctrs --kernel-trace --output-format csv -d $d -- $OLDPWD/build/rtbench -s big -n 2000 -m 2000 -r 3
     i=$((i+1))
   done
 fi

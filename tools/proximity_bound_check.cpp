@@ -1,4 +1,4 @@
-// proximity_bound_check.cpp -- CPU check of the box test rt_nearest_spheres prunes with (lane_core.h: box_may_hold, proximity_slack;
+// proximity_bound_check.cpp -- CPU check of the box test rt_nearest_spheres prunes with (query_core.h: box_may_hold, proximity_slack;
 // DESIGN.md 3.5e).  Not a product path: a hammer for a proof, in the CPU test suite (a short run).
 //
 // Scenes are built by the product's host builder (rt::build_lbvh: the same boxes the device builder writes, partial top boxes of tall trees
@@ -21,7 +21,7 @@
 #include <random>
 #include <vector>
 
-#include "lane_core.h"
+#include "query_core.h"
 #include "rt_host.hpp"
 
 using namespace rtk;

@@ -1,4 +1,4 @@
-// The per-sphere rule of the sphere casts (lane_core.h: sweep_contact, what sweep_lane runs at a leaf) on the host, over cases read from a
+// The per-sphere rule of the sphere casts (query_core.h: sweep_contact, what sweep_lane runs at a leaf) on the host, over cases read from a
 // file: the CPU suite holds the numpy restatement (tests/sweep_ref.py: rule_cases) equal to this arithmetic bit for bit, without a GPU.
 // A case is 13 float32: ray origin xyz, direction xyz, sphere centre xyz, sphere radius, query radius, t_min, t_max.  For each case two
 // uint32 are written: the kind (0 none, 1 entry contact, 2 overlap at the start) and tau's bits (0 for none).
@@ -8,7 +8,7 @@
 #include <cstring>
 #include <vector>
 
-#include "lane_core.h"
+#include "query_core.h"
 
 using namespace rtk;
 
