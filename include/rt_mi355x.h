@@ -339,6 +339,41 @@ int rt_sweep_spheres(rt_context *ctx, const rt_prepared *ps, int64_t n, const fl
 int rt_sweep_spheres_ranged(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, const float *radius_dev,
                             const float *t_min_dev, const float *t_max_dev, const int32_t *exclude_dev, int32_t k,
                             int32_t *count_dev, int32_t *index_dev, uint8_t *start_dev, float *hit7_dev);
+/* Ray paths: the mirror-bounce chain of each ray -- the sequence of spheres and hit points ray_colour (ray.fut:126-148) follows through up to
+ * max_depth bounces, exactly as the render path and rt_trace_rays run it (binary32, no contraction, the reference's association order).
+ * Iteration s = 0, 1, .. calls objs_hit objs r_s 0.0 1e9 (ray.fut:130, :76-86) on the current ray r_s, r_0 being the caller's; a #some hit is
+ * VERTEX s: bit for bit what rt_intersect_rays(.., 0.0f, 1e9f, ..) returns for r_s -- the sphere's index in L and {t, p.xyz, normal.xyz} --
+ * the (0.0, t + 1) re-intersection and ties to the lowest leaf included.  scatter (ray.fut:116-124): u = (1.0f / sqrtf(d.d)) * d,
+ * refl = u - (2.0f * dot(u, normal)) * normal; the chain continues iff dot(refl, normal) > 0.0f, with r_{s+1} = {hit.p, refl} and
+ * light = light * colour(L[j]) component-wise from (1, 1, 1).
+ * count_dev: n int32, the number of vertices -- every objs_hit that returned #some, an absorbing last one included; never capped at k,
+ *   0 <= count <= max_depth.
+ * end_dev: n uint8, how the loop left.  RT_PATH_ESCAPED: the last objs_hit was #none.  RT_PATH_ABSORBED: the last vertex's scatter was #none.
+ *   RT_PATH_TRUNCATED: max_depth vertices, each of which scattered (max_depth == 0: count 0, TRUNCATED).  The number of objs_hit calls is
+ *   count + (end == RT_PATH_ESCAPED).
+ * light3_dev (n x 3), last_ray6_dev (n x 6), colour3_dev (n x 3) float32: the loop variables light, r and the result at exit.  ESCAPED: r is the
+ *   ray that missed, colour = light * sky(r).  ABSORBED: r is the ray that hit the absorbing vertex, light does not include that vertex's colour,
+ *   colour = light * 0.  TRUNCATED: r is the scattered ray ray_colour never traced, light INCLUDES the last vertex's colour; colour is
+ *   ray_colour's light * 0 with the light before that vertex.  colour3 is rt_trace_rays's colour3, bit for bit.
+ * index_dev n x k int32, hit7_dev n x k x 7 float32, row-major per ray (64-bit offsets): the first min(count, k) vertices; the slots past
+ *   them are -1 and seven zero floats.  The answer for k = a is a prefix of the answer for k = b > a.
+ * Any output may be NULL, not all seven.  Refused (non-zero, rt_last_error set, nothing launched): as the other caller-ray entries (n out
+ * of range, NULL rays, a multi-device context), k < 1 or k > 1024, max_depth < 0, and a rays_per_wave that is neither 0 nor a multiple of
+ * 64 in [64, 4096].  n == 0 succeeds without a launch.  For a ray with a non-finite component or a zero direction the outputs are
+ * unspecified, but its lane terminates, count <= max_depth, end is one of the three codes, nothing is read or written out of range and no
+ * other ray's answer changes.
+ * One lane kernel under every variant: a wave owns rays_per_wave consecutive rays and its lanes pick up the block's next ray when theirs
+ * ends (chain lengths diverge: most rays end within four vertices, a few run to max_depth).  The shape changes no bit of the answer.
+ * rt_trace_paths chooses it: 64 while n <= 64 * 8 * CUs, above that the smallest multiple of 64 that keeps the grid at 8 * CUs waves, at
+ * most 256 (fitted to measurements: DESIGN.md 3.5h); rt_trace_paths_shaped takes it from the caller (0: the same rule).
+ * rt_context_last_launch: "family=paths k=<k> depth=<max_depth> rays/wave=<R>". */
+enum { RT_PATH_ESCAPED = 0, RT_PATH_ABSORBED = 1, RT_PATH_TRUNCATED = 2 };
+int rt_trace_paths(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, int32_t max_depth, int32_t k,
+                   int32_t *count_dev, uint8_t *end_dev, int32_t *index_dev, float *hit7_dev,
+                   float *light3_dev, float *last_ray6_dev, float *colour3_dev);
+int rt_trace_paths_shaped(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, int32_t max_depth, int32_t k,
+                          int32_t *count_dev, uint8_t *end_dev, int32_t *index_dev, float *hit7_dev,
+                          float *light3_dev, float *last_ray6_dev, float *colour3_dev, int32_t rays_per_wave);
 /* ---- proximity: the spheres nearest to caller-supplied points ------------------------------------------------------------------
  * For a point p and sphere j of the prepared scene's L (centre c, radius r) the gap is the signed distance from p to the sphere's surface,
  * negative inside, as exactly this float32 arithmetic (no contraction, correctly rounded sqrtf):

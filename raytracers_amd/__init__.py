@@ -10,6 +10,7 @@ from .api import (Context, Prepared, RtError, Scene, MAX_DEPTH, ROWS_PER_TILE, V
                   camera_rays_into, occluded_rays, occluded_rays_into, intersect_rays_ranged_into, occluded_rays_ranged_into,
                   multi_hit_rays, multi_hit_rays_into, multi_hit_rays_ranged_into,
                   sweep_spheres, sweep_spheres_into, sweep_spheres_ranged_into,
+                  trace_paths, trace_paths_into, PATH_ESCAPED, PATH_ABSORBED, PATH_TRUNCATED,
                   nearest_spheres, nearest_spheres_into, nearest_spheres_ranged_into,
                   spheres_within, spheres_within_count_into, spheres_within_fill_into,
                   contact_pairs, contact_pairs_count_into, contact_pairs_fill_into)

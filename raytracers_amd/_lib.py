@@ -21,7 +21,7 @@ RT_SYMBOLS = [
     "rt_render", "rt_render_part", "rt_render_image", "rt_render_batch", "rt_render_part_inplace", "rt_ipc_export", "rt_ipc_import", "rt_ipc_close", "rt_part_rows", "rt_place_part", "rt_place_parts", "rt_place_parts_strided", "rt_place_parts_batch", "rt_render_stats", "rt_render_trace",
     "rt_render_timed",
     "rt_trace_rays", "rt_intersect_rays", "rt_occluded_rays", "rt_intersect_rays_ranged", "rt_occluded_rays_ranged",
-    "rt_multi_hit_rays", "rt_multi_hit_rays_ranged", "rt_sweep_spheres", "rt_sweep_spheres_ranged", "rt_nearest_spheres", "rt_nearest_spheres_ranged", "rt_prepared_get_sphere_ids",
+    "rt_multi_hit_rays", "rt_multi_hit_rays_ranged", "rt_sweep_spheres", "rt_sweep_spheres_ranged", "rt_trace_paths", "rt_trace_paths_shaped", "rt_nearest_spheres", "rt_nearest_spheres_ranged", "rt_prepared_get_sphere_ids",
     "rt_spheres_within_count", "rt_spheres_within_fill", "rt_contact_pairs_count", "rt_contact_pairs_fill",
     "rt_camera_rays",
     "rt_device_alloc", "rt_device_free", "rt_copy_to_host", "rt_copy_to_device",
@@ -112,6 +112,8 @@ def _load():
         "rt_multi_hit_rays_ranged": (C.c_int, [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp]),
         "rt_sweep_spheres": (C.c_int, [vp, vp, i64, vp, C.c_float, C.c_float, C.c_float, i32, vp, vp, vp, vp]),
         "rt_sweep_spheres_ranged": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
+        "rt_trace_paths": (C.c_int, [vp, vp, i64, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "rt_trace_paths_shaped": (C.c_int, [vp, vp, i64, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32]),
         "rt_nearest_spheres": (C.c_int, [vp, vp, i64, vp, C.c_float, i32, vp, vp, vp]),
         "rt_nearest_spheres_ranged": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, vp, vp]),
         "rt_prepared_get_sphere_ids": (C.c_int, [vp, vp, vp]),

@@ -17,6 +17,7 @@ from ._lib import lib
 
 VARIANT_AUTO, VARIANT_PIXEL, VARIANT_PERSISTENT, VARIANT_POOLED = 0, 1, 2, 3
 MAX_DEPTH = 50          # ray.fut:154
+PATH_ESCAPED, PATH_ABSORBED, PATH_TRUNCATED = 0, 1, 2   # rt_trace_paths's end codes (RT_PATH_*)
 ROWS_PER_TILE = 8       # cyclic row-tile height of the multi-GPU partition
 
 
@@ -495,6 +496,22 @@ def multi_hit_rays_ranged_into(rays_ptr, n, prepared, t_min_ptr, t_max_ptr, k, c
                                             int(k), C.c_void_p(count_ptr), C.c_void_p(index_ptr), C.c_void_p(root_ptr), C.c_void_p(hit_ptr)))
 
 
+def trace_paths_into(rays_ptr, n, prepared, k, count_ptr=None, end_ptr=None, index_ptr=None, hit_ptr=None, light_ptr=None, last_ray_ptr=None,
+                     colour_ptr=None, max_depth=MAX_DEPTH, rays_per_wave=0):
+    """Enqueue the mirror-bounce chains of `n` rays (rt_trace_paths; rt_trace_paths_shaped when rays_per_wave is not 0): per ray the number
+    of vertices (n int32, not capped at k) to count_ptr, how the chain ended (n uint8: PATH_ESCAPED, PATH_ABSORBED, PATH_TRUNCATED) to end_ptr,
+    the first k vertices' sphere indices (n x k int32, -1 past the count) to index_ptr and {t, p.xyz, normal.xyz} (n x k x 7 float32) to
+    hit_ptr, and ray_colour's loop variables at exit: light (n x 3), the last ray (n x 6) and the colour (n x 3 float32, rt_trace_rays's).
+    Any pointer may be None, not all seven.  rays_per_wave: 0 (the library's rule), or the rays a wave owns, a multiple of 64 in [64, 4096];
+    it changes no bit of the answer."""
+    ctx = prepared.ctx
+    outs = [C.c_void_p(q) for q in (count_ptr, end_ptr, index_ptr, hit_ptr, light_ptr, last_ray_ptr, colour_ptr)]
+    if rays_per_wave == 0:
+        ctx._check(lib.rt_trace_paths(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), int(max_depth), int(k), *outs))
+    else:
+        ctx._check(lib.rt_trace_paths_shaped(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), int(max_depth), int(k), *outs, int(rays_per_wave)))
+
+
 def nearest_spheres_into(points_ptr, n, prepared, k, count_ptr, index_ptr, gap_ptr=None, max_dist=1e9):
     """Enqueue the proximity query of `n` points (n x 3 float32 at points_ptr; rt_nearest_spheres): per point, the spheres whose gap
     (signed distance from the point to the surface, negative inside) is <= max_dist, ordered by (gap, sphere index): their count
@@ -767,6 +784,23 @@ def sweep_spheres(prepared, rays, radius, k=1, t_min=0.0, t_max=1.0, exclude=Non
         else:
             sweep_spheres_into(ptr, n, prepared, radius, k, cnt.ptr, idx.ptr, start.ptr, hit.ptr, t_min, t_max)
         return (cnt.to_host((n,)), idx.to_host((n, k)), start.to_host((n, k), np.uint8), hit.to_host((n, k, 7), np.float32))
+
+
+def trace_paths(prepared, rays, k, max_depth=MAX_DEPTH, rays_per_wave=0):
+    """The mirror-bounce chain of every ray (rt_trace_paths): ray_colour's loop (ray.fut:126-148) with its vertices kept -> (count (n,) int32,
+    end (n,) uint8, index (n, k) int32, hit (n, k, 7) float32, light (n, 3), last_ray (n, 6), colour (n, 3) float32) numpy arrays.  Vertex s
+    of a ray is what intersect_rays(0, 1e9) gives for the chain's s-th ray; count is not capped at k; end is PATH_ESCAPED, PATH_ABSORBED or
+    PATH_TRUNCATED; light, last_ray and colour are the loop's variables at exit (colour: trace_rays's).  rays: an (n, 6) numpy array, or a
+    float32 device tensor used in place."""
+    k = int(k)
+    with _Scope(prepared.ctx) as s:
+        ptr, n = _device_rows(s, rays, *_RAYS)
+        nk = n * max(k, 0)
+        cnt, end, idx, hit = s.alloc(4 * n), s.alloc(n), s.alloc(4 * nk), s.alloc(28 * nk)
+        light, last, col = s.alloc(12 * n), s.alloc(24 * n), s.alloc(12 * n)
+        trace_paths_into(ptr, n, prepared, k, cnt.ptr, end.ptr, idx.ptr, hit.ptr, light.ptr, last.ptr, col.ptr, max_depth, rays_per_wave)
+        return (cnt.to_host((n,)), end.to_host((n,), np.uint8), idx.to_host((n, k)), hit.to_host((n, k, 7), np.float32),
+                light.to_host((n, 3), np.float32), last.to_host((n, 6), np.float32), col.to_host((n, 3), np.float32))
 
 
 def nearest_spheres(prepared, points, k, max_dist=1e9, count=True):

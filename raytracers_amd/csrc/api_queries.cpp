@@ -1,5 +1,5 @@
 // api_queries.cpp -- the caller queries of the rt_* surface (include/rt_mi355x.h): rays traced, intersected, tested for occlusion, multi-hit,
-// sphere casts, the proximity and range queries, contact pairs, a frame's primary rays.  Checks and launches only: the lane kernels are
+// sphere casts, ray paths, the proximity and range queries, contact pairs, a frame's primary rays.  Checks and launches only: the lane kernels are
 // query_kernels.hip, and where an entry runs the pooled family (rt_trace_rays, rt_occluded_rays[_ranged]) its plan, parameters and launch
 // are the render policy's (api.cpp, through rt_internal.hpp).
 #include <hip/hip_runtime.h>
@@ -266,11 +266,53 @@ extern "C" int rt_sweep_spheres_ranged(rt_context *ctx, const rt_prepared *ps, i
   return sweep_launch(ctx, ps, n, p, radius_dev, 0.0f, exclude_dev, k, count_dev, index_dev, start_dev, hit7_dev);
 }
 
+// a refusal's message behind the entry's name
+static int fail_in(rt_context *ctx, const char *what, const char *msg) { return fail(ctx, std::string(what) + msg); }
+
+// The path entries: checks, then the lane kernel under every variant.  rays_per_wave == 0: the auto rule (query_device.hpp:
+// paths_auto_per_wave, from the context's CU count).  The caller holds the context lock.
+static int paths_entry(rt_context *ctx, const rt_prepared *ps, const char *what, int64_t n, const float *rays_dev, int32_t max_depth, int32_t k,
+                       int32_t *count_dev, uint8_t *end_dev, int32_t *index_dev, float *hit7_dev, float *light3_dev, float *last_ray6_dev,
+                       float *colour3_dev, int32_t rays_per_wave) {
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!count_dev && !end_dev && !index_dev && !hit7_dev && !light3_dev && !last_ray6_dev && !colour3_dev)
+    return fail_in(ctx, what, ": all seven outputs are NULL");
+  if (k < 1 || k > rtk::kPathsMaxK) return fail_in(ctx, what, ": need 1 <= k <= 1024");
+  if (max_depth < 0) return fail_in(ctx, what, ": negative max_depth");
+  if (rays_per_wave != 0 && (rays_per_wave < 64 || rays_per_wave > rtk::kPathsMaxPerWave || rays_per_wave % 64 != 0))
+    return fail_in(ctx, what, ": rays_per_wave must be 0 or a multiple of 64 in [64, 4096]");
+  return locked_launch(ctx, ps, n, kNoRays, [&] {
+    const int per_wave = rays_per_wave != 0 ? rays_per_wave : rtk::paths_auto_per_wave(n, ctx->num_cu);
+    RT_HIP(ctx, rtk::launch_trace_paths(p, max_depth, k, per_wave, count_dev, end_dev, index_dev, hit7_dev, light3_dev, last_ray6_dev, colour3_dev,
+                                        ctx->stream));
+    ctx->last_launch = "family=paths k=" + std::to_string(k) + " depth=" + std::to_string(max_depth) + " rays/wave=" + std::to_string(per_wave);
+    return 0;
+  });
+}
+
+extern "C" int rt_trace_paths(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, int32_t max_depth, int32_t k,
+                              int32_t *count_dev, uint8_t *end_dev, int32_t *index_dev, float *hit7_dev, float *light3_dev,
+                              float *last_ray6_dev, float *colour3_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return paths_entry(ctx, ps, "rt_trace_paths", n, rays_dev, max_depth, k, count_dev, end_dev, index_dev, hit7_dev, light3_dev, last_ray6_dev,
+                     colour3_dev, 0);
+}
+
+extern "C" int rt_trace_paths_shaped(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, int32_t max_depth, int32_t k,
+                                     int32_t *count_dev, uint8_t *end_dev, int32_t *index_dev, float *hit7_dev, float *light3_dev,
+                                     float *last_ray6_dev, float *colour3_dev, int32_t rays_per_wave) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return paths_entry(ctx, ps, "rt_trace_paths_shaped", n, rays_dev, max_depth, k, count_dev, end_dev, index_dev, hit7_dev, light3_dev,
+                     last_ray6_dev, colour3_dev, rays_per_wave);
+}
+
 // The checks the point entries share, `what` being the entry's name in their messages (self: the points are the scene's own centres, *n
 // their number), and past them the parameter block of n points with exact_depth, the depth from which the walk tests boxes: the boxes
 // that contain their subtrees are those of the nodes whose subtree is at most `sweeps` levels tall (the AABB propagation's
 // floor(log2 n) + 2 Jacobi sweeps from zero boxes, bvh.fut:44-58), which every node at depth >= height - sweeps is.
-static int fail_in(rt_context *ctx, const char *what, const char *msg) { return fail(ctx, std::string(what) + msg); }
 static int point_entry_checks(rt_context *ctx, const rt_prepared *ps, const char *what, bool self, int64_t *n, const float *points3_dev) {
   if (!ps) return fail(ctx, "null prepared scene");
   if (ctx->group) return fail_in(ctx, what, ": a multi-device context is not supported (use a context on one device)");

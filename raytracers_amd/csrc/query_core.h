@@ -1,6 +1,6 @@
 // query_core.h -- per-lane arithmetic of the caller queries that no render-path kernel calls: both roots of a sphere and the sphere
-// casts' contact rule, the proximity queries' gap, box bound, slack and selection key.  Shared by query_kernels.hip and the host-side
-// checks (tools/sweep_check.cpp, tools/proximity_bound_check.cpp).  Same parity contract as lane_core.h, which holds what the render
+// casts' contact rule, the proximity queries' gap, box bound, slack and selection key, a ray path's bounce.  Shared by query_kernels.hip and the host-side
+// checks (tools/sweep_check.cpp, tools/path_check.cpp, tools/proximity_bound_check.cpp).  Same parity contract as lane_core.h, which holds what the render
 // path shares with the queries (box_hit_interval, sphere_hit_any, interval_ok, rehit_range).
 #pragma once
 #include "lane_core.h"
@@ -107,5 +107,47 @@ RT_HD bool point_ok(float px, float py, float pz) {
   return fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz)) <= 3.40282347e38f && px == px && py == py && pz == pz;
 }
 RT_HD bool max_dist_ok(float m) { return (m >= 0.0f) & (m <= kTMax); }
+
+// ---- ray paths: one iteration of ray_colour's loop behind objs_hit (rt_trace_paths) ---------------------------------
+// `have` / `t`: the re-intersection's result for the ray r (rehit_full), sphere {sp, colour sc, inv_rad = 1.0f / radius}; `light` the loop's
+// light, `depth` the number of vertices before this one.  Writes the vertex record hit7 = {t, p.xyz, normal.xyz} (seven zeros without a hit)
+// and the loop variables behind the iteration: the ray *nr, the light nl[3] and ray_colour's result col[3]; returns how the loop goes on.
+//   kPathContinue : the vertex scattered and depth + 1 < max_depth: nr = {p, reflected} with its derived fields, nl = light * colour
+//   kPathEscaped  : no hit.  nr = r, nl = light, col = light * sky(r) -- shade_ray_emit's sky arithmetic (lane_core.h)
+//   kPathAbsorbed : scatter gave #none (dot(reflected, normal) > 0 is false, NaN included).  nr = r, nl = light, col = light * 0
+//   kPathTruncated: the vertex scattered and was the max_depth-th: nr and nl as for kPathContinue (the ray ray_colour never traces, the light
+//                   with this vertex's colour), col = light * 0 with the light BEFORE the vertex, as ray_colour's tuple evaluates it
+// The arithmetic of a hit is shade_ray_emit's, operation for operation (normalise, the hit record, reflect, scatter's test); what differs
+// is what is kept: shade_ray_emit folds absorbed and truncated into one branch and updates neither the ray nor the light there.
+constexpr int kPathContinue = -1, kPathEscaped = 0, kPathAbsorbed = 1, kPathTruncated = 2;
+RT_HD int path_bounce(const Ray &r, bool have, float t, float spx, float spy, float spz, float scr, float scg, float scb, float inv_rad,
+                      float lr, float lg, float lb, int depth, int max_depth, float *hit7, Ray *nr, float *nl, float *col) {
+  const float inv_norm = 1.0f / sqrtf(r.a);   // normalise r.dir = scale (1/norm d) d
+  *nr = r;
+  nl[0] = lr; nl[1] = lg; nl[2] = lb;
+  if (!have) {
+    for (int q = 0; q < 7; ++q) hit7[q] = 0.0f;
+    const float uy = inv_norm * r.dy;
+    const float tt = 0.5f * (uy + 1.0f);
+    const float w = 1.0f - tt;
+    col[0] = lr * (w * 1.0f + tt * 0.5f); col[1] = lg * (w * 1.0f + tt * 0.7f); col[2] = lb * (w * 1.0f + tt * 1.0f);
+    return kPathEscaped;
+  }
+  const float hpx = r.ox + t * r.dx, hpy = r.oy + t * r.dy, hpz = r.oz + t * r.dz;
+  const float nx = inv_rad * (hpx - spx), ny = inv_rad * (hpy - spy), nz = inv_rad * (hpz - spz);
+  hit7[0] = t;
+  hit7[1] = hpx; hit7[2] = hpy; hit7[3] = hpz;
+  hit7[4] = nx; hit7[5] = ny; hit7[6] = nz;
+  const float ux = inv_norm * r.dx, uy = inv_norm * r.dy, uz = inv_norm * r.dz;
+  const float k = 2.0f * dot3(ux, uy, uz, nx, ny, nz);
+  const float rx = ux - k * nx, ry = uy - k * ny, rz = uz - k * nz;
+  col[0] = lr * 0.0f; col[1] = lg * 0.0f; col[2] = lb * 0.0f;
+  if (!(dot3(rx, ry, rz, nx, ny, nz) > 0.0f)) return kPathAbsorbed;
+  nr->ox = hpx; nr->oy = hpy; nr->oz = hpz;
+  nr->dx = rx; nr->dy = ry; nr->dz = rz;
+  ray_derive(*nr);
+  nl[0] = lr * scr; nl[1] = lg * scg; nl[2] = lb * scb;
+  return depth + 1 < max_depth ? kPathContinue : kPathTruncated;
+}
 
 }  // namespace rtk

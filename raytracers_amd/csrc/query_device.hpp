@@ -43,6 +43,21 @@ hipError_t launch_within_fill(const KParams &p, const float *pts, const float *m
 constexpr int kSweepMaxK = 32;
 hipError_t launch_sweep_spheres(const KParams &p, const float *radius_dev, float radius, const int32_t *exclude, int k, int32_t *count,
                                 int32_t *index, uint8_t *start, float *hit7, hipStream_t stream);
+// rt_trace_paths[_shaped]: the bounce chain of each ray (ray_colour with objs_hit r 0 1e9, up to max_depth >= 0 vertices): count[i], end[i]
+// (kPathEscaped / kPathAbsorbed / kPathTruncated, query_core.h), the first min(count, k) vertices at index [i * k + s] and hit7
+// [(i * k + s) * 7 ..] (1 <= k <= kPathsMaxK; padded with -1 and seven zeros), light3 / last_ray6 / colour3 [i]: the loop variables at exit
+// (any may be nullptr, not all).  One wave per `per_wave` consecutive rays (a multiple of 64 in [64, kPathsMaxPerWave]): its lanes refill
+// from the block in-wave.  paths_auto_per_wave: the launch shape of rt_trace_paths (fitted to the measured sweep)
+constexpr int kPathsMaxK = 1024, kPathsMaxPerWave = 4096;
+constexpr int kPathsWavesPerCu = 8, kPathsAutoCap = 256;
+inline int paths_auto_per_wave(int64_t n, int num_cu) {
+  const int64_t waves = (int64_t)kPathsWavesPerCu * (num_cu > 0 ? num_cu : 1);
+  if (n <= 64 * waves) return 64;
+  const int64_t per = ((n + waves - 1) / waves + 63) / 64 * 64;
+  return (int)(per < kPathsAutoCap ? per : kPathsAutoCap);
+}
+hipError_t launch_trace_paths(const KParams &p, int max_depth, int k, int per_wave, int32_t *count, uint8_t *end, int32_t *index, float *hit7,
+                              float *light3, float *last_ray6, float *colour3, hipStream_t stream);
 // the primary rays of an h x w frame through p.cam (get_ray at pixel_u / pixel_v), row-major from the top row: rays[6 (row w + col) ..]
 hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStream_t stream);
 

@@ -1,5 +1,5 @@
 // query_kernels.hip -- the lane kernels of the caller queries, one lane per ray or point: closest hit (rt_intersect_rays), occlusion
-// (rt_occluded_rays), multi-hit, sphere casts, the nearest spheres, the range queries / contact pairs with their scan, and the primary
+// (rt_occluded_rays), multi-hit, sphere casts, ray paths, the nearest spheres, the range queries / contact pairs with their scan, and the primary
 // rays of a frame (rt_camera_rays).  The render path -- pixel_kernel, persistent_kernel, pooled_kernel and their RAYS modes -- is
 // render_kernels.hip; nothing here is launched by a render entry.  Build: as render_kernels.hip (-ffp-contract=off, bit-exact fp32).
 #include <hip/hip_runtime.h>
@@ -723,6 +723,166 @@ hipError_t launch_within_fill(const KParams &p, const float *pts, const float *m
   else
     hipLaunchKernelGGL((within_kernel<true, false>), grid, block, 0, stream, p, pts, max_dist_dev, max_dist, first_dev, exact_depth, nullptr, offsets,
                        capacity, index, gap, point);
+  return hipGetLastError();
+}
+
+// rt_trace_paths: the mirror-bounce chain of each ray -- ray_colour's loop (ray.fut:126-148) with every vertex kept.  One wave per
+// workgroup; the wave owns the block of `per_wave` consecutive rays [blockIdx.x * per_wave, ...) and its lanes start on the block's first 64.
+// A lane holds one ray's loop state (the ray, light, depth) and the fold of the current objs_hit: intersect_lane's stack walk over (0, 1e9)
+// (box_hit_interval, sphere_root / closest_update), then rehit_range(r, 0.0f, best, ..) and path_bounce (query_core.h).  Vertex s is stored
+// when it is found, at slot s < k of the ray's row, so k costs no registers; the padding behind min(count, k) and the per-ray outputs are
+// written when the ray ends.
+// Phases: lanes whose stack is not empty walk one node per step; a lane whose fold is finished waits until kPathsVote lanes wait or nobody
+// walks, then those lanes bounce together (the bounce is ~10 node steps long: two divisions and two square roots).
+// Refill: behind a bounce phase the idle lanes (ray ended, or none yet) claim the block's next unclaimed rays in lane order -- a ballot of
+// the idle lanes, each one's rank among them by mbcnt, the cursor advanced by their number: wave-uniform, no atomics, no barriers.  The
+// wave leaves when no lane holds a ray and the block is used up.  Every loop is bounded: the walk by the tree (sp <= height + 1), the bounces
+// of a ray by max_depth, the refills by per_wave, the padding by k.  Ray i's outputs are a function of ray i alone: per_wave cannot
+// change a bit.  A non-finite or zero-direction ray takes the same bounded loops (its compares fail or pass, nothing else).
+constexpr int kPathsVote = 24;   // (measured against 1, 8, 40 and 64: DESIGN.md 3.5h)
+__global__ __launch_bounds__(64) void paths_kernel(KParams p, int max_depth, int k, int per_wave, int32_t *count, uint8_t *end, int32_t *index,
+                                                   float *hit7, float *light3, float *last_ray6, float *colour3) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const long long block_lo = (long long)blockIdx.x * per_wave;
+  const long long block_hi = block_lo + per_wave < (long long)p.nrays ? block_lo + per_wave : (long long)p.nrays;
+  long long cursor = block_lo;   // the block's next unclaimed ray (wave-uniform)
+  bool active = false;
+  int i = 0, sp = 0, depth = 0, bestj = -1;
+  float best = kTMax, lr = 1.0f, lg = 1.0f, lb = 1.0f;
+  Ray r = {};
+
+  // the ray has ended: its padding and per-ray outputs (cnt vertices, the first min(cnt, k) already stored)
+  auto finish = [&](int code, int cnt, const Ray &last, const float *lt, const float *col) {
+    if (count != nullptr) count[i] = cnt;
+    if (end != nullptr) end[i] = (uint8_t)code;
+    const size_t row = (size_t)i * (size_t)k;
+    for (int s = cnt < k ? cnt : k; s < k; ++s) {
+      if (index != nullptr) index[row + s] = -1;
+      if (hit7 != nullptr) {
+        float *const o = hit7 + (row + s) * 7;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) o[q] = 0.0f;
+      }
+    }
+    if (light3 != nullptr) {
+      float *const o = light3 + (size_t)i * 3;
+      o[0] = lt[0]; o[1] = lt[1]; o[2] = lt[2];
+    }
+    if (last_ray6 != nullptr) {
+      float *const o = last_ray6 + (size_t)i * 6;
+      o[0] = last.ox; o[1] = last.oy; o[2] = last.oz;
+      o[3] = last.dx; o[4] = last.dy; o[5] = last.dz;
+    }
+    if (colour3 != nullptr) {
+      float *const o = colour3 + (size_t)i * 3;
+      o[0] = col[0]; o[1] = col[1]; o[2] = col[2];
+    }
+  };
+
+  for (;;) {
+    // refill: the idle lanes claim the next rays of the block
+    const unsigned long long idle = __ballot(!active);
+    if (idle != 0ull && cursor < block_hi) {
+      const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
+      const long long mine = cursor + rank;
+      if (!active && mine < block_hi) {
+        i = (int)mine;
+        r = load_ray(p.rays, i);
+        lr = lg = lb = 1.0f;
+        depth = 0;
+        if (max_depth > 0) {
+          active = true;
+          best = kTMax;
+          bestj = -1;
+          stack[0][lane] = 0;
+          sp = 1;
+        } else {
+          // `while depth < 0`: no objs_hit at all -- the initial loop variables, colour (0, 0, 0)
+          const float lt[3] = {1.0f, 1.0f, 1.0f}, col[3] = {0.0f, 0.0f, 0.0f};
+          finish(kPathTruncated, 0, r, lt, col);
+        }
+      }
+      cursor += __popcll(idle);
+    }
+    const unsigned long long act = __ballot(active);
+    if (act == 0ull) {
+      if (cursor >= block_hi) break;
+      continue;
+    }
+    // walk: one node per step, until enough lanes wait with a finished fold
+    for (;;) {
+      const bool walking = active && sp > 0;
+      const unsigned long long wk = __ballot(walking);
+      if (wk == 0ull || __popcll(act) - __popcll(wk) >= kPathsVote) break;
+      if (walking) {
+        const int ni = stack[--sp][lane];
+        const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+        if (box_hit_interval(r, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, 0.0f, kTMax)) {
+          const int kids[2] = {f2i(lo.w), f2i(hi.w)};
+#pragma unroll
+          for (int c2 = 0; c2 < 2; ++c2) {
+            const int c = kids[c2];
+            if (c < 0) {
+              const int j = ~c;
+              const float4 s = buf_load16(rs_sph, j * 16);
+              closest_update(sphere_root(r, s.x, s.y, s.z, s.w), j, best, bestj);
+            } else {
+              stack[sp++][lane] = c;   // (at most one pending sibling per level: sp <= tree height + 1 <= kStackPixel)
+            }
+          }
+        }
+      }
+    }
+    // bounce: the lanes whose fold is finished
+    if (active && sp == 0) {
+      float t = 0.0f;
+      bool have = false;
+      float4 s = make_float4(0.f, 0.f, 0.f, 0.f), c = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (bestj >= 0) {
+        s = p.sph[bestj];
+        c = p.col[bestj];   // {colour, 1.0f / radius}
+        have = rehit_range(r, 0.0f, best, s.x, s.y, s.z, s.w, &t);
+      }
+      float h[7], nl[3], col[3];
+      Ray nr;
+      const int code = path_bounce(r, have, t, s.x, s.y, s.z, c.x, c.y, c.z, c.w, lr, lg, lb, depth, max_depth, h, &nr, nl, col);
+      if (have && depth < k) {
+        const size_t slot = (size_t)i * (size_t)k + (size_t)depth;
+        if (index != nullptr) index[slot] = bestj;
+        if (hit7 != nullptr) {
+          float *const o = hit7 + slot * 7;
+#pragma unroll
+          for (int q = 0; q < 7; ++q) o[q] = h[q];
+        }
+      }
+      if (code == kPathContinue) {
+        r = nr;
+        lr = nl[0]; lg = nl[1]; lb = nl[2];
+        depth += 1;
+        best = kTMax;
+        bestj = -1;
+        stack[0][lane] = 0;
+        sp = 1;
+      } else {
+        finish(code, have ? depth + 1 : depth, nr, nl, col);
+        active = false;
+      }
+    }
+  }
+}
+
+hipError_t launch_trace_paths(const KParams &p, int max_depth, int k, int per_wave, int32_t *count, uint8_t *end, int32_t *index, float *hit7,
+                              float *light3, float *last_ray6, float *colour3, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (max_depth < 0 || k < 1 || k > kPathsMaxK || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (per_wave < 64 || per_wave > kPathsMaxPerWave || per_wave % 64 != 0) return hipErrorInvalidValue;
+  if (count == nullptr && end == nullptr && index == nullptr && hit7 == nullptr && light3 == nullptr && last_ray6 == nullptr && colour3 == nullptr)
+    return hipErrorInvalidValue;
+  const unsigned grid = (unsigned)(((long long)p.nrays + per_wave - 1) / per_wave);
+  hipLaunchKernelGGL(paths_kernel, dim3(grid), dim3(64), 0, stream, p, max_depth, k, per_wave, count, end, index, hit7, light3, last_ray6, colour3);
   return hipGetLastError();
 }
 
