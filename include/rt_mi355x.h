@@ -77,6 +77,7 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *   "family=sweep k=K" [" (per-query)"] [" exclude"]   rt_sweep_spheres / rt_sweep_spheres_ranged (K: the caller's k)
  *   "family=nearest k=K[ pruned][ (per-point)]" | "family=none (no points)"   rt_nearest_spheres / rt_nearest_spheres_ranged (below)
  *   "family=within count|fill[ (per-point)][ first][ self]"   rt_spheres_within_count / _fill, rt_contact_pairs_count / _fill (" self"; below)
+ *   "family=boxes count|fill[ (per-box)][ first]"   rt_spheres_in_boxes_count / _fill (below)
  *   "family=none (no rows)"       the part owns no row of the image
  *   "family=pixel" | "family=pixel (instrumented)" | "family=persistent"
  *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2[ nodes=sign-ordered|planes]"
@@ -438,6 +439,34 @@ int rt_spheres_within_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, co
 int rt_contact_pairs_count(rt_context *ctx, const rt_prepared *ps, float margin, int64_t *offsets_dev);
 int rt_contact_pairs_fill(rt_context *ctx, const rt_prepared *ps, float margin, const int64_t *offsets_dev, int64_t capacity,
                           int32_t *pair_dev, float *gap_dev);
+/* ---- box queries: EVERY sphere that meets a caller-supplied axis-aligned box, with no cap ---------------------------------------------
+ * A query is a box {lo.xyz, hi.xyz} and a margin.  boxes6_dev: n x 6 float32 in the context's device memory, rows of 24 bytes; only 4-byte
+ * alignment is assumed.  For sphere j of L (centre c, radius r) the gap is the signed distance from the box to the sphere's surface, in
+ * exactly this float32 arithmetic (no contraction, correctly rounded sqrtf):
+ *   ex = fmaxf(fmaxf(lo.x - c.x, c.x - hi.x), 0.0f);   ey, ez likewise;   gap = sqrtf((ex*ex + ey*ey) + ez*ez) - r
+ * Sphere j is selected iff gap <= margin -- and, where first_dev is given, j >= first_dev[i].  Margin 0 is the exact closed sphere / box
+ * overlap test: tangency (gap == 0) is selected; it is not the overlap of the sphere's own bounding box with the box.  A sphere whose
+ * centre lies inside the box has gap -r.  Brute force over all spheres defines the answer; no tree, builder or variant enters it.
+ * IDENTITY: with lo == hi == p the expression is rt_nearest_spheres's gap of the point p, bit for bit (the excess of an axis is |fl(p - c)|),
+ * so a degenerate box reproduces rt_spheres_within_* at p with max_dist = margin exactly: offsets, index and gap bits.
+ * A box is valid iff its six components are finite and lo_k <= hi_k for every k; zero extent in any or all axes is valid.  A per-box margin
+ * follows the per-point bounds' rule: NaN, +-inf, negative or above 1e9 is invalid, -0.0 behaves as 0.0.  An invalid box or margin gives an
+ * empty row.  Exact for scenes whose spheres are finite with radius >= 0; for other scenes unspecified, but nothing is read or written out of
+ * range.
+ * The output is rt_spheres_within_count / _fill's, with the same two-phase protocol: offsets (n + 1 int64), then index (int32, ASCENDING j
+ * within a row), gap (float32) and point (int32, the row number of each entry: the COO form); any of the last three may be NULL, not all.
+ * _fill writes entry offsets[i] + rank only below offsets[i + 1] and below capacity: negative or foreign offsets never cause a write outside
+ * [0, capacity).  margin_dev == NULL: the scalar margin for every box; otherwise n float32, one margin per box, and the scalar is ignored.
+ * first_dev: as for rt_spheres_within_*.
+ * Refused (non-zero, rt_last_error set, nothing launched or written): a null scene, a multi-device context, n < 0 or n >= 2^31, NULL
+ * boxes6_dev, NULL offsets_dev, a negative capacity, every output NULL, a scalar margin (when it is used) outside [0, 1e9] or not finite.
+ * n == 0 succeeds and _count still writes offsets_dev[0] = 0.  One lane per box under every variant; rt_context_last_launch:
+ * "family=boxes count" / "family=boxes fill", then " (per-box)" with margin_dev, " first" with first_dev. */
+int rt_spheres_in_boxes_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *boxes6_dev, float margin,
+                              const float *margin_dev, const int32_t *first_dev, int64_t *offsets_dev);
+int rt_spheres_in_boxes_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *boxes6_dev, float margin,
+                             const float *margin_dev, const int32_t *first_dev, const int64_t *offsets_dev, int64_t capacity,
+                             int32_t *index_dev, float *gap_dev, int32_t *point_dev);
 /* ids_dev: n int32 in the context's device memory; ids_dev[i] = the caller's index of L[i]: the position in spheres7 given to
  * rt_scene_from_spheres / rt_prepare_scene_device / the last rt_prepared_update_spheres, or in the generator's output for rt_scene_rgbbox /
  * _irreg / _floor.  The Morton sort is stable, so both builders (option gpu_build) give the same ids, ascending within a run of equal keys.

@@ -552,6 +552,26 @@ def spheres_within_fill_into(points_ptr, n, prepared, offsets_ptr, capacity, ind
                                           C.c_void_p(gap_ptr), C.c_void_p(point_ptr)))
 
 
+def spheres_in_boxes_count_into(boxes_ptr, n, prepared, offsets_ptr, margin=0.0, margin_ptr=None, first_ptr=None):
+    """Enqueue the count pass of the box query of `n` boxes (n x 6 float32 at boxes_ptr, rows {lo.xyz, hi.xyz}; rt_spheres_in_boxes_count):
+    offsets_ptr receives n + 1 int64, offsets[i + 1] - offsets[i] = the number of spheres whose gap to box i is <= the box's margin -- the scalar
+    margin, or margin_ptr[i] (n float32 on the device) -- and index >= first_ptr[i] (n int32 on the device; None: no lower bound).
+    Asynchronous, as spheres_within_count_into; then call spheres_in_boxes_fill_into with the same arguments."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_spheres_in_boxes_count(ctx._h, prepared._h, int(n), C.c_void_p(boxes_ptr), float(margin), C.c_void_p(margin_ptr),
+                                             C.c_void_p(first_ptr), C.c_void_p(offsets_ptr)))
+
+
+def spheres_in_boxes_fill_into(boxes_ptr, n, prepared, offsets_ptr, capacity, index_ptr, gap_ptr=None, point_ptr=None, margin=0.0,
+                               margin_ptr=None, first_ptr=None):
+    """Enqueue the fill pass (rt_spheres_in_boxes_fill) for the offsets of spheres_in_boxes_count_into on the same boxes, margins and scene:
+    the arrays of spheres_within_fill_into (point_ptr: the row, i.e. box, number of each entry); nothing is written at or past `capacity`."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_spheres_in_boxes_fill(ctx._h, prepared._h, int(n), C.c_void_p(boxes_ptr), float(margin), C.c_void_p(margin_ptr),
+                                            C.c_void_p(first_ptr), C.c_void_p(offsets_ptr), int(capacity), C.c_void_p(index_ptr),
+                                            C.c_void_p(gap_ptr), C.c_void_p(point_ptr)))
+
+
 def contact_pairs_count_into(prepared, offsets_ptr, margin=0.0):
     """Enqueue the count pass of the scene's contact pairs (rt_contact_pairs_count): offsets_ptr receives num_spheres + 1 int64, row i counting
     the j > i with gap(centre_i, L[j]) <= radius_i + margin.  Asynchronous, as spheres_within_count_into."""
@@ -633,6 +653,7 @@ def _check_tensor(t, dev, dtype, name):
 
 _RAYS = ("rays", 6, "rays must be (n, 6): origin.xyz, dir.xyz")
 _POINTS = ("points", 3, "points must be (n, 3)")
+_BOXES = ("boxes", 6, "boxes must be (n, 6): lo.xyz, hi.xyz")
 
 
 def _device_rows(scope, rows, name, cols, shape_error):
@@ -855,6 +876,35 @@ def spheres_within(prepared, points, max_dist, first=None, gaps=True, rows=False
         if total:
             spheres_within_fill_into(ptr, n, prepared, off.ptr, total, idx.ptr, gap.ptr if gap else None, row.ptr if row else None, md,
                                      md_ptr, first_ptr)
+        res = (offsets, idx.to_host((total,)), gap.to_host((total,), np.float32) if gap else None)
+        return res + (row.to_host((total,)),) if rows else res
+
+
+def spheres_in_boxes(prepared, boxes, margin=0.0, first=None, gaps=True, rows=False):
+    """EVERY sphere that meets every axis-aligned box (rt_spheres_in_boxes_count / _fill), with no cap, in spheres_within's CSR form ->
+    (offsets (n + 1,) int64, index (total,) int32, gap (total,) float32 or None[, point (total,) int32]) numpy arrays.  `boxes`: (n, 6)
+    float32, rows (lo.xyz, hi.xyz), a numpy array or a device tensor.  Sphere j is selected for box i iff its gap -- in float32,
+    e_k = max(lo_k - c_k, c_k - hi_k, 0), gap = sqrtf((ex*ex + ey*ey) + ez*ez) - r: the signed distance from the box to the sphere's surface, -r
+    where the centre is inside the box -- is <= the box's margin.  margin 0 is the exact closed sphere / box overlap test (tangency is
+    selected).  A box with lo == hi == p selects exactly what spheres_within selects at p with max_dist = margin, with the same gap bits.
+    margin: a scalar in [0, 1e9], or an (n,) array / device tensor, one per box (an invalid one gives an empty row).  A box with a
+    non-finite component or lo_k > hi_k has an empty row; zero extent is valid.  first, gaps, rows and the row order (ASCENDING sphere index
+    into L): as spheres_within."""
+    ranged = _is_bound_array(margin)
+    with _Scope(prepared.ctx) as s:
+        ptr, n = _device_rows(s, boxes, *_BOXES)
+        dev = s.ctx.device_info()["device"]
+        mg_ptr = _device_bound(s, dev, n, "margin", margin, per="box") if ranged else None
+        mg = 0.0 if ranged else margin
+        first_ptr = _device_first(s, dev, n, first, per="box") if first is not None else None
+        off = s.alloc(8 * (n + 1))
+        spheres_in_boxes_count_into(ptr, n, prepared, off.ptr, mg, mg_ptr, first_ptr)
+        offsets = off.to_host((n + 1,), np.int64)
+        total = int(offsets[n])
+        idx, gap, row = (s.alloc(4 * total) if want else None for want in (True, gaps, rows))
+        if total:
+            spheres_in_boxes_fill_into(ptr, n, prepared, off.ptr, total, idx.ptr, gap.ptr if gap else None, row.ptr if row else None, mg,
+                                       mg_ptr, first_ptr)
         res = (offsets, idx.to_host((total,)), gap.to_host((total,), np.float32) if gap else None)
         return res + (row.to_host((total,)),) if rows else res
 

@@ -443,6 +443,55 @@ extern "C" int rt_contact_pairs_fill(rt_context *ctx, const rt_prepared *ps, flo
                       nullptr, gap_dev, pair_dev);
 }
 
+// The box entries (rt_spheres_in_boxes_*): the range entries' checks in the boxes' words, then boxes_lane under every variant; the count pass
+// shares the range queries' cached scratch.
+static int boxes_entry(rt_context *ctx, const rt_prepared *ps, const char *what, bool fill, int64_t n, const float *boxes6_dev, float margin,
+                       const float *margin_dev, const int32_t *first_dev, int64_t *offsets_dev, int64_t capacity, int32_t *index_dev,
+                       float *gap_dev, int32_t *point_dev) {
+  if (!ps) return fail(ctx, "null prepared scene");
+  if (ctx->group) return fail_in(ctx, what, ": a multi-device context is not supported (use a context on one device)");
+  if (n < 0 || n >= (int64_t(1) << 31)) return fail_in(ctx, what, ": box count out of range: 0 <= n < 2^31");
+  if (!boxes6_dev) return fail_in(ctx, what, ": null boxes pointer");
+  if (!offsets_dev) return fail_in(ctx, what, ": null offsets pointer");
+  if (fill && capacity < 0) return fail_in(ctx, what, ": negative capacity");
+  if (fill && !index_dev && !gap_dev && !point_dev) return fail_in(ctx, what, ": every output is NULL");
+  if (!margin_dev && !distance_ok(margin)) return fail_in(ctx, what, ": need 0 <= margin <= 1e9, finite");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  int exact_depth;
+  const rtk::KParams p = point_params(ps, n, &exact_depth);
+  if (fill) {
+    ctx->synced_since_render = false;
+    RT_HIP(ctx, rtk::launch_boxes_fill(p, boxes6_dev, margin_dev, margin, first_dev, exact_depth, offsets_dev, capacity, index_dev, gap_dev, point_dev,
+                                       ctx->stream));
+  } else {
+    char *scratch = nullptr;
+    if (n > 0 && within_scratch(ctx, n, &scratch) != 0) return 1;
+    ctx->synced_since_render = false;
+    RT_HIP(ctx, rtk::launch_boxes_count(p, boxes6_dev, margin_dev, margin, first_dev, exact_depth, scratch, offsets_dev, ctx->stream));
+  }
+  ctx->last_launch = std::string(fill ? "family=boxes fill" : "family=boxes count") + (margin_dev ? " (per-box)" : "") + (first_dev ? " first" : "");
+  return 0;
+}
+
+extern "C" int rt_spheres_in_boxes_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *boxes6_dev, float margin,
+                                         const float *margin_dev, const int32_t *first_dev, int64_t *offsets_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return boxes_entry(ctx, ps, "rt_spheres_in_boxes_count", false, n, boxes6_dev, margin, margin_dev, first_dev, offsets_dev, 0, nullptr, nullptr,
+                     nullptr);
+}
+
+extern "C" int rt_spheres_in_boxes_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *boxes6_dev, float margin,
+                                        const float *margin_dev, const int32_t *first_dev, const int64_t *offsets_dev, int64_t capacity,
+                                        int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return boxes_entry(ctx, ps, "rt_spheres_in_boxes_fill", true, n, boxes6_dev, margin, margin_dev, first_dev, const_cast<int64_t *>(offsets_dev),
+                     capacity, index_dev, gap_dev, point_dev);
+}
+
 extern "C" int rt_prepared_get_sphere_ids(rt_context *ctx, const rt_prepared *ps, int32_t *ids_dev) {
   if (!ctx) return 1;
   RT_LOCK(ctx);

@@ -1,6 +1,7 @@
 // query_core.h -- per-lane arithmetic of the caller queries that no render-path kernel calls: both roots of a sphere and the sphere
-// casts' contact rule, the proximity queries' gap, box bound, slack and selection key, a ray path's bounce.  Shared by query_kernels.hip and the host-side
-// checks (tools/sweep_check.cpp, tools/path_check.cpp, tools/proximity_bound_check.cpp).  Same parity contract as lane_core.h, which holds what the render
+// casts' contact rule, the proximity queries' gap, box bound, slack and selection key, the box queries' gap and node test, a ray path's bounce.  Shared by
+// query_kernels.hip and the host-side checks (tools/sweep_check.cpp, tools/path_check.cpp, tools/proximity_bound_check.cpp,
+// tools/box_query_bound_check.cpp).  Same parity contract as lane_core.h, which holds what the render
 // path shares with the queries (box_hit_interval, sphere_hit_any, interval_ok, rehit_range).
 #pragma once
 #include "lane_core.h"
@@ -107,6 +108,55 @@ RT_HD bool point_ok(float px, float py, float pz) {
   return fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz)) <= 3.40282347e38f && px == px && py == py && pz == pz;
 }
 RT_HD bool max_dist_ok(float m) { return (m >= 0.0f) & (m <= kTMax); }
+
+// ---- box queries: the spheres that meet an axis-aligned box (rt_spheres_in_boxes_*) ---------------------------------
+// A caller's box {lo, hi}.  Valid iff its six components are finite and lo_k <= hi_k for every k (zero extent is valid); an invalid box
+// gets no walk, as a point failing point_ok.
+struct QBox {
+  float lox, loy, loz, hix, hiy, hiz;
+};
+RT_HD bool qbox_ok(const QBox &q) {
+  return box_mag(q.lox, q.loy, q.loz, q.hix, q.hiy, q.hiz) <= 3.40282347e38f && q.lox <= q.hix && q.loy <= q.hiy && q.loz <= q.hiz;   // (a NaN fails a <=)
+}
+// The gap of box q to sphere (c, r): the signed distance from the box to the sphere's surface, -r where the centre is inside the box.  This
+// exact binary32 arithmetic IS the definition (as point_gap: no contraction, a correctly rounded sqrtf).  With lo == hi == p the excess of an
+// axis is fmaxf(fmaxf(p - c, c - p), 0) = |fl(p - c)| (fl(c - p) = -fl(p - c)), whose square is point_gap's dx * dx: box_gap of a degenerate
+// box IS point_gap(p, ...), bit for bit.
+RT_HD float box_gap(const QBox &q, float cx, float cy, float cz, float r) {
+  const float ex = fmaxf(fmaxf(q.lox - cx, cx - q.hix), 0.0f);
+  const float ey = fmaxf(fmaxf(q.loy - cy, cy - q.hiy), 0.0f);
+  const float ez = fmaxf(fmaxf(q.loz - cz, cz - q.hiz), 0.0f);
+  return sqrtf(dot3(ex, ey, ez, ex, ey, ez)) - r;
+}
+// The box-to-box distance of q and the node's box [lo, hi], computed in binary32.  With q.lo == q.hi == p it is box_gap_bound(p, lo, hi),
+// operation for operation (lo - p, p - hi), so the walk of a degenerate box is the point walk.
+RT_HD float box_box_bound(const QBox &q, float lox, float loy, float loz, float hix, float hiy, float hiz) {
+  const float ex = fmaxf(fmaxf(lox - q.hix, q.lox - hix), 0.0f);
+  const float ey = fmaxf(fmaxf(loy - q.hiy, q.loy - hiy), 0.0f);
+  const float ez = fmaxf(fmaxf(loz - q.hiz, q.loz - hiz), 0.0f);
+  return sqrtf(dot3(ex, ey, ez, ex, ey, ez));
+}
+// The slack of the box-to-box test.  u, M and t as for proximity_slack; now g is the exact gap of the box q to a sphere (c, r) below the node
+// (the exact distance from q to c, minus r), G = box_gap (computed), B = box_box_bound (computed), and P = the largest magnitude among
+// q's SIX coordinates.  Every excess, at the leaf and at the node, is still ONE rounded subtraction of a query coordinate and a scene
+// coordinate, then clamped: fl is monotone and odd, so fmaxf(fmaxf(fl(a), fl(b)), 0) = fl(max(a, b, 0)) = (exact excess)(1 + e), |e| <= u --
+// the clamps add no error, and an excess is at most P + M in magnitude.  So the three steps keep their coefficients:
+//   (Q1)  |G - g| <= 4.6 u D + u r + 2^-62,   D = the exact distance from q to c <= sqrt(3) (P + M) (1 + 3u),  r <= M (1 + 2u)
+//         (P1's chain on the three excesses in place of p - c)
+//   (Q2)  the stored box misses at most d = u M (1 + 2u) of the sphere's exact box on each side (P2), so per axis the exact excess of q
+//         against the node's box is at most a_k + d, a_k = max(c_k - r - qhi_k, qlo_k - c_k - r, 0) being the excess against the sphere's exact
+//         box; the ball lies inside that box, so |a| <= max(g, 0), and the exact box-to-box distance is at most max(g, 0) + sqrt(3) d
+//   (Q3)  B <= (1 + 3.5 u) (exact box-to-box distance) + 2^-62 (P3's chain)
+// Hence G <= T implies B <= t + u (3.6 t + 9.8 P + 12.6 M) + 2^-61 exactly as for points, and proximity_slack(t, P, M) with this P covers it
+// with the same factor of two to spare.  P must be the maximum over all six coordinates: an excess subtracts q.hi on one side and q.lo on the
+// other.  tools/box_query_bound_check.cpp searches for counterexamples; with the slack set to 0 it finds them (the degenerate boxes alone
+// guarantee that: they are the point checker's cases).
+RT_HD bool box_may_meet(const QBox &q, float qmag, float lox, float loy, float loz, float hix, float hiy, float hiz, float T,
+                        float slack_scale = 1.0f) {
+  const float t = fmaxf(T, 0.0f);
+  const float b = box_box_bound(q, lox, loy, loz, hix, hiy, hiz);
+  return !(b > t + slack_scale * proximity_slack(t, qmag, box_mag(lox, loy, loz, hix, hiy, hiz)));
+}
 
 // ---- ray paths: one iteration of ray_colour's loop behind objs_hit (rt_trace_paths) ---------------------------------
 // `have` / `t`: the re-intersection's result for the ray r (rehit_full), sphere {sp, colour sc, inv_rad = 1.0f / radius}; `light` the loop's

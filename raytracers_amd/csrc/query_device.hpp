@@ -36,6 +36,13 @@ hipError_t launch_within_count(const KParams &p, const float *pts, const float *
 hipError_t launch_within_fill(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
                               int exact_depth, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point,
                               hipStream_t stream);
+// rt_spheres_in_boxes_*: for p.nrays boxes (boxes: n x 6 float32, {lo.xyz, hi.xyz}, 4-byte aligned) EVERY sphere of L with box_gap <= the box's
+// margin -- `margin`, or box i's own margin_dev[i] -- and j >= first_dev[i], in the range queries' CSR form and two passes: the same scratch
+// (within_scratch_bytes(n)), scan, capacity guard and exact_depth rule as launch_within_count / launch_within_fill.
+hipError_t launch_boxes_count(const KParams &p, const float *boxes, const float *margin_dev, float margin, const int32_t *first_dev, int exact_depth,
+                              char *scratch, int64_t *offsets, hipStream_t stream);
+hipError_t launch_boxes_fill(const KParams &p, const float *boxes, const float *margin_dev, float margin, const int32_t *first_dev, int exact_depth,
+                             const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point, hipStream_t stream);
 // rt_sweep_spheres[_ranged]: the first k (1 <= k <= kSweepMaxK) contacts of a sphere moving along each ray, in (tau, j) order, and their count,
 // one lane per query: count[i], index / start [i * k + s], hit7 [(i * k + s) * 7 ..] (any may be nullptr, not all).  radius_dev == nullptr:
 // the radius `radius` (0 <= radius <= 1e9) and the interval (p.ray_tlo, p.ray_thi) for every query; otherwise query i's own radius_dev[i]

@@ -1,5 +1,5 @@
 // query_kernels.hip -- the lane kernels of the caller queries, one lane per ray or point: closest hit (rt_intersect_rays), occlusion
-// (rt_occluded_rays), multi-hit, sphere casts, ray paths, the nearest spheres, the range queries / contact pairs with their scan, and the primary
+// (rt_occluded_rays), multi-hit, sphere casts, ray paths, the nearest spheres, the range queries / contact pairs with their scan, the box queries, and the primary
 // rays of a frame (rt_camera_rays).  The render path -- pixel_kernel, persistent_kernel, pooled_kernel and their RAYS modes -- is
 // render_kernels.hip; nothing here is launched by a render entry.  Build: as render_kernels.hip (-ffp-contract=off, bit-exact fp32).
 #include <hip/hip_runtime.h>
@@ -723,6 +723,119 @@ hipError_t launch_within_fill(const KParams &p, const float *pts, const float *m
   else
     hipLaunchKernelGGL((within_kernel<true, false>), grid, block, 0, stream, p, pts, max_dist_dev, max_dist, first_dev, exact_depth, nullptr, offsets,
                        capacity, index, gap, point);
+  return hipGetLastError();
+}
+
+// rt_spheres_in_boxes_*: EVERY sphere whose gap to the lane's box is <= the box's margin, in CSR form.  One lane per box:
+// within_lane's walk -- the same stack entries, loads, right-then-left pushes with leaf entries (rows in ascending j), the untested descent
+// above exact_depth, the same count / fill protocol and capacity guard -- with box_may_meet at the nodes and box_gap at the leaves
+// (query_core.h).  A row of `boxes` is {lo.xyz, hi.xyz}, 24 bytes: six 4-byte loads, only 4-byte alignment is assumed.  A box failing qbox_ok
+// or a margin failing max_dist_ok does not start its walk.
+template <bool FILL>
+__device__ __forceinline__ void boxes_lane(const KParams &p, const float *boxes, const float *margin_dev, float margin, const int32_t *first_dev,
+                                           int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap,
+                                           int32_t *point) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const float *const row = boxes + (size_t)i * 6;
+  const QBox q = {row[0], row[1], row[2], row[3], row[4], row[5]};
+  if (margin_dev != nullptr) margin = margin_dev[i] + 0.0f;   // (-0.0 -> +0.0)
+  int first = 0;
+  if (first_dev != nullptr) first = first_dev[i] > 0 ? first_dev[i] : 0;
+  const bool valid = qbox_ok(q) && max_dist_ok(margin);
+  const float qmag = box_mag(q.lox, q.loy, q.loz, q.hix, q.hiy, q.hiz);
+  int cnt = 0;
+  int64_t at = 0, end = 0;
+  if constexpr (FILL) {
+    at = offsets[i];
+    end = offsets[i + 1] < capacity ? offsets[i + 1] : capacity;
+    if (at < 0) at = end;   // (offsets that are not a scan of counts: nothing is written)
+  }
+  int sp = 0;
+  if (valid) stack[sp++][lane] = within_node_entry(0, 0);
+  while (sp > 0) {
+    const unsigned e = (unsigned)stack[--sp][lane];
+    const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
+    int leaf[2] = {-1, -1};
+    if (depth == kWithinLeaf) {
+      leaf[0] = ni;
+    } else {
+      const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+      if (depth >= exact_depth && !box_may_meet(q, qmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, margin)) continue;
+      const int l = f2i(lo.w), r = f2i(hi.w);
+      // (one pending sibling per level: sp <= height + 1 <= kStackPixel)
+      if (l < 0) {
+        leaf[0] = ~l;
+        if (r < 0) leaf[1] = ~r;
+        else stack[sp++][lane] = within_node_entry(r, depth + 1);
+      } else {
+        stack[sp++][lane] = r < 0 ? within_leaf_entry(~r) : within_node_entry(r, depth + 1);
+        stack[sp++][lane] = within_node_entry(l, depth + 1);
+      }
+    }
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      const int j = leaf[c2];
+      if (j >= first) {   // (first >= 0: an empty leaf slot, -1, never passes)
+        const float4 s = buf_load16(rs_sph, j * 16);
+        const float g = box_gap(q, s.x, s.y, s.z, s.w);
+        if (g <= margin) {
+          if constexpr (FILL) {
+            if (at < end) {
+              if (index != nullptr) index[at] = j;
+              if (point != nullptr) point[at] = i;
+              if (gap != nullptr) gap[at] = g;
+            }
+            ++at;
+          } else {
+            ++cnt;
+          }
+        }
+      }
+    }
+  }
+  if constexpr (!FILL) count[i] = cnt;
+}
+template <bool FILL>
+__global__ __launch_bounds__(64) void boxes_kernel(KParams p, const float *boxes, const float *margin_dev, float margin, const int32_t *first_dev,
+                                                   int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index,
+                                                   float *gap, int32_t *point) {
+  boxes_lane<FILL>(p, boxes, margin_dev, margin, first_dev, exact_depth, count, offsets, capacity, index, gap, point);
+}
+
+// the count pass and the range queries' scan (the same three launches over the same scratch layout), then the fill pass
+hipError_t launch_boxes_count(const KParams &p, const float *boxes, const float *margin_dev, float margin, const int32_t *first_dev, int exact_depth,
+                              char *scratch, int64_t *offsets, hipStream_t stream) {
+  if (offsets == nullptr) return hipErrorInvalidValue;
+  if (p.nrays <= 0) return hipMemsetAsync(offsets, 0, sizeof(int64_t), stream);
+  if (boxes == nullptr || scratch == nullptr || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (margin_dev == nullptr && !max_dist_ok(margin)) return hipErrorInvalidValue;
+  margin += 0.0f;   // (-0.0 -> +0.0)
+  const int n = p.nrays;
+  int32_t *const counts = reinterpret_cast<int32_t *>(scratch);
+  long long *const sums = reinterpret_cast<long long *>(scratch + (((size_t)n * 4 + 255) & ~(size_t)255));
+  hipLaunchKernelGGL((boxes_kernel<false>), dim3(((unsigned)n + 63u) / 64u), dim3(64), 0, stream, p, boxes, margin_dev, margin, first_dev, exact_depth,
+                     counts, nullptr, (int64_t)0, nullptr, nullptr, nullptr);
+  const int nblocks = (int)(((int64_t)n + kWithinScanItems - 1) / kWithinScanItems);
+  hipLaunchKernelGGL(within_scan_sums_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums);
+  hipLaunchKernelGGL(within_scan_carry_kernel, dim3(1), dim3(kWithinScanThreads), 0, stream, sums, nblocks);
+  hipLaunchKernelGGL(within_scan_apply_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums, offsets);
+  return hipGetLastError();
+}
+
+hipError_t launch_boxes_fill(const KParams &p, const float *boxes, const float *margin_dev, float margin, const int32_t *first_dev, int exact_depth,
+                             const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (boxes == nullptr || offsets == nullptr || capacity < 0 || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (index == nullptr && gap == nullptr && point == nullptr) return hipErrorInvalidValue;
+  if (margin_dev == nullptr && !max_dist_ok(margin)) return hipErrorInvalidValue;
+  margin += 0.0f;   // (-0.0 -> +0.0)
+  hipLaunchKernelGGL((boxes_kernel<true>), dim3(((unsigned)p.nrays + 63u) / 64u), dim3(64), 0, stream, p, boxes, margin_dev, margin, first_dev,
+                     exact_depth, nullptr, offsets, capacity, index, gap, point);
   return hipGetLastError();
 }
 
