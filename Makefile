@@ -109,6 +109,12 @@ build/box_query_bound_check: tools/box_query_bound_check.cpp $(CSRC)/query_core.
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -fopenmp -I$(CSRC) -o $@ tools/box_query_bound_check.cpp $(OBJ)/host_build.o -lquadmath
 
+# the node test of the plane-set queries (query_core.h: planes_may_meet) and the gap's error bound hammered with host-built boxes and __float128;
+# in the CPU test suite
+build/plane_query_bound_check: tools/plane_query_bound_check.cpp $(CSRC)/query_core.h $(CSRC)/lane_core.h $(CSRC)/rt_host.hpp $(OBJ)/host_build.o
+	@mkdir -p build
+	$(CXX) $(HOSTFLAGS) -fopenmp -I$(CSRC) -o $@ tools/plane_query_bound_check.cpp $(OBJ)/host_build.o -lquadmath
+
 # the culling guards in two stages (statistics + finish) against the one-pass function, and the device's reduction of the statistics
 # modelled on the host (random partitions and merge orders); in the CPU test suite
 build/cull_stats_check: tools/cull_stats_check.cpp $(CSRC)/rt_host.hpp $(OBJ)/host_build.o
@@ -174,7 +180,7 @@ build/first_call_probe: tools/first_call_probe.c include/ray.h $(LIB)
 	@mkdir -p build
 	$(CC) -O2 -std=gnu99 -Wall -Iinclude -o $@ tools/first_call_probe.c -Lraytracers_amd -lray_mi355x -Wl,-rpath,'$$ORIGIN/../raytracers_amd'
 
-tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/box_presorted_check build/sweep_check build/path_check build/view_order_check
+tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/plane_query_bound_check build/box_presorted_check build/sweep_check build/path_check build/view_order_check
 
 oracle:
 	$(MAKE) -s -C oracle

@@ -78,6 +78,7 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *   "family=nearest k=K[ pruned][ (per-point)]" | "family=none (no points)"   rt_nearest_spheres / rt_nearest_spheres_ranged (below)
  *   "family=within count|fill[ (per-point)][ first][ self]"   rt_spheres_within_count / _fill, rt_contact_pairs_count / _fill (" self"; below)
  *   "family=boxes count|fill[ (per-box)][ first]"   rt_spheres_in_boxes_count / _fill (below)
+ *   "family=planes count|fill k=K[ (per-query)][ first]"   rt_spheres_in_planes_count / _fill (below; K: the caller's nplanes)
  *   "family=none (no rows)"       the part owns no row of the image
  *   "family=pixel" | "family=pixel (instrumented)" | "family=persistent"
  *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2[ nodes=sign-ordered|planes]"
@@ -467,6 +468,40 @@ int rt_spheres_in_boxes_count(rt_context *ctx, const rt_prepared *ps, int64_t n,
 int rt_spheres_in_boxes_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *boxes6_dev, float margin,
                              const float *margin_dev, const int32_t *first_dev, const int64_t *offsets_dev, int64_t capacity,
                              int32_t *index_dev, float *gap_dev, int32_t *point_dev);
+/* ---- plane-set queries: EVERY sphere inside a caller-supplied frustum or convex polytope, with no cap --------------------------------
+ * A query is nplanes planes and a margin; 1 <= nplanes <= 8, the same for every query of a call (a query that needs fewer repeats a plane:
+ * a repeated plane changes nothing).  planes4_dev: n x nplanes x 4 float32 in the context's device memory, rows {a, b, c, d} of 16 bytes;
+ * only 4-byte alignment is assumed.  The INSIDE of a plane is a x + b y + c z + d >= 0: normals point inward.  A frustum or a box is six
+ * planes; eight leave room for a clipped frustum or a portal.  Each plane is normalised once per query, and for sphere j of L (centre c,
+ * radius r) the gap is, in exactly this float32 arithmetic (no contraction, correctly rounded sqrtf and /):
+ *   len = sqrtf((a*a + b*b) + c*c);   nx = a/len; ny = b/len; nz = c/len; w = d/len
+ *   depth_k = ((nx*c.x + ny*c.y) + nz*c.z) + w                                                  for plane k
+ *   gap = fmaxf(fmaxf(... fmaxf(0.0f, -depth_0) ..., -depth_{K-2}), -depth_{K-1}) - r           (planes in the caller's order)
+ * Sphere j is selected iff gap <= margin -- and, where first_dev is given, j >= first_dev[i].  At margin 0 that is exactly "the closed ball
+ * meets every closed half-space", the standard frustum-culling test.  It is CONSERVATIVE for the polytope itself: a sphere outside an edge
+ * or a corner of it can be selected; a sphere that meets the polytope is never dropped.  A centre inside every half-space has gap -r.
+ * Brute force over all spheres defines the answer; no tree, builder or variant enters it.
+ * A plane is valid iff a, b, c, d are finite, 2^-40 <= len <= 2^40 and the four quotients are finite.  A per-query margin follows the box
+ * queries' rule: NaN, +-inf, negative or above 1e9 is invalid, -0.0 behaves as 0.0.  A query with an invalid plane or margin gives an empty
+ * row.  Exact for scenes whose spheres are finite with radius >= 0; for other scenes unspecified, but nothing is read or written out of range.
+ * RELATION TO THE BOX QUERIES: a box {lo, hi} written as the six planes (1,0,0,-lo.x), (0,1,0,-lo.y), (0,0,1,-lo.z), (-1,0,0,hi.x),
+ * (0,-1,0,hi.y), (0,0,-1,hi.z) has len exactly 1, and every -depth is rt_spheres_in_boxes_*'s per-axis excess, bit for bit.  So the plane
+ * gap is <= the box gap for every sphere -- the plane row is a superset of the box row -- and where at most one axis has a positive excess e
+ * the two gaps are equal in every bit (sqrtf(fl(e*e)) == e).
+ * The output is rt_spheres_in_boxes_count / _fill's, with the same two-phase protocol: offsets (n + 1 int64), then index (int32, ASCENDING j
+ * within a row), gap (float32) and point (int32, the row number of each entry: the COO form); any of the last three may be NULL, not all.
+ * _fill writes entry offsets[i] + rank only below offsets[i + 1] and below capacity: negative or foreign offsets never cause a write outside
+ * [0, capacity).  margin_dev == NULL: the scalar margin for every query; otherwise n float32, one margin per query, and the scalar is
+ * ignored.  first_dev: as for rt_spheres_within_*.
+ * Refused (non-zero, rt_last_error set, nothing launched or written): a null scene, a multi-device context, n < 0 or n >= 2^31, nplanes < 1
+ * or nplanes > 8, NULL planes4_dev, NULL offsets_dev, a negative capacity, every output NULL, a scalar margin (when it is used) outside
+ * [0, 1e9] or not finite.  n == 0 succeeds and _count still writes offsets_dev[0] = 0.  One lane per query under every variant;
+ * rt_context_last_launch: "family=planes count k=K" / "family=planes fill k=K", then " (per-query)" with margin_dev, " first" with first_dev. */
+int rt_spheres_in_planes_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *planes4_dev, int32_t nplanes, float margin,
+                               const float *margin_dev, const int32_t *first_dev, int64_t *offsets_dev);
+int rt_spheres_in_planes_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *planes4_dev, int32_t nplanes, float margin,
+                              const float *margin_dev, const int32_t *first_dev, const int64_t *offsets_dev, int64_t capacity,
+                              int32_t *index_dev, float *gap_dev, int32_t *point_dev);
 /* ids_dev: n int32 in the context's device memory; ids_dev[i] = the caller's index of L[i]: the position in spheres7 given to
  * rt_scene_from_spheres / rt_prepare_scene_device / the last rt_prepared_update_spheres, or in the generator's output for rt_scene_rgbbox /
  * _irreg / _floor.  The Morton sort is stable, so both builders (option gpu_build) give the same ids, ascending within a run of equal keys.

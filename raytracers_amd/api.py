@@ -572,6 +572,28 @@ def spheres_in_boxes_fill_into(boxes_ptr, n, prepared, offsets_ptr, capacity, in
                                             C.c_void_p(gap_ptr), C.c_void_p(point_ptr)))
 
 
+def spheres_in_planes_count_into(planes_ptr, n, nplanes, prepared, offsets_ptr, margin=0.0, margin_ptr=None, first_ptr=None):
+    """Enqueue the count pass of the plane-set query of `n` queries of `nplanes` planes each (n x nplanes x 4 float32 at planes_ptr, rows
+    {a, b, c, d}, inside a x + b y + c z + d >= 0; 1 <= nplanes <= 8; rt_spheres_in_planes_count): offsets_ptr receives n + 1 int64,
+    offsets[i + 1] - offsets[i] = the number of spheres whose gap to query i's planes is <= the query's margin -- the scalar margin, or
+    margin_ptr[i] (n float32 on the device) -- and index >= first_ptr[i] (n int32 on the device; None: no lower bound).  Asynchronous, as
+    spheres_in_boxes_count_into; then call spheres_in_planes_fill_into with the same arguments."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_spheres_in_planes_count(ctx._h, prepared._h, int(n), C.c_void_p(planes_ptr), int(nplanes), float(margin),
+                                              C.c_void_p(margin_ptr), C.c_void_p(first_ptr), C.c_void_p(offsets_ptr)))
+
+
+def spheres_in_planes_fill_into(planes_ptr, n, nplanes, prepared, offsets_ptr, capacity, index_ptr, gap_ptr=None, point_ptr=None, margin=0.0,
+                                margin_ptr=None, first_ptr=None):
+    """Enqueue the fill pass (rt_spheres_in_planes_fill) for the offsets of spheres_in_planes_count_into on the same planes, margins and
+    scene: the arrays of spheres_in_boxes_fill_into (point_ptr: the row, i.e. query, number of each entry); nothing is written at or past
+    `capacity`."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_spheres_in_planes_fill(ctx._h, prepared._h, int(n), C.c_void_p(planes_ptr), int(nplanes), float(margin),
+                                             C.c_void_p(margin_ptr), C.c_void_p(first_ptr), C.c_void_p(offsets_ptr), int(capacity),
+                                             C.c_void_p(index_ptr), C.c_void_p(gap_ptr), C.c_void_p(point_ptr)))
+
+
 def contact_pairs_count_into(prepared, offsets_ptr, margin=0.0):
     """Enqueue the count pass of the scene's contact pairs (rt_contact_pairs_count): offsets_ptr receives num_spheres + 1 int64, row i counting
     the j > i with gap(centre_i, L[j]) <= radius_i + margin.  Asynchronous, as spheres_within_count_into."""
@@ -907,6 +929,104 @@ def spheres_in_boxes(prepared, boxes, margin=0.0, first=None, gaps=True, rows=Fa
                                        mg_ptr, first_ptr)
         res = (offsets, idx.to_host((total,)), gap.to_host((total,), np.float32) if gap else None)
         return res + (row.to_host((total,)),) if rows else res
+
+
+_PLANES_SHAPE = "planes must be (n, K, 4) with 1 <= K <= 8: rows a, b, c, d"
+
+
+def _device_planes(scope, planes):
+    """(pointer, n, K) for `planes` (n x K x 4 float32): a numpy array is uploaded to a buffer of the scope; a contiguous float32 torch tensor
+    on the context's device is used in place."""
+    if hasattr(planes, "data_ptr"):
+        _check_tensor(planes, scope.ctx.device_info()["device"], "float32", "planes")
+        shape = tuple(planes.shape)
+        ptr = planes.data_ptr()
+    else:
+        planes = np.ascontiguousarray(planes, dtype=np.float32)
+        shape = planes.shape
+        ptr = None
+    if len(shape) != 3 or shape[2] != 4 or not 1 <= shape[1] <= 8:
+        raise ValueError(_PLANES_SHAPE)
+    return (scope.upload(planes) if ptr is None else ptr), int(shape[0]), int(shape[1])
+
+
+def spheres_in_planes(prepared, planes, margin=0.0, first=None, gaps=True, rows=False):
+    """EVERY sphere inside every query's planes -- a frustum, a slab, an oriented box, any convex polytope of up to 8 half-spaces
+    (rt_spheres_in_planes_count / _fill) -- with no cap, in spheres_in_boxes's CSR form -> (offsets (n + 1,) int64, index (total,) int32,
+    gap (total,) float32 or None[, point (total,) int32]) numpy arrays.  `planes`: (n, K, 4) float32, rows (a, b, c, d) whose inside is
+    a x + b y + c z + d >= 0 (normals point inward), a numpy array or a device tensor; a query that needs fewer than K planes repeats one.
+    Each plane is normalised in float32 (len = sqrtf((a*a + b*b) + c*c), n = (a, b, c) / len, w = d / len), depth_k = ((nx*cx + ny*cy) +
+    nz*cz) + w, and sphere j is selected for query i iff gap = max(0, -depth_0, ..., -depth_{K-1}) - r <= the query's margin.  margin 0 is
+    "the closed ball meets every closed half-space", the standard frustum-culling test: conservative for the polytope (a sphere outside an
+    edge or a corner can be selected; one that meets the polytope is never dropped).  A centre inside every half-space has gap -r.
+    margin: a scalar in [0, 1e9], or an (n,) array / device tensor, one per query (an invalid one gives an empty row).  A query with a
+    non-finite plane or a normal whose length is outside [2^-40, 2^40] has an empty row.  first, gaps, rows and the row order (ASCENDING
+    sphere index into L): as spheres_within.  frustum_planes and tile_frusta make the planes of a camera."""
+    ranged = _is_bound_array(margin)
+    with _Scope(prepared.ctx) as s:
+        ptr, n, k = _device_planes(s, planes)
+        dev = s.ctx.device_info()["device"]
+        mg_ptr = _device_bound(s, dev, n, "margin", margin, per="query") if ranged else None
+        mg = 0.0 if ranged else margin
+        first_ptr = _device_first(s, dev, n, first, per="query") if first is not None else None
+        off = s.alloc(8 * (n + 1))
+        spheres_in_planes_count_into(ptr, n, k, prepared, off.ptr, mg, mg_ptr, first_ptr)
+        offsets = off.to_host((n + 1,), np.int64)
+        total = int(offsets[n])
+        idx, gap, row = (s.alloc(4 * total) if want else None for want in (True, gaps, rows))
+        if total:
+            spheres_in_planes_fill_into(ptr, n, k, prepared, off.ptr, total, idx.ptr, gap.ptr if gap else None, row.ptr if row else None, mg,
+                                        mg_ptr, first_ptr)
+        res = (offsets, idx.to_host((total,)), gap.to_host((total,), np.float32) if gap else None)
+        return res + (row.to_host((total,)),) if rows else res
+
+
+def _unit(v):
+    return v / np.sqrt((v * v).sum())
+
+
+def frustum_planes(cam12, u0=0.0, u1=1.0, v0=0.0, v1=1.0, near=None, far=None):
+    """The planes of the part [u0, u1] x [v0, v1] of a camera's image (cam12: origin, lower-left corner, horizontal, vertical, as
+    Prepared.camera() and rt_camera_rays; the ray of (u, v) has direction llc + u * horizontal + v * vertical - origin) -> (4 | 5 | 6, 4)
+    float32 rows (a, b, c, d) with unit inward normals, computed in float64: left (u = u0), right (u = u1), bottom (v = v0), top (v = v1),
+    then the near and the far plane where given.  Each side plane passes through the origin, contains two corner directions and is oriented so
+    that the central direction has positive depth.  near / far: distances from the origin along the unit normal of the image plane,
+    cross(horizontal, vertical), oriented towards llc - origin."""
+    c = np.asarray(cam12, dtype=np.float64).reshape(12)
+    o, llc, hor, ver = c[0:3], c[3:6], c[6:9], c[9:12]
+    d = lambda u, v: llc + u * hor + v * ver - o   # noqa: E731
+    mid = d(0.5 * (u0 + u1), 0.5 * (v0 + v1))
+    out = []
+    for p, q in ((d(u0, v0), d(u0, v1)), (d(u1, v0), d(u1, v1)), (d(u0, v0), d(u1, v0)), (d(u0, v1), d(u1, v1))):
+        n = _unit(np.cross(p, q))
+        if n @ mid < 0.0:
+            n = -n
+        out.append(np.append(n, -(n @ o)))
+    f = _unit(np.cross(hor, ver))
+    if f @ (llc - o) < 0.0:
+        f = -f
+    if near is not None:
+        out.append(np.append(f, -(f @ o) - float(near)))
+    if far is not None:
+        out.append(np.append(-f, (f @ o) + float(far)))
+    return np.ascontiguousarray(np.stack(out), dtype=np.float32)
+
+
+def tile_frusta(cam12, h, w, tile_h, tile_w):
+    """The side planes of every tile of an h x w frame cut into tiles of tile_h x tile_w pixels (the last row and column of tiles may be
+    smaller) -> (tiles_y * tiles_x, 4, 4) float32, tiles row-major from the top row, each frustum_planes of the tile's part of the image:
+    the tile of rows [y0, y1) and columns [x0, x1) gets u in [x0 / w, x1 / w] and v in [(h - y1) / h, (h - y0) / h] -- rt_camera_rays puts
+    row 0 at v = 1 -- which holds the primary ray of each of its pixels."""
+    h, w, tile_h, tile_w = int(h), int(w), int(tile_h), int(tile_w)
+    if h < 1 or w < 1 or tile_h < 1 or tile_w < 1:
+        raise ValueError("tile_frusta: h, w, tile_h and tile_w must be positive")
+    out = []
+    for y0 in range(0, h, tile_h):
+        y1 = min(h, y0 + tile_h)
+        for x0 in range(0, w, tile_w):
+            x1 = min(w, x0 + tile_w)
+            out.append(frustum_planes(cam12, x0 / w, x1 / w, (h - y1) / h, (h - y0) / h))
+    return np.ascontiguousarray(np.stack(out), dtype=np.float32)
 
 
 def contact_pairs(prepared, margin=0.0, gaps=True):

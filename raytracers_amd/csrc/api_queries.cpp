@@ -1,5 +1,5 @@
 // api_queries.cpp -- the caller queries of the rt_* surface (include/rt_mi355x.h): rays traced, intersected, tested for occlusion, multi-hit,
-// sphere casts, ray paths, the proximity and range queries, contact pairs, a frame's primary rays.  Checks and launches only: the lane kernels are
+// sphere casts, ray paths, the proximity, range, box and plane-set queries, contact pairs, a frame's primary rays.  Checks and launches only: the lane kernels are
 // query_kernels.hip, and where an entry runs the pooled family (rt_trace_rays, rt_occluded_rays[_ranged]) its plan, parameters and launch
 // are the render policy's (api.cpp, through rt_internal.hpp).
 #include <hip/hip_runtime.h>
@@ -490,6 +490,57 @@ extern "C" int rt_spheres_in_boxes_fill(rt_context *ctx, const rt_prepared *ps, 
   RT_LOCK(ctx);
   return boxes_entry(ctx, ps, "rt_spheres_in_boxes_fill", true, n, boxes6_dev, margin, margin_dev, first_dev, const_cast<int64_t *>(offsets_dev),
                      capacity, index_dev, gap_dev, point_dev);
+}
+
+// The plane-set entries (rt_spheres_in_planes_*): the box entries' checks in the planes' words and the plane count's, then planes_lane under
+// every variant; the count pass shares the range queries' cached scratch.
+static int planes_entry(rt_context *ctx, const rt_prepared *ps, const char *what, bool fill, int64_t n, const float *planes4_dev, int32_t nplanes,
+                        float margin, const float *margin_dev, const int32_t *first_dev, int64_t *offsets_dev, int64_t capacity,
+                        int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
+  if (!ps) return fail(ctx, "null prepared scene");
+  if (ctx->group) return fail_in(ctx, what, ": a multi-device context is not supported (use a context on one device)");
+  if (n < 0 || n >= (int64_t(1) << 31)) return fail_in(ctx, what, ": query count out of range: 0 <= n < 2^31");
+  if (nplanes < 1 || nplanes > rtk::kMaxPlanes) return fail_in(ctx, what, ": plane count out of range: 1 <= nplanes <= 8");
+  if (!planes4_dev) return fail_in(ctx, what, ": null planes pointer");
+  if (!offsets_dev) return fail_in(ctx, what, ": null offsets pointer");
+  if (fill && capacity < 0) return fail_in(ctx, what, ": negative capacity");
+  if (fill && !index_dev && !gap_dev && !point_dev) return fail_in(ctx, what, ": every output is NULL");
+  if (!margin_dev && !distance_ok(margin)) return fail_in(ctx, what, ": need 0 <= margin <= 1e9, finite");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  int exact_depth;
+  const rtk::KParams p = point_params(ps, n, &exact_depth);
+  if (fill) {
+    ctx->synced_since_render = false;
+    RT_HIP(ctx, rtk::launch_planes_fill(p, planes4_dev, nplanes, margin_dev, margin, first_dev, exact_depth, offsets_dev, capacity, index_dev, gap_dev,
+                                        point_dev, ctx->stream));
+  } else {
+    char *scratch = nullptr;
+    if (n > 0 && within_scratch(ctx, n, &scratch) != 0) return 1;
+    ctx->synced_since_render = false;
+    RT_HIP(ctx, rtk::launch_planes_count(p, planes4_dev, nplanes, margin_dev, margin, first_dev, exact_depth, scratch, offsets_dev, ctx->stream));
+  }
+  ctx->last_launch = std::string(fill ? "family=planes fill k=" : "family=planes count k=") + std::to_string(nplanes) +
+                     (margin_dev ? " (per-query)" : "") + (first_dev ? " first" : "");
+  return 0;
+}
+
+extern "C" int rt_spheres_in_planes_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *planes4_dev, int32_t nplanes, float margin,
+                                          const float *margin_dev, const int32_t *first_dev, int64_t *offsets_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return planes_entry(ctx, ps, "rt_spheres_in_planes_count", false, n, planes4_dev, nplanes, margin, margin_dev, first_dev, offsets_dev, 0, nullptr,
+                      nullptr, nullptr);
+}
+
+extern "C" int rt_spheres_in_planes_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *planes4_dev, int32_t nplanes, float margin,
+                                         const float *margin_dev, const int32_t *first_dev, const int64_t *offsets_dev, int64_t capacity,
+                                         int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return planes_entry(ctx, ps, "rt_spheres_in_planes_fill", true, n, planes4_dev, nplanes, margin, margin_dev, first_dev,
+                      const_cast<int64_t *>(offsets_dev), capacity, index_dev, gap_dev, point_dev);
 }
 
 extern "C" int rt_prepared_get_sphere_ids(rt_context *ctx, const rt_prepared *ps, int32_t *ids_dev) {

@@ -1,7 +1,7 @@
 // query_core.h -- per-lane arithmetic of the caller queries that no render-path kernel calls: both roots of a sphere and the sphere
-// casts' contact rule, the proximity queries' gap, box bound, slack and selection key, the box queries' gap and node test, a ray path's bounce.  Shared by
-// query_kernels.hip and the host-side checks (tools/sweep_check.cpp, tools/path_check.cpp, tools/proximity_bound_check.cpp,
-// tools/box_query_bound_check.cpp).  Same parity contract as lane_core.h, which holds what the render
+// casts' contact rule, the proximity queries' gap, box bound, slack and selection key, the box queries' gap and node test, the plane-set
+// queries' normalisation, gap and node test, a ray path's bounce.  Shared by query_kernels.hip and the host-side checks (tools/sweep_check.cpp, tools/path_check.cpp, tools/proximity_bound_check.cpp,
+// tools/box_query_bound_check.cpp, tools/plane_query_bound_check.cpp).  Same parity contract as lane_core.h, which holds what the render
 // path shares with the queries (box_hit_interval, sphere_hit_any, interval_ok, rehit_range).
 #pragma once
 #include "lane_core.h"
@@ -156,6 +156,88 @@ RT_HD bool box_may_meet(const QBox &q, float qmag, float lox, float loy, float l
   const float t = fmaxf(T, 0.0f);
   const float b = box_box_bound(q, lox, loy, loz, hix, hiy, hiz);
   return !(b > t + slack_scale * proximity_slack(t, qmag, box_mag(lox, loy, loz, hix, hiy, hiz)));
+}
+
+// ---- plane-set queries: the spheres inside a frustum or convex polytope (rt_spheres_in_planes_*) ---------------------
+// A caller's plane {a, b, c, d} (inside: a x + b y + c z + d >= 0) normalised once per query: n = (a, b, c) / len, w = d / len.  This exact
+// binary32 arithmetic IS the definition (no contraction, correctly rounded sqrtf and /).  Valid iff the four inputs are finite,
+// 2^-40 <= len <= 2^40 and the four quotients are finite (a NaN fails every compare); a query with an invalid plane gets no walk.
+struct QPlane {
+  float nx, ny, nz, w;
+};
+#if defined(__clang__)
+#define RT_UNROLL _Pragma("unroll")   // (the loops over a query's K planes: K is a template parameter, the planes stay in registers)
+#else
+#define RT_UNROLL
+#endif
+RT_HD bool plane_normalise(float a, float b, float c, float d, QPlane *p) {
+  const float len = sqrtf((a * a + b * b) + c * c);
+  p->nx = a / len;
+  p->ny = b / len;
+  p->nz = c / len;
+  p->w = d / len;
+  // Three compares say all of it: a NaN or infinite a, b or c, or one of 2^64 and more, makes len NaN or +inf; with len in range each of
+  // |a|, |b|, |c| is at most len (1 + 3u), so three quotients are finite; and w is finite iff d is finite and d / len does not overflow.
+  return len >= 0x1p-40f && len <= 0x1p40f && fabsf(p->w) <= 3.40282347e38f;
+}
+// The signed depth of the point x inside the plane, positive inside.
+RT_HD float plane_depth(const QPlane &p, float x, float y, float z) { return dot3(p.nx, p.ny, p.nz, x, y, z) + p.w; }
+// The gap of the plane set pl[0 .. K) to sphere (c, r): how far the sphere's surface is outside the half-space it is furthest outside of,
+// -r where the centre is inside every half-space (as box_gap's).  The planes enter in the caller's order; a repeated plane changes nothing.
+template <int K>
+RT_HD float plane_gap(const QPlane (&pl)[K], float cx, float cy, float cz, float r) {
+  float e = 0.0f;
+RT_UNROLL
+  for (int k = 0; k < K; ++k) e = fmaxf(e, -plane_depth(pl[k], cx, cy, cz));
+  return e - r;
+}
+// The node test.  For plane k the largest depth over the node's box [lo, hi] is taken at its most-inside vertex v (v_j = hi_j where
+// n_j >= 0, else lo_j); D_k = plane_depth(k, v) computed in binary32.  The node is skipped iff some plane has -D_k > t + slack.  No radius
+// enters: the sphere's own box lies inside the node's box.  Let u = 2^-24, n^ = (a, b, c) / |(a, b, c)| and w^ = d / |(a, b, c)| the exact
+// unit plane, g = max(0, max_k -(n^_k . c + w^_k)) - r the exact gap, G = plane_gap (computed), W = max_k |w_k|, M = box_mag of the node's
+// box, t = max(T, 0).  |x| is the Euclidean norm.
+//   (R0)  len = |(a, b, c)| (1 + e), |e| <= 2.5 u (three roundings on a sum of squares, halved by the root, and the root's own); each
+//         quotient adds u: n_j = n^_j (1 + e_j), w = w^ (1 + e_w), |e_j|, |e_w| <= 3.6 u, so |n|_2 = 1 + e_n, |e_n| <= 3.6 u.  (With
+//         len >= 2^-40 a square that underflows is below 2^-46 of the sum.)
+//   (R1)  |G - g| <= u (8.8 |c| + 5.8 W + r) + 2^-62.  A computed depth is within u (4 |n . c|* + |w|), |n . c|* = sum_j |n_j c_j| <= |n| |c|,
+//         of n . c + w in exact arithmetic (the first product meets four roundings, w one), and that is within 3.6 u (|c| + |w^|) of the
+//         exact plane's depth (R0): 7.7 u |c| + 4.7 u W together.  max and the clamp at 0 add nothing; the subtraction of r adds
+//         u |G| <= u (|c| + W + r) (1 + 9u).  2^-62 covers products that underflow, flushed or not.
+//   (R2)  the stored box misses at most d = u M (1 + 2u) of the sphere's exact box on each side (P2), and a centre lies INSIDE its stored
+//         box (fl(c - r) <= c <= fl(c + r)).  Over the sphere's exact box the largest depth is n . c + w + r |n|_1, and |n|_1 >= |n|_2 >=
+//         1 - 3.6 u, |n|_1 <= sqrt(3) (1 + 3.6 u); so in exact arithmetic on the computed plane
+//         -(n . v + w) <= -(n . c + w) - r (1 - 3.6 u) + sqrt(3) (1 + 4u) d.
+//   (R3)  D_k is within u (4 sqrt(3) M + W) (1 + 4u) of n . v + w (|v_j| <= M), and the leaf's depth_k within the same of n . c + w
+//         (|c_j| <= M).
+// G <= T means fl(E - r) <= t for E = max(0, max_k -depth_k), hence -depth_k <= E <= r + t + u (r + t) (1 + 2u).  Chaining R3, R2, R3:
+//   -D_k <= t + u (t + 4.6 r + (8 sqrt(3) + sqrt(3)) M + 2 W) <= t + u (t + 20.2 M + 2 W) + 2^-61     (r <= M (1 + 2u))
+// with second-order terms folded into the decimals.  plane_slack is 2^-18 = 64 u times t + W + M, plus 2^-56: more than twice every
+// coefficient (the factor proximity_slack keeps), which also absorbs the rounding of the slack's own additions and of t + slack.  A NaN D_k
+// (inf - inf at |coordinates| near 2^127) skips nothing, and -D_k = +inf skips only where every leaf depth below is -inf as well: every
+// product and partial sum at v is >= the one at a centre inside the box, rounding being monotone.  tools/plane_query_bound_check.cpp
+// searches for counterexamples; with the slack scaled to 0 it finds them.
+RT_HD float plane_slack(float t, float wmag, float bmag) { return 0x1p-18f * ((t + wmag) + bmag) + 0x1p-56f; }
+template <int K>
+RT_HD float planes_wmag(const QPlane (&pl)[K]) {
+  float m = 0.0f;
+RT_UNROLL
+  for (int k = 0; k < K; ++k) m = fmaxf(m, fabsf(pl[k].w));
+  return m;
+}
+template <int K>
+RT_HD bool planes_may_meet(const QPlane (&pl)[K], float wmag, float lox, float loy, float loz, float hix, float hiy, float hiz, float T,
+                           float slack_scale = 1.0f) {
+  const float t = fmaxf(T, 0.0f);
+  const float lim = t + slack_scale * plane_slack(t, wmag, box_mag(lox, loy, loz, hix, hiy, hiz));
+  // fl(n_j v_j) is taken as fmaxf(fl(n_j lo_j), fl(n_j hi_j)): rounding is monotone, so the larger rounded product IS the rounded product at the
+  // most-inside vertex (the sign of a zero aside, which the compare below cannot see) -- and the walk keeps no sign masks per plane and axis.
+RT_UNROLL
+  for (int k = 0; k < K; ++k) {
+    const float px = fmaxf(pl[k].nx * lox, pl[k].nx * hix), py = fmaxf(pl[k].ny * loy, pl[k].ny * hiy), pz = fmaxf(pl[k].nz * loz, pl[k].nz * hiz);
+    const float D = ((px + py) + pz) + pl[k].w;
+    if (-D > lim) return false;
+  }
+  return true;
 }
 
 // ---- ray paths: one iteration of ray_colour's loop behind objs_hit (rt_trace_paths) ---------------------------------

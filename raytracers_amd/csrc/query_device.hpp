@@ -43,6 +43,15 @@ hipError_t launch_boxes_count(const KParams &p, const float *boxes, const float 
                               char *scratch, int64_t *offsets, hipStream_t stream);
 hipError_t launch_boxes_fill(const KParams &p, const float *boxes, const float *margin_dev, float margin, const int32_t *first_dev, int exact_depth,
                              const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point, hipStream_t stream);
+// rt_spheres_in_planes_*: for p.nrays queries of `nplanes` planes each (planes: n x nplanes x 4 float32, rows {a, b, c, d}, 4-byte aligned;
+// 1 <= nplanes <= kMaxPlanes, else hipErrorInvalidValue) EVERY sphere of L with plane_gap <= the query's margin and j >= first_dev[i]: the box
+// queries' CSR form, two passes, scratch, scan, capacity guard and exact_depth rule (launch_boxes_count / launch_boxes_fill).
+constexpr int kMaxPlanes = 8;
+hipError_t launch_planes_count(const KParams &p, const float *planes, int nplanes, const float *margin_dev, float margin, const int32_t *first_dev,
+                               int exact_depth, char *scratch, int64_t *offsets, hipStream_t stream);
+hipError_t launch_planes_fill(const KParams &p, const float *planes, int nplanes, const float *margin_dev, float margin, const int32_t *first_dev,
+                              int exact_depth, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point,
+                              hipStream_t stream);
 // rt_sweep_spheres[_ranged]: the first k (1 <= k <= kSweepMaxK) contacts of a sphere moving along each ray, in (tau, j) order, and their count,
 // one lane per query: count[i], index / start [i * k + s], hit7 [(i * k + s) * 7 ..] (any may be nullptr, not all).  radius_dev == nullptr:
 // the radius `radius` (0 <= radius <= 1e9) and the interval (p.ray_tlo, p.ray_thi) for every query; otherwise query i's own radius_dev[i]

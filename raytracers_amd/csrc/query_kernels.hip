@@ -1,5 +1,5 @@
 // query_kernels.hip -- the lane kernels of the caller queries, one lane per ray or point: closest hit (rt_intersect_rays), occlusion
-// (rt_occluded_rays), multi-hit, sphere casts, ray paths, the nearest spheres, the range queries / contact pairs with their scan, the box queries, and the primary
+// (rt_occluded_rays), multi-hit, sphere casts, ray paths, the nearest spheres, the range queries / contact pairs with their scan, the box and plane-set queries, and the primary
 // rays of a frame (rt_camera_rays).  The render path -- pixel_kernel, persistent_kernel, pooled_kernel and their RAYS modes -- is
 // render_kernels.hip; nothing here is launched by a render entry.  Build: as render_kernels.hip (-ffp-contract=off, bit-exact fp32).
 #include <hip/hip_runtime.h>
@@ -836,6 +836,140 @@ hipError_t launch_boxes_fill(const KParams &p, const float *boxes, const float *
   margin += 0.0f;   // (-0.0 -> +0.0)
   hipLaunchKernelGGL((boxes_kernel<true>), dim3(((unsigned)p.nrays + 63u) / 64u), dim3(64), 0, stream, p, boxes, margin_dev, margin, first_dev,
                      exact_depth, nullptr, offsets, capacity, index, gap, point);
+  return hipGetLastError();
+}
+
+// rt_spheres_in_planes_*: EVERY sphere whose gap to the lane's K planes is <= the query's margin, in CSR form.  One lane
+// per query: boxes_lane's walk -- the same stack entries, loads, right-then-left pushes with leaf entries (rows in ascending j), the untested
+// descent above exact_depth, the same count / fill protocol and capacity guard -- with planes_may_meet at the nodes and plane_gap at the
+// leaves (query_core.h).  A query's planes are K rows {a, b, c, d} of 16 bytes: 4 K 4-byte loads, only 4-byte alignment is assumed, and one
+// normalisation per plane before the walk.  K is a template parameter, so the planes stay in 4 K registers through the fully unrolled loops.  A
+// query with a plane failing plane_normalise or a margin failing max_dist_ok does not start its walk.
+template <int K, bool FILL>
+__device__ __forceinline__ void planes_lane(const KParams &p, const float *planes, const float *margin_dev, float margin, const int32_t *first_dev,
+                                            int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap,
+                                            int32_t *point) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const float *const row = planes + (size_t)i * (4 * K);
+  QPlane pl[K];
+  bool valid = true;
+#pragma unroll
+  for (int k = 0; k < K; ++k) valid &= plane_normalise(row[4 * k], row[4 * k + 1], row[4 * k + 2], row[4 * k + 3], &pl[k]);
+  if (margin_dev != nullptr) margin = margin_dev[i] + 0.0f;   // (-0.0 -> +0.0)
+  int first = 0;
+  if (first_dev != nullptr) first = first_dev[i] > 0 ? first_dev[i] : 0;
+  valid = valid && max_dist_ok(margin);
+  const float wmag = planes_wmag(pl);
+  int cnt = 0;
+  int64_t at = 0, end = 0;
+  if constexpr (FILL) {
+    at = offsets[i];
+    end = offsets[i + 1] < capacity ? offsets[i + 1] : capacity;
+    if (at < 0) at = end;   // (offsets that are not a scan of counts: nothing is written)
+  }
+  int sp = 0;
+  if (valid) stack[sp++][lane] = within_node_entry(0, 0);
+  while (sp > 0) {
+    const unsigned e = (unsigned)stack[--sp][lane];
+    const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
+    int leaf[2] = {-1, -1};
+    if (depth == kWithinLeaf) {
+      leaf[0] = ni;
+    } else {
+      const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+      if (depth >= exact_depth && !planes_may_meet(pl, wmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, margin)) continue;
+      const int l = f2i(lo.w), r = f2i(hi.w);
+      // (one pending sibling per level: sp <= height + 1 <= kStackPixel)
+      if (l < 0) {
+        leaf[0] = ~l;
+        if (r < 0) leaf[1] = ~r;
+        else stack[sp++][lane] = within_node_entry(r, depth + 1);
+      } else {
+        stack[sp++][lane] = r < 0 ? within_leaf_entry(~r) : within_node_entry(r, depth + 1);
+        stack[sp++][lane] = within_node_entry(l, depth + 1);
+      }
+    }
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      const int j = leaf[c2];
+      if (j >= first) {   // (first >= 0: an empty leaf slot, -1, never passes)
+        const float4 s = buf_load16(rs_sph, j * 16);
+        const float g = plane_gap(pl, s.x, s.y, s.z, s.w);
+        if (g <= margin) {
+          if constexpr (FILL) {
+            if (at < end) {
+              if (index != nullptr) index[at] = j;
+              if (point != nullptr) point[at] = i;
+              if (gap != nullptr) gap[at] = g;
+            }
+            ++at;
+          } else {
+            ++cnt;
+          }
+        }
+      }
+    }
+  }
+  if constexpr (!FILL) count[i] = cnt;
+}
+template <int K, bool FILL>
+__global__ __launch_bounds__(64) void planes_kernel(KParams p, const float *planes, const float *margin_dev, float margin, const int32_t *first_dev,
+                                                    int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index,
+                                                    float *gap, int32_t *point) {
+  planes_lane<K, FILL>(p, planes, margin_dev, margin, first_dev, exact_depth, count, offsets, capacity, index, gap, point);
+}
+// one instantiation per plane count, 1 .. kMaxPlanes
+template <bool FILL>
+static void launch_planes_kernel(int nplanes, const KParams &p, const float *planes, const float *margin_dev, float margin, const int32_t *first_dev,
+                                 int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap,
+                                 int32_t *point, hipStream_t stream) {
+  const dim3 grid(((unsigned)p.nrays + 63u) / 64u), block(64);
+#define RT_PLANES_CASE(KK)                                                                                                                       \
+  case KK:                                                                                                                                        \
+    hipLaunchKernelGGL((planes_kernel<KK, FILL>), grid, block, 0, stream, p, planes, margin_dev, margin, first_dev, exact_depth, count, offsets, \
+                       capacity, index, gap, point);                                                                                              \
+    break;
+  switch (nplanes) {
+    RT_PLANES_CASE(1) RT_PLANES_CASE(2) RT_PLANES_CASE(3) RT_PLANES_CASE(4) RT_PLANES_CASE(5) RT_PLANES_CASE(6) RT_PLANES_CASE(7) RT_PLANES_CASE(8)
+  }
+#undef RT_PLANES_CASE
+}
+
+// the count pass and the range queries' scan (the same three launches over the same scratch layout), then the fill pass
+hipError_t launch_planes_count(const KParams &p, const float *planes, int nplanes, const float *margin_dev, float margin, const int32_t *first_dev,
+                               int exact_depth, char *scratch, int64_t *offsets, hipStream_t stream) {
+  if (offsets == nullptr || nplanes < 1 || nplanes > kMaxPlanes) return hipErrorInvalidValue;
+  if (p.nrays <= 0) return hipMemsetAsync(offsets, 0, sizeof(int64_t), stream);
+  if (planes == nullptr || scratch == nullptr || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (margin_dev == nullptr && !max_dist_ok(margin)) return hipErrorInvalidValue;
+  margin += 0.0f;   // (-0.0 -> +0.0)
+  const int n = p.nrays;
+  int32_t *const counts = reinterpret_cast<int32_t *>(scratch);
+  long long *const sums = reinterpret_cast<long long *>(scratch + (((size_t)n * 4 + 255) & ~(size_t)255));
+  launch_planes_kernel<false>(nplanes, p, planes, margin_dev, margin, first_dev, exact_depth, counts, nullptr, (int64_t)0, nullptr, nullptr, nullptr,
+                              stream);
+  const int nblocks = (int)(((int64_t)n + kWithinScanItems - 1) / kWithinScanItems);
+  hipLaunchKernelGGL(within_scan_sums_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums);
+  hipLaunchKernelGGL(within_scan_carry_kernel, dim3(1), dim3(kWithinScanThreads), 0, stream, sums, nblocks);
+  hipLaunchKernelGGL(within_scan_apply_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums, offsets);
+  return hipGetLastError();
+}
+
+hipError_t launch_planes_fill(const KParams &p, const float *planes, int nplanes, const float *margin_dev, float margin, const int32_t *first_dev,
+                              int exact_depth, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point,
+                              hipStream_t stream) {
+  if (nplanes < 1 || nplanes > kMaxPlanes) return hipErrorInvalidValue;
+  if (p.nrays <= 0) return hipSuccess;
+  if (planes == nullptr || offsets == nullptr || capacity < 0 || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (index == nullptr && gap == nullptr && point == nullptr) return hipErrorInvalidValue;
+  if (margin_dev == nullptr && !max_dist_ok(margin)) return hipErrorInvalidValue;
+  margin += 0.0f;   // (-0.0 -> +0.0)
+  launch_planes_kernel<true>(nplanes, p, planes, margin_dev, margin, first_dev, exact_depth, nullptr, offsets, capacity, index, gap, point, stream);
   return hipGetLastError();
 }
 
