@@ -131,6 +131,12 @@ build/sweep_check: tools/sweep_check.cpp $(CSRC)/query_core.h $(CSRC)/lane_core.
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -I$(CSRC) -o $@ tools/sweep_check.cpp
 
+# the along-ray queries' per-sphere rule (query_core.h: sweep_contact_roots) over the same case files: kind, tau and the two roots written as
+# bits, kind and tau held equal to sweep_contact's; in the CPU test suite
+build/along_check: tools/along_check.cpp $(CSRC)/query_core.h $(CSRC)/lane_core.h
+	@mkdir -p build
+	$(CXX) $(HOSTFLAGS) -I$(CSRC) -o $@ tools/along_check.cpp
+
 # one bounce of a ray path (query_core.h: path_bounce behind sphere_root and rehit_full, what paths_kernel runs when a fold ends) over cases read
 # from a file, the outcome and the new loop variables written as bits; in the CPU test suite
 build/path_check: tools/path_check.cpp $(CSRC)/query_core.h $(CSRC)/lane_core.h
@@ -180,7 +186,7 @@ build/first_call_probe: tools/first_call_probe.c include/ray.h $(LIB)
 	@mkdir -p build
 	$(CC) -O2 -std=gnu99 -Wall -Iinclude -o $@ tools/first_call_probe.c -Lraytracers_amd -lray_mi355x -Wl,-rpath,'$$ORIGIN/../raytracers_amd'
 
-tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/plane_query_bound_check build/box_presorted_check build/sweep_check build/path_check build/view_order_check
+tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/plane_query_bound_check build/box_presorted_check build/sweep_check build/along_check build/path_check build/view_order_check
 
 oracle:
 	$(MAKE) -s -C oracle

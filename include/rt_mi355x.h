@@ -79,6 +79,7 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *   "family=within count|fill[ (per-point)][ first][ self]"   rt_spheres_within_count / _fill, rt_contact_pairs_count / _fill (" self"; below)
  *   "family=boxes count|fill[ (per-box)][ first]"   rt_spheres_in_boxes_count / _fill (below)
  *   "family=planes count|fill k=K[ (per-query)][ first]"   rt_spheres_in_planes_count / _fill (below; K: the caller's nplanes)
+ *   "family=along count|fill[ (per-query)][ exclude][ first]"   rt_spheres_along_rays_count / _fill (below)
  *   "family=none (no rows)"       the part owns no row of the image
  *   "family=pixel" | "family=pixel (instrumented)" | "family=persistent"
  *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2[ nodes=sign-ordered|planes]"
@@ -502,6 +503,51 @@ int rt_spheres_in_planes_count(rt_context *ctx, const rt_prepared *ps, int64_t n
 int rt_spheres_in_planes_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *planes4_dev, int32_t nplanes, float margin,
                               const float *margin_dev, const int32_t *first_dev, const int64_t *offsets_dev, int64_t capacity,
                               int32_t *index_dev, float *gap_dev, int32_t *point_dev);
+/* ---- along-ray queries: EVERY sphere a ray crosses, or a moving sphere touches, over its whole interval, with no cap ---------------------
+ * rt_multi_hit_rays and rt_sweep_spheres return the first k <= 32 crossings or contacts and an uncapped count; these entries return the rest.
+ * A query is a ray {o, d} (rays_dev: the n x 6 float32 layout of the ray queries), a radius rq and an interval (t_min, t_max); optionally an
+ * excluded index (rt_sweep_spheres_ranged's rule) and a lower index bound `first` (rt_spheres_within_*'s rule).
+ * SELECTION: rt_sweep_spheres's rule, unchanged.  Sphere j of L is selected for query i iff
+ *   - it is consulted: every inner node on its root path passes aabb_hit over (t_min, t_max) on the node's box widened by rq per component,
+ *     fl(lo_k - rq) and fl(hi_k + rq);
+ *   - the contact rule above gives a contact (an entry contact or an overlap at the start) against (c, R = r + rq);
+ *   - j != exclude_dev[i] (exclude_dev given; a value no sphere has excludes nothing);
+ *   - j >= first_dev[i] (first_dev given; <= 0 selects from 0, >= the sphere count gives an empty row; a compare at the leaf, no pruning).
+ * There is no k.  Like the sweep's, the answer is defined by the tree: on a tree taller than the AABB propagation's floor(log2 n) + 2 sweeps
+ * the partial boxes nearest the root enter it.
+ * OUTPUT: CSR, in rt_spheres_within_count / _fill's two phases (count and scan, read offsets_dev[n], allocate, fill with the SAME query):
+ *   offsets : n + 1 int64; offsets[0] = 0, offsets[n] the total.
+ *   index   : total int32; row i at [offsets[i], offsets[i + 1]), in ASCENDING j -- not by tau.
+ *   roots   : total x 2 float32, rows {t1, t2}: the two roots of sphere_hit against (c, R), exactly the values the contact rule compared,
+ *             UNCLAMPED -- t1 may lie before t_min, t2 past t_max.  Written as one 8-byte store per row; 4-byte alignment suffices.
+ *   start   : total uint8; 0 an entry contact (tau = t1), 1 an overlap at the start (tau = t_min + 0.0f).
+ *   query   : total int32, the row number i of each entry (the COO form).
+ * Any of the four entry arrays may be NULL, not all.  _fill writes entry offsets[i] + rank only below offsets[i + 1] and below capacity, and
+ * nothing for a negative offsets[i]: foreign offsets never cause a write outside [0, capacity).
+ * PER-QUERY VALUES: radius_dev == NULL: the scalar radius for every query; otherwise n float32 and the scalar is ignored.  t_min_dev and
+ * t_max_dev: both NULL (the scalar pair for every query) or both given (n float32 each; the scalar pair is ignored).  A per-query interval
+ * that fails 0 <= t_min <= t_max <= 1e9 or radius that fails 0 <= radius <= 1e9 (NaN, +-inf included) gives an empty row, its walk does not
+ * start; -0.0 behaves as +0.0.
+ * IDENTITIES (each follows from the shared rule):
+ *   1. Without first_dev, row i's length is rt_sweep_spheres_ranged's count_dev[i] for the same query.
+ *   2. A row with count <= 32, ordered by (tau, j) with tau = start ? t_min + 0.0f : t1, is rt_sweep_spheres's index, start and
+ *      hit7[.., 0], bit for bit.
+ *   3. At rq = 0 the consulted leaves are rt_multi_hit_rays's and R = r + 0 is r.  The roots of a row's entries that lie strictly inside
+ *      (t_min, t_max), ordered by (t, j, root): their number is rt_multi_hit_rays's count, and the first min(count, 32) are its index, root
+ *      and hit7[.., 0], bit for bit.  The selected set is a SUPERSET of the crossed spheres: a segment wholly inside a sphere is selected
+ *      (an overlap at the start) with no root inside the interval.
+ * Refused (non-zero, rt_last_error set, nothing launched or written): a null scene, a multi-device context, n < 0 or n >= 2^31, NULL
+ * rays_dev, NULL offsets_dev, a negative capacity, every output NULL, exactly one of t_min_dev / t_max_dev NULL, a scalar interval (when it
+ * is used) that fails the rule, a scalar radius (when it is used) outside [0, 1e9] or not finite.  n == 0 succeeds and _count still writes
+ * offsets_dev[0] = 0.  One lane per query under every variant; rt_context_last_launch: "family=along count" / "family=along fill", then
+ * " (per-query)" with any of radius_dev, t_min_dev, t_max_dev, " exclude" with exclude_dev, " first" with first_dev. */
+int rt_spheres_along_rays_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float radius,
+                                const float *radius_dev, float t_min, float t_max, const float *t_min_dev, const float *t_max_dev,
+                                const int32_t *exclude_dev, const int32_t *first_dev, int64_t *offsets_dev);
+int rt_spheres_along_rays_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float radius,
+                               const float *radius_dev, float t_min, float t_max, const float *t_min_dev, const float *t_max_dev,
+                               const int32_t *exclude_dev, const int32_t *first_dev, const int64_t *offsets_dev, int64_t capacity,
+                               int32_t *index_dev, float *roots_dev, uint8_t *start_dev, int32_t *query_dev);
 /* ids_dev: n int32 in the context's device memory; ids_dev[i] = the caller's index of L[i]: the position in spheres7 given to
  * rt_scene_from_spheres / rt_prepare_scene_device / the last rt_prepared_update_spheres, or in the generator's output for rt_scene_rgbbox /
  * _irreg / _floor.  The Morton sort is stable, so both builders (option gpu_build) give the same ids, ascending within a run of equal keys.

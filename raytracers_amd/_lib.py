@@ -25,6 +25,7 @@ RT_SYMBOLS = [
     "rt_spheres_within_count", "rt_spheres_within_fill", "rt_contact_pairs_count", "rt_contact_pairs_fill",
     "rt_spheres_in_boxes_count", "rt_spheres_in_boxes_fill",
     "rt_spheres_in_planes_count", "rt_spheres_in_planes_fill",
+    "rt_spheres_along_rays_count", "rt_spheres_along_rays_fill",
     "rt_camera_rays",
     "rt_device_alloc", "rt_device_free", "rt_copy_to_host", "rt_copy_to_device",
 ]
@@ -127,6 +128,8 @@ def _load():
         "rt_spheres_in_boxes_fill": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, vp, vp, i64, vp, vp, vp]),
         "rt_spheres_in_planes_count": (C.c_int, [vp, vp, i64, vp, C.c_int32, C.c_float, vp, vp, vp]),
         "rt_spheres_in_planes_fill": (C.c_int, [vp, vp, i64, vp, C.c_int32, C.c_float, vp, vp, vp, i64, vp, vp, vp]),
+        "rt_spheres_along_rays_count": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
+        "rt_spheres_along_rays_fill": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
         "rt_camera_rays": (C.c_int, [vp, vp, i64, i64, vp, vp]),
     }
     for name, (res, args) in sig.items():

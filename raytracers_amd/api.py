@@ -631,6 +631,35 @@ def sweep_spheres_ranged_into(rays_ptr, n, prepared, radius_ptr, t_min_ptr, t_ma
                                            C.c_void_p(index_ptr), C.c_void_p(start_ptr), C.c_void_p(hit_ptr)))
 
 
+def spheres_along_rays_count_into(rays_ptr, n, prepared, offsets_ptr, radius=0.0, t_min=0.0, t_max=1e9, radius_ptr=None, t_min_ptr=None,
+                                  t_max_ptr=None, exclude_ptr=None, first_ptr=None):
+    """Enqueue the count pass of the along-ray query of `n` queries (n x 6 float32 at rays_ptr; rt_spheres_along_rays_count): offsets_ptr
+    receives n + 1 int64, offsets[i + 1] - offsets[i] = the number of spheres the moving sphere of query i touches over its interval -- every
+    contact sweep_spheres would count -- with index != exclude_ptr[i] and index >= first_ptr[i] (n int32 each on the device; None: no such
+    filter).  radius_ptr: None (the scalar radius for every query) or n float32 on the device; t_min_ptr / t_max_ptr: both None (the scalar
+    pair) or both n float32 on the device.  Asynchronous, as spheres_within_count_into; then call spheres_along_rays_fill_into with the same
+    arguments."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_spheres_along_rays_count(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), float(radius), C.c_void_p(radius_ptr),
+                                               float(t_min), float(t_max), C.c_void_p(t_min_ptr), C.c_void_p(t_max_ptr),
+                                               C.c_void_p(exclude_ptr), C.c_void_p(first_ptr), C.c_void_p(offsets_ptr)))
+
+
+def spheres_along_rays_fill_into(rays_ptr, n, prepared, offsets_ptr, capacity, index_ptr, roots_ptr=None, start_ptr=None, query_ptr=None,
+                                 radius=0.0, t_min=0.0, t_max=1e9, radius_ptr=None, t_min_ptr=None, t_max_ptr=None, exclude_ptr=None,
+                                 first_ptr=None):
+    """Enqueue the fill pass (rt_spheres_along_rays_fill) for the offsets of spheres_along_rays_count_into on the same queries and scene: row
+    i at [offsets[i], offsets[i + 1]) of index_ptr (int32, ascending sphere index into L), roots_ptr (rows of two float32: the unclamped roots
+    t1, t2 against the sphere widened by the query's radius), start_ptr (uint8: 1 for an overlap where the interval begins) and query_ptr
+    (int32, the row number of each entry); `capacity` = the entries each array holds: nothing is written at or past it.  Any pointer may be
+    None, not all four."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_spheres_along_rays_fill(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), float(radius), C.c_void_p(radius_ptr),
+                                              float(t_min), float(t_max), C.c_void_p(t_min_ptr), C.c_void_p(t_max_ptr),
+                                              C.c_void_p(exclude_ptr), C.c_void_p(first_ptr), C.c_void_p(offsets_ptr), int(capacity),
+                                              C.c_void_p(index_ptr), C.c_void_p(roots_ptr), C.c_void_p(start_ptr), C.c_void_p(query_ptr)))
+
+
 def camera_rays_into(rays_ptr, h, w, prepared, cam=None):
     """Enqueue the h * w primary rays rt_render_image would trace (rt_camera_rays) into rays_ptr (h * w x 6 float32)."""
     ctx = prepared.ctx
@@ -1027,6 +1056,107 @@ def tile_frusta(cam12, h, w, tile_h, tile_w):
             x1 = min(w, x0 + tile_w)
             out.append(frustum_planes(cam12, x0 / w, x1 / w, (h - y1) / h, (h - y0) / h))
     return np.ascontiguousarray(np.stack(out), dtype=np.float32)
+
+
+def spheres_along_rays(prepared, rays, radius=0.0, t_min=0.0, t_max=1e9, exclude=None, first=None, roots=True, rows=False):
+    """EVERY sphere a ray crosses (radius 0) or a moving sphere of radius `radius` touches over (t_min, t_max), with no cap
+    (rt_spheres_along_rays_count / _fill), in spheres_within's CSR form -> (offsets (n + 1,) int64, index (total,) int32, roots (total, 2)
+    float32 or None, start (total,) uint8[, query (total,) int32]) numpy arrays.  The selection is sweep_spheres's: row i holds every contact
+    sweep_spheres would count for query i -- its length is that count -- in ASCENDING sphere index (an index into L), not by time.  roots:
+    the two roots t1 <= t2 of the ray against the sphere widened by the query's radius, unclamped (t1 may lie before t_min, t2 past t_max);
+    start: 0 for an entry contact (the contact is at t1), 1 for an overlap that already exists where the interval begins (the contact is at
+    t_min).  row_contacts turns rows into sweep_spheres's view (by time, padded to k), row_crossings into multi_hit_rays's.
+    radius, t_min, t_max: each a scalar, or an (n,) array / float32 device tensor, one per query (a scalar next to an array bound is
+    broadcast; an invalid array value gives an empty row; an invalid scalar, or a scalar pair with t_min > t_max, is an RtError).  exclude:
+    None, or an (n,) integer array / int32 device tensor -- sphere exclude[i] is skipped for query i.  first: as spheres_within.
+    roots=False: no roots array (None in its place).  rows=True: also `query`, the row number of every entry.  `rays`: (n, 6) float32, a
+    numpy array or a device tensor."""
+    with _Scope(prepared.ctx) as s:
+        ptr, n = _device_rows(s, rays, *_RAYS)
+        dev = s.ctx.device_info()["device"]
+        kw = {"radius": 0.0, "t_min": 0.0, "t_max": 0.0}
+        if _is_bound_array(radius):
+            kw["radius_ptr"] = _device_bound(s, dev, n, "radius", radius, per="query")
+        else:
+            kw["radius"] = radius
+        if _is_bound_array(t_min) or _is_bound_array(t_max):
+            kw["t_min_ptr"] = _device_bound(s, dev, n, "t_min", t_min, per="query")
+            kw["t_max_ptr"] = _device_bound(s, dev, n, "t_max", t_max, per="query")
+        else:
+            if not np.float32(t_min) <= np.float32(t_max):
+                raise RtError(f"t_min = {t_min!r}, t_max = {t_max!r}: scalar bounds must satisfy t_min <= t_max")
+            kw["t_min"], kw["t_max"] = t_min, t_max
+        kw["exclude_ptr"] = _device_first(s, dev, n, exclude, name="exclude", per="query") if exclude is not None else None
+        kw["first_ptr"] = _device_first(s, dev, n, first, per="query") if first is not None else None
+        off = s.alloc(8 * (n + 1))
+        spheres_along_rays_count_into(ptr, n, prepared, off.ptr, **kw)
+        offsets = off.to_host((n + 1,), np.int64)
+        total = int(offsets[n])
+        idx, rts, st, row = (s.alloc(size * total) if want else None for size, want in ((4, True), (8, roots), (1, True), (4, rows)))
+        if total:
+            spheres_along_rays_fill_into(ptr, n, prepared, off.ptr, total, idx.ptr, rts.ptr if rts else None, st.ptr, row.ptr if row else None,
+                                         **kw)
+        res = (offsets, idx.to_host((total,)), rts.to_host((total, 2), np.float32) if rts else None, st.to_host((total,), np.uint8))
+        return res + (row.to_host((total,)),) if rows else res
+
+
+def _row_bound(n, b):
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(b, dtype=np.float32), (n,)))
+
+
+def _ranked_rows(n, k, row, keys, columns):
+    """Entries with row numbers `row` sorted by (row, keys...), the first k of every row scattered into (n, k) arrays: `columns` is a list of
+    (values, padding, dtype) -> (count (n,) int32, [array (n, k) ...])."""
+    k = int(k)
+    order = np.lexsort(tuple(reversed(keys)) + (row,))
+    row = row[order]
+    count = np.bincount(row, minlength=n).astype(np.int32)
+    begin = np.concatenate([[0], np.cumsum(count, dtype=np.int64)[:-1]])
+    slot = np.arange(row.size) - begin[row]
+    sel = slot < k
+    out = []
+    for values, pad, dtype in columns:
+        a = np.full((n, k), pad, dtype)
+        a[row[sel], slot[sel]] = values[order][sel]
+        out.append(a)
+    return count, out
+
+
+def row_contacts(offsets, index, roots, start, t_min, k):
+    """The rows of spheres_along_rays as sweep_spheres sees them -> (count (n,) int32, index (n, k) int32, start (n, k) uint8, tau (n, k)
+    float32): every row ordered by (tau, index) with tau = t_min + 0.0 for an overlap at the start and t1 for an entry contact, the first
+    min(count, k) kept, the slots past them -1, 0 and 0.0 -- sweep_spheres's count, index, start and hit[..., 0] for the same queries.
+    t_min: the queries' scalar t_min, or their (n,) array.  Host-side numpy on the arrays spheres_along_rays returned."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    n = offsets.size - 1
+    row = np.repeat(np.arange(n), np.diff(offsets))
+    index, start = np.asarray(index), np.asarray(start)
+    lo = _row_bound(n, t_min)
+    with np.errstate(invalid="ignore"):
+        tau = np.where(start != 0, lo[row] + np.float32(0), np.asarray(roots, dtype=np.float32).reshape(-1, 2)[:, 0]).astype(np.float32)
+    count, (idx, st, tk) = _ranked_rows(n, k, row, (tau, index), ((index, -1, np.int32), (start, 0, np.uint8), (tau, 0, np.float32)))
+    return count, idx, st, tk
+
+
+def row_crossings(offsets, index, roots, t_min, t_max, k):
+    """The rows of spheres_along_rays (radius 0) as multi_hit_rays sees them -> (count (n,) int32, index (n, k) int32, root (n, k) uint8,
+    t (n, k) float32): the roots of every row's entries that lie strictly inside (t_min, t_max), ordered by (t, index, root) with root 1
+    for t1 and 2 for t2, the first min(count, k) kept, the slots past them -1, 0 and 0.0 -- multi_hit_rays's count, index, root and
+    hit[..., 0] for the same rays.  An entry with no root inside the interval (the segment lies wholly inside the sphere) contributes none.
+    t_min, t_max: the queries' scalars, or their (n,) arrays.  Host-side numpy on the arrays spheres_along_rays returned."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    n = offsets.size - 1
+    row = np.repeat(np.arange(n), np.diff(offsets))
+    index = np.asarray(index)
+    roots = np.asarray(roots, dtype=np.float32).reshape(-1, 2)
+    lo, hi = _row_bound(n, t_min)[row], _row_bound(n, t_max)[row]
+    t = np.concatenate([roots[:, 0], roots[:, 1]])
+    with np.errstate(invalid="ignore"):
+        keep = (t > np.concatenate([lo, lo])) & (t < np.concatenate([hi, hi]))
+    which = np.concatenate([np.full(row.size, 1, np.uint8), np.full(row.size, 2, np.uint8)])[keep]
+    row2, idx2, t = np.concatenate([row, row])[keep], np.concatenate([index, index])[keep], t[keep]
+    count, (idx, rt, tk) = _ranked_rows(n, k, row2, (t, idx2, which), ((idx2, -1, np.int32), (which, 0, np.uint8), (t, 0, np.float32)))
+    return count, idx, rt, tk
 
 
 def contact_pairs(prepared, margin=0.0, gaps=True):

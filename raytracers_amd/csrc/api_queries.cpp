@@ -1,5 +1,5 @@
 // api_queries.cpp -- the caller queries of the rt_* surface (include/rt_mi355x.h): rays traced, intersected, tested for occlusion, multi-hit,
-// sphere casts, ray paths, the proximity, range, box and plane-set queries, contact pairs, a frame's primary rays.  Checks and launches only: the lane kernels are
+// sphere casts, ray paths, the proximity, range, box, plane-set and along-ray queries, contact pairs, a frame's primary rays.  Checks and launches only: the lane kernels are
 // query_kernels.hip, and where an entry runs the pooled family (rt_trace_rays, rt_occluded_rays[_ranged]) its plan, parameters and launch
 // are the render policy's (api.cpp, through rt_internal.hpp).
 #include <hip/hip_runtime.h>
@@ -541,6 +541,64 @@ extern "C" int rt_spheres_in_planes_fill(rt_context *ctx, const rt_prepared *ps,
   RT_LOCK(ctx);
   return planes_entry(ctx, ps, "rt_spheres_in_planes_fill", true, n, planes4_dev, nplanes, margin, margin_dev, first_dev,
                       const_cast<int64_t *>(offsets_dev), capacity, index_dev, gap_dev, point_dev);
+}
+
+// The along-ray entries (rt_spheres_along_rays_*): the range entries' checks in a ray query's words, the scalar interval and radius checked
+// where they are used, then along_lane under every variant; the count pass shares the range queries' cached scratch.
+static int along_entry(rt_context *ctx, const rt_prepared *ps, const char *what, bool fill, int64_t n, const float *rays_dev, float radius,
+                       const float *radius_dev, float t_min, float t_max, const float *t_min_dev, const float *t_max_dev,
+                       const int32_t *exclude_dev, const int32_t *first_dev, int64_t *offsets_dev, int64_t capacity, int32_t *index_dev,
+                       float *roots_dev, uint8_t *start_dev, int32_t *query_dev) {
+  if (!ps) return fail(ctx, "null prepared scene");
+  if (ctx->group) return fail_in(ctx, what, ": a multi-device context is not supported (use a context on one device)");
+  if (n < 0 || n >= (int64_t(1) << 31)) return fail_in(ctx, what, ": query count out of range: 0 <= n < 2^31");
+  if (!rays_dev) return fail_in(ctx, what, ": null rays pointer");
+  if (!offsets_dev) return fail_in(ctx, what, ": null offsets pointer");
+  if (fill && capacity < 0) return fail_in(ctx, what, ": negative capacity");
+  if (fill && !index_dev && !roots_dev && !start_dev && !query_dev) return fail_in(ctx, what, ": every output is NULL");
+  if ((t_min_dev == nullptr) != (t_max_dev == nullptr)) return fail_in(ctx, what, ": t_min_dev and t_max_dev must both be NULL or both be given");
+  if (!t_min_dev && !ray_interval_ok(t_min, t_max)) return fail_in(ctx, what, ": need 0 <= t_min <= t_max <= 1e9, both finite");
+  if (!radius_dev && !distance_ok(radius)) return fail_in(ctx, what, ": need 0 <= radius <= 1e9, finite");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  rtk::KParams p{};
+  rti::scene_params(ps, &p);
+  p.rays = rays_dev;
+  p.nrays = static_cast<int>(n);
+  if (fill) {
+    ctx->synced_since_render = false;
+    RT_HIP(ctx, rtk::launch_along_fill(p, radius_dev, radius, t_min_dev, t_max_dev, t_min, t_max, exclude_dev, first_dev, offsets_dev, capacity,
+                                       index_dev, roots_dev, start_dev, query_dev, ctx->stream));
+  } else {
+    char *scratch = nullptr;
+    if (n > 0 && within_scratch(ctx, n, &scratch) != 0) return 1;
+    ctx->synced_since_render = false;
+    RT_HIP(ctx, rtk::launch_along_count(p, radius_dev, radius, t_min_dev, t_max_dev, t_min, t_max, exclude_dev, first_dev, scratch, offsets_dev,
+                                        ctx->stream));
+  }
+  ctx->last_launch = std::string(fill ? "family=along fill" : "family=along count") + (radius_dev || t_min_dev ? " (per-query)" : "") +
+                     (exclude_dev ? " exclude" : "") + (first_dev ? " first" : "");
+  return 0;
+}
+
+extern "C" int rt_spheres_along_rays_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float radius,
+                                           const float *radius_dev, float t_min, float t_max, const float *t_min_dev, const float *t_max_dev,
+                                           const int32_t *exclude_dev, const int32_t *first_dev, int64_t *offsets_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return along_entry(ctx, ps, "rt_spheres_along_rays_count", false, n, rays_dev, radius, radius_dev, t_min, t_max, t_min_dev, t_max_dev, exclude_dev,
+                     first_dev, offsets_dev, 0, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int rt_spheres_along_rays_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float radius,
+                                          const float *radius_dev, float t_min, float t_max, const float *t_min_dev, const float *t_max_dev,
+                                          const int32_t *exclude_dev, const int32_t *first_dev, const int64_t *offsets_dev, int64_t capacity,
+                                          int32_t *index_dev, float *roots_dev, uint8_t *start_dev, int32_t *query_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return along_entry(ctx, ps, "rt_spheres_along_rays_fill", true, n, rays_dev, radius, radius_dev, t_min, t_max, t_min_dev, t_max_dev, exclude_dev,
+                     first_dev, const_cast<int64_t *>(offsets_dev), capacity, index_dev, roots_dev, start_dev, query_dev);
 }
 
 extern "C" int rt_prepared_get_sphere_ids(rt_context *ctx, const rt_prepared *ps, int32_t *ids_dev) {

@@ -1,6 +1,6 @@
 // query_core.h -- per-lane arithmetic of the caller queries that no render-path kernel calls: both roots of a sphere and the sphere
 // casts' contact rule, the proximity queries' gap, box bound, slack and selection key, the box queries' gap and node test, the plane-set
-// queries' normalisation, gap and node test, a ray path's bounce.  Shared by query_kernels.hip and the host-side checks (tools/sweep_check.cpp, tools/path_check.cpp, tools/proximity_bound_check.cpp,
+// queries' normalisation, gap and node test, a ray path's bounce.  Shared by query_kernels.hip and the host-side checks (tools/sweep_check.cpp, tools/along_check.cpp, tools/path_check.cpp, tools/proximity_bound_check.cpp,
 // tools/box_query_bound_check.cpp, tools/plane_query_bound_check.cpp).  Same parity contract as lane_core.h, which holds what the render
 // path shares with the queries (box_hit_interval, sphere_hit_any, interval_ok, rehit_range).
 #pragma once
@@ -39,6 +39,24 @@ RT_HD int sweep_contact(const Ray &r, float spx, float spy, float spz, float sra
     return kSweepEntry;
   }
   if ((t2 > tlo) && (tlo < thi)) {
+    *tau = tlo + 0.0f;
+    return kSweepStart;
+  }
+  return kSweepNone;
+}
+// sweep_contact with the two roots handed back (rt_spheres_along_rays_*): the same operations in the same order, so kind and
+// *tau are sweep_contact's bit for bit; *t1 and *t2 are the roots it compared -- of (sp, R = srad + rq), unclamped -- and are written
+// whenever the discriminant is positive (a NaN discriminant: two NaN roots, kSweepNone), also for kSweepNone.
+RT_HD int sweep_contact_roots(const Ray &r, float spx, float spy, float spz, float srad, float rq, float tlo, float thi, float *tau, float *t1,
+                              float *t2) {
+  const float R = srad + rq;
+  if (!sphere_roots(r, spx, spy, spz, R, t1, t2)) return kSweepNone;
+  if (*t1 > tlo) {
+    if (!(*t1 < thi)) return kSweepNone;
+    *tau = *t1;
+    return kSweepEntry;
+  }
+  if ((*t2 > tlo) && (tlo < thi)) {
     *tau = tlo + 0.0f;
     return kSweepStart;
   }

@@ -59,6 +59,17 @@ hipError_t launch_planes_fill(const KParams &p, const float *planes, int nplanes
 constexpr int kSweepMaxK = 32;
 hipError_t launch_sweep_spheres(const KParams &p, const float *radius_dev, float radius, const int32_t *exclude, int k, int32_t *count,
                                 int32_t *index, uint8_t *start, float *hit7, hipStream_t stream);
+// rt_spheres_along_rays_*: for p.nrays queries (p.rays: n x 6 float32) EVERY sphere rt_sweep_spheres_ranged would count -- the widened box test
+// on every node, sweep_contact at the leaf, j != exclude[i] -- and j >= first_dev[i], in the range queries' CSR form and two passes: the same
+// scratch (within_scratch_bytes(n)), scan and capacity guard as launch_within_count / launch_within_fill, rows in ascending j.  radius_dev
+// nullptr: `radius` for every query; tlo_dev / thi_dev both nullptr: (t_min, t_max) for every query, else both set (a scalar that is used and
+// fails its rule: hipErrorInvalidValue).  exclude / first_dev: nullptr, or n int32.  The entry arrays: index, roots (rows {t1, t2} of the
+// sphere (c, r + rq), unclamped), start (0 entry contact, 1 overlap at the start), query (the row number) -- any may be nullptr, not all.
+hipError_t launch_along_count(const KParams &p, const float *radius_dev, float radius, const float *tlo_dev, const float *thi_dev, float t_min,
+                              float t_max, const int32_t *exclude, const int32_t *first_dev, char *scratch, int64_t *offsets, hipStream_t stream);
+hipError_t launch_along_fill(const KParams &p, const float *radius_dev, float radius, const float *tlo_dev, const float *thi_dev, float t_min,
+                             float t_max, const int32_t *exclude, const int32_t *first_dev, const int64_t *offsets, int64_t capacity,
+                             int32_t *index, float *roots, uint8_t *start, int32_t *query, hipStream_t stream);
 // rt_trace_paths[_shaped]: the bounce chain of each ray (ray_colour with objs_hit r 0 1e9, up to max_depth >= 0 vertices): count[i], end[i]
 // (kPathEscaped / kPathAbsorbed / kPathTruncated, query_core.h), the first min(count, k) vertices at index [i * k + s] and hit7
 // [(i * k + s) * 7 ..] (1 <= k <= kPathsMaxK; padded with -1 and seven zeros), light3 / last_ray6 / colour3 [i]: the loop variables at exit

@@ -1,5 +1,5 @@
 // query_kernels.hip -- the lane kernels of the caller queries, one lane per ray or point: closest hit (rt_intersect_rays), occlusion
-// (rt_occluded_rays), multi-hit, sphere casts, ray paths, the nearest spheres, the range queries / contact pairs with their scan, the box and plane-set queries, and the primary
+// (rt_occluded_rays), multi-hit, sphere casts, ray paths, the nearest spheres, the range queries / contact pairs with their scan, the box, plane-set and along-ray queries, and the primary
 // rays of a frame (rt_camera_rays).  The render path -- pixel_kernel, persistent_kernel, pooled_kernel and their RAYS modes -- is
 // render_kernels.hip; nothing here is launched by a render entry.  Build: as render_kernels.hip (-ffp-contract=off, bit-exact fp32).
 #include <hip/hip_runtime.h>
@@ -970,6 +970,143 @@ hipError_t launch_planes_fill(const KParams &p, const float *planes, int nplanes
   if (margin_dev == nullptr && !max_dist_ok(margin)) return hipErrorInvalidValue;
   margin += 0.0f;   // (-0.0 -> +0.0)
   launch_planes_kernel<true>(nplanes, p, planes, margin_dev, margin, first_dev, exact_depth, nullptr, offsets, capacity, index, gap, point, stream);
+  return hipGetLastError();
+}
+
+// rt_spheres_along_rays_*: EVERY sphere a ray crosses or a moving sphere touches over its interval, in CSR form.  One lane
+// per query, two existing lanes combined.  From sweep_lane's RANGED form the SELECTION: every popped node's box widened by the query's rq
+// (six additions) through box_hit_interval over (t_min, t_max) -- the root included, no exact_depth: the answer is the tree's, as the sweep's --
+// the leaf's j != skip, and the contact rule (sweep_contact_roots: sweep_contact's kind, plus the two roots it compared).  From within_lane
+// the ORDER and the protocol: children pushed right then left, a leaf right child waiting on the stack as a leaf entry (within_leaf_entry;
+// a node entry carries depth 0, the walk reads no depth), so the leaves are met in ascending j; the `first` compare at the leaf; count pass
+// and fill pass evaluating the same predicate; the fill's at / end guard.  No sorted list: one counter, or one cursor.  The per-query radius
+// and interval are kernel arguments, each scalar or per query: radius_dev / tlo_dev / thi_dev nullptr means the scalar next to it (tlo_dev and
+// thi_dev: both or neither).  A per-query interval failing interval_ok or radius failing max_dist_ok does not start its walk.  A row of `roots`
+// is {t1, t2}, one 8-byte store; only 4-byte alignment of the array is assumed (as the pair rows of within_lane<.., SELF>).
+template <bool FILL>
+__device__ __forceinline__ void along_lane(const KParams &p, const float *radius_dev, float rq, const float *tlo_dev, const float *thi_dev,
+                                           float t_min, float t_max, const int32_t *exclude, const int32_t *first_dev, int32_t *count,
+                                           const int64_t *offsets, int64_t capacity, int32_t *index, float *roots, uint8_t *start,
+                                           int32_t *query) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.nrays) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const Ray r = load_ray(p.rays, i);
+  bool valid = true;
+  if (tlo_dev != nullptr) {
+    t_min = tlo_dev[i];
+    t_max = thi_dev[i];
+    valid = interval_ok(t_min, t_max);
+  }
+  if (radius_dev != nullptr) {
+    rq = radius_dev[i] + 0.0f;   // (-0.0 -> +0.0)
+    valid = valid && max_dist_ok(rq);
+  }
+  const int skip = exclude != nullptr ? exclude[i] : -1;
+  int first = 0;
+  if (first_dev != nullptr) first = first_dev[i] > 0 ? first_dev[i] : 0;
+  int cnt = 0;
+  int64_t at = 0, end = 0;
+  if constexpr (FILL) {
+    at = offsets[i];
+    end = offsets[i + 1] < capacity ? offsets[i + 1] : capacity;
+    if (at < 0) at = end;   // (offsets that are not a scan of counts: nothing is written)
+  }
+  int sp = 0;
+  if (valid) stack[sp++][lane] = within_node_entry(0, 0);
+  while (sp > 0) {
+    const unsigned e = (unsigned)stack[--sp][lane];
+    const int ni = (int)(e & 0x3ffffffu);
+    int leaf[2] = {-1, -1};
+    if ((int)(e >> 26) == kWithinLeaf) {
+      leaf[0] = ni;
+    } else {
+      const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+      if (!box_hit_interval(r, lo.x - rq, lo.y - rq, lo.z - rq, hi.x + rq, hi.y + rq, hi.z + rq, t_min, t_max)) continue;
+      const int l = f2i(lo.w), rc = f2i(hi.w);
+      // (one pending sibling per level: sp <= height + 1 <= kStackPixel)
+      if (l < 0) {
+        leaf[0] = ~l;
+        if (rc < 0) leaf[1] = ~rc;
+        else stack[sp++][lane] = within_node_entry(rc, 0);
+      } else {
+        stack[sp++][lane] = rc < 0 ? within_leaf_entry(~rc) : within_node_entry(rc, 0);
+        stack[sp++][lane] = within_node_entry(l, 0);
+      }
+    }
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      const int j = leaf[c2];
+      if (j >= first && j != skip) {   // (first >= 0: an empty leaf slot, -1, never passes)
+        const float4 s = buf_load16(rs_sph, j * 16);
+        float tau, t1, t2;
+        const int what = sweep_contact_roots(r, s.x, s.y, s.z, s.w, rq, t_min, t_max, &tau, &t1, &t2);
+        if (what != kSweepNone) {
+          if constexpr (FILL) {
+            if (at < end) {
+              if (index != nullptr) index[at] = j;
+              if (roots != nullptr) *reinterpret_cast<float2 *>(roots + 2 * at) = make_float2(t1, t2);
+              if (start != nullptr) start[at] = what == kSweepStart ? (uint8_t)1 : (uint8_t)0;
+              if (query != nullptr) query[at] = i;
+            }
+            ++at;
+          } else {
+            ++cnt;
+          }
+        }
+      }
+    }
+  }
+  if constexpr (!FILL) count[i] = cnt;
+}
+template <bool FILL>
+__global__ __launch_bounds__(64) void along_kernel(KParams p, const float *radius_dev, float rq, const float *tlo_dev, const float *thi_dev,
+                                                   float t_min, float t_max, const int32_t *exclude, const int32_t *first_dev, int32_t *count,
+                                                   const int64_t *offsets, int64_t capacity, int32_t *index, float *roots, uint8_t *start,
+                                                   int32_t *query) {
+  along_lane<FILL>(p, radius_dev, rq, tlo_dev, thi_dev, t_min, t_max, exclude, first_dev, count, offsets, capacity, index, roots, start, query);
+}
+
+// the launchers' shared argument rule: a scalar interval or radius is checked only where it is used
+static bool along_args_ok(const float *radius_dev, float radius, const float *tlo_dev, const float *thi_dev, float t_min, float t_max) {
+  if ((tlo_dev == nullptr) != (thi_dev == nullptr)) return false;
+  if (tlo_dev == nullptr && !interval_ok(t_min, t_max)) return false;
+  return radius_dev != nullptr || max_dist_ok(radius);
+}
+
+// the count pass and the range queries' scan (the same three launches over the same scratch layout), then the fill pass
+hipError_t launch_along_count(const KParams &p, const float *radius_dev, float radius, const float *tlo_dev, const float *thi_dev, float t_min,
+                              float t_max, const int32_t *exclude, const int32_t *first_dev, char *scratch, int64_t *offsets, hipStream_t stream) {
+  if (offsets == nullptr) return hipErrorInvalidValue;
+  if (p.nrays <= 0) return hipMemsetAsync(offsets, 0, sizeof(int64_t), stream);
+  if (p.rays == nullptr || scratch == nullptr || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (!along_args_ok(radius_dev, radius, tlo_dev, thi_dev, t_min, t_max)) return hipErrorInvalidValue;
+  radius += 0.0f;   // (-0.0 -> +0.0)
+  const int n = p.nrays;
+  int32_t *const counts = reinterpret_cast<int32_t *>(scratch);
+  long long *const sums = reinterpret_cast<long long *>(scratch + (((size_t)n * 4 + 255) & ~(size_t)255));
+  hipLaunchKernelGGL((along_kernel<false>), dim3(((unsigned)n + 63u) / 64u), dim3(64), 0, stream, p, radius_dev, radius, tlo_dev, thi_dev, t_min,
+                     t_max, exclude, first_dev, counts, nullptr, (int64_t)0, nullptr, nullptr, nullptr, nullptr);
+  const int nblocks = (int)(((int64_t)n + kWithinScanItems - 1) / kWithinScanItems);
+  hipLaunchKernelGGL(within_scan_sums_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums);
+  hipLaunchKernelGGL(within_scan_carry_kernel, dim3(1), dim3(kWithinScanThreads), 0, stream, sums, nblocks);
+  hipLaunchKernelGGL(within_scan_apply_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums, offsets);
+  return hipGetLastError();
+}
+
+hipError_t launch_along_fill(const KParams &p, const float *radius_dev, float radius, const float *tlo_dev, const float *thi_dev, float t_min,
+                             float t_max, const int32_t *exclude, const int32_t *first_dev, const int64_t *offsets, int64_t capacity,
+                             int32_t *index, float *roots, uint8_t *start, int32_t *query, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (p.rays == nullptr || offsets == nullptr || capacity < 0 || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (index == nullptr && roots == nullptr && start == nullptr && query == nullptr) return hipErrorInvalidValue;
+  if (!along_args_ok(radius_dev, radius, tlo_dev, thi_dev, t_min, t_max)) return hipErrorInvalidValue;
+  radius += 0.0f;   // (-0.0 -> +0.0)
+  hipLaunchKernelGGL((along_kernel<true>), dim3(((unsigned)p.nrays + 63u) / 64u), dim3(64), 0, stream, p, radius_dev, radius, tlo_dev, thi_dev,
+                     t_min, t_max, exclude, first_dev, nullptr, offsets, capacity, index, roots, start, query);
   return hipGetLastError();
 }
 
