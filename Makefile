@@ -99,6 +99,12 @@ build/cull_guard_check: tools/cull_guard_check.cpp $(CSRC)/lane_core.h $(CSRC)/r
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -I$(CSRC) -o $@ tools/cull_guard_check.cpp $(OBJ)/host_build.o
 
+# the render path's dark stop (lane_core.h: light_is_dead): every pixel's chain walked in full and stopped where SHADE would stop it -- pixels
+# compared, rays / box tests / sphere tests of both; in the CPU test suite
+build/dark_stop_check: tools/dark_stop_check.cpp $(CSRC)/lane_core.h $(CSRC)/rt_host.hpp $(OBJ)/host_build.o
+	@mkdir -p build
+	$(CXX) $(HOSTFLAGS) -I$(CSRC) -o $@ tools/dark_stop_check.cpp $(OBJ)/host_build.o
+
 # the box test of the proximity queries (query_core.h: box_may_hold) hammered with host-built boxes and __float128; in the CPU test suite
 build/proximity_bound_check: tools/proximity_bound_check.cpp $(CSRC)/query_core.h $(CSRC)/lane_core.h $(CSRC)/rt_host.hpp $(OBJ)/host_build.o
 	@mkdir -p build
@@ -186,7 +192,7 @@ build/first_call_probe: tools/first_call_probe.c include/ray.h $(LIB)
 	@mkdir -p build
 	$(CC) -O2 -std=gnu99 -Wall -Iinclude -o $@ tools/first_call_probe.c -Lraytracers_amd -lray_mi355x -Wl,-rpath,'$$ORIGIN/../raytracers_amd'
 
-tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/plane_query_bound_check build/box_presorted_check build/sweep_check build/along_check build/path_check build/view_order_check
+tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/dark_stop_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/plane_query_bound_check build/box_presorted_check build/sweep_check build/along_check build/path_check build/view_order_check
 
 oracle:
 	$(MAKE) -s -C oracle

@@ -522,6 +522,13 @@ void set_cull(const rt_context *ctx, const rt_prepared *ps, const Plan &pl, cons
   p->cull_kappa = ps->cull.kappa;
 }
 
+// The dark stop (lane_core.h: light_is_dead; DESIGN.md 3.1, SHADE): which pooled render launches finish a chain whose light is exactly zero as pixel 0.
+// Every one that does not record (a view's record is the full chains' lengths) -- and, of the instrumented launches, rt_render_trace's
+// under dark_stop = 1 only.
+void set_dark(const rt_context *ctx, bool instrumented, rtk::KParams *p) {
+  p->dark = (ctx->dark_stop != 0 && p->cost == nullptr && (!instrumented || ctx->dark_stop > 0)) ? 1 : 0;
+}
+
 // The name of the pooled instantiation these parameters launch (rt_context_last_launch)
 std::string pooled_launch_name(const rtk::KParams &p, int waves, int rays = 0) {
   rtk::PooledKey k{};
@@ -1013,14 +1020,15 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
   Tickets t;
   if (int rc = choose_tickets(ctx, ps, to, xq, tick, p, pl, &t)) return rc;
   set_cull(ctx, ps, pl, cams_dev, &p);
+  set_dark(ctx, false, &p);
   tick("before launch");
   RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream));
   tick("launch_pooled");
   char buf[256];
-  std::snprintf(buf, sizeof buf, "family=pooled tickets=%s%s instantiation=%s frames=%d tiles=%d grid=%d waves=%d counters=%d%s deep_class=%d deep_split=%d recording=%d nodes=%s",
+  std::snprintf(buf, sizeof buf, "family=pooled tickets=%s%s instantiation=%s frames=%d tiles=%d grid=%d waves=%d counters=%d%s deep_class=%d deep_split=%d recording=%d nodes=%s,dark=%d",
                 p.px_hdr ? "pixel-list" : t.first_order ? "tiles-bit-reversed" : (p.order ? "tiles-ordered" : "tiles-raster"), t.borrowed ? "(borrowed)" : "",
                 pooled_launch_name(p, pl.waves).c_str(), p.nframes, p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "", p.px_hdr ? 0 : p.deep_class,
-                p.px_hdr ? 0 : p.deep_split, p.cost ? (p.cost_px ? 2 : 1) : 0, pooled_launch_nodes(p, pl.waves));
+                p.px_hdr ? 0 : p.deep_split, p.cost ? (p.cost_px ? 2 : 1) : 0, pooled_launch_nodes(p, pl.waves), p.dark);
   ctx->last_launch = buf;
   if (to && p.cost) {
     // This frame recorded the view's bounce chains.  The sorts that turn the record into the view's tile order and pixel list are
@@ -1289,6 +1297,8 @@ extern "C" int rt_context_set_option(rt_context *ctx, const char *name, int64_t 
     ctx->wide_waves = std::max(0, std::min(2, v));
   } else if (k == "cull") {
     ctx->cull = std::max(-1, std::min(1, v));
+  } else if (k == "dark_stop") {
+    ctx->dark_stop = std::max(-1, std::min(1, v));
   } else if (k == "sync_policy") {
     ctx->sync_policy = v != 0;
   } else {
@@ -1963,6 +1973,7 @@ extern "C" int rt_render_trace(rt_context *ctx, const rt_prepared *ps, int64_t h
       }
     nw = pl.grid * pl.waves;
     set_cull(ctx, ps, pl, nullptr, &p);   // as enqueue_render launches this view
+    set_dark(ctx, true, &p);              // (dark_stop = 1: the stopped chains of production; else the full chains, the reference's counts)
     e = rtk::launch_pooled(p, true, pl.grid, pl.waves, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) e = hipMemcpy(records, trace, sizeof(unsigned long long) * rtk::kTraceWords * static_cast<size_t>(nw), hipMemcpyDeviceToHost);

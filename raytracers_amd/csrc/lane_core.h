@@ -341,6 +341,19 @@ RT_HD bool shade_ray(Ray &r, bool have, float t, float spx, float spy, float spz
                                 [&](float cr, float cg, float cb) { *pixel = pack_pixel(cr, cg, cb); });
 }
 
+// A chain whose light is exactly zero cannot change its pixel any more (the render path's dark stop; DESIGN.md 3.1, SHADE).  Asked where a fold
+// has just scattered: shade_ray returned true and lr, lg, lb hold the NEW light.
+//  - ray_colour (ray.fut:126-148) keeps colour = (0,0,0) until the chain ends and then returns light * sky (a miss, :140-148) or light * 0
+//    (absorbed, or the bounce budget spent); light is the running product of the colours of the spheres hit so far (:136-138).
+//  - `== 0.0f` holds for +0 and -0 and fails for NaN.  From a channel that is +-0 every later value of that channel is 0 * colour: +-0 for a
+//    finite colour, NaN for an infinite or NaN one, never anything else -- and NaN stays NaN.
+//  - colour_to_pixel's operand (:158-162) is that value times the sky term or times 0.0f: +-0 or NaN again, whatever the sky term is (finite,
+//    inf or NaN from a degenerate direction).  255.99f * (+-0 | NaN) is +-0 or NaN, the device's float -> int conversion gives 0 for both, and
+//    (0 << 16) | (0 << 8) | 0 == 0.
+// So a pixel stored as 0 here is what the full chain would have stored: no guard on the scene, the camera or max_depth.  Only for PACKED
+// pixels: the entries that return float colours (rt_trace_rays, rt_trace_paths) show -0 and NaN payloads and never stop.
+RT_HD bool light_is_dead(float lr, float lg, float lb) { return (lr == 0.0f) & (lg == 0.0f) & (lb == 0.0f); }
+
 // One whole iteration of ray_colour's loop body AFTER the fold: re-intersect the winning
 // sphere with (0.0, best+1), then scatter or terminate.
 RT_HD bool finish_ray(Ray &r, float best, int bestj, float spx, float spy, float spz, float srad,

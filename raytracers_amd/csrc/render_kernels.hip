@@ -455,6 +455,7 @@ __device__ __attribute__((noinline)) void solo_trace(KParamsArg pp_v, unsigned s
   const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(pp->sph, (unsigned)pp->n_sph * 16u);
   const __amdgpu_buffer_rsrc_t rs_col = make_rsrc(pp->col, (unsigned)pp->n_sph * 16u);
   const int max_depth = pp->max_depth;
+  const bool dark = pp->dark != 0;
   const float cull_c2 = pp->cull_c2, cull_kappa = pp->cull_kappa;
   const float rlx = pp->root_lo[0], rly = pp->root_lo[1], rlz = pp->root_lo[2];
   const float rhx = pp->root_hi[0], rhy = pp->root_hi[1], rhz = pp->root_hi[2];
@@ -586,8 +587,11 @@ __device__ __attribute__((noinline)) void solo_trace(KParamsArg pp_v, unsigned s
     bool have = hit;
     float t = best;
     if (hit && !rehit_is_best(best, ((unsigned)key & 1u) != 0u)) have = rehit_full(r, best, s.x, s.y, s.z, s.w, &t);
-    int32_t pixel;
-    if (!shade_ray<false>(r, have, t, s.x, s.y, s.z, c.x, c.y, c.z, c.w, lr, lg, lb, depth, max_depth, &pixel)) {
+    // (the dark stop, lane_core.h: a chain that has just scattered into light == (0, 0, 0) ends here with the pixel it would end in whatever it meets --
+    // 0, which `pixel` still holds: shade_ray writes it in its finishing branches only.  One branch, as before: a lone wave pays for every instruction)
+    int32_t pixel = 0;
+    const bool more = shade_ray<false>(r, have, t, s.x, s.y, s.z, c.x, c.y, c.z, c.w, lr, lg, lb, depth, max_depth, &pixel);
+    if (!more | (dark & light_is_dead(lr, lg, lb))) {
       if (lane == 0) {
         pp->out[pix] = pixel;
         if (pp->cost != nullptr) {
@@ -646,6 +650,12 @@ __device__ __attribute__((noinline)) void solo_trace(KParamsArg pp_v, unsigned s
 // sphere has a root inside the interval, and from then on the slot's boxes are tested over (t_min, 0) -- empty, so its remaining items drain
 // without appending anything; SHADE stores key == kKeyAnyHit at the ray's index (no re-hit, no bounce).  A ray whose own interval fails
 // interval_ok misses the root box and is stored as 0.
+// KParams::dark of the running launch, loaded where it is asked for: read as p.dark the compiler loads it ahead of the loop and keeps it in a scalar register
+// across every operation -- the instantiations that call solo_trace then spill one more scalar pair and reload it in every BOX operation
+__device__ __forceinline__ int launch_dark() {
+  return *reinterpret_cast<const volatile __attribute__((address_space(4))) int *>(&((KParamsArg)__builtin_amdgcn_kernarg_segment_ptr())->dark);
+}
+
 template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, int RAYS = 0>
 __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 4) void pooled_kernel(KParams p) {
   constexpr bool COLD = TAIL == 1, DONATE = TAIL == 2;
@@ -936,12 +946,27 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
             // (RAYS: the finished colour is stored at the ray's index, from the branch of shade_ray that produces it; the render
             // path's store stays behind the call -- inside it the SPILL kernels spilled one more VGPR)
             int32_t pixel;
+            if constexpr (!SPILL) pixel = 0;
             bool more;
             if constexpr (RAYS)
               more = shade_ray_emit<false>(r, have, t, s.x, s.y, s.z, c.x, c.y, c.z, c.w, lr, lg, lb, depth, p.max_depth,
                                            [&](float cr, float cg, float cb) { store_ray_result(p, pix, cr, cg, cb); });
             else
               more = shade_ray<false>(r, have, t, s.x, s.y, s.z, c.x, c.y, c.z, c.w, lr, lg, lb, depth, p.max_depth, &pixel);
+            // the dark stop (lane_core.h: light_is_dead): a chain that has just scattered into light == (0, 0, 0) is finished as pixel 0 -- the value
+            // every continuation of it ends in, and what `pixel` still holds (shade_ray writes it in its finishing branches only) -- through the store
+            // below: no root, nothing donated.  Mask logic, no branch.  (p.dark: never set with p.cost, api.cpp: set_dark)
+            // (SPILL: as a branch that sets the pixel -- in the mask form the plain SPILL kernels spilled one more dword, 20 -> 24 bytes of scratch)
+            if constexpr (!RAYS && !SPILL) {
+              const bool dark = launch_dark() != 0, dead = light_is_dead(lr, lg, lb);
+              more = more & !(dark & dead);
+            }
+            if constexpr (!RAYS && SPILL != 0) {
+              if (more && launch_dark() && light_is_dead(lr, lg, lb)) {
+                more = false;
+                pixel = 0;
+              }
+            }
             if (more) {
               root = true;
             } else if constexpr (RAYS) {

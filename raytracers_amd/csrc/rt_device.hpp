@@ -263,6 +263,9 @@ struct KParams {
   int cull;              // pooled family, workgroups of 16 waves: != 0 = the CULL instantiations (boxes are tested against the slot's best root so far: lane_core.h, cull_limit) ...
   float cull_c2;         // ... the scene's constant in a ray's weight W2 = max|1 / d_k| * (d.d) * c2 ...
   float cull_kappa;      // ... and in the limit best + W2 (best^2 + kappa)   (api.cpp: the prepared scene's CullConst)
+  int dark;              // pooled family, render launches (RAYS == 0): != 0 = a chain whose light has become exactly zero is finished as pixel 0 instead of being traced on (lane_core.h:
+                         // light_is_dead).  The host's decision (api.cpp: set_dark): never with a recording launch -- the record is the FULL chain's length.  Read in SHADE and in
+                         // solo_trace only.  (in the four bytes of padding ahead of u_tab: no field's offset in the argument block moves, and the block keeps its size)
   const float *u_tab;    // [w]  pixel_u(col, w)
   const float *v_tab;    // [h]  pixel_v(row, h), indexed by the FULL image row
   // pooled family, workgroups of four waves (the shape of twenty waves per CU): a box stack whose LDS capacity `capb` is BELOW its bound (64 H + 63: trees taller

@@ -9,6 +9,7 @@
 //     voting policy, and the SIMT lane efficiency of each phase.
 //
 //   build/wavesim <rgbbox|irreg|floor:n:k> <h> <w> [thr_shade thr_leaf lmax nwaves policy]
+//   (policy 13: policy 10 with the dark stop -- chains whose light is exactly zero are finished as pixel 0, lane_core.h: light_is_dead)
 //   (policy 10 / 11: the pooled design with 64 / 128 items per operation; 12: policy 10 plus the LDS cost of every BOX operation's node
 //   reads under the four-plane layout and the candidate sign-ordered layouts -- e.g. wavesim rgbbox 1000 1000 32 0 64 4096 12)
 #include <omp.h>
@@ -262,7 +263,7 @@ struct PWave {
 
 struct PCounters {
   unsigned long long ops[3] = {0, 0, 0}, lanes[3] = {0, 0, 0};
-  unsigned long long rays = 0, box = 0, sphere = 0, fetches = 0;
+  unsigned long long rays = 0, box = 0, sphere = 0, fetches = 0, stopped = 0;
   size_t max_box = 0, max_leaf = 0;
 };
 
@@ -360,6 +361,8 @@ static void lds_model_box(const int *rec, const bool (*sg)[3], int n) {
   lds_inst(g_lds[L_PAIRS], a, 2, 2, 64);
 }
 
+static bool g_dark_stop = false;   // (policy 13)
+
 static bool pwave_step(PWave &W, const SceneData &S, int width, int thr_shade, unsigned &next_ticket,
                        std::vector<int32_t> &out, PCounters &C) {
   const size_t nbox = W.box.size(), nleaf = W.leaf.size();
@@ -441,7 +444,13 @@ static bool pwave_step(PWave &W, const SceneData &S, int width, int thr_shade, u
         F4 sp{0, 0, 0, 1}, c{0, 0, 0, 0};
         if (bestj >= 0) { sp = S.sph[bestj]; c = S.col[bestj]; }
         int32_t pixel;
-        if (finish_ray(s.r, best, bestj, sp.x, sp.y, sp.z, sp.w, c.x, c.y, c.z, c.w, s.lr, s.lg, s.lb, s.depth, S.max_depth, &pixel)) {
+        bool more = finish_ray(s.r, best, bestj, sp.x, sp.y, sp.z, sp.w, c.x, c.y, c.z, c.w, s.lr, s.lg, s.lb, s.depth, S.max_depth, &pixel);
+        if (more && g_dark_stop && light_is_dead(s.lr, s.lg, s.lb)) {   // (policy 13) the dark stop: the chain's pixel is 0 whatever it meets from here
+          more = false;
+          pixel = 0;
+          C.stopped++;
+        }
+        if (more) {
           s.key = kKeyInit; s.cnt = 1;
           W.box.push_back(((unsigned)l << 24) | 0u);
           C.rays++;
@@ -495,8 +504,9 @@ static int run_pooled(const SceneData &S, const std::vector<int32_t> &ref, int n
   }
   size_t diff = 0;
   for (size_t i = 0; i < ref.size(); ++i) diff += ref[i] != out[i];
-  std::printf("pooled(width %d, thr_shade %d, %d waves): checksum %08x diff_vs_simple %zu rays %llu box %llu sphere %llu fetches %llu\n",
-              width, thr_shade, nwaves, checksum(out), diff, C.rays, C.box, C.sphere, C.fetches);
+  std::printf("pooled(width %d, thr_shade %d, %d waves): checksum %08x diff_vs_simple %zu rays %llu box %llu sphere %llu fetches %llu%s\n",
+              width, thr_shade, nwaves, checksum(out), diff, C.rays, C.box, C.sphere, C.fetches,
+              g_dark_stop ? (" dark stop: " + std::to_string(C.stopped) + " chains cut").c_str() : "");
   const char *names[3] = {"BOX", "LEAF", "SHADE"};
   for (int i = 0; i < 3; ++i)
     std::printf("  %-5s wave-ops %10llu lanes %12llu efficiency %.3f\n", names[i], C.ops[i], C.lanes[i],
@@ -562,7 +572,9 @@ int main(int argc, char **argv) {
 
   if (P.kind >= 10) {
     // pooled design: kind 10 -> 64 items per op, kind 11 -> 128 items per op, kind 12 -> 10 with the LDS model of the node reads
+    // kind 13 -> 10 with the dark stop (lane_core.h: light_is_dead): the same image, fewer operations
     g_lds_model = P.kind == 12;
+    g_dark_stop = P.kind == 13;
     if (P.lmax >= 64) g_nslots = P.lmax;   // reuse the lmax argument: slots per wave
     return run_pooled(S, ref, nwaves, P.kind == 11 ? 128 : 64, P.thr_shade);
   }
