@@ -40,7 +40,7 @@ $(OBJ)/multi_gpu.o: $(CSRC)/multi_gpu.cpp $(CSRC)/rt_internal.hpp $(CSRC)/rt_dev
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(OBJ)/host_build.o: $(CSRC)/host_build.cpp $(CSRC)/rt_host.hpp $(CSRC)/treelet.h
+$(OBJ)/host_build.o: $(CSRC)/host_build.cpp $(CSRC)/rt_host.hpp $(CSRC)/lane_core.h $(CSRC)/treelet.h
 	@mkdir -p $(OBJ)
 	$(CXX) $(HOSTFLAGS) -c $< -o $@
 
@@ -104,6 +104,13 @@ build/cull_guard_check: tools/cull_guard_check.cpp $(CSRC)/lane_core.h $(CSRC)/r
 build/dark_stop_check: tools/dark_stop_check.cpp $(CSRC)/lane_core.h $(CSRC)/rt_host.hpp $(OBJ)/host_build.o
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -I$(CSRC) -o $@ tools/dark_stop_check.cpp $(OBJ)/host_build.o
+
+# the leaf's own box of the pooled records (lane_core.h: leaf_box_eps): every chain of a frame walked over the product's records unfiltered and
+# filtered -- sphere tests of both, accepted roots lost, pixels compared -- and the claim behind the margin hammered against __float128, with the
+# shrunk boxes that must be found; in the CPU test suite
+build/leaf_box_check: tools/leaf_box_check.cpp $(CSRC)/lane_core.h $(CSRC)/rt_host.hpp $(OBJ)/host_build.o
+	@mkdir -p build
+	$(CXX) $(HOSTFLAGS) -fopenmp -I$(CSRC) -o $@ tools/leaf_box_check.cpp $(OBJ)/host_build.o -lquadmath
 
 # the box test of the proximity queries (query_core.h: box_may_hold) hammered with host-built boxes and __float128; in the CPU test suite
 build/proximity_bound_check: tools/proximity_bound_check.cpp $(CSRC)/query_core.h $(CSRC)/lane_core.h $(CSRC)/rt_host.hpp $(OBJ)/host_build.o
@@ -192,7 +199,7 @@ build/first_call_probe: tools/first_call_probe.c include/ray.h $(LIB)
 	@mkdir -p build
 	$(CC) -O2 -std=gnu99 -Wall -Iinclude -o $@ tools/first_call_probe.c -Lraytracers_amd -lray_mi355x -Wl,-rpath,'$$ORIGIN/../raytracers_amd'
 
-tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/dark_stop_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/plane_query_bound_check build/box_presorted_check build/sweep_check build/along_check build/path_check build/view_order_check
+tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/dark_stop_check build/leaf_box_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/plane_query_bound_check build/box_presorted_check build/sweep_check build/along_check build/path_check build/view_order_check
 
 oracle:
 	$(MAKE) -s -C oracle

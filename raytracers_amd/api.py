@@ -75,7 +75,8 @@ class Context:
     @property
     def last_launch(self):
         """what the last render entry enqueued: family, tickets (pixel list / ordered tiles / raster), instantiation, launch shape, and for a pooled render
-        launch whether it stops chains whose light is exactly zero ("dark=0|1", option dark_stop: -1 default, 0 never, 1 also the instrumented launch)"""
+        launch whether it stops chains whose light is exactly zero ("dark=0|1", option dark_stop: -1 default, 0 never, 1 also the instrumented launch)
+        and whether it drops sphere tests whose own widened box the ray misses ("leaf_box=0|1", option leaf_box, the same three values)"""
         return lib.rt_context_last_launch(self._h).decode()
 
     @property

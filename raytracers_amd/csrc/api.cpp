@@ -529,6 +529,23 @@ void set_dark(const rt_context *ctx, bool instrumented, rtk::KParams *p) {
   p->dark = (ctx->dark_stop != 0 && p->cost == nullptr && (!instrumented || ctx->dark_stop > 0)) ? 1 : 0;
 }
 
+// The leaf's own box (lane_core.h: leaf_box_eps): which pooled render launches let BOX / BOX2 drop a leaf child whose slot fails.
+// Every one whose scene lives in LDS whole (a scene read from L2 gains nothing measurable: rt_device.hpp, pooled_leaf_box) with its slots filled
+// (rt_prepared::leaf) and whose cameras -- the launch's one, or every camera of a batch, read from
+// the context's pinned copy as set_cull does; cameras that live only on the device switch the filter off -- pass leaf_box_camera_ok; of the
+// instrumented launches rt_render_trace's under leaf_box = 1 only (its default item counts are the reference's test set).
+void set_leaf_box(const rt_context *ctx, const rt_prepared *ps, const Plan &pl, const float *cams_dev, bool instrumented, rtk::KParams *p) {
+  p->leaf_box = 0;
+  if (ctx->leaf_box == 0 || !ps->leaf.ok || pl.variant != RT_VARIANT_POOLED || (instrumented && ctx->leaf_box <= 0)) return;
+  if (pl.lds_nodes != p->n_nodes || pl.lds_sph != p->n_sph) return;
+  if (cams_dev == nullptr ? !rt::leaf_box_camera_ok(ps->leaf, &p->cam.ox) : (cams_dev != ctx->cams_dev || ctx->cams_host == nullptr)) return;
+  for (int f = 0; cams_dev != nullptr && f < p->nframes; ++f)
+    if (!rt::leaf_box_camera_ok(ps->leaf, ctx->cams_host + 12 * f)) return;
+  rtk::PooledKey k{};   // (... and the instantiation is one that filters: rt_device.hpp, pooled_leaf_box)
+  if (!rtk::choose_pooled(*p, instrumented, pl.waves, 0, &k) || !rtk::pooled_leaf_box(k)) return;
+  p->leaf_box = 1;
+}
+
 // The name of the pooled instantiation these parameters launch (rt_context_last_launch)
 std::string pooled_launch_name(const rtk::KParams &p, int waves, int rays = 0) {
   rtk::PooledKey k{};
@@ -1021,14 +1038,15 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
   if (int rc = choose_tickets(ctx, ps, to, xq, tick, p, pl, &t)) return rc;
   set_cull(ctx, ps, pl, cams_dev, &p);
   set_dark(ctx, false, &p);
+  set_leaf_box(ctx, ps, pl, cams_dev, false, &p);
   tick("before launch");
   RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream));
   tick("launch_pooled");
-  char buf[256];
-  std::snprintf(buf, sizeof buf, "family=pooled tickets=%s%s instantiation=%s frames=%d tiles=%d grid=%d waves=%d counters=%d%s deep_class=%d deep_split=%d recording=%d nodes=%s,dark=%d",
+  char buf[320];
+  std::snprintf(buf, sizeof buf, "family=pooled tickets=%s%s instantiation=%s frames=%d tiles=%d grid=%d waves=%d counters=%d%s deep_class=%d deep_split=%d recording=%d nodes=%s,dark=%d,leaf_box=%d",
                 p.px_hdr ? "pixel-list" : t.first_order ? "tiles-bit-reversed" : (p.order ? "tiles-ordered" : "tiles-raster"), t.borrowed ? "(borrowed)" : "",
                 pooled_launch_name(p, pl.waves).c_str(), p.nframes, p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "", p.px_hdr ? 0 : p.deep_class,
-                p.px_hdr ? 0 : p.deep_split, p.cost ? (p.cost_px ? 2 : 1) : 0, pooled_launch_nodes(p, pl.waves), p.dark);
+                p.px_hdr ? 0 : p.deep_split, p.cost ? (p.cost_px ? 2 : 1) : 0, pooled_launch_nodes(p, pl.waves), p.dark, p.leaf_box);
   ctx->last_launch = buf;
   if (to && p.cost) {
     // This frame recorded the view's bounce chains.  The sorts that turn the record into the view's tile order and pixel list are
@@ -1299,6 +1317,8 @@ extern "C" int rt_context_set_option(rt_context *ctx, const char *name, int64_t 
     ctx->cull = std::max(-1, std::min(1, v));
   } else if (k == "dark_stop") {
     ctx->dark_stop = std::max(-1, std::min(1, v));
+  } else if (k == "leaf_box") {
+    ctx->leaf_box = std::max(-1, std::min(1, v));
   } else if (k == "sync_policy") {
     ctx->sync_policy = v != 0;
   } else {
@@ -1393,6 +1413,7 @@ hipError_t alloc_prepared_block(rt_context *ctx, rt_prepared *ps) {
 
 // gpu_build = 0: the BVH built on the host and uploaded into ps's block (height, treelet depth, root box set).  Returns non-zero with
 // the context's error set when a copy cannot be enqueued; *e: the final synchronisation's status.
+// (ps->leaf, set by the caller: the leaf-child slots of the 64-byte records are filled before the upload)
 int host_build_upload(rt_context *ctx, rt_prepared *ps, const std::vector<rt::Sphere> &spheres, hipError_t *e) {
   const size_t n = spheres.size(), ni = n - 1;
   int rc = 0;
@@ -1400,7 +1421,8 @@ int host_build_upload(rt_context *ctx, rt_prepared *ps, const std::vector<rt::Sp
     if (!rc && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(ctx, "hipMemcpyAsync failed");
   };
   const rt::Lbvh bvh = rt::build_lbvh(spheres);
-  const rt::TravLayout tl = rt::make_trav_layout(bvh, ctx->treelet);
+  rt::TravLayout tl = rt::make_trav_layout(bvh, ctx->treelet);
+  rt::fill_leaf_boxes(tl, ps->leaf);
   ps->height = tl.height;
   ps->tl_depth = tl.treelet_depth;
   put(ps->L7, bvh.L.data(), n * sizeof(rt::Sphere));
@@ -1441,6 +1463,18 @@ extern "C" int rt_prepare_scene(rt_context *ctx, rt_prepared **out, int64_t h, i
   // multi-device context: the other devices build their replicas while this one builds its own (no early return from
   // here to group_prepare_end)
   if (ctx->group) rti::group_prepare_begin(ctx, ps.get(), h, w, scene);
+  {
+    // culling by the best hit (lane_core.h: cull_limit) and the leaves' own boxes (leaf_box_eps): the scene's guards and constants; the spheres'
+    // side once per scene, ahead of the build (the host builder fills the leaf slots itself)
+    std::lock_guard<std::mutex> lock(scene->mu);
+    if (!scene->cull_done) {
+      const rt::CullStats st = rt::cull_stats(scene->desc.spheres.data(), n);
+      scene->cull = rt::cull_finish(st, n, 0);
+      scene->leaf = rt::leaf_box_finish(st, n);
+      scene->cull_done = true;
+    }
+    ps->leaf = scene->leaf;
+  }
   if (ctx->gpu_build) {
     // ---- BVH construction on the GPU (bvh_build.hip): upload the spheres, build in place ----
     // (a multi-device prepare_scene uploads from one host thread per device: the lock covers the look-up and the
@@ -1486,6 +1520,8 @@ extern "C" int rt_prepare_scene(rt_context *ctx, rt_prepared **out, int64_t h, i
       e = rtk::gpu_build_bvh(scene_dev, static_cast<int>(n), o, tmp, ctx->pinned, ctx->stream, &ps->height, ps->root_lo,
                              ps->root_hi);
       ps->tl_depth = rtk::kTreeletDepth;
+      if (e == hipSuccess && ps->leaf.ok)
+        e = rtk::launch_leaf_boxes(ps->nodes64, ps->sph, static_cast<int>(n) - 1, ps->leaf.q, ps->leaf.lin, ps->leaf.abs, ctx->stream);
     }
     if (tmp) {
       (void)hipStreamSynchronize(ctx->stream);
@@ -1495,12 +1531,7 @@ extern "C" int rt_prepare_scene(rt_context *ctx, rt_prepared **out, int64_t h, i
     rc = host_build_upload(ctx, ps.get(), scene->desc.spheres, &e);
   }
   if (!rc && e == hipSuccess) {
-    // culling by the best hit (lane_core.h: cull_limit): the scene's guards and constants; the spheres' side once per scene
     std::lock_guard<std::mutex> lock(scene->mu);
-    if (!scene->cull_done) {
-      scene->cull = rt::cull_scene_constants(scene->desc.spheres, 0);
-      scene->cull_done = true;
-    }
     ps->cull = scene->cull;
     ps->cull.ok = ps->cull.ok && ps->height <= static_cast<int>(log2f(static_cast<float>(n))) + 2;   // every box contains its subtree (bvh.fut:47)
   }
@@ -1576,14 +1607,23 @@ int build_from_device(rt_context *ctx, rt_prepared *ps, const float *spheres7_de
     st.c_max = slot->c_max;
     st.bad = slot->bad != 0;
     ps->cull = rt::cull_finish(st, n, 0);
+    // (the leaf slots of the records just built are zero: filled behind the build, the constants being known only now)
+    ps->leaf = rt::leaf_box_finish(st, n);
+    if (ps->leaf.ok) {
+      *e = rtk::launch_leaf_boxes(ps->nodes64, ps->sph, static_cast<int>(n) - 1, ps->leaf.q, ps->leaf.lin, ps->leaf.abs, ctx->stream);
+      if (*e == hipSuccess) *e = hipStreamSynchronize(ctx->stream);
+      if (*e != hipSuccess) return 0;
+    }
   } else {
     std::vector<rt::Sphere> host(n);
     *e = hipMemcpyAsync(host.data(), spheres7_dev, n * sizeof(rt::Sphere), hipMemcpyDeviceToHost, ctx->stream);
     if (*e == hipSuccess) *e = hipStreamSynchronize(ctx->stream);
     if (*e != hipSuccess) return 0;
+    const rt::CullStats st = rt::cull_stats(host.data(), n);
+    ps->leaf = rt::leaf_box_finish(st, n);
     if (int rc = host_build_upload(ctx, ps, host, e)) return rc;
     if (*e != hipSuccess) return 0;
-    ps->cull = rt::cull_scene_constants(host, 0);
+    ps->cull = rt::cull_finish(st, n, 0);
   }
   // (as rt_prepare_scene: every box contains its subtree, bvh.fut:47; a tree taller than 15 levels gets the spill regions here)
   ps->cull.ok = ps->cull.ok && ps->height <= static_cast<int>(log2f(static_cast<float>(n))) + 2;
@@ -1974,6 +2014,7 @@ extern "C" int rt_render_trace(rt_context *ctx, const rt_prepared *ps, int64_t h
     nw = pl.grid * pl.waves;
     set_cull(ctx, ps, pl, nullptr, &p);   // as enqueue_render launches this view
     set_dark(ctx, true, &p);              // (dark_stop = 1: the stopped chains of production; else the full chains, the reference's counts)
+    set_leaf_box(ctx, ps, pl, nullptr, true, &p);   // (leaf_box = 1: production's filtered sphere tests; else every leaf child of a passing node, the reference's)
     e = rtk::launch_pooled(p, true, pl.grid, pl.waves, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) e = hipMemcpy(records, trace, sizeof(unsigned long long) * rtk::kTraceWords * static_cast<size_t>(nw), hipMemcpyDeviceToHost);

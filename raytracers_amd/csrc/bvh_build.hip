@@ -1712,6 +1712,36 @@ __global__ __launch_bounds__(kBT) void cull_stats_final_kernel(const CullStatsDe
 }
 }  // namespace
 
+// ---------------------------------------------------------------------------------
+// The leaf-child slots of the 64-byte records (rt_device.hpp: launch_leaf_boxes; the host's rt::fill_leaf_boxes): a thread per record, the
+// slot of a child whose pre-shifted reference is negative gets leaf_box_bounds of that sphere.  The .w of every quarter (references, treelet
+// masks) is left alone.
+// ---------------------------------------------------------------------------------
+namespace {
+__global__ __launch_bounds__(kBT) void leaf_boxes_kernel(float4 *nodes64, const float4 *__restrict__ sph, int ni, float q, float lin, float abs) {
+  const int t = blockIdx.x * kBT + threadIdx.x;
+  if (t >= ni) return;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int ref8 = __float_as_int(nodes64[4 * (size_t)t + k].w);
+    if (ref8 >= 0) continue;
+    const float4 s = sph[~(ref8 >> 8)];
+    float lo[3], hi[3];
+    leaf_box_bounds(s.x, s.y, s.z, s.w, q, lin, abs, lo, hi);
+    float4 *const slot = nodes64 + 4 * (size_t)t + 2 * k;
+    const float w0 = slot[0].w, w1 = slot[1].w;
+    slot[0] = make_float4(lo[0], lo[1], lo[2], w0);
+    slot[1] = make_float4(hi[0], hi[1], hi[2], w1);
+  }
+}
+}  // namespace
+
+hipError_t launch_leaf_boxes(float4 *nodes64, const float4 *sph, int n_nodes, float q, float lin, float abs, hipStream_t st) {
+  if (n_nodes < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(leaf_boxes_kernel, dim3(cdiv(n_nodes, kBT)), dim3(kBT), 0, st, nodes64, sph, n_nodes, q, lin, abs);
+  return hipGetLastError();
+}
+
 hipError_t launch_cull_stats(const float *sph7_dev, int n, CullStatsDev *partial, CullStatsDev *out, hipStream_t st) {
   const int nb = cdiv(n, kBT), blocks = nb < kCullStatsBlocks ? nb : kCullStatsBlocks;
   if (blocks < 1) return hipErrorInvalidValue;

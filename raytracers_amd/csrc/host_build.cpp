@@ -7,6 +7,7 @@
 //   bvh_mk   futhark/bvh.fut:30-59         morton  futhark/bvh.fut:8-22
 //   radix tree  futhark/radixtree.fut:11-72 (Karras 2012, index tie-break on equal keys)
 #include "rt_host.hpp"
+#include "lane_core.h"
 
 #include <algorithm>
 #include <cmath>
@@ -432,6 +433,65 @@ CullConst cull_finish(const CullStats &s, size_t n, int height) {
   c.kappa = std::nextafter(static_cast<float>(c0 / (c2 * 0.015625)), INFINITY);   // / kCullALo: W2 kappa >= max|1 / d_k| c0 for every a >= 2^-6
   c.ok = std::isfinite(c.c2) && std::isfinite(c.kappa);
   return c;
+}
+
+// ---- the leaf's own box (rt_host.hpp; the argument is DESIGN.md 3.4a) ----
+LeafBoxConst leaf_box_finish(const CullStats &s, size_t n) {
+  LeafBoxConst c;
+  if (n < 2 || s.bad) return c;
+  const double r_min = s.r_min, r_max = s.r_max, c_max = s.c_max;
+  if (c_max > 0x1p40) return c;
+  double diag2 = 0.0;
+  for (int a = 0; a < 3; ++a) {
+    c.centre[a] = 0.5 * (s.lo[a] + s.hi[a]);
+    diag2 += (s.hi[a] - s.lo[a]) * (s.hi[a] - s.lo[a]);
+  }
+  const double R = 0.5 * std::sqrt(diag2) * (1.0 + 0x1p-20);
+  c.d_eps = 2.0 * (R + r_max);
+  c.cam_max = c.d_eps - R;
+  if (c_max + c.d_eps > 0x1p15 * r_min) return c;
+  if (0x1p-18 * (c.d_eps * c.d_eps / (r_min * r_min) + 1.0) > 0.4375 * (1.0 - 0x1p-10)) return c;
+  // rho / 2 = 2^-19 (D^2 / r + r); the slab margin 4u (D + 2 r); the corners' rounding 4u C_max; 1 % for eps's own three roundings and r + eps's
+  c.q = std::nextafter(static_cast<float>(1.01 * 0x1p-19 * c.d_eps * c.d_eps), INFINITY);
+  c.lin = std::nextafter(static_cast<float>(1.01 * (0x1p-19 + 0x1p-21)), INFINITY);
+  c.abs = std::nextafter(static_cast<float>(1.01 * 0x1p-22 * (c.d_eps + c_max)), INFINITY);
+  c.ok = std::isfinite(c.q) && std::isfinite(c.abs) && c.q > 0.0f;
+  return c;
+}
+
+bool leaf_box_camera_ok(const LeafBoxConst &c, const float cam12[12]) {
+  if (!c.ok) return false;
+  double m = 0.0;
+  for (int i = 0; i < 12; ++i) {
+    if (!std::isfinite(cam12[i])) return false;
+    m = std::max(m, std::fabs(static_cast<double>(cam12[i])));
+  }
+  if (m > 0x1p15) return false;
+  const double o[3] = {cam12[0], cam12[1], cam12[2]}, l[3] = {cam12[3] - o[0], cam12[4] - o[1], cam12[5] - o[2]};
+  const double hv[3] = {cam12[6], cam12[7], cam12[8]}, vv[3] = {cam12[9], cam12[10], cam12[11]};
+  double d2 = 0.0;
+  for (int a = 0; a < 3; ++a) d2 += (o[a] - c.centre[a]) * (o[a] - c.centre[a]);
+  if (!(std::sqrt(d2) * (1.0 + 0x1p-20) <= c.cam_max)) return false;
+  const double nx = hv[1] * vv[2] - hv[2] * vv[1], ny = hv[2] * vv[0] - hv[0] * vv[2], nz = hv[0] * vv[1] - hv[1] * vv[0];
+  const double nn = std::sqrt(nx * nx + ny * ny + nz * nz);
+  if (!(nn > 0.0)) return false;
+  const double plane = std::fabs(l[0] * nx + l[1] * ny + l[2] * nz) / nn;
+  return plane * (1.0 - 0x1p-20) - 0x1p-19 * m >= 0x1p-12;
+}
+
+void fill_leaf_boxes(TravLayout &t, const LeafBoxConst &c) {
+  if (!c.ok) return;
+  const size_t ni = t.nodes64.size() / 16;
+  for (size_t ti = 0; ti < ni; ++ti) {
+    float *q = &t.nodes64[16 * ti];
+    for (int k = 0; k < 2; ++k) {
+      int32_t ref8;
+      std::memcpy(&ref8, &q[3 + 4 * k], 4);
+      if (ref8 >= 0) continue;
+      const float *s = &t.sph[4 * static_cast<size_t>(~(ref8 >> 8))];
+      rtk::leaf_box_bounds(s[0], s[1], s[2], s[3], c.q, c.lin, c.abs, &q[8 * k], &q[8 * k + 4]);
+    }
+  }
 }
 
 bool cull_origin_ok(const CullConst &c, const float origin[3]) {

@@ -185,6 +185,26 @@ RT_HD float cull_limit(float best, float w2, float kappa) {       // the interva
   return fminf(__builtin_fmaf(w2, __builtin_fmaf(best, best, kappa), best), kTMax);
 }
 
+// ---- the leaf's own box (the pooled kernel's BOX / BOX2 append a leaf child only if it passes) ------------
+// The record of an inner node has a box slot for either child; the slot of a LEAF child holds the sphere's own box widened by
+// eps(r) on every side, [p - (r + eps), p + (r + eps)] in binary32, and BOX's test of that slot -- the arithmetic it always ran
+// there -- decides whether the sphere is tested at all.  Claim: whenever sphere_root accepts a root g (0.1 < g < 1e9) for a ray
+// (o, d) and a sphere (p, r), box_hit / box_hit_presorted pass on that box over (0, 1e9) -- the CULL instantiations never filter.
+// With D = |o - p| <= D_eps:
+//   (E1)  | |P - p|^2 - r^2 | <= 2^-18 (D^2 + r^2) for P = o + g d, so P lies at most r (sqrt(1 + phi) - 1) <= rho / 2 OUTSIDE
+//         the sphere, rho = 2^-18 (D^2 / r + r), phi = rho / r;
+//   slab: each of the six products is exact within (1 -+ 2^-24)^3, so the interval computed for a box that holds P with
+//         m >= 4 * 2^-24 |P - o| to spare on every side contains g (a NaN slab is skipped, an infinite one has the right sign);
+//   corner: fl(p -+ fl(r + eps)) gives away at most 4 * 2^-24 C_max.
+// eps(r) = q / r + lin r + abs covers the three with 1 % to spare for its own roundings (rt_host.hpp: leaf_box_finish sets q,
+// lin, abs from the scene's statistics and D_eps = 2 (R + r_max); leaf_box_camera_ok admits a launch's cameras).
+RT_HD float leaf_box_eps(float rad, float q, float lin, float abs) { return (q / rad + lin * rad) + abs; }
+RT_HD void leaf_box_bounds(float px, float py, float pz, float rad, float q, float lin, float abs, float lo[3], float hi[3]) {
+  const float rw = rad + leaf_box_eps(rad, q, lin, abs);
+  lo[0] = px - rw; lo[1] = py - rw; lo[2] = pz - rw;
+  hi[0] = px + rw; hi[1] = py + rw; hi[2] = pz + rw;
+}
+
 // The root closest_hit would accept for this sphere if its running t_max were large
 // (ray.fut:32-51 called with t_min = 0.1, :79): root1 if root1 > 0.1, else root2 if
 // root2 > 0.1, else none.  (root2 >= root1, so "root1 >= t_max, try root2" can never

@@ -656,6 +656,16 @@ __device__ __forceinline__ int launch_dark() {
   return *reinterpret_cast<const volatile __attribute__((address_space(4))) int *>(&((KParamsArg)__builtin_amdgcn_kernarg_segment_ptr())->dark);
 }
 
+// KParams::leaf_box of the running launch as the mask BOX / BOX2 or into a leaf child's own box test: all ones = unfiltered.  Loaded where it is asked for, as
+// launch_dark is and for its reason -- but it feeds SCALAR mask logic, so it must come by a scalar load: a volatile load is selected as a vector one.  The
+// argument block's address passes through an empty asm instead (a uniform value the compiler knows nothing about: the load behind it cannot be hoisted out of
+// the loop, and stays an s_load_dword that goes out with the operation's LDS reads and is needed behind its last compare).
+__device__ __forceinline__ unsigned long long launch_leaf_off() {
+  KParamsArg kp = (KParamsArg)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(kp));
+  return (unsigned long long)(unsigned)kp->leaf_box - 1ull;   // (the host stores 0 or 1: all ones, or zero -- a subtraction, not a select)
+}
+
 template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, int RAYS = 0>
 __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 4) void pooled_kernel(KParams p) {
   constexpr bool COLD = TAIL == 1, DONATE = TAIL == 2;
@@ -667,6 +677,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
   // place of the 64-byte record) and every box item carries its ray's sign offsets: BOX and BOX2 read near / far bounds at selected addresses
   // instead of selecting among products (box_hit_presorted).  The instantiations that call solo_trace keep the four planes its treelet reads use.
   constexpr bool PRESORT = pooled_presort(ALL_LDS, SOLO, TAIL, ORD, RAYS);
+  constexpr bool LEAFBOX = pooled_leaf_box(THREADS, ALL_LDS, STATS, SOLO, CULL, RAYS);   // BOX / BOX2 honour KParams::leaf_box (rt_device.hpp)
   extern __shared__ float4 smem[];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -1337,7 +1348,10 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         const unsigned long long m_ln = bal(cl8 < 0), m_rn = bal(cr8 < 0);
         // an inner child continues iff its box passes; a leaf child is tested because this node passed
         const unsigned long long m_inl = m_act & ~m_ln & m_hl, m_inr = m_act & ~m_rn & m_hr;
-        const unsigned long long m_lfl = m_act & m_ln, m_lfr = m_act & m_rn;
+        // (a leaf child's slot holds the sphere's own widened box, lane_core.h: leaf_box_eps -- the test above ran on it as on any slot; where the launch is
+        // admitted, m_off == 0, its verdict decides whether the sphere is tested: scalar mask logic only.  The caller-ray loops are never filtered)
+        const unsigned long long m_off = LEAFBOX ? launch_leaf_off() : ~0ull;
+        const unsigned long long m_lfl = m_act & m_ln & (m_hl | m_off), m_lfr = m_act & m_rn & (m_hr | m_off);
         if (STATS) n_box += __popcll(m_act & ~m_ln & (1ull << lane)) + __popcll(m_act & ~m_rn & (1ull << lane));
         // append: left children first, then right children (two independent prefix ranks per list; the right
         // children's ranks start at the left children's count: mbcnt's addend).  ONE store per child: to the box
@@ -1381,7 +1395,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         q.ox = ra.x; q.oy = ra.y; q.oz = ra.z;
         q.ix = ri.x; q.iy = ri.y; q.iz = ri.z;
         int ref, cl8, cr8;
-        bool pass, child_leaf;
+        bool pass, child_leaf, own;                   // own: the verdict on this lane's child's slot, whatever the child is
         unsigned long long m_pass, m_cleaf, m_hl, m_hr;
         if constexpr (PRESORT) {
           // this lane's child: dword `role` of the entries of the item's record; then the child's own record as in BOX
@@ -1392,7 +1406,8 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           const float cnz = lds_load4f(RT_PS_NEAR(cell, tz, kPsZ)), cfz = lds_load4f(RT_PS_FAR(cell, tz, kPsZ, kSignZ));
           ref = f2i(lds_load4f(cell + kPsRefs));
           child_leaf = act & (ref < 0);
-          pass = act & (ref >= 0) && box_hit_presorted(q, cnx, cfx, cny, cfy, cnz, cfz, 0.0f, kTMax);
+          own = box_hit_presorted(q, cnx, cfx, cny, cfy, cnz, cfz, 0.0f, kTMax);
+          pass = act & (ref >= 0) & own;
           const lds_cp cell2 = lds_ptr((unsigned)(size_t)smem + (pass ? (unsigned)ref >> kPsItemShift : 0u));
           const v2f nx = lds_load8(RT_PS_NEAR(cell2, tx, kPsX)), fx = lds_load8(RT_PS_FAR(cell2, tx, kPsX, kSignX));
           const v2f ny = lds_load8(RT_PS_NEAR(cell2, ty, kPsY)), fy = lds_load8(RT_PS_FAR(cell2, ty, kPsY, kSignY));
@@ -1426,7 +1441,13 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           limc = __uint_as_float(*reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(wkey) + 2 * sl4 + 4));
         }
         child_leaf = act & (ref < 0);
-        pass = act & (ref >= 0) && box_hit_interval(q, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, limlo, limc);
+        if constexpr (!LEAFBOX) {                      // (never filtered: the expression these instantiations were compiled from)
+          pass = act & (ref >= 0) && box_hit_interval(q, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, limlo, limc);
+          own = pass;
+        } else {
+          own = box_hit_interval(q, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, limlo, limc);
+          pass = act & (ref >= 0) & own;
+        }
         if (STATS) n_box += (act & (ref >= 0)) ? 1 : 0;
         // second level: the child's own record (a virtual item `ref | sl4`)
         const int ci16 = pass ? (int)(((unsigned)ref >> 4) & 0xfffffff0u) : 0;
@@ -1451,7 +1472,9 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         const unsigned long long m_ln = bal(cl8 < 0), m_rn = bal(cr8 < 0);
         const unsigned long long m_inl = m_pass & ~m_ln & m_hl, m_inr = m_pass & ~m_rn & m_hr;
         // leaf appends: the child itself (lanes whose child is a leaf), or its leaf children -- never both for one lane
-        const unsigned long long m_lfl = (m_pass & m_ln) | m_cleaf, m_lfr = m_pass & m_rn;
+        // (filtered launches: a leaf grandchild by its slot of the child's record, the leaf child itself by its slot of the item's record -- `own`)
+        const unsigned long long m_off = LEAFBOX ? launch_leaf_off() : ~0ull, m_own = bal(own);
+        const unsigned long long m_lfl = (m_pass & m_ln & (m_hl | m_off)) | (m_cleaf & (m_own | m_off)), m_lfr = m_pass & m_rn & (m_hr | m_off);
         if (STATS) n_box += __popcll(m_pass & ~m_ln & (1ull << lane)) + __popcll(m_pass & ~m_rn & (1ull << lane));
         const int c_inl = __popcll(m_inl), c_lfl = __popcll(m_lfl);
         const int dump = (int)(size_t)(wdump);

@@ -272,6 +272,9 @@ struct KParams {
   // than 15 levels) keeps its oldest items in device memory when it would overflow -- [waves][spill_stride] dwords, a wave's own region (nullptr: capb holds the bound)
   unsigned *spill;
   int spill_stride;
+  int leaf_box;          // pooled family, render launches (RAYS == 0): != 0 = BOX / BOX2 append a leaf child only if the box in its slot -- the sphere's own, widened (lane_core.h:
+                         // leaf_box_eps) -- passes.  The host's decision (api.cpp: set_leaf_box): the scene's slots filled and every camera of the launch inside the guard.  (in the
+                         // four bytes of padding behind spill_stride: no field's offset in the argument block moves, and the block keeps its size)
   // caller-supplied rays (rt_trace_rays: the RAYS instantiations of the pixel and pooled kernels): ray i is rays[6 i .. 6 i + 6) = {o.xyz, d.xyz};
   // its colour goes to colour3[3 i ..] and / or its packed pixel to out[i] (either pointer may be nullptr, not both)
   const float *rays;
@@ -412,6 +415,19 @@ inline bool choose_pooled(const KParams &p, bool stats, int waves_per_wg, int ra
 constexpr bool pooled_presort(bool all_lds, bool solo, int tail, bool ord, int rays) { return all_lds && !solo && tail == 0 && !ord && rays == 0; }
 constexpr bool pooled_presort(const PooledKey &k) { return pooled_presort(k.all_lds, k.solo, k.tail, k.ord, k.rays); }
 
+// The instantiations whose BOX / BOX2 can filter leaf children by their own box (KParams::leaf_box): the render kernels of a scene that lives in LDS whole
+// (ALL_LDS), and the instrumented ones without CULL (rt_render_trace counts what the filter leaves of such a scene's frame).  Left out, and so the parent's
+// instructions:
+//  * every kernel that reads the scene from L2, CULL or not: those launches already skip most of the sphere tests the filter would (irreg's batch: -3.5 % VALU
+//    instructions for -32 % sphere tests, its launch 0.1069 -> 0.1065 ms, inside the noise) and pay for the flag's scalar load in every BOX operation -- its
+//    ordered single frames, bound by their chains, were 0.5 - 1 % slower with it.  The host admits LDS-resident scenes only (api.cpp: set_leaf_box);
+//  * four waves, scene in LDS, SOLO: three more VGPRs put it at 96 with a larger private segment;
+//  * the caller-ray loops (no guard covers a caller's origins).
+constexpr bool pooled_leaf_box(int threads, bool all_lds, bool stats, bool solo, bool cull, int rays) {
+  return rays == 0 && !cull && (stats || (all_lds && !(threads == 256 && solo)));
+}
+constexpr bool pooled_leaf_box(const PooledKey &k) { return pooled_leaf_box(k.threads, k.all_lds, k.stats, k.solo, k.cull, k.rays); }
+
 // The instantiation's name in rt_context_last_launch: plain, SOLO, COLD, COLD+SOLO, DONATE, DONATE+SOLO, ORD, ORD+SOLO, ORD+DONATE, ORD+SOLO+DONATE,
 // any (the occlusion loop); then +CULL, +SPILL
 inline std::string pooled_name(const PooledKey &k) {
@@ -472,7 +488,11 @@ constexpr int kCullStatsBlocks = 1024;           // partials: at most this many
 constexpr size_t cull_stats_scratch_bytes() { return sizeof(CullStatsDev) * kCullStatsBlocks; }
 hipError_t launch_cull_stats(const float *sph7_dev, int n, CullStatsDev *partial, CullStatsDev *out, hipStream_t stream);
 
-constexpr int kOrderBlocksMax = 64;                                   // workgroups per shard of the tile-order sort
+// The leaf-child slots of nodes64 from sph (the device's copy of rt::fill_leaf_boxes: the same leaf_box_bounds, the same bits), behind a build
+// on the device -- whose records come out with zeroed slots -- once the host has the scene's constants
+hipError_t launch_leaf_boxes(float4 *nodes64, const float4 *sph, int n_nodes, float q, float lin, float abs, hipStream_t stream);
+
+constexpr int kOrderBlocksMax = 64;                                  // workgroups per shard of the tile-order sort
 constexpr int kOrderScratchInts = kMaxShards * 64 * kOrderBlocksMax;   // its scratch: [shard][bin][workgroup] counts
 hipError_t launch_tile_order(int *cost, int *order, int ntiles, int tiles_x, int nshards, int *scratch, hipStream_t stream);
 // The view's pixel list from the per-pixel record of its first frame (px_count / px_scan / px_place kernels): pixels by

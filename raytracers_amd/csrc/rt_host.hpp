@@ -119,6 +119,28 @@ CullStats cull_stats_merge(const CullStats &a, const CullStats &b);
 CullConst cull_finish(const CullStats &s, size_t n, int height);
 bool cull_origin_ok(const CullConst &c, const float origin[3]);   // |origin - centre| + R + r_max <= 2^15 r_min
 
+// ---- the leaf's own box in the pooled records (lane_core.h: leaf_box_eps) ----
+// The scene's side: whether the leaf-child slots of nodes64 hold the spheres' widened boxes at all, and the constants of
+// eps(r) = q / r + lin r + abs.  `ok` needs (no guard on the tree's height: a leaf's box is its own)
+//   * finite spheres with 2^-20 <= radius, |coordinate| + radius <= 2^40 (CullStats::bad) -- a scene with non-finite sphere data keeps
+//     zeroed slots and is never filtered;
+//   * with D_eps = 2 (R + r_max), the bound on any render ray's distance to any centre: C_max + D_eps <= 2^15 r_min (a hit point's
+//     rounding stays below r_min / 64) and 2^-18 (D_eps^2 / r_min^2 + 1) <= 7/16 (a hit point's normal keeps 3/4 of its length, so a
+//     scattered direction keeps d.d >= 2^-8: (E1) stays free of underflow along the whole chain).
+// A launch additionally needs every camera inside leaf_box_camera_ok.
+struct LeafBoxConst {
+  bool ok = false;
+  float q = 0.0f, lin = 0.0f, abs = 0.0f;
+  double centre[3] = {0, 0, 0}, d_eps = 0.0, cam_max = 0.0;   // centre of the centres' box; D_eps; the largest |origin - centre| = D_eps - R
+};
+LeafBoxConst leaf_box_finish(const CullStats &s, size_t n);
+// finite, every |component| <= 2^15, the origin within cam_max of the centre, and the image plane at least 2^-12 (plus the primary
+// directions' rounding, 2^-19 of the largest component) away from the origin: 2^-24 <= d.d <= 2^38 for every primary ray
+bool leaf_box_camera_ok(const LeafBoxConst &c, const float cam12[12]);
+// the leaf-child slots of t.nodes64 from t.sph (c.ok; otherwise they stay zero).  The device's copy of the same loop: bvh_build.hip,
+// launch_leaf_boxes -- both call leaf_box_bounds
+void fill_leaf_boxes(TravLayout &t, const LeafBoxConst &c);
+
 // rows owned by part p of nparts under the cyclic row-tile partition
 int64_t part_rows(int64_t h, int32_t rows_per_tile, int32_t part, int32_t nparts);
 

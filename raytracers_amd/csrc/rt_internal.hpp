@@ -75,7 +75,8 @@ struct rt_context {
   int wide_waves = 1;       // pooled family: five workgroups of four waves per CU (five waves per SIMD) for scenes read from L2 -- 1 (default): launches of 100 000 tiles or more (batches; frames beyond the pixel list's range; from 40 000 tiles for scenes larger than the L2s); 2: every launch (testing); 0: never
   int cull = -1;            // pooled family, workgroups of 16 waves: the CULL instantiations -- boxes tested against the slot's best root so far (lane_core.h: cull_limit; same pixels, fewer tests).  -1 (auto): where the scene and the camera pass the proof's guards (rt_host.hpp: CullConst) and the scene is not wholly LDS resident (rgbbox-sized scenes: the walk is short, the tests saved do not pay for the limit's three instructions per item); 1: wherever the guards pass; 0: never
   int dark_stop = -1;       // pooled family: a bounce chain whose light is exactly (0, 0, 0) is finished as pixel 0 instead of being traced on (lane_core.h: light_is_dead; same pixels, fewer rays).  -1 (default): every render launch that does not record and is not instrumented; 0: never; 1: as -1, and the instrumented launch of rt_render_trace too (its item counts are then production's).  Never a recording frame (a view's record is the full chains' lengths), never rt_render_stats (the reference's counts)
-  int eager_sort = 1;       // pooled family: 1 = the sorts that turn a view's record into its tile order and pixel list are launched right behind the recording frame on the context's SECOND stream (they run while the caller synchronises / sets up its next call; the view's next frame -- or a new view that borrows the order -- waits for their event, usually long past); 0 = lazily on the main stream, ahead of the view's next frame (round 5)
+  int leaf_box = -1;        // pooled family: BOX / BOX2 append a leaf child only if the box in its slot of the record -- the sphere's own, widened by a proven margin (lane_core.h: leaf_box_eps; same pixels, fewer sphere tests) -- passes.  -1 (default): every render launch whose scene and cameras pass the guards (rt_host.hpp: LeafBoxConst) and that is not instrumented; 0: never; 1: as -1, and the instrumented launch of rt_render_trace too.  Never the pixel or persistent families, the caller-ray loops or rt_render_stats
+  int eager_sort = 1;      // pooled family: 1 = the sorts that turn a view's record into its tile order and pixel list are launched right behind the recording frame on the context's SECOND stream (they run while the caller synchronises / sets up its next call; the view's next frame -- or a new view that borrows the order -- waits for their event, usually long past); 0 = lazily on the main stream, ahead of the view's next frame (round 5)
   int borrow = 1;           // pooled family: a NEW view (same image size, partition and bounce limit as a view of this prepared scene already rendered, another camera) renders its first frame through that view's order / pixel list while it records its own -- the order of independent pixels never changes them; the mispredicted long chains are what the DONATE tail is for.  0: a new view's first frame is unordered; 1 (auto): scenes read from L2 only, through the other view's pixel list (a scene that lives in LDS renders its new views unordered: measured as fast); 2: the tile order, 3: the pixel list, for either kind of scene; 4: the pixel list without its holds (testing)
   int sync_policy = 0;      // 1: a render entry WAITS for the view's class table (deep_policy) instead of polling for it -- which instantiation renders frame k is then the same in every run (measurements, PMC passes); 0: no render entry ever waits for the device
   // ticket counters of the persistent families (rtk::kQueueDwords): all zero between launches -- the last
@@ -141,6 +142,7 @@ struct rt_scene {
   mutable std::vector<DevCopy> copies;
   mutable bool cull_done = false;        // the spheres' side of the culling guards (rt_host.hpp: CullConst), computed by the first prepare_scene
   mutable rt::CullConst cull;
+  mutable rt::LeafBoxConst leaf;         // ... and of the leaf boxes (rt_host.hpp: LeafBoxConst), with it
 };
 
 // Tile-order state of one (image size, partition, depth, camera) view of a prepared scene.
@@ -189,6 +191,7 @@ struct rt_prepared {
   int height = 0;   // tree height
   int tl_depth = 1; // levels per treelet of the traversal copy (1: no treelets)
   rt::CullConst cull;   // may this scene's rays be culled by their best hit, and with which constants (ok == false: never)
+  rt::LeafBoxConst leaf;   // do the leaf-child slots of nodes64 hold the spheres' widened boxes, and with which constants (ok == false: zeroed slots, never filtered)
   // canonical {L, I} on the device (SoA, as bvh.fut:28 lays them out)
   float *L7 = nullptr, *bmin = nullptr, *bmax = nullptr;
   int32_t *left = nullptr, *right = nullptr, *parent = nullptr;

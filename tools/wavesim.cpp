@@ -9,6 +9,7 @@
 //     voting policy, and the SIMT lane efficiency of each phase.
 //
 //   build/wavesim <rgbbox|irreg|floor:n:k> <h> <w> [thr_shade thr_leaf lmax nwaves policy]
+//   (policy 14: policy 13 plus the leaf filter of BOX -- a leaf child is appended only if the sphere's own widened box passes, lane_core.h: leaf_box_eps)
 //   (policy 13: policy 10 with the dark stop -- chains whose light is exactly zero are finished as pixel 0, lane_core.h: light_is_dead)
 //   (policy 10 / 11: the pooled design with 64 / 128 items per operation; 12: policy 10 plus the LDS cost of every BOX operation's node
 //   reads under the four-plane layout and the candidate sign-ordered layouts -- e.g. wavesim rgbbox 1000 1000 32 0 64 4096 12)
@@ -362,6 +363,10 @@ static void lds_model_box(const int *rec, const bool (*sg)[3], int n) {
 }
 
 static bool g_dark_stop = false;   // (policy 13)
+// (policy 14: policy 13 plus BOX's leaf filter -- a leaf child is appended only if the sphere's own widened box passes, lane_core.h: leaf_box_eps;
+// the boxes are the product's, rt::leaf_box_finish + leaf_box_bounds)
+static bool g_leaf_box = false;
+static std::vector<float> g_leaf_lo, g_leaf_hi;   // [n][3]
 
 static bool pwave_step(PWave &W, const SceneData &S, int width, int thr_shade, unsigned &next_ticket,
                        std::vector<int32_t> &out, PCounters &C) {
@@ -407,11 +412,18 @@ static bool pwave_step(PWave &W, const SceneData &S, int width, int thr_shade, u
       C.box++;
       if (box_hit(s.r, nd.lo[0], nd.lo[1], nd.lo[2], nd.hi[0], nd.hi[1], nd.hi[2])) {
         const int kids[2] = {nd.left, nd.right};
+        int pushed = 0;
         for (int c : kids) {
-          if (c < 0) W.leaf.push_back(((unsigned)sl << 24) | (unsigned)~c);
-          else W.box.push_back(((unsigned)sl << 24) | (unsigned)c);
+          if (c < 0) {
+            if (g_leaf_box) {
+              const float *lo = &g_leaf_lo[3 * (size_t)~c], *hi = &g_leaf_hi[3 * (size_t)~c];
+              if (!box_hit(s.r, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2])) continue;
+            }
+            W.leaf.push_back(((unsigned)sl << 24) | (unsigned)~c);
+          } else W.box.push_back(((unsigned)sl << 24) | (unsigned)c);
+          ++pushed;
         }
-        s.cnt += 1;
+        s.cnt += pushed - 1;
       } else
         s.cnt -= 1;
     }
@@ -574,7 +586,18 @@ int main(int argc, char **argv) {
     // pooled design: kind 10 -> 64 items per op, kind 11 -> 128 items per op, kind 12 -> 10 with the LDS model of the node reads
     // kind 13 -> 10 with the dark stop (lane_core.h: light_is_dead): the same image, fewer operations
     g_lds_model = P.kind == 12;
-    g_dark_stop = P.kind == 13;
+    g_dark_stop = P.kind == 13 || P.kind == 14;
+    g_leaf_box = P.kind == 14;
+    if (g_leaf_box) {
+      const rt::LeafBoxConst k = rt::leaf_box_finish(rt::cull_stats(sc.spheres.data(), sc.spheres.size()), sc.spheres.size());
+      if (!k.ok || !rt::leaf_box_camera_ok(k, &S.cam.ox)) {
+        std::fprintf(stderr, "policy 14: the scene or its camera fails the leaf-box guards\n");
+        return 2;
+      }
+      g_leaf_lo.resize(3 * (size_t)bvh.n); g_leaf_hi.resize(3 * (size_t)bvh.n);
+      for (int64_t j = 0; j < bvh.n; ++j)
+        leaf_box_bounds(S.sph[j].x, S.sph[j].y, S.sph[j].z, S.sph[j].w, k.q, k.lin, k.abs, &g_leaf_lo[3 * (size_t)j], &g_leaf_hi[3 * (size_t)j]);
+    }
     if (P.lmax >= 64) g_nslots = P.lmax;   // reuse the lmax argument: slots per wave
     return run_pooled(S, ref, nwaves, P.kind == 11 ? 128 : 64, P.thr_shade);
   }
