@@ -80,6 +80,7 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *   "family=boxes count|fill[ (per-box)][ first]"   rt_spheres_in_boxes_count / _fill (below)
  *   "family=planes count|fill k=K[ (per-query)][ first]"   rt_spheres_in_planes_count / _fill (below; K: the caller's nplanes)
  *   "family=along count|fill[ (per-query)][ exclude][ first]"   rt_spheres_along_rays_count / _fill (below)
+ *   "family=pairs targets|directions[ mask][ count][ words/wave=K]"   rt_visible_pairs / rt_visible_pairs_shaped (below; K: the caller's words_per_wave)
  *   "family=none (no rows)"       the part owns no row of the image
  *   "family=pixel" | "family=pixel (instrumented)" | "family=persistent"
  *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2[ nodes=sign-ordered|planes,dark=0|1,leaf_box=0|1]"
@@ -556,6 +557,41 @@ int rt_spheres_along_rays_fill(rt_context *ctx, const rt_prepared *ps, int64_t n
                                const float *radius_dev, float t_min, float t_max, const float *t_min_dev, const float *t_max_dev,
                                const int32_t *exclude_dev, const int32_t *first_dev, const int64_t *offsets_dev, int64_t capacity,
                                int32_t *index_dev, float *roots_dev, uint8_t *start_dev, int32_t *query_dev);
+/* ---- visibility matrices: EVERY point against EVERY target or direction, one bit per pair, with no n x m ray buffer ---------------------
+ * n shading points against m lights, n sensors against m landmarks, n surface points against a fan of m hemisphere directions: a PRODUCT
+ * of queries.  Through rt_occluded_rays it needs n * m * 24 bytes of rays in device memory; here each pair's ray is made in registers.
+ * points3_dev: n x 3 float32.  targets3_dev: m x 3 float32, positions (RT_PAIRS_TARGETS) or directions (RT_PAIRS_DIRECTIONS).  Both need
+ * only 4-byte alignment (the rows are 12 bytes).
+ * DEFINITION, in binary32 without contraction.  Pair (i, j) has the ray o = P_i and
+ *   RT_PAIRS_TARGETS    : d = (fl(T_j.x - P_i.x), fl(T_j.y - P_i.y), fl(T_j.z - P_i.z));
+ *   RT_PAIRS_DIRECTIONS : d = T_j.
+ * The pair is VALID iff all six components of o and d are finite and d is not (+-0, +-0, +-0).  It is VISIBLE iff it is valid and
+ * rt_occluded_rays on that ray over (t_min, t_max) gives 0: no leaf whose every inner ancestor passes aabb_hit over (t_min, t_max) has a
+ * root strictly inside the interval.  An invalid pair is not visible and its walk does not start: a point equal to its target, any pair
+ * of a NaN point, an infinite target, a zero direction.  A shadow test is RT_PAIRS_TARGETS over (eps, 1); ambient occlusion is
+ * RT_PAIRS_DIRECTIONS over (eps, radius).
+ * OUTPUT (either may be NULL, not both):
+ *   visible_dev : n x W uint64, W = (m + 63) / 64, 8-byte aligned.  Bit j & 63 of word visible[i * W + (j >> 6)] is 1 iff pair (i, j) is
+ *                 visible; bits j >= m of a row's last word are 0.  The words are the device's little-endian 64-bit integers, so byte b of a
+ *                 row holds pairs 8 b .. 8 b + 7, lowest bit first: in Python, a uint8 view of the words through
+ *                 numpy.unpackbits(..., bitorder="little") is the n x 64 W matrix.
+ *   count_dev   : n int32, the number of set bits of row i.  Exact and the same on every call: an integer sum.
+ * Refused (non-zero, rt_last_error set, nothing launched or written): a null scene, a multi-device context, n < 0 or n >= 2^31, m < 1 or
+ * m > 2^24, n * W >= 2^31, NULL points3_dev or targets3_dev, both outputs NULL, a mode other than the two, an interval that fails
+ * rt_occluded_rays's rule (0 <= t_min <= t_max <= 1e9, both finite).  n == 0 succeeds without a launch ("family=none (no points)").
+ * Enqueued on the context's stream (completion: rt_context_sync); count_dev may be zeroed on the stream ahead of the kernel, so it must not
+ * be in use by work on another stream.  The same kernels under every variant: a wave owns one point and a run of consecutive words of its
+ * row, or, for m <= 32, the whole rows of 64 / G consecutive points (G the least power of two >= m).
+ * rt_context_last_launch: "family=pairs targets" or "family=pairs directions", then " mask" with visible_dev and " count" with count_dev.
+ * rt_visible_pairs_shaped: the same answer, bit for bit, with the caller's launch shape -- words_per_wave, the number of consecutive words
+ * of a row that one wave owns, one point per wave: 0 (the library's rule, which is what rt_visible_pairs runs) or positive (above W: the
+ * whole row); negative is refused.  A positive value is appended to the launch string as " words/wave=<K>". */
+enum { RT_PAIRS_TARGETS = 0, RT_PAIRS_DIRECTIONS = 1 };
+int rt_visible_pairs(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, int64_t m, const float *targets3_dev,
+                     int32_t mode, float t_min, float t_max, uint64_t *visible_dev, int32_t *count_dev);
+int rt_visible_pairs_shaped(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, int64_t m,
+                            const float *targets3_dev, int32_t mode, float t_min, float t_max, uint64_t *visible_dev, int32_t *count_dev,
+                            int32_t words_per_wave);
 /* ids_dev: n int32 in the context's device memory; ids_dev[i] = the caller's index of L[i]: the position in spheres7 given to
  * rt_scene_from_spheres / rt_prepare_scene_device / the last rt_prepared_update_spheres, or in the generator's output for rt_scene_rgbbox /
  * _irreg / _floor.  The Morton sort is stable, so both builders (option gpu_build) give the same ids, ascending within a run of equal keys.

@@ -26,6 +26,7 @@ RT_SYMBOLS = [
     "rt_spheres_in_boxes_count", "rt_spheres_in_boxes_fill",
     "rt_spheres_in_planes_count", "rt_spheres_in_planes_fill",
     "rt_spheres_along_rays_count", "rt_spheres_along_rays_fill",
+    "rt_visible_pairs", "rt_visible_pairs_shaped",
     "rt_camera_rays",
     "rt_device_alloc", "rt_device_free", "rt_copy_to_host", "rt_copy_to_device",
 ]
@@ -130,6 +131,8 @@ def _load():
         "rt_spheres_in_planes_fill": (C.c_int, [vp, vp, i64, vp, C.c_int32, C.c_float, vp, vp, vp, i64, vp, vp, vp]),
         "rt_spheres_along_rays_count": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
         "rt_spheres_along_rays_fill": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
+        "rt_visible_pairs": (C.c_int, [vp, vp, i64, vp, i64, vp, i32, C.c_float, C.c_float, vp, vp]),
+        "rt_visible_pairs_shaped": (C.c_int, [vp, vp, i64, vp, i64, vp, i32, C.c_float, C.c_float, vp, vp, i32]),
         "rt_camera_rays": (C.c_int, [vp, vp, i64, i64, vp, vp]),
     }
     for name, (res, args) in sig.items():

@@ -18,6 +18,7 @@ from ._lib import lib
 VARIANT_AUTO, VARIANT_PIXEL, VARIANT_PERSISTENT, VARIANT_POOLED = 0, 1, 2, 3
 MAX_DEPTH = 50          # ray.fut:154
 PATH_ESCAPED, PATH_ABSORBED, PATH_TRUNCATED = 0, 1, 2   # rt_trace_paths's end codes (RT_PATH_*)
+PAIRS_TARGETS, PAIRS_DIRECTIONS = 0, 1                  # rt_visible_pairs's modes (RT_PAIRS_*)
 ROWS_PER_TILE = 8       # cyclic row-tile height of the multi-GPU partition
 
 
@@ -662,6 +663,22 @@ def spheres_along_rays_fill_into(rays_ptr, n, prepared, offsets_ptr, capacity, i
                                               C.c_void_p(index_ptr), C.c_void_p(roots_ptr), C.c_void_p(start_ptr), C.c_void_p(query_ptr)))
 
 
+def visible_pairs_into(points_ptr, n, targets_ptr, m, prepared, mode, visible_ptr=None, count_ptr=None, t_min=0.0, t_max=1e9, words_per_wave=0):
+    """Enqueue the visibility matrix of `n` points (n x 3 float32 at points_ptr) against `m` targets or directions (m x 3 float32 at
+    targets_ptr; mode PAIRS_TARGETS: the ray of pair (i, j) is o = P_i, d = T_j - P_i; PAIRS_DIRECTIONS: d = T_j) over (t_min, t_max)
+    (rt_visible_pairs; rt_visible_pairs_shaped when words_per_wave is not 0): n x W uint64 words, W = (m + 63) // 64, to visible_ptr -- bit
+    j & 63 of word [i, j >> 6] is 1 iff the pair's ray is valid and occluded_rays answers False for it -- and the set bits of each row
+    (n int32) to count_ptr.  Either pointer may be None, not both.  words_per_wave: 0 (the library's rule), or the consecutive words of a
+    row that one wave owns; it changes no bit of the answer.  Asynchronous: ctx.sync() completes it."""
+    ctx = prepared.ctx
+    args = (ctx._h, prepared._h, int(n), C.c_void_p(points_ptr), int(m), C.c_void_p(targets_ptr), int(mode), float(t_min), float(t_max),
+            C.c_void_p(visible_ptr), C.c_void_p(count_ptr))
+    if words_per_wave == 0:
+        ctx._check(lib.rt_visible_pairs(*args))
+    else:
+        ctx._check(lib.rt_visible_pairs_shaped(*args, int(words_per_wave)))
+
+
 def camera_rays_into(rays_ptr, h, w, prepared, cam=None):
     """Enqueue the h * w primary rays rt_render_image would trace (rt_camera_rays) into rays_ptr (h * w x 6 float32)."""
     ctx = prepared.ctx
@@ -1159,6 +1176,40 @@ def row_crossings(offsets, index, roots, t_min, t_max, k):
     row2, idx2, t = np.concatenate([row, row])[keep], np.concatenate([index, index])[keep], t[keep]
     count, (idx, rt, tk) = _ranked_rows(n, k, row2, (t, idx2, which), ((idx2, -1, np.int32), (which, 0, np.uint8), (t, 0, np.float32)))
     return count, idx, rt, tk
+
+
+def visible_pairs(prepared, points, targets=None, directions=None, t_min=0.0, t_max=1e9, mask=True, count=True, words_per_wave=0):
+    """The visibility matrix of every point against every target or direction (rt_visible_pairs) -> (visible (n, W) uint64 or None, count
+    (n,) int32 or None) numpy arrays, W = (m + 63) // 64.  Exactly one of `targets` (m positions: the ray of pair (i, j) is o = points[i],
+    d = targets[j] - points[i] in float32; a shadow test is t_min = eps, t_max = 1) and `directions` (m directions: d = directions[j];
+    ambient occlusion is t_min = eps, t_max = the radius) is given.  Bit j & 63 of visible[i, j >> 6] is 1 iff the pair is valid -- o and d
+    finite, d not zero -- and occluded_rays answers False for its ray over (t_min, t_max); the bits past m are 0; count[i] is the number of
+    set bits of row i.  unpack_visible(visible, m) is the (n, m) bool matrix.  No n x m ray buffer is made: the rays exist in registers
+    only.  mask=False / count=False: that output is not computed (None in its place; not both).  `points`, `targets`, `directions`:
+    (., 3) float32, numpy arrays or device tensors used in place.  words_per_wave: as visible_pairs_into."""
+    if (targets is None) == (directions is None):
+        raise ValueError("visible_pairs: exactly one of targets and directions must be given")
+    if not mask and not count:
+        raise ValueError("visible_pairs: mask and count cannot both be False")
+    mode = PAIRS_TARGETS if directions is None else PAIRS_DIRECTIONS
+    with _Scope(prepared.ctx) as s:
+        ptr, n = _device_rows(s, points, *_POINTS)
+        tptr, m = (_device_rows(s, targets, "targets", 3, "targets must be (m, 3)") if directions is None else
+                   _device_rows(s, directions, "directions", 3, "directions must be (m, 3)"))
+        words = (m + 63) // 64
+        vis = s.alloc(8 * n * words) if mask else None
+        cnt = s.alloc(4 * n) if count else None
+        visible_pairs_into(ptr, n, tptr, m, prepared, mode, vis.ptr if vis else None, cnt.ptr if cnt else None, t_min, t_max, words_per_wave)
+        return (vis.to_host((n, words), np.uint64) if vis else None, cnt.to_host((n,)) if cnt else None)
+
+
+def unpack_visible(words, m):
+    """The (n, m) bool matrix of visible_pairs's (n, W) uint64 words (little-endian: bit j & 63 of word j >> 6 is pair j).  Host-side numpy."""
+    w = np.ascontiguousarray(words, dtype="<u8")
+    if w.ndim != 2 or not 0 <= int(m) <= 64 * w.shape[1]:
+        raise ValueError("unpack_visible: words must be (n, W) with m <= 64 * W")
+    bits = np.unpackbits(w.view(np.uint8).reshape(w.shape[0], 8 * w.shape[1]), axis=1, bitorder="little")
+    return bits[:, :int(m)].astype(bool)
 
 
 def contact_pairs(prepared, margin=0.0, gaps=True):

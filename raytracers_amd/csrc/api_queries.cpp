@@ -1,5 +1,5 @@
 // api_queries.cpp -- the caller queries of the rt_* surface (include/rt_mi355x.h): rays traced, intersected, tested for occlusion, multi-hit,
-// sphere casts, ray paths, the proximity, range, box, plane-set and along-ray queries, contact pairs, a frame's primary rays.  Checks and launches only: the lane kernels are
+// sphere casts, ray paths, the proximity, range, box, plane-set and along-ray queries, contact pairs, visibility matrices, a frame's primary rays.  Checks and launches only: the lane kernels are
 // query_kernels.hip, and where an entry runs the pooled family (rt_trace_rays, rt_occluded_rays[_ranged]) its plan, parameters and launch
 // are the render policy's (api.cpp, through rt_internal.hpp).
 #include <hip/hip_runtime.h>
@@ -599,6 +599,55 @@ extern "C" int rt_spheres_along_rays_fill(rt_context *ctx, const rt_prepared *ps
   RT_LOCK(ctx);
   return along_entry(ctx, ps, "rt_spheres_along_rays_fill", true, n, rays_dev, radius, radius_dev, t_min, t_max, t_min_dev, t_max_dev, exclude_dev,
                      first_dev, const_cast<int64_t *>(offsets_dev), capacity, index_dev, roots_dev, start_dev, query_dev);
+}
+
+// The visibility-matrix entries (rt_visible_pairs[_shaped]): checks, then the pairs kernels under every variant.  words_per_wave == 0: the
+// auto rule (query_device.hpp: pairs_auto_words_per_wave, from the context's CU count -- the packed shape for short rows, else a run length);
+// a caller's positive value is a run length of the general shape.  The caller holds the context lock.
+static int pairs_entry(rt_context *ctx, const rt_prepared *ps, const char *what, int64_t n, const float *points3_dev, int64_t m,
+                       const float *targets3_dev, int32_t mode, float t_min, float t_max, uint64_t *visible_dev, int32_t *count_dev,
+                       int32_t words_per_wave) {
+  if (!ps) return fail(ctx, "null prepared scene");
+  if (ctx->group) return fail_in(ctx, what, ": a multi-device context is not supported (use a context on one device)");
+  if (n < 0 || n >= (int64_t(1) << 31)) return fail_in(ctx, what, ": point count out of range: 0 <= n < 2^31");
+  if (m < 1 || m > rtk::kPairsMaxTargets) return fail_in(ctx, what, ": target count out of range: 1 <= m <= 2^24");
+  const int64_t words = (m + 63) / 64;
+  if (n * words >= (int64_t(1) << 31)) return fail_in(ctx, what, ": too many words: need n * ((m + 63) / 64) < 2^31");
+  if (!points3_dev) return fail_in(ctx, what, ": null points pointer");
+  if (!targets3_dev) return fail_in(ctx, what, ": null targets pointer");
+  if (!visible_dev && !count_dev) return fail_in(ctx, what, ": both outputs are NULL");
+  if (mode != RT_PAIRS_TARGETS && mode != RT_PAIRS_DIRECTIONS) return fail_in(ctx, what, ": mode must be RT_PAIRS_TARGETS or RT_PAIRS_DIRECTIONS");
+  if (!ray_interval_ok(t_min, t_max)) return fail_in(ctx, what, ": need 0 <= t_min <= t_max <= 1e9, both finite");
+  if (words_per_wave < 0) return fail_in(ctx, what, ": words_per_wave must be 0 (the library's rule) or positive");
+  return locked_launch(ctx, ps, n, kNoPoints, [&] {
+    rtk::KParams p{};
+    rti::scene_params(ps, &p);
+    p.nrays = static_cast<int>(n);
+    const int per_wave = words_per_wave != 0 ? static_cast<int>(std::min<int64_t>(words_per_wave, words))
+                                             : rtk::pairs_auto_words_per_wave(n, m, ctx->num_cu);
+    RT_HIP(ctx, rtk::launch_visible_pairs(p, points3_dev, targets3_dev, static_cast<int>(m), mode == RT_PAIRS_DIRECTIONS, per_wave, t_min, t_max,
+                                          reinterpret_cast<unsigned long long *>(visible_dev), count_dev, ctx->stream));
+    ctx->last_launch = std::string(mode == RT_PAIRS_DIRECTIONS ? "family=pairs directions" : "family=pairs targets") +
+                       (visible_dev ? " mask" : "") + (count_dev ? " count" : "") +
+                       (words_per_wave != 0 ? " words/wave=" + std::to_string(per_wave) : std::string());
+    return 0;
+  });
+}
+
+extern "C" int rt_visible_pairs(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, int64_t m, const float *targets3_dev,
+                                int32_t mode, float t_min, float t_max, uint64_t *visible_dev, int32_t *count_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return pairs_entry(ctx, ps, "rt_visible_pairs", n, points3_dev, m, targets3_dev, mode, t_min, t_max, visible_dev, count_dev, 0);
+}
+
+extern "C" int rt_visible_pairs_shaped(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, int64_t m,
+                                       const float *targets3_dev, int32_t mode, float t_min, float t_max, uint64_t *visible_dev,
+                                       int32_t *count_dev, int32_t words_per_wave) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return pairs_entry(ctx, ps, "rt_visible_pairs_shaped", n, points3_dev, m, targets3_dev, mode, t_min, t_max, visible_dev, count_dev,
+                     words_per_wave);
 }
 
 extern "C" int rt_prepared_get_sphere_ids(rt_context *ctx, const rt_prepared *ps, int32_t *ids_dev) {

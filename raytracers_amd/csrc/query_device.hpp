@@ -85,6 +85,31 @@ inline int paths_auto_per_wave(int64_t n, int num_cu) {
 }
 hipError_t launch_trace_paths(const KParams &p, int max_depth, int k, int per_wave, int32_t *count, uint8_t *end, int32_t *index, float *hit7,
                               float *light3, float *last_ray6, float *colour3, hipStream_t stream);
+// rt_visible_pairs[_shaped]: p.nrays points (points: n x 3 float32) against m targets or directions (targets: m x 3 float32; both 4-byte
+// aligned), 1 <= m <= kPairsMaxTargets, n * words < 2^31 with words = (m + 63) / 64: visible[i * words + (j >> 6)] bit j & 63 = pair (i, j)
+// is valid and rt_occluded_rays's predicate over (t_min, t_max) is false for its ray; count[i] = the set bits of row i (either may be nullptr,
+// not both).  words_per_wave >= 1: one wave per point and run of that many words (above `words`: the whole row); where a row is cut into
+// several runs, count is zeroed on the stream ahead of the kernel and the waves add to it.  words_per_wave == kPairsPacked (m <=
+// kPairsPackedMax only): one wave per 64 / G consecutive points, G the least power of two >= m.  The shape changes no bit.
+// pairs_auto_words_per_wave: the launch shape of rt_visible_pairs, fitted to the measured sweeps.  Short rows are packed: with
+// a point per wave, 16 targets leave 48 lanes without a pair (measured 2.5 x the time of the packed shape's).  Otherwise a row is cut into
+// runs of at most kPairsAutoCap words (runs of 8 or 16 were the fastest where the points alone fill the machine; the whole row of 256 words
+// as one run was 12 x slower on 256 points), and into more and shorter runs, down to one word, until the grid has kPairsWavesPerCu waves per
+// CU -- about six rounds of the 10 waves a CU holds (16 KB of LDS stack each): runs of 2 or 4 words were the fastest on 256 points x 256 words.
+constexpr int kPairsMaxTargets = 1 << 24;
+constexpr int kPairsPacked = 0, kPairsPackedMax = 32;
+constexpr int kPairsWavesPerCu = 64, kPairsAutoCap = 8;
+inline int pairs_auto_words_per_wave(int64_t n, int64_t m, int num_cu) {
+  if (m <= kPairsPackedMax) return kPairsPacked;
+  const int64_t words = (m + 63) / 64;
+  const int64_t waves = (int64_t)kPairsWavesPerCu * (num_cu > 0 ? num_cu : 1);
+  int64_t chunks = (words + kPairsAutoCap - 1) / kPairsAutoCap;
+  const int64_t fill = (waves + n - 1) / (n > 0 ? n : 1);
+  if (chunks < fill) chunks = fill < words ? fill : words;
+  return (int)((words + chunks - 1) / chunks);
+}
+hipError_t launch_visible_pairs(const KParams &p, const float *points, const float *targets, int m, bool directions, int words_per_wave,
+                                float t_min, float t_max, unsigned long long *visible, int32_t *count, hipStream_t stream);
 // the primary rays of an h x w frame through p.cam (get_ray at pixel_u / pixel_v), row-major from the top row: rays[6 (row w + col) ..]
 hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStream_t stream);
 

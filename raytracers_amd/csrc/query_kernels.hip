@@ -1,5 +1,5 @@
 // query_kernels.hip -- the lane kernels of the caller queries, one lane per ray or point: closest hit (rt_intersect_rays), occlusion
-// (rt_occluded_rays), multi-hit, sphere casts, ray paths, the nearest spheres, the range queries / contact pairs with their scan, the box, plane-set and along-ray queries, and the primary
+// (rt_occluded_rays), multi-hit, sphere casts, ray paths, the nearest spheres, the range queries / contact pairs with their scan, the box, plane-set and along-ray queries, the visibility matrices, and the primary
 // rays of a frame (rt_camera_rays).  The render path -- pixel_kernel, persistent_kernel, pooled_kernel and their RAYS modes -- is
 // render_kernels.hip; nothing here is launched by a render entry.  Build: as render_kernels.hip (-ffp-contract=off, bit-exact fp32).
 #include <hip/hip_runtime.h>
@@ -1267,6 +1267,141 @@ hipError_t launch_trace_paths(const KParams &p, int max_depth, int k, int per_wa
     return hipErrorInvalidValue;
   const unsigned grid = (unsigned)(((long long)p.nrays + per_wave - 1) / per_wave);
   hipLaunchKernelGGL(paths_kernel, dim3(grid), dim3(64), 0, stream, p, max_depth, k, per_wave, count, end, index, hit7, light3, last_ray6, colour3);
+  return hipGetLastError();
+}
+
+// rt_visible_pairs: every point against every target (DIRS false: d = fl(T_j - P_i) per component) or direction (DIRS true: d = T_j), one bit
+// per pair and a count per point.  pair_visible is one lane's pair: the ray is built in registers from the point and the
+// target row `tg` (three 4-byte loads: 12-byte rows, 4-byte aligned) and walked as occluded_lane walks it -- the same stack,
+// box_hit_interval, sphere_hit_any and early exit -- so the answer is what rt_occluded_rays gives for that ray, negated.  A pair whose o or d
+// has a non-finite component, or whose d is (+-0, +-0, +-0), is not visible and does not start its walk; neither does a lane that holds no pair
+// (`have` false: nothing is loaded).
+template <bool DIRS>
+__device__ __forceinline__ bool pair_visible(const __amdgpu_buffer_rsrc_t rs_nodes, const __amdgpu_buffer_rsrc_t rs_sph, int (*stack)[64], int lane,
+                                             bool have, float px, float py, float pz, const float *tg, float t_min, float t_max) {
+  bool valid = have && point_ok(px, py, pz);
+  Ray r;
+  r.ox = px; r.oy = py; r.oz = pz;
+  r.dx = r.dy = r.dz = 1.0f;
+  if (valid) {
+    const float tx = tg[0], ty = tg[1], tz = tg[2];
+    r.dx = DIRS ? tx : tx - px;
+    r.dy = DIRS ? ty : ty - py;
+    r.dz = DIRS ? tz : tz - pz;
+    valid = point_ok(r.dx, r.dy, r.dz) && !(r.dx == 0.0f && r.dy == 0.0f && r.dz == 0.0f);
+  }
+  ray_derive(r);
+  bool hit = false;
+  int sp = 0;
+  if (valid) stack[sp++][lane] = 0;
+  while (sp > 0 && !hit) {
+    const int ni = stack[--sp][lane];
+    const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+    if (!box_hit_interval(r, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, t_min, t_max)) continue;
+    const int kids[2] = {f2i(lo.w), f2i(hi.w)};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int ch = kids[k];
+      if (ch < 0) {
+        const float4 s = buf_load16(rs_sph, ~ch * 16);
+        hit = hit || sphere_hit_any(r, t_min, t_max, s.x, s.y, s.z, s.w);
+      } else {
+        stack[sp++][lane] = ch;   // (at most one pending sibling per level: sp <= tree height + 1 <= kStackPixel)
+      }
+    }
+  }
+  return valid && !hit;
+}
+
+// The general shape, one wave per workgroup.  A wave owns ONE point i and the run of `words_per_wave` consecutive 64-target words
+// [c * words_per_wave, ...) of its row, blockIdx.x = i * chunks + c with chunks = ceil(words / words_per_wave); lane l of word w is pair
+// (i, 64 w + l).  i is wave-uniform, so the point's three floats are uniform loads.  A lane with j >= m holds no pair, so the tail bits of a
+// row's last word are 0 by construction.  The word is the wave's ballot, stored by lane 0 with one 8-byte vector store.  The count is the sum
+// of the words' popcounts: stored once where the wave owns the whole row (chunks == 1), else added with atomicAdd to count[i], which the
+// launcher zeroed on the same stream -- integer sums, so exact whatever the order.  words_per_wave changes no bit of either output.
+template <bool DIRS>
+__global__ __launch_bounds__(64) void pairs_kernel(KParams p, const float *points, const float *targets, int m, int words, int words_per_wave,
+                                                   float t_min, float t_max, unsigned long long *visible, int32_t *count) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const unsigned chunks = ((unsigned)words + (unsigned)words_per_wave - 1u) / (unsigned)words_per_wave;
+  const unsigned i = blockIdx.x / chunks, c = blockIdx.x - i * chunks;   // (the grid is n * chunks: i < n)
+  const float *const pt = points + (size_t)i * 3;
+  const float px = pt[0], py = pt[1], pz = pt[2];
+  const int w_lo = (int)c * words_per_wave, w_hi = w_lo + words_per_wave < words ? w_lo + words_per_wave : words;
+  int total = 0;
+  for (int w = w_lo; w < w_hi; ++w) {
+    const int j = w * 64 + lane;
+    const bool vis = pair_visible<DIRS>(rs_nodes, rs_sph, stack, lane, j < m, px, py, pz, targets + (size_t)j * 3, t_min, t_max);
+    const unsigned long long word = __ballot(vis);
+    if (visible != nullptr && lane == 0) visible[(size_t)i * (size_t)words + (size_t)w] = word;
+    total += __popcll(word);
+  }
+  if (count != nullptr && lane == 0) {
+    if (chunks == 1u) count[i] = total;
+    else if (total != 0) atomicAdd(&count[i], total);
+  }
+}
+
+// The shape for short rows, m <= kPairsPackedMax = 32 (a row is one word): with one point per wave 64 - m lanes would hold no pair, so a
+// wave owns the 64 >> shift consecutive points [blockIdx.x * (64 >> shift), ...), G = 1 << shift being the least power of two >= m: lane l is
+// pair (that base + l / G, l % G).  The point is then a per-lane load.  A point's word is its G lanes' slice of the wave's ballot, stored
+// by the slice's first lane with its popcount -- whole rows, so no atomics.  The same pair_visible: the shape changes no bit.
+template <bool DIRS>
+__global__ __launch_bounds__(64) void pairs_packed_kernel(KParams p, const float *points, const float *targets, int m, int shift, float t_min,
+                                                          float t_max, unsigned long long *visible, int32_t *count) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const long long i = (long long)blockIdx.x * (64 >> shift) + (lane >> shift);
+  const int j = lane & ((1 << shift) - 1);
+  const bool have = i < (long long)p.nrays && j < m;
+  float px = 0.0f, py = 0.0f, pz = 0.0f;
+  if (have) {
+    const float *const pt = points + (size_t)i * 3;
+    px = pt[0], py = pt[1], pz = pt[2];
+  }
+  const bool vis = pair_visible<DIRS>(rs_nodes, rs_sph, stack, lane, have, px, py, pz, targets + (size_t)j * 3, t_min, t_max);
+  const unsigned long long all = __ballot(vis);
+  const unsigned long long word = (all >> (lane - j)) & ((1ull << (1 << shift)) - 1ull);   // (1 << shift <= 32)
+  if (j == 0 && i < (long long)p.nrays) {
+    if (visible != nullptr) visible[i] = word;
+    if (count != nullptr) count[i] = __popcll(word);
+  }
+}
+
+// words_per_wave: kPairsPacked (m <= kPairsPackedMax: the packed shape), or the general shape's run length >= 1 (above `words`: the whole row)
+hipError_t launch_visible_pairs(const KParams &p, const float *points, const float *targets, int m, bool directions, int words_per_wave,
+                                float t_min, float t_max, unsigned long long *visible, int32_t *count, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (points == nullptr || targets == nullptr || m < 1 || m > kPairsMaxTargets || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (visible == nullptr && count == nullptr) return hipErrorInvalidValue;
+  if (!interval_ok(t_min, t_max)) return hipErrorInvalidValue;
+  const int words = (m + 63) / 64;
+  if ((long long)p.nrays * words >= (1ll << 31)) return hipErrorInvalidValue;
+  if (words_per_wave == kPairsPacked) {
+    if (m > kPairsPackedMax) return hipErrorInvalidValue;
+    int shift = 0;
+    while ((1 << shift) < m) ++shift;
+    const int per_wave = 64 >> shift;
+    const dim3 grid((unsigned)(((long long)p.nrays + per_wave - 1) / per_wave)), block(64);
+    if (directions) hipLaunchKernelGGL((pairs_packed_kernel<true>), grid, block, 0, stream, p, points, targets, m, shift, t_min, t_max, visible, count);
+    else hipLaunchKernelGGL((pairs_packed_kernel<false>), grid, block, 0, stream, p, points, targets, m, shift, t_min, t_max, visible, count);
+    return hipGetLastError();
+  }
+  if (words_per_wave < 1) return hipErrorInvalidValue;
+  if (words_per_wave > words) words_per_wave = words;
+  const int chunks = (words + words_per_wave - 1) / words_per_wave;
+  if (count != nullptr && chunks > 1) {
+    const hipError_t e = hipMemsetAsync(count, 0, sizeof(int32_t) * (size_t)p.nrays, stream);
+    if (e != hipSuccess) return e;
+  }
+  const dim3 grid((unsigned)((long long)p.nrays * chunks)), block(64);   // (n * chunks <= n * words < 2^31)
+  if (directions) hipLaunchKernelGGL((pairs_kernel<true>), grid, block, 0, stream, p, points, targets, m, words, words_per_wave, t_min, t_max, visible, count);
+  else hipLaunchKernelGGL((pairs_kernel<false>), grid, block, 0, stream, p, points, targets, m, words, words_per_wave, t_min, t_max, visible, count);
   return hipGetLastError();
 }
 
