@@ -77,6 +77,7 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *   "family=sweep k=K" [" (per-query)"] [" exclude"]   rt_sweep_spheres / rt_sweep_spheres_ranged (K: the caller's k)
  *   "family=nearest k=K[ pruned][ (per-point)]" | "family=none (no points)"   rt_nearest_spheres / rt_nearest_spheres_ranged (below)
  *   "family=within count|fill[ (per-point)][ first][ self]"   rt_spheres_within_count / _fill, rt_contact_pairs_count / _fill (" self"; below)
+ *   "family=clusters"             rt_contact_clusters (below)
  *   "family=boxes count|fill[ (per-box)][ first]"   rt_spheres_in_boxes_count / _fill (below)
  *   "family=planes count|fill k=K[ (per-query)][ first]"   rt_spheres_in_planes_count / _fill (below; K: the caller's nplanes)
  *   "family=along count|fill[ (per-query)][ exclude][ first]"   rt_spheres_along_rays_count / _fill (below)
@@ -450,6 +451,23 @@ int rt_spheres_within_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, co
 int rt_contact_pairs_count(rt_context *ctx, const rt_prepared *ps, float margin, int64_t *offsets_dev);
 int rt_contact_pairs_fill(rt_context *ctx, const rt_prepared *ps, float margin, const int64_t *offsets_dev, int64_t capacity,
                           int32_t *pair_dev, float *gap_dev);
+/* ---- contact clusters: the connected components of the contact pairs' graph, reduced on the device ------------------------------------
+ * The vertices are the scene's n spheres L[0 .. n) in Morton order; the edges are EXACTLY the rows rt_contact_pairs_fill reports at the same
+ * margin (the one-sided float32 predicate above, evaluated from the lower index; a sphere whose bound is not in [0, 1e9] or whose centre is
+ * not finite offers no edge as i, and may still be some lower sphere's j).  No pair is materialised: the walk of rt_contact_pairs_count unites
+ * i and j in a lock-free union-find where that pass would count.
+ *   root_dev    : n int32, required.  root[i] = the smallest index in i's component, so root[i] == i marks one representative per cluster.
+ *                 (It is the union-find's parent array while the call runs.)
+ *   cluster_dev : n int32 or NULL.  A dense id in [0, num): clusters are numbered in ascending order of their root.
+ *   size_dev    : n int32 or NULL.  The number of spheres in i's cluster, written for every member.
+ *   num_dev     : 1 int64 or NULL (4-byte alignment suffices).  The number of clusters.
+ * Integers only, and the same answer whatever the interleaving of the lanes: a tree's final root is its smallest index.  Indices are into
+ * L: rt_prepared_get_sphere_ids maps them to the caller's order.  A scene of one sphere gives root = {0}, num = 1.
+ * Enqueued on the context's stream (completion: rt_context_sync).  Scratch for the ids and the count is cached on the context (the range
+ * queries' buffer, grown on demand).  Refused (non-zero, rt_last_error set, nothing launched or written): a null scene, a multi-device
+ * context, NULL root_dev, a margin outside [0, 1e9] or not finite (-0.0 counts as 0).  rt_context_last_launch: "family=clusters". */
+int rt_contact_clusters(rt_context *ctx, const rt_prepared *ps, float margin, int32_t *root_dev, int32_t *cluster_dev, int32_t *size_dev,
+                        int64_t *num_dev);
 /* ---- box queries: EVERY sphere that meets a caller-supplied axis-aligned box, with no cap ---------------------------------------------
  * A query is a box {lo.xyz, hi.xyz} and a margin.  boxes6_dev: n x 6 float32 in the context's device memory, rows of 24 bytes; only 4-byte
  * alignment is assumed.  For sphere j of L (centre c, radius r) the gap is the signed distance from the box to the sphere's surface, in

@@ -17,4 +17,5 @@ from .api import (Context, Prepared, RtError, Scene, MAX_DEPTH, ROWS_PER_TILE, V
                   spheres_in_planes, spheres_in_planes_count_into, spheres_in_planes_fill_into, frustum_planes, tile_frusta,
                   spheres_along_rays, spheres_along_rays_count_into, spheres_along_rays_fill_into, row_contacts, row_crossings,
                   visible_pairs, visible_pairs_into, unpack_visible, PAIRS_TARGETS, PAIRS_DIRECTIONS,
-                  contact_pairs, contact_pairs_count_into, contact_pairs_fill_into)
+                  contact_pairs, contact_pairs_count_into, contact_pairs_fill_into,
+                  contact_clusters, contact_clusters_into, cluster_members)

@@ -22,7 +22,7 @@ RT_SYMBOLS = [
     "rt_render_timed",
     "rt_trace_rays", "rt_intersect_rays", "rt_occluded_rays", "rt_intersect_rays_ranged", "rt_occluded_rays_ranged",
     "rt_multi_hit_rays", "rt_multi_hit_rays_ranged", "rt_sweep_spheres", "rt_sweep_spheres_ranged", "rt_trace_paths", "rt_trace_paths_shaped", "rt_nearest_spheres", "rt_nearest_spheres_ranged", "rt_prepared_get_sphere_ids",
-    "rt_spheres_within_count", "rt_spheres_within_fill", "rt_contact_pairs_count", "rt_contact_pairs_fill",
+    "rt_spheres_within_count", "rt_spheres_within_fill", "rt_contact_pairs_count", "rt_contact_pairs_fill", "rt_contact_clusters",
     "rt_spheres_in_boxes_count", "rt_spheres_in_boxes_fill",
     "rt_spheres_in_planes_count", "rt_spheres_in_planes_fill",
     "rt_spheres_along_rays_count", "rt_spheres_along_rays_fill",
@@ -125,6 +125,7 @@ def _load():
         "rt_spheres_within_fill": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, vp, vp, i64, vp, vp, vp]),
         "rt_contact_pairs_count": (C.c_int, [vp, vp, C.c_float, vp]),
         "rt_contact_pairs_fill": (C.c_int, [vp, vp, C.c_float, vp, i64, vp, vp]),
+        "rt_contact_clusters": (C.c_int, [vp, vp, C.c_float, vp, vp, vp, vp]),
         "rt_spheres_in_boxes_count": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, vp, vp]),
         "rt_spheres_in_boxes_fill": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, vp, vp, i64, vp, vp, vp]),
         "rt_spheres_in_planes_count": (C.c_int, [vp, vp, i64, vp, C.c_int32, C.c_float, vp, vp, vp]),

@@ -612,6 +612,16 @@ def contact_pairs_fill_into(prepared, offsets_ptr, capacity, pair_ptr, gap_ptr=N
                                          C.c_void_p(gap_ptr)))
 
 
+def contact_clusters_into(prepared, root_ptr, cluster_ptr=None, size_ptr=None, num_ptr=None, margin=0.0):
+    """Enqueue the connected components of the contact pairs' graph at `margin` (rt_contact_clusters): root_ptr receives num_spheres int32,
+    root[i] = the smallest index in i's component; cluster_ptr num_spheres int32, dense ids in ascending order of the root; size_ptr
+    num_spheres int32, the size of i's cluster; num_ptr one int64, the number of clusters.  All but root_ptr may be None.  Indices are into L
+    (Morton order): prepared.sphere_ids() maps them to the caller's order.  Asynchronous, as contact_pairs_count_into."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_contact_clusters(ctx._h, prepared._h, float(margin), C.c_void_p(root_ptr), C.c_void_p(cluster_ptr), C.c_void_p(size_ptr),
+                                       C.c_void_p(num_ptr)))
+
+
 def sweep_spheres_into(rays_ptr, n, prepared, radius, k, count_ptr, index_ptr, start_ptr=None, hit_ptr=None, t_min=0.0, t_max=1.0):
     """Enqueue the first k (1 <= k <= 32) contacts of `n` moving spheres of radius `radius` (rt_sweep_spheres): ray i is the centre's
     origin and its displacement per unit t, the contacts over (t_min, t_max) are ordered by (tau, sphere).  Their count (n int32, not capped
@@ -1227,6 +1237,32 @@ def contact_pairs(prepared, margin=0.0, gaps=True):
         if total:
             contact_pairs_fill_into(prepared, off.ptr, total, pair.ptr, gap.ptr if gap else None, margin)
         return pair.to_host((total, 2)), gap.to_host((total,), np.float32) if gap else None
+
+
+def contact_clusters(prepared, margin=0.0):
+    """The connected components of the scene's contact graph (rt_contact_clusters) -> (root (n,) int32, cluster (n,) int32, size (n,) int32,
+    num int) with numpy arrays.  The edges are exactly contact_pairs(prepared, margin)'s rows; no pair list is built.  root[i] is the
+    smallest index in i's component (root[i] == i marks one representative per cluster), cluster[i] a dense id in [0, num) numbered in
+    ascending order of the root, size[i] the number of spheres in i's cluster.  All indices are into L (Morton order):
+    prepared.sphere_ids() maps them to the caller's order.  margin: a scalar in [0, 1e9]."""
+    n = prepared.num_spheres
+    with _Scope(prepared.ctx) as s:
+        root, cluster, size, num = s.alloc(4 * n), s.alloc(4 * n), s.alloc(4 * n), s.alloc(8)
+        contact_clusters_into(prepared, root.ptr, cluster.ptr, size.ptr, num.ptr, margin)
+        return root.to_host((n,)), cluster.to_host((n,)), size.to_host((n,)), int(num.to_host((1,), np.int64)[0])
+
+
+def cluster_members(cluster, num):
+    """The member list of each cluster in CSR form -> (offsets (num + 1,) int64, members (n,) int32): cluster c holds
+    members[offsets[c]:offsets[c + 1]], ascending.  `cluster` and `num` as contact_clusters returns them; the members are indices into L
+    (prepared.sphere_ids() maps them to the caller's order).  Host-side numpy: a stable argsort."""
+    c = np.ascontiguousarray(cluster)
+    num = int(num)
+    if c.ndim != 1 or c.dtype.kind not in "iu" or num < 0 or (c.size and (int(c.min()) < 0 or int(c.max()) >= num)):
+        raise ValueError("cluster_members: cluster must be a 1-d integer array with values in [0, num)")
+    offsets = np.zeros(num + 1, np.int64)
+    np.cumsum(np.bincount(c, minlength=num), out=offsets[1:])
+    return offsets, np.argsort(c, kind="stable").astype(np.int32)
 
 
 def camera_rays(prepared, h, w, cam=None):

@@ -1,5 +1,5 @@
 // api_queries.cpp -- the caller queries of the rt_* surface (include/rt_mi355x.h): rays traced, intersected, tested for occlusion, multi-hit,
-// sphere casts, ray paths, the proximity, range, box, plane-set and along-ray queries, contact pairs, visibility matrices, a frame's primary rays.  Checks and launches only: the lane kernels are
+// sphere casts, ray paths, the proximity, range, box, plane-set and along-ray queries, contact pairs and clusters, visibility matrices, a frame's primary rays.  Checks and launches only: the lane kernels are
 // query_kernels.hip, and where an entry runs the pooled family (rt_trace_rays, rt_occluded_rays[_ranged]) its plan, parameters and launch
 // are the render policy's (api.cpp, through rt_internal.hpp).
 #include <hip/hip_runtime.h>
@@ -367,8 +367,7 @@ extern "C" int rt_nearest_spheres_ranged(rt_context *ctx, const rt_prepared *ps,
 // The range entries (rt_spheres_within_*, rt_contact_pairs_*): checks, then within_lane under every variant.  self: the contact pairs (the
 // points are the scene's own centres, `max_dist` is the margin).  The count pass keeps its int32 counts and the scan's block sums in a buffer
 // cached on the context, grown when a call needs more (the steady path allocates nothing).
-static int within_scratch(rt_context *ctx, int64_t n, char **out) {
-  const size_t want = rtk::within_scratch_bytes(n);
+static int query_scratch(rt_context *ctx, size_t want, char **out) {
   if (want > ctx->within_bytes) {
     if (ctx->within_scratch) {
       RT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (an earlier count pass may still be reading it)
@@ -383,6 +382,7 @@ static int within_scratch(rt_context *ctx, int64_t n, char **out) {
   *out = ctx->within_scratch;
   return 0;
 }
+static int within_scratch(rt_context *ctx, int64_t n, char **out) { return query_scratch(ctx, rtk::within_scratch_bytes(n), out); }
 static int within_entry(rt_context *ctx, const rt_prepared *ps, const char *what, bool fill, bool self, int64_t n, const float *points3_dev,
                         float max_dist, const float *max_dist_dev, const int32_t *first_dev, int64_t *offsets_dev, int64_t capacity,
                         int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
@@ -441,6 +441,31 @@ extern "C" int rt_contact_pairs_fill(rt_context *ctx, const rt_prepared *ps, flo
   RT_LOCK(ctx);
   return within_entry(ctx, ps, "rt_contact_pairs_fill", true, true, 0, nullptr, margin, nullptr, nullptr, const_cast<int64_t *>(offsets_dev), capacity,
                       nullptr, gap_dev, pair_dev);
+}
+
+// The contact clusters (rt_contact_clusters): the checks of the contact pairs' entries, then the union-find over the same walk
+// (query_kernels.hip: launch_contact_clusters).  The dense ids and the count go through the range queries' scan, in the same cached buffer.
+// A scene of one sphere has no node: point_params / launch_within_count refuse it, this entry answers it (one cluster) without a walk.
+extern "C" int rt_contact_clusters(rt_context *ctx, const rt_prepared *ps, float margin, int32_t *root_dev, int32_t *cluster_dev, int32_t *size_dev,
+                                   int64_t *num_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  const char *const what = "rt_contact_clusters";
+  int64_t n = 0;
+  if (int rc = point_entry_checks(ctx, ps, what, true, &n, nullptr)) return rc;
+  if (!root_dev) return fail_in(ctx, what, ": null root pointer");
+  if (!distance_ok(margin)) return fail_in(ctx, what, ": need 0 <= margin <= 1e9, finite");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  int exact_depth;
+  const rtk::KParams p = point_params(ps, n, &exact_depth);
+  char *scratch = nullptr;
+  if ((cluster_dev || num_dev) && query_scratch(ctx, rtk::clusters_scratch_bytes(n), &scratch) != 0) return 1;
+  ctx->synced_since_render = false;
+  RT_HIP(ctx, rtk::launch_contact_clusters(p, margin, exact_depth, scratch, root_dev, cluster_dev, size_dev, num_dev, ctx->stream));
+  ctx->last_launch = "family=clusters";
+  return 0;
 }
 
 // The box entries (rt_spheres_in_boxes_*): the range entries' checks in the boxes' words, then boxes_lane under every variant; the count pass

@@ -1,6 +1,6 @@
 // query_core.h -- per-lane arithmetic of the caller queries that no render-path kernel calls: both roots of a sphere and the sphere
 // casts' contact rule, the proximity queries' gap, box bound, slack and selection key, the box queries' gap and node test, the plane-set
-// queries' normalisation, gap and node test, a ray path's bounce.  Shared by query_kernels.hip and the host-side checks (tools/sweep_check.cpp, tools/along_check.cpp, tools/path_check.cpp, tools/proximity_bound_check.cpp,
+// queries' normalisation, gap and node test, a ray path's bounce, the contact clusters' union-find.  Shared by query_kernels.hip and the host-side checks (tools/sweep_check.cpp, tools/along_check.cpp, tools/path_check.cpp, tools/clusters_check.cpp, tools/proximity_bound_check.cpp,
 // tools/box_query_bound_check.cpp, tools/plane_query_bound_check.cpp).  Same parity contract as lane_core.h, which holds what the render
 // path shares with the queries (box_hit_interval, sphere_hit_any, interval_ok, rehit_range).
 #pragma once
@@ -298,6 +298,61 @@ RT_HD int path_bounce(const Ray &r, bool have, float t, float spx, float spy, fl
   ray_derive(*nr);
   nl[0] = lr * scr; nl[1] = lg * scg; nl[2] = lb * scb;
   return depth + 1 < max_depth ? kPathContinue : kPathTruncated;
+}
+
+// The contact clusters' union-find (rt_contact_clusters) over a parent array reached through an atomic-ops policy A:
+//   int32_t A::load(int32_t x)                          parent[x], relaxed
+//   void    A::store(int32_t x, int32_t v)              parent[x] = v, relaxed
+//   int32_t A::cas(int32_t x, int32_t expect, int32_t v)   strong compare-exchange of parent[x], relaxed; returns the value it found
+// (the device's policy is query_kernels.hip's ParentOps, agent-scope __hip_atomic_*; a host's is std::atomic<int32_t>, tools/clusters_check.cpp).
+// Invariants, under any interleaving of any number of callers: parent[x] <= x; parent[x] is a vertex of x's tree; a vertex with
+// parent[x] == x (a root) loses that only to a successful cas of uf_unite, which hangs it under a SMALLER vertex of the tree it joins.  So
+// every chain x, parent[x], .. strictly descends and ends at a root, trees only ever merge, and a tree's only root is its smallest vertex.
+// A load may return any EARLIER value of its word (a stale cache line): every earlier value was a vertex of the same tree that is <= x.
+//
+// uf_find: a root of x's tree at some moment during the call (it may have been hooked since), with path halving: a vertex passed on the way
+// is re-pointed at its grandparent -- a vertex of its tree below it, never at a root's own word (the store's target had a parent != itself,
+// and a vertex that was once not a root never is one again), so it cannot undo a hook.
+template <class A>
+RT_HD int32_t uf_find(const A &a, int32_t x) {
+  for (;;) {
+    const int32_t p = a.load(x);
+    if (p == x) return x;
+    const int32_t g = a.load(p);
+    if (g == p) return p;
+    a.store(x, g);
+    x = g;
+  }
+}
+// uf_root: the same walk without a store -- for the flatten pass, where a halving store that lands behind the owner's final store would
+// leave a word pointing at a vertex that is not the root.
+template <class A>
+RT_HD int32_t uf_root(const A &a, int32_t x) {
+  for (;;) {
+    const int32_t p = a.load(x);
+    if (p == x) return x;
+    x = p;
+  }
+}
+// uf_unite: afterwards x and y are in one tree; returns a vertex of it that was its root when the call ended its work (the lane's next
+// starting point).  The LARGER root's word is swung from itself to the smaller root by one cas: it succeeds only if that vertex is still a
+// root, so no link is ever overwritten; where it fails, another caller hooked that vertex first, and the walk goes on from the value the cas
+// found -- a retry is always another caller's progress, nothing waits.
+template <class A>
+RT_HD int32_t uf_unite(const A &a, int32_t x, int32_t y) {
+  for (;;) {
+    x = uf_find(a, x);
+    y = uf_find(a, y);
+    if (x == y) return x;
+    if (x > y) {
+      const int32_t t = x;
+      x = y;
+      y = t;
+    }
+    const int32_t seen = a.cas(y, y, x);
+    if (seen == y) return x;
+    y = seen;
+  }
 }
 
 }  // namespace rtk

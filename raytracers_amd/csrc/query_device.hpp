@@ -36,6 +36,14 @@ hipError_t launch_within_count(const KParams &p, const float *pts, const float *
 hipError_t launch_within_fill(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
                               int exact_depth, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point,
                               hipStream_t stream);
+// rt_contact_clusters: the connected components of the graph whose edges are launch_within_fill's self rows at the same margin, for the
+// p.n_sph >= 1 spheres of the scene: root[i] = the smallest index of i's component (the union-find's parent array, in place), cluster[i] = the
+// rank of root[i] among the roots, size[i] = the component's sphere count, *num = the number of components (each but root may be nullptr;
+// num needs only 4-byte alignment).  scratch: clusters_scratch_bytes(n) bytes, needed when cluster or num is asked for (the root flags, the
+// scan's block sums and its n + 1 offsets).  p.n_sph == 1 launches no walk (such a scene has no node).
+size_t clusters_scratch_bytes(int64_t n);
+hipError_t launch_contact_clusters(const KParams &p, float margin, int exact_depth, char *scratch, int32_t *root, int32_t *cluster, int32_t *size,
+                                   int64_t *num, hipStream_t stream);
 // rt_spheres_in_boxes_*: for p.nrays boxes (boxes: n x 6 float32, {lo.xyz, hi.xyz}, 4-byte aligned) EVERY sphere of L with box_gap <= the box's
 // margin -- `margin`, or box i's own margin_dev[i] -- and j >= first_dev[i], in the range queries' CSR form and two passes: the same scratch
 // (within_scratch_bytes(n)), scan, capacity guard and exact_depth rule as launch_within_count / launch_within_fill.

@@ -1,5 +1,5 @@
 // query_kernels.hip -- the lane kernels of the caller queries, one lane per ray or point: closest hit (rt_intersect_rays), occlusion
-// (rt_occluded_rays), multi-hit, sphere casts, ray paths, the nearest spheres, the range queries / contact pairs with their scan, the box, plane-set and along-ray queries, the visibility matrices, and the primary
+// (rt_occluded_rays), multi-hit, sphere casts, ray paths, the nearest spheres, the range queries / contact pairs with their scan, the contact clusters, the box, plane-set and along-ray queries, the visibility matrices, and the primary
 // rays of a frame (rt_camera_rays).  The render path -- pixel_kernel, persistent_kernel, pooled_kernel and their RAYS modes -- is
 // render_kernels.hip; nothing here is launched by a render entry.  Build: as render_kernels.hip (-ffp-contract=off, bit-exact fp32).
 #include <hip/hip_runtime.h>
@@ -724,6 +724,160 @@ hipError_t launch_within_fill(const KParams &p, const float *pts, const float *m
     hipLaunchKernelGGL((within_kernel<true, false>), grid, block, 0, stream, p, pts, max_dist_dev, max_dist, first_dev, exact_depth, nullptr, offsets,
                        capacity, index, gap, point);
   return hipGetLastError();
+}
+
+// rt_contact_clusters: the connected components of the contact pairs' graph, with no pair list.  `root` is the union-find's
+// parent array in place: clusters_init_kernel (root[i] = i), clusters_hook_kernel (the unions), clusters_flatten_kernel (root[i] = its root),
+// then, as asked for, the dense ids through the range queries' scan and the sizes through integer atomics.
+// Inside the hook and the flatten kernels EVERY access to the parent array goes through ParentOps: relaxed agent-scope atomics, which are
+// served past the CU's L1.  No plain load, no fence: a stale parent is still a vertex of the same tree below its child, and root-ness is decided
+// by the compare-exchange alone (query_core.h: uf_find / uf_unite); the kernel boundaries carry the array from one launch to the next.
+struct ParentOps {
+  int32_t *parent;
+  __device__ __forceinline__ int32_t load(int32_t x) const { return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  __device__ __forceinline__ void store(int32_t x, int32_t v) const {
+    __hip_atomic_store(parent + x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ int32_t cas(int32_t x, int32_t expect, int32_t v) const {
+    (void)__hip_atomic_compare_exchange_strong(parent + x, &expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return expect;
+  }
+};
+constexpr int kClustersThreads = 256;
+__global__ __launch_bounds__(kClustersThreads) void clusters_init_kernel(int32_t *root, int n) {
+  const long long i = (long long)blockIdx.x * kClustersThreads + threadIdx.x;
+  if (i < n) root[i] = (int32_t)i;
+}
+// The hook: within_lane<false, true>'s walk -- the same stack entries, loads, box_may_hold with T = the sphere's bound, first = i + 1, the
+// same predicate at the leaf -- and, where the count pass counts, the union of i and j.  `mine` is the lane's own root so far, kept across its
+// row: when j's root equals it (on a dense scene nearly every edge) there is no atomic.  It may have been hooked by another lane since;
+// uf_unite then walks on from it.
+__global__ __launch_bounds__(64) void clusters_hook_kernel(KParams p, float margin, int exact_depth, int32_t *root) {
+  __shared__ int stack[kStackPixel][64];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  if (i >= p.n_sph) return;
+  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
+  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const ParentOps ops{root};
+  const float4 me = p.sph[i];
+  const float px = me.x, py = me.y, pz = me.z;
+  const float max_dist = (me.w + margin) + 0.0f;
+  const int first = i + 1;
+  const bool valid = point_ok(px, py, pz) && max_dist_ok(max_dist);
+  const float pmag = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
+  int32_t mine = i;
+  int sp = 0;
+  if (valid) stack[sp++][lane] = within_node_entry(0, 0);
+  while (sp > 0) {
+    const unsigned e = (unsigned)stack[--sp][lane];
+    const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
+    int leaf[2] = {-1, -1};
+    if (depth == kWithinLeaf) {
+      leaf[0] = ni;
+    } else {
+      const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+      if (depth >= exact_depth && !box_may_hold(px, py, pz, pmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, max_dist)) continue;
+      const int l = f2i(lo.w), r = f2i(hi.w);
+      // (one pending sibling per level: sp <= height + 1 <= kStackPixel)
+      if (l < 0) {
+        leaf[0] = ~l;
+        if (r < 0) leaf[1] = ~r;
+        else stack[sp++][lane] = within_node_entry(r, depth + 1);
+      } else {
+        stack[sp++][lane] = r < 0 ? within_leaf_entry(~r) : within_node_entry(r, depth + 1);
+        stack[sp++][lane] = within_node_entry(l, depth + 1);
+      }
+    }
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      const int j = leaf[c2];
+      if (j >= first && j < p.n_sph) {   // (first >= 1: an empty leaf slot, -1, never passes; j indexes root[], which no descriptor guards)
+        const float4 s = buf_load16(rs_sph, j * 16);
+        const float g = point_gap(px, py, pz, s.x, s.y, s.z, s.w);
+        if (g <= max_dist) {
+          const int32_t theirs = uf_find(ops, j);
+          if (theirs != mine) mine = uf_unite(ops, mine, theirs);
+        }
+      }
+    }
+  }
+}
+// In place, and safe: no union runs any more, so every tree has its final root; the only store to word i is its owner's, of that root, and
+// the walk stores nothing else (uf_root, not uf_find: a halving store landing behind the owner's would leave a non-root in the answer).  A
+// lane that passes through a word reads its old parent or the root -- both lead to the root.
+__global__ __launch_bounds__(kClustersThreads) void clusters_flatten_kernel(int32_t *root, int n) {
+  const long long i = (long long)blockIdx.x * kClustersThreads + threadIdx.x;
+  if (i >= n) return;
+  const ParentOps ops{root};
+  const int32_t r = uf_root(ops, (int32_t)i);
+  if (r != (int32_t)i) ops.store((int32_t)i, r);
+}
+// root is final from here on: plain loads.  flag[i] = 1 at a cluster's root (the scan's input); size[] zeroed by the launcher.  The sizes are
+// counted a wave at a time: the lanes that share the first active lane's root are counted by ballot and added once, then the rest go round
+// again -- neighbours in L mostly share a root, and one cluster of 10^6 spheres is 15 625 atomics on its word instead of 10^6.
+__global__ __launch_bounds__(kClustersThreads) void clusters_count_kernel(const int32_t *root, int n, int32_t *flag, int32_t *size) {
+  const long long i = (long long)blockIdx.x * kClustersThreads + threadIdx.x;
+  if (i >= n) return;
+  const int32_t r = root[i];
+  if (flag != nullptr) flag[i] = r == (int32_t)i ? 1 : 0;
+  if (size == nullptr) return;
+  for (;;) {
+    const int32_t lead = __builtin_amdgcn_readfirstlane(r);
+    const unsigned long long same = __ballot(r == lead);
+    if (r == lead) {
+      if ((int)(threadIdx.x & 63) == __builtin_ctzll(same)) atomicAdd(size + lead, __builtin_popcountll(same));
+      return;
+    }
+  }
+}
+// cluster[i] = the number of roots below root[i]; size[i] = its root's count (a root's own entry already holds it and is only read here)
+__global__ __launch_bounds__(kClustersThreads) void clusters_label_kernel(const int32_t *root, int n, const int64_t *offsets, int32_t *cluster,
+                                                                          int32_t *size) {
+  const long long i = (long long)blockIdx.x * kClustersThreads + threadIdx.x;
+  if (i >= n) return;
+  const int32_t r = root[i];
+  if (cluster != nullptr) cluster[i] = (int32_t)offsets[r];
+  if (size != nullptr && r != (int32_t)i) size[i] = size[r];
+}
+
+size_t clusters_scratch_bytes(int64_t n) { return ((within_scratch_bytes(n) + 255) & ~(size_t)255) + ((size_t)n + 1) * 8; }
+
+hipError_t launch_contact_clusters(const KParams &p, float margin, int exact_depth, char *scratch, int32_t *root, int32_t *cluster, int32_t *size,
+                                   int64_t *num, hipStream_t stream) {
+  const int n = p.n_sph;
+  if (n < 1 || root == nullptr || !max_dist_ok(margin)) return hipErrorInvalidValue;
+  if (n > 1 && p.n_nodes < 1) return hipErrorInvalidValue;
+  const bool ids = cluster != nullptr || num != nullptr;
+  if (ids && scratch == nullptr) return hipErrorInvalidValue;
+  margin += 0.0f;   // (-0.0 -> +0.0)
+  const dim3 flat((unsigned)(((int64_t)n + kClustersThreads - 1) / kClustersThreads)), threads(kClustersThreads);
+  hipLaunchKernelGGL(clusters_init_kernel, flat, threads, 0, stream, root, n);
+  if (n > 1) {   // (one sphere: no tree, no edge)
+    hipLaunchKernelGGL(clusters_hook_kernel, dim3(((unsigned)n + 63u) / 64u), dim3(64), 0, stream, p, margin, exact_depth, root);
+    hipLaunchKernelGGL(clusters_flatten_kernel, flat, threads, 0, stream, root, n);
+  }
+  if (!ids && size == nullptr) return hipGetLastError();
+  int32_t *const flag = ids ? reinterpret_cast<int32_t *>(scratch) : nullptr;
+  int64_t *const offsets = ids ? reinterpret_cast<int64_t *>(scratch + ((within_scratch_bytes(n) + 255) & ~(size_t)255)) : nullptr;
+  if (size != nullptr) {
+    const hipError_t rc = hipMemsetAsync(size, 0, sizeof(int32_t) * (size_t)n, stream);
+    if (rc != hipSuccess) return rc;
+  }
+  hipLaunchKernelGGL(clusters_count_kernel, flat, threads, 0, stream, root, n, flag, size);
+  if (ids) {
+    long long *const sums = reinterpret_cast<long long *>(scratch + (((size_t)n * 4 + 255) & ~(size_t)255));
+    const int nblocks = (int)(((int64_t)n + kWithinScanItems - 1) / kWithinScanItems);
+    hipLaunchKernelGGL(within_scan_sums_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, flag, n, sums);
+    hipLaunchKernelGGL(within_scan_carry_kernel, dim3(1), dim3(kWithinScanThreads), 0, stream, sums, nblocks);
+    hipLaunchKernelGGL(within_scan_apply_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, flag, n, sums, offsets);
+  }
+  if (cluster != nullptr || size != nullptr) hipLaunchKernelGGL(clusters_label_kernel, flat, threads, 0, stream, root, n, offsets, cluster, size);
+  const hipError_t rc = hipGetLastError();
+  if (rc != hipSuccess) return rc;
+  // (a copy, not a store from a kernel: num_dev needs only 4-byte alignment)
+  if (num != nullptr) return hipMemcpyAsync(num, offsets + n, sizeof(int64_t), hipMemcpyDeviceToDevice, stream);
+  return hipSuccess;
 }
 
 // rt_spheres_in_boxes_*: EVERY sphere whose gap to the lane's box is <= the box's margin, in CSR form.  One lane per box:

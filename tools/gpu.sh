@@ -13,6 +13,7 @@
 #   cold[:size]      tools/cold_probe.py (first frames of new views, a camera path view by view) -> cold_probe_<size>.txt
 #   pmc              tools/gpu_pmc.sh passes -> pmc_summary.csv, pmc.json
 #   parts[:W]        tools/part_probe.py irreg 4000 W -> part_probe.txt;   scale   tools/scale_prediction.py -> scale_prediction.json
+#   clusters[:args]  tools/clusters_probe.py <args> (contact clusters against the count pass and the host route) -> clusters_probe.jsonl
 #   round            the round's measurement set: tools/gpu_round.sh <tag>
 cd "$(dirname "$0")/.."
 TAG=${1:?tag}; shift
@@ -45,6 +46,7 @@ for step in "$@"; do
     pmc) bash tools/gpu_pmc.sh $TAG ;;
     parts) timeout 200 python tools/part_probe.py irreg 4000 ${arg:-8} "" 2>&1 | grep -v amdgpu > $OUT/part_probe.txt; cat $OUT/part_probe.txt ;;
     scale) timeout 500 python tools/scale_prediction.py 20 > $OUT/scale_prediction.json 2> $OUT/scale_prediction.err; tail -n4 $OUT/scale_prediction.err ;;
+    clusters) timeout 540 python tools/clusters_probe.py ${arg} 2> $OUT/clusters_probe.err | grep '^{' > $OUT/clusters_probe.jsonl; echo "clusters_probe exit ${PIPESTATUS[0]}"; tail -n 4 $OUT/clusters_probe.jsonl ;;
     round) bash tools/gpu_round.sh $TAG ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
