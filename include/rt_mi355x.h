@@ -84,20 +84,29 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *   "family=pairs targets|directions[ mask][ count][ words/wave=K]"   rt_visible_pairs / rt_visible_pairs_shaped (below; K: the caller's words_per_wave)
  *   "family=none (no rows)"       the part owns no row of the image
  *   "family=pixel" | "family=pixel (instrumented)" | "family=persistent"
- *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2[ nodes=sign-ordered|planes,dark=0|1,leaf_box=0|1]"
+ *   "family=pooled tickets=T instantiation=I[+CULL] frames=.. tiles=.. grid=.. waves=.. counters=..[(turns)] deep_class=.. deep_split=.. recording=0|1|2[ nodes=sign-ordered|planes,entry=lists|root,dark=0|1,leaf_box=0|1]"
  *     T = rays (rt_trace_rays: blocks of 64 caller rays, instantiation plain[+SPILL]; rt_occluded_rays: instantiation any[+SPILL]; rt_occluded_rays_ranged:
  *         the same, with " intervals=per-ray" appended to the string) | pixel-list | tiles-ordered | tiles-bit-reversed (a view's first frame with nothing to borrow, first_order = 1) | tiles-raster,
  *         followed by "(borrowed)" when the order / list is another view's (a new view of a prepared scene that has rendered a view of the same shape)
  *     I = plain | SOLO | COLD | COLD+SOLO | DONATE | DONATE+SOLO | ORD | ORD+SOLO | ORD+DONATE | ORD+SOLO+DONATE;  +CULL: boxes tested against the best hit so far; +SPILL: a box stack that may overflow into device memory (twenty waves per CU, trees taller than 15 levels)
  *     recording: 0 nothing, 1 the tiles' longest chains, 2 also every pixel's chain length
  *     nodes (render launches): the layout of the node records staged in LDS -- sign-ordered: the plain instantiations on a scene that is in LDS whole; planes: every other launch
- *     dark (render launches, in the same token: "nodes=planes,dark=1"): 1 = the launch finishes a bounce chain whose light is exactly (0, 0, 0) as pixel 0 instead of tracing it on --
+ *     entry (render launches, in the same token: "nodes=sign-ordered,entry=lists"): lists = a new primary ray starts at its 8 x 8 tile's entry list -- at most one inner node and
+ *         six leaves that the root walk of every ray of the tile provably reaches -- instead of at the root (option entry_lists: -1, the default, launches of the
+ *         instantiation that exists with such lists -- plain tile tickets, 16 waves, the scene in LDS whole -- whose tiles are 8 consecutive image rows; 0 never; 1 every launch of
+ *         that instantiation); root = every ray starts at the root
+ *     dark (render launches, in the same token: "nodes=planes,entry=root,dark=1"): 1 = the launch finishes a bounce chain whose light is exactly (0, 0, 0) as pixel 0 instead of tracing it on --
  *         the pixel it ends in whatever it meets (option dark_stop: -1, the default, every render launch that does not record; 0 never; 1 also rt_render_trace's instrumented launch);
  *         0 = full chains: every recording launch (recording != 0), dark_stop = 0
- *     leaf_box (render launches, in the same token: "nodes=planes,dark=1,leaf_box=1"): 1 = BOX / BOX2 append a leaf child only if the sphere's own box, widened by a proven
+ *     leaf_box (render launches, in the same token: "nodes=planes,entry=root,dark=1,leaf_box=1"): 1 = BOX / BOX2 append a leaf child only if the sphere's own box, widened by a proven
  *         margin and kept in the leaf child's slot of the node record, passes (option leaf_box: -1, the default, every render launch whose scene and cameras pass the guards of
  *         DESIGN.md 3.4a and whose instantiation was compiled with the filter; 0 never; 1 also rt_render_trace's instrumented launch); 0 = every leaf child of a passing node is tested */
 const char *rt_context_last_launch(const rt_context *ctx);
+/* Under option "entry_count" = 1 a launch that says entry=lists runs a counting twin of its kernel (same pixels): per wave, the primary rays that started from their
+ * tile's list and those that had a list but took the root because the lists of the rays their wave started together would not fit its leaf list.  The counts of the
+ * context's LAST pooled render launch, summed, and per wave {lists, fallbacks} into per_wave[2 * cap_waves] when given; *waves = 0: that launch counted nothing
+ * (no table, or the option off).  Synchronises the context. */
+int rt_context_entry_counts(rt_context *ctx, uint64_t *lists, uint64_t *fallbacks, int64_t *waves, uint64_t *per_wave, int64_t cap_waves);
 int rt_context_sync(rt_context *ctx);
 /* Threads: every entry that takes a context holds that context's lock for the duration of the call (as a Futhark context does:
  * SURVEY.md 8b) -- host threads may share a context, a prepared scene and a scene; their calls are serialised and their frames
@@ -106,7 +115,8 @@ int rt_context_sync(rt_context *ctx);
 int rt_context_set_variant(rt_context *ctx, int variant);
 /* Tuning knobs by name (see DESIGN.md "knobs"); unknown name -> error.  None changes a pixel.  Among them "dark_stop" (-1 | 0 | 1, see rt_context_last_launch above):
  * rt_render_stats always counts the reference's full chains; rt_render_trace counts the stopped chains under dark_stop = 1 only.  "leaf_box" (-1 | 0 | 1) likewise:
- * rt_render_trace's leaf items are the reference's sphere tests unless leaf_box = 1. */
+ * rt_render_trace's leaf items are the reference's sphere tests unless leaf_box = 1.  "entry_lists" (-1 | 0 | 1): see rt_context_last_launch above; the instrumented launches
+ * always start at the root. */
 int rt_context_set_option(rt_context *ctx, const char *name, int64_t value);
 int rt_context_device_info(const rt_context *ctx, int *device, int *num_cu, int *lds_bytes, char *name, int name_len);
 

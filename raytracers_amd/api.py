@@ -77,8 +77,19 @@ class Context:
     def last_launch(self):
         """what the last render entry enqueued: family, tickets (pixel list / ordered tiles / raster), instantiation, launch shape, and for a pooled render
         launch whether it stops chains whose light is exactly zero ("dark=0|1", option dark_stop: -1 default, 0 never, 1 also the instrumented launch)
-        and whether it drops sphere tests whose own widened box the ray misses ("leaf_box=0|1", option leaf_box, the same three values)"""
+        and whether it drops sphere tests whose own widened box the ray misses ("leaf_box=0|1", option leaf_box, the same three values);
+        "entry=lists|root": whether new primary rays start at their tile's entry list (option entry_lists: -1 default, 0 never, 1 wherever legal)"""
         return lib.rt_context_last_launch(self._h).decode()
+
+    def entry_counts(self):
+        """option entry_count = 1: what the last pooled render launch counted -- {"lists": primary rays started from their tile's entry list, "fallbacks": rays
+        that had a list and took the root (their wave's leaf list had no room), "waves": waves that counted (0: the launch carried no table), "per_wave": (waves, 2)}"""
+        lists, falls, nw = C.c_uint64(), C.c_uint64(), C.c_int64()
+        self._check(lib.rt_context_entry_counts(self._h, C.byref(lists), C.byref(falls), C.byref(nw), None, 0))
+        per = np.zeros((nw.value, 2), np.uint64)
+        if nw.value:
+            self._check(lib.rt_context_entry_counts(self._h, None, None, None, per.ctypes.data_as(C.POINTER(C.c_uint64)), nw.value))
+        return {"lists": lists.value, "fallbacks": falls.value, "waves": nw.value, "per_wave": per}
 
     @property
     def rccl_ranks(self):

@@ -546,6 +546,34 @@ void set_leaf_box(const rt_context *ctx, const rt_prepared *ps, const Plan &pl, 
   p->leaf_box = 1;
 }
 
+// Per-tile entry lists (lane_core.h: tile_entry): which pooled render launches start their primary rays at their tile's list.  Option
+// entry_lists: 0 never; 1 every launch whose instantiation exists with ENTRY (rt_device.hpp: pooled_entry_ok) on a tree with an inner node; -1 (the default)
+// of those the launches whose tiles are 8 consecutive rows of the image -- a tile of a cyclic partition with fewer rows per row tile spans the rows of other
+// parts, and its corner rays bound little.  Called behind set_cull and set_leaf_box (the key and the filter are the launch's).  The table is one block of the
+// context's arena / pool, kept and grown: launches of one context are ordered on its stream, and tile_entry_kernel refills it there ahead of each.
+int set_entry(rt_context *ctx, const Plan &pl, rtk::KParams *p) {
+  p->entry = nullptr;
+  rtk::PooledKey k{};
+  if (ctx->entry_lists == 0 || pl.variant != RT_VARIANT_POOLED || p->n_nodes < 1 || !rtk::choose_pooled(*p, false, pl.waves, 0, &k) || !rtk::pooled_entry_ok(k)) return 0;
+  if (ctx->entry_lists < 0 && p->nparts > 1 && p->rpt_log2 < 3) return 0;
+  // (one camera: a list per tile, shared by the launch's frames.  A camera per frame: a list per frame and tile, found at the TICKET position -- the kernels
+  // carry no other index through their loop: only launches whose positions are frame * nchunks + tile, i.e. no order table and one queue over all tiles)
+  if (p->cams != nullptr && (p->order != nullptr || !(p->nshards == 1 || p->interleave))) return 0;
+  const size_t need = sizeof(unsigned) * rtk::kEntryDw * static_cast<size_t>(p->cams != nullptr ? p->nframes : 1) * static_cast<size_t>(p->nchunks);
+  if (ctx->entry_bytes < need) {
+    drain_streams(ctx);
+    pool_free(ctx, reinterpret_cast<char *>(ctx->entry_dev), ctx->entry_bytes);
+    ctx->entry_dev = nullptr; ctx->entry_bytes = 0;
+    char *blk = nullptr;
+    size_t bytes = need;
+    RT_HIP(ctx, pool_alloc(ctx, &blk, &bytes));
+    ctx->entry_dev = reinterpret_cast<unsigned *>(blk);
+    ctx->entry_bytes = bytes;
+  }
+  p->entry = ctx->entry_dev;
+  return 0;
+}
+
 // The name of the pooled instantiation these parameters launch (rt_context_last_launch)
 std::string pooled_launch_name(const rtk::KParams &p, int waves, int rays = 0) {
   rtk::PooledKey k{};
@@ -1039,14 +1067,35 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
   set_cull(ctx, ps, pl, cams_dev, &p);
   set_dark(ctx, false, &p);
   set_leaf_box(ctx, ps, pl, cams_dev, false, &p);
+  if (int rc = set_entry(ctx, pl, &p)) return rc;
+  int entry = 0;
+  if (p.entry) {
+    RT_HIP(ctx, rtk::launch_tile_entry(p, false, pl.waves, ctx->stream));
+    entry = rtk::kEntryLists;
+    if (ctx->entry_count) {
+      // (option entry_count, a test's aid: the counting twin, two words per wave -- rays started from a list, rays sent back to the root -- read by rt_context_entry_counts)
+      const size_t nw = static_cast<size_t>(pl.grid) * static_cast<size_t>(pl.waves), bytes = nw * 2 * sizeof(unsigned long long);
+      if (ctx->entry_counts_bytes < bytes) {
+        drain_streams(ctx);
+        if (ctx->entry_counts_dev) (void)hipFree(ctx->entry_counts_dev);
+        ctx->entry_counts_dev = nullptr; ctx->entry_counts_bytes = 0;
+        RT_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->entry_counts_dev), bytes));
+        ctx->entry_counts_bytes = bytes;
+      }
+      RT_HIP(ctx, hipMemsetAsync(ctx->entry_counts_dev, 0, bytes, ctx->stream));
+      p.trace = ctx->entry_counts_dev;
+      entry = rtk::kEntryCount;
+    }
+  }
+  ctx->entry_counts_waves = entry == rtk::kEntryCount ? static_cast<int64_t>(pl.grid) * pl.waves : 0;   // (the counts are the LAST pooled render launch's, or none)
   tick("before launch");
-  RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream));
+  RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream, 0, entry));
   tick("launch_pooled");
-  char buf[320];
-  std::snprintf(buf, sizeof buf, "family=pooled tickets=%s%s instantiation=%s frames=%d tiles=%d grid=%d waves=%d counters=%d%s deep_class=%d deep_split=%d recording=%d nodes=%s,dark=%d,leaf_box=%d",
+  char buf[352];
+  std::snprintf(buf, sizeof buf, "family=pooled tickets=%s%s instantiation=%s frames=%d tiles=%d grid=%d waves=%d counters=%d%s deep_class=%d deep_split=%d recording=%d nodes=%s,entry=%s,dark=%d,leaf_box=%d",
                 p.px_hdr ? "pixel-list" : t.first_order ? "tiles-bit-reversed" : (p.order ? "tiles-ordered" : "tiles-raster"), t.borrowed ? "(borrowed)" : "",
                 pooled_launch_name(p, pl.waves).c_str(), p.nframes, p.nchunks, pl.grid, pl.waves, p.nshards, p.interleave ? "(turns)" : "", p.px_hdr ? 0 : p.deep_class,
-                p.px_hdr ? 0 : p.deep_split, p.cost ? (p.cost_px ? 2 : 1) : 0, pooled_launch_nodes(p, pl.waves), p.dark, p.leaf_box);
+                p.px_hdr ? 0 : p.deep_split, p.cost ? (p.cost_px ? 2 : 1) : 0, pooled_launch_nodes(p, pl.waves), p.entry ? "lists" : "root", p.dark, p.leaf_box);
   ctx->last_launch = buf;
   if (to && p.cost) {
     // This frame recorded the view's bounce chains.  The sorts that turn the record into the view's tile order and pixel list are
@@ -1152,6 +1201,8 @@ extern "C" void rt_context_destroy(rt_context *ctx) {
   if (ctx->cams_event) (void)hipEventDestroy(ctx->cams_event);
   if (ctx->queue_dev) (void)hipFree(ctx->queue_dev);
   if (ctx->spill_dev) (void)hipFree(ctx->spill_dev);
+  pool_free(ctx, reinterpret_cast<char *>(ctx->entry_dev), ctx->entry_bytes);
+  if (ctx->entry_counts_dev) (void)hipFree(ctx->entry_counts_dev);
   if (ctx->order_scratch) (void)hipFree(ctx->order_scratch);
   if (ctx->px_scratch) (void)hipFree(ctx->px_scratch);
   if (ctx->within_scratch) (void)hipFree(ctx->within_scratch);
@@ -1170,6 +1221,27 @@ extern "C" int rt_device_count(void) {
 }
 
 extern "C" const char *rt_last_error(const rt_context *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
+// What the last pooled render launch of this context counted under option entry_count (0 waves: it carried no table, or the option was off): over all waves, and
+// per wave {lists, fallbacks} into per_wave[2 * cap_waves] when given.  Synchronises the context's stream.
+extern "C" int rt_context_entry_counts(rt_context *ctx, uint64_t *lists, uint64_t *fallbacks, int64_t *waves, uint64_t *per_wave, int64_t cap_waves) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const int64_t nw = ctx->entry_counts_waves;
+  std::vector<unsigned long long> h(static_cast<size_t>(nw) * 2);
+  if (nw > 0) RT_HIP(ctx, hipMemcpy(h.data(), ctx->entry_counts_dev, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  uint64_t l = 0, f = 0;
+  for (int64_t i = 0; i < nw; ++i) {
+    l += h[2 * i]; f += h[2 * i + 1];
+    if (per_wave && i < cap_waves) { per_wave[2 * i] = h[2 * i]; per_wave[2 * i + 1] = h[2 * i + 1]; }
+  }
+  if (lists) *lists = l;
+  if (fallbacks) *fallbacks = f;
+  if (waves) *waves = nw;
+  return 0;
+}
+
 extern "C" const char *rt_context_last_launch(const rt_context *ctx) { return ctx ? ctx->last_launch.c_str() : ""; }
 
 extern "C" int rt_context_sync(rt_context *ctx) {
@@ -1319,6 +1391,10 @@ extern "C" int rt_context_set_option(rt_context *ctx, const char *name, int64_t 
     ctx->dark_stop = std::max(-1, std::min(1, v));
   } else if (k == "leaf_box") {
     ctx->leaf_box = std::max(-1, std::min(1, v));
+  } else if (k == "entry_lists") {
+    ctx->entry_lists = std::max(-1, std::min(1, v));
+  } else if (k == "entry_count") {
+    ctx->entry_count = v != 0;
   } else if (k == "sync_policy") {
     ctx->sync_policy = v != 0;
   } else {

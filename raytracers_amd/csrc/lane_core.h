@@ -392,4 +392,137 @@ RT_HD bool finish_ray_emit(Ray &r, float best, int bestj, float spx, float spy, 
   return shade_ray_emit<true>(r, have, t, spx, spy, spz, scr, scg, scb, inv_rad, lr, lg, lb, depth, max_depth, emit);
 }
 
+// ---- per-tile entry lists (the ENTRY instantiations of the pooled kernel) ---------------------------------
+// The primary rays of one tile share their origin and nearly their direction: for most upper nodes box_hit gives all of them the
+// same verdict, and that is proven once per tile.  tile_rays bounds every ray's 1 / d_k from the tile's corner pixels;
+// tile_verdict folds those bounds through box_hit_presorted's own chain; tile_frontier walks the tree while both children of a
+// node have one verdict for the whole tile, and what it stops at -- at most one inner node and kEntryLeaves leaves -- is what a
+// new primary ray of the tile starts from instead of the root.  A tile with no list starts at the root: same pixels either way.
+// `MUT`: the faults tools/entry_check.cpp must find (1: ALLMISS decided with < instead of <=; 2: bounds from two corners; 3: the
+// sign check dropped); 0 everywhere else.
+constexpr int kEntryLeaves = 6;              // leaves a kept list holds at most (with one inner item and the header: kEntryDw dwords)
+constexpr int kEntryDw = 8;                  // dwords per position of the table: header, inner item or 0, kEntryLeaves leaf references
+constexpr int kEntryStack = 24;              // tile_frontier's private stack (overflow: no list)
+constexpr uint32_t kEntryValid = 1u, kEntryInner = 2u;   // header: bit 0 the position has a list, bit 1 it holds an inner item, ...
+constexpr int kEntryCountShift = 4;                      // ... bits 4 .. 7 its number of leaves
+enum { kTileMixed = 0, kTileAllHit = 1, kTileAllMiss = 2 };
+struct TileRays {
+  float o[3];
+  float imin[3], imax[3];   // every ray's 1 / d_k lies in [imin_k, imax_k]; both finite, non-zero, of one sign
+};
+
+// (u0, u1) x (v0, v1): u and v of the tile's first / last column and row THAT EXIST.  Each d_k = ((l_k + u h_k) + v v_k) - o_k is a chain
+// of rounded binary32 operations, monotone in u for fixed v and in v for fixed u, and the tables are monotone in column and row: over the
+// tile's pixel rectangle d_k takes its extremes at the four corners.  Four corners finite, non-zero and of one sign: so is every ray's
+// d_k, and 1 / d_k (monotone on either side of zero) lies between the corners' extremes.  A quotient that is not finite (a subnormal d_k)
+// gives no bounds either: tile_verdict's products must never meet 0 * inf.
+template <int MUT = 0>
+RT_HD bool tile_rays(const Cam &c, float u0, float u1, float v0, float v1, TileRays *t) {
+  Ray q[4];
+  primary_dir_uv(c, u0, v0, q[0]);
+  primary_dir_uv(c, u1, v1, q[3]);
+  if (MUT == 2) { q[1] = q[0]; q[2] = q[3]; }
+  else { primary_dir_uv(c, u1, v0, q[1]); primary_dir_uv(c, u0, v1, q[2]); }
+  t->o[0] = c.ox; t->o[1] = c.oy; t->o[2] = c.oz;
+  bool ok = true;
+  for (int k = 0; k < 3; ++k) {
+    float lo = 0.0f, hi = 0.0f;
+    bool pos = true, neg = true;
+    for (int j = 0; j < 4; ++j) {
+      const float d = k == 0 ? q[j].dx : k == 1 ? q[j].dy : q[j].dz;
+      const float i = 1.0f / d;
+      pos = pos & (d > 0.0f) & (i > 0.0f) & (i < kNoHit);
+      neg = neg & (d < 0.0f) & (i < 0.0f) & (i > -kNoHit);
+      lo = j == 0 || i < lo ? i : lo;
+      hi = j == 0 || i > hi ? i : hi;
+    }
+    if (MUT != 3) ok = ok & (pos | neg);
+    t->imin[k] = lo; t->imax[k] = hi;
+  }
+  return ok;
+}
+
+// box_hit_presorted over (0, 1e9) for every ray of the tile at once.  near_k - o_k and far_k - o_k are one float each for the whole tile
+// (one origin, one sign per axis); a product c * i is monotone in i, so it lies between c * imin and c * imax, both attained; fmaxf / fminf
+// over non-NaN values are monotone, so the folds of the lower ends bound every ray's tmin / tmax from below and those of the upper ends
+// from above.  ALLHIT: every ray has tmax > tmin; ALLMISS: every ray has tmax <= tmin.
+template <int MUT = 0>
+RT_HD int tile_verdict(const TileRays &t, const float lo[3], const float hi[3]) {
+  float tmin_lo = 0.0f, tmin_hi = 0.0f, tmax_lo = kTMax, tmax_hi = kTMax;
+  for (int k = 0; k < 3; ++k) {
+    const bool neg = t.imax[k] < 0.0f;
+    const float cn = (neg ? hi[k] : lo[k]) - t.o[k], cf = (neg ? lo[k] : hi[k]) - t.o[k];
+    const float na = cn * t.imin[k], nb = cn * t.imax[k], fa = cf * t.imin[k], fb = cf * t.imax[k];
+    tmin_lo = fmaxf(na < nb ? na : nb, tmin_lo);
+    tmin_hi = fmaxf(na < nb ? nb : na, tmin_hi);
+    tmax_lo = fminf(fa < fb ? fa : fb, tmax_lo);
+    tmax_hi = fminf(fa < fb ? fb : fa, tmax_hi);
+  }
+  if (tmax_lo > tmin_hi) return kTileAllHit;
+  if (MUT == 1 ? tmax_hi < tmin_lo : tmax_hi <= tmin_lo) return kTileAllMiss;
+  return kTileMixed;
+}
+
+// The frontier of a tile over the pooled records (nodes64: 16 floats per inner node -- {L.lo, left << 8} {L.hi, right << 8} {R.lo, .} {R.hi, .},
+// a leaf child's slot holding the sphere's own widened box where the scene's slots are filled).  A child is UNIFORM when the whole tile
+// agrees on what a BOX operation does with it: an inner child that is ALLHIT or ALLMISS; a leaf child of an unfiltered launch (always
+// tested); a leaf child of a filtering launch (`filter`, 3.4a) whose slot is ALLHIT (tested) or ALLMISS (dropped).  An ALLHIT node with two
+// uniform children is expanded here; every other reached node is emitted as an inner item.  false: no list (the root is not ALLHIT, the
+// stack or a cap overflowed, or the list is the root alone).
+template <int MUT, int MAXI, int MAXL>
+RT_HD bool tile_frontier(const TileRays &t, const float root_lo[3], const float root_hi[3], const float *nodes64, int n_nodes, bool filter,
+                         int *inner, int *n_inner, int *leaf, int *n_leaf) {
+  *n_inner = 0; *n_leaf = 0;
+  if (n_nodes < 1 || tile_verdict<MUT>(t, root_lo, root_hi) != kTileAllHit) return false;
+  int stack[kEntryStack], sp = 0, ni = 0, nl = 0;
+  stack[sp++] = 0;
+  while (sp > 0) {
+    const int node = stack[--sp];
+    const float *const rec = nodes64 + 16 * (size_t)node;
+    int child[2], verdict[2];
+    bool uniform = true;
+    for (int s = 0; s < 2; ++s) {
+      int32_t w;
+      __builtin_memcpy(&w, rec + 4 * s + 3, 4);
+      child[s] = w >> 8;
+      verdict[s] = tile_verdict<MUT>(t, rec + 8 * s, rec + 8 * s + 4);
+      if (child[s] < 0 && !filter) verdict[s] = kTileAllHit;
+      uniform = uniform & (verdict[s] != kTileMixed);
+    }
+    if (!uniform) {
+      if (node == 0 || ni >= MAXI) return false;
+      inner[ni++] = node;
+      continue;
+    }
+    for (int s = 0; s < 2; ++s) {
+      if (verdict[s] != kTileAllHit) continue;
+      if (child[s] < 0) {
+        if (nl >= MAXL) return false;
+        leaf[nl++] = ~child[s];
+      } else {
+        if (sp >= kEntryStack) return false;
+        stack[sp++] = child[s];
+      }
+    }
+  }
+  *n_inner = ni; *n_leaf = nl;
+  return true;
+}
+
+// One position of the table: the header, the inner item and the leaf references in the form the consuming kernel's work items carry them
+// (render_kernels.hip: an inner node as (node * node_mul) << ref_shift, a leaf as ~leaf << ref_shift; the slot and the ray's signs are
+// ORed in by the ray that pushes them).  All zero: no list.
+template <int MUT = 0>
+RT_HD void tile_entry(const TileRays &t, bool rays_ok, const float root_lo[3], const float root_hi[3], const float *nodes64, int n_nodes, bool filter,
+                      int ref_shift, int node_mul, uint32_t out[kEntryDw]) {
+  int inner[1], leaf[kEntryLeaves], ni = 0, nl = 0;
+  const bool ok = rays_ok && tile_frontier<MUT, 1, kEntryLeaves>(t, root_lo, root_hi, nodes64, n_nodes, filter, inner, &ni, leaf, &nl);
+  for (int i = 0; i < kEntryDw; ++i) out[i] = 0u;
+  if (!ok) return;
+  out[0] = kEntryValid | (ni ? kEntryInner : 0u) | (uint32_t)nl << kEntryCountShift;
+  if (ni) out[1] = (uint32_t)(inner[0] * node_mul) << ref_shift;
+  for (int i = 0; i < kEntryLeaves; ++i)
+    if (i < nl) out[2 + i] = (uint32_t)~leaf[i] << ref_shift;
+}
+
 }  // namespace rtk

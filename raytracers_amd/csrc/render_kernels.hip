@@ -666,10 +666,17 @@ __device__ __forceinline__ unsigned long long launch_leaf_off() {
   return (unsigned long long)(unsigned)kp->leaf_box - 1ull;   // (the host stores 0 or 1: all ones, or zero -- a subtraction, not a select)
 }
 
-template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, int RAYS = 0>
+// ENTRY: the plain tile-ticket kernel of batches and large frames on a scene wholly in LDS a second time (rt_device.hpp: pooled_entry_ok).  A new PRIMARY ray that passes its root test
+// pushes its position's entry list (p.entry, filled by tile_entry_kernel ahead of the launch; lane_core.h: tile_entry) instead of the root item:
+// at most one inner item to the box stack and kEntryLeaves leaves to the leaf list -- what the root walk of every ray of its tile provably reaches.  Only SHADE
+// differs; a position without a list, a scattered ray, and every new ray of a SHADE whose lists would not fit the leaf list start at the root as before.
+// ENTRY == kEntryCount: the same kernel with two counters per wave -- the rays that started from a list, and the rays that had one and took the root because
+// their SHADE's leaves would not fit -- written to p.trace[2 * wave_index ..] when the wave ends (option entry_count; rt_context_entry_counts).
+template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, int RAYS = 0, int ENTRY = 0>
 __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 4) void pooled_kernel(KParams p) {
   constexpr bool COLD = TAIL == 1, DONATE = TAIL == 2;
   constexpr bool ANY = RAYS == kRaysAny;
+  static_assert(!ENTRY || (THREADS == 1024 && ALL_LDS && !STATS && !SOLO && TAIL == 0 && !ORD && !CULL && SPILL == 0 && RAYS == 0), "ENTRY: the plain 16-wave kernel of a scene in LDS only");
   static_assert(!RAYS || (!STATS && !SOLO && TAIL == 0 && !ORD && !CULL), "RAYS: the plain instantiations only");
   static_assert(!ORD || TAIL != 1, "ORD: no COLD variant");   // (ORD + DONATE: a frame rendered through a pixel list BORROWED from a neighbouring view, round 6)
   static_assert(!CULL || !ALL_LDS, "CULL: instantiated for the general scene path only");
@@ -729,6 +736,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
   unsigned long long n_rays = 0, n_box = 0, n_sph = 0;
   // ---- wave state (uniform) ----
   int nbox = 0, nleaf = 0;
+  unsigned ec_lists = 0u, ec_fall = 0u;   // (ENTRY == kEntryCount)
   // SPILL (four-wave workgroups in the shape of twenty waves per CU, tall trees): p.capb is smaller than the stack's bound (trees taller than 15 levels do not
   // leave a wave 64 H + 63 dwords there).  A full BOX operation that could push beyond it first moves the OLDEST half of the stack -- its bottom -- to the wave's
   // region of p.spill; the newest spilled chunk comes back when the LDS stack has run empty; no SHADE while anything is spilled.  The order of the operations is
@@ -994,6 +1002,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           }
           bool want = (pix < 0) & !exhausted & !hold;
           int slot = -1;
+          uint4 ent0 = make_uint4(0u, 0u, 0u, 0u), ent1 = ent0;   // (ENTRY) the list of a new primary ray's position; header 0: none
           float a_lo = p.ray_tlo, a_hi = p.ray_thi;   // (ANY: the interval of the ray a lane draws)
           unsigned long long m = bal(want);
           while (ORD && m != 0ull) {     // pixel tickets: the next pixels of the view's list
@@ -1078,8 +1087,8 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
               // entering a tile: where it is.  A batch launch hands out the tiles of frame 0, then of frame 1, ...:
               // frame f's pixels go to out + f * frame_stride and (when the batch carries cameras) through cams[f]
               unsigned t = q_next >> 6;
+              unsigned f = 0;
               if (p.nframes > 1) {
-                unsigned f;
                 if (p.order != nullptr) {
                   // one view, ordered tiles: CLASS-major over the batch -- every frame's tiles of the most expensive
                   // class (longest bounce chains) first, so the last frame's chains do not start last
@@ -1140,6 +1149,14 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
                 slot = q_frame_off + lrow * p.w + col + k * p.out_skip;   // (out_skip: 0 packed, else the pixel's place in the full image)
                 ptile = q_tile;
                 const int grow = ((k * p.nparts + p.part) << p.rpt_log2) + (lrow & ((1 << p.rpt_log2) - 1));
+                if constexpr (ENTRY) {   // the tile's list: two 16-byte loads that go out with the two table loads
+                  // (one camera: the table is the tile's, whatever the frame.  A camera per frame: frame * nchunks + tile, which is the ticket position
+                  // itself -- such a launch carries a table only without an order table and with one queue over all tiles, api.cpp: set_entry.  Nothing
+                  // more is carried through the loop)
+                  const uint4 *const ep = reinterpret_cast<const uint4 *>(p.entry) + 2 * (size_t)(p.cams != nullptr ? (int)(q_next >> 6) : q_tile);
+                  ent0 = ep[0];
+                  ent1 = ep[1];
+                }
                 primary_dir_uv(q_cam, p.u_tab[col], p.v_tab[grow], r);
                 want = false;
               }
@@ -1210,17 +1227,51 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           if (root) ray_derive(r);   // one place for both scattered and primary rays
           const bool root_hit = root && (ANY ? interval_ok(a_lo, a_hi) && box_hit_interval(r, p.root_lo[0], p.root_lo[1], p.root_lo[2], p.root_hi[0], p.root_hi[1], p.root_hi[2], a_lo, a_hi)
                                              : box_hit(r, p.root_lo[0], p.root_lo[1], p.root_lo[2], p.root_hi[0], p.root_hi[1], p.root_hi[2]));
+          // ENTRY: which new primary rays start from their list, and the inner item each ray pushes.  The leaves must fit: the leaf list holds nleaf (0 behind
+          // a drained list) + at most 64 * kEntryLeaves new items in p.capl -- decided for the wave as a whole, on the exact count (ballots and popcounts only)
+          unsigned ent_hdr = 0u;
+          bool push_box = root_hit;
+          if constexpr (ENTRY) {
+            ent_hdr = (root_hit & (slot >= 0)) ? ent0.x : 0u;
+            // (counted only when as many full lists would not fit: a SHADE that starts 32 rays or fewer never counts)
+            if (__builtin_expect((int)__popcll(bal(ent_hdr != 0u)) * kEntryLeaves > p.capl - nleaf, 0)) {
+              const int nl = (int)(ent_hdr >> kEntryCountShift) & 15;
+              int total = 0;
+              for (int k = 0; k < kEntryLeaves; ++k) total += __popcll(bal(nl > k));
+              if (uni(total) > p.capl - nleaf) {
+                if constexpr (ENTRY == kEntryCount) ec_fall += (unsigned)__popcll(bal(ent_hdr != 0u));
+                ent_hdr = 0u;
+              }
+            }
+            if constexpr (ENTRY == kEntryCount) ec_lists += (unsigned)__popcll(bal((ent_hdr & kEntryValid) != 0u));
+            push_box = root_hit & ((ent_hdr & kEntryValid) == 0u || (ent_hdr & kEntryInner) != 0u);
+          }
           if (root) {
             wkey[lane] = ANY ? any_key_seed(a_hi) : kKeyInit;
-            wcnt[lane] = root_hit ? 1 : 0;    // 0: the fold is already complete (a miss), shaded next time
+            wcnt[lane] = push_box ? 1 : 0;    // 0: the fold is already complete (a miss, or a list of leaves alone), shaded next time
             wray[lane] = make_float4(r.ox, r.oy, r.oz, r.a);
             wray[64 + lane] = make_float4(r.ix, r.iy, r.iz, CULL ? cull_weight(r, p.cull_c2) : ANY ? a_lo : 0.0f);   // (CULL: the ray's W2; ANY: t_min)
             if (p.ray_planes == 3) wray[128 + lane] = make_float4(r.dx, r.dy, r.dz, 0.0f);
             if (STATS) { n_rays++; n_box++; }
           }
-          const unsigned long long m_root = bal(root_hit);
-          if (root_hit) wbox[nbox + lane_rank(m_root)] = (unsigned)lane << 2 | (PRESORT ? sign_offsets(r) << 5 : 0u);   // (node 0, slot = lane; PRESORT: + the ray's signs)
-          nbox = uni(nbox + __popcll(m_root));
+          const unsigned long long m_root = bal(push_box);
+          if constexpr (!ENTRY) {
+            if (root_hit) wbox[nbox + lane_rank(m_root)] = (unsigned)lane << 2 | (PRESORT ? sign_offsets(r) << 5 : 0u);   // (node 0, slot = lane; PRESORT: + the ray's signs)
+            nbox = uni(nbox + __popcll(m_root));
+          } else {
+            const unsigned low = (unsigned)lane << 2 | (PRESORT ? sign_offsets(r) << 5 : 0u);   // (slot = lane; PRESORT: + the ray's signs)
+            if (push_box) wbox[nbox + lane_rank(m_root)] = ((ent_hdr & kEntryValid) != 0u ? ent0.y : 0u) | low;   // (node 0, or the list's inner item)
+            nbox = uni(nbox + __popcll(m_root));
+            // the lists' leaves: leaf k of every list that has one, by ranks -- the items LEAF drains next
+            const unsigned lf[kEntryLeaves] = {ent0.z, ent0.w, ent1.x, ent1.y, ent1.z, ent1.w};
+            const int nl = (ent_hdr & kEntryValid) != 0u ? (int)(ent_hdr >> kEntryCountShift) & 15 : 0;
+            for (int k = 0; k < kEntryLeaves; ++k) {
+              const unsigned long long m_k = bal(nl > k);
+              if (m_k == 0ull) break;          // (wave-uniform: as many rounds as the longest list has leaves)
+              if (nl > k) wleaf[nleaf + lane_rank(m_k)] = lf[k] | low;
+              nleaf = uni(nleaf + __popcll(m_k));
+            }
+          }
           // Issue priority follows the deepest bounce chain this wave carries: the frame cannot
           // end before its longest chain (up to 50 dependent folds) does, and a wave that shares
           // its SIMD's issue slots evenly with 3 others walks that chain 4x slower.
@@ -1558,6 +1609,12 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
     }
   }
   queue_leave(p, nwaves, lane);
+  if constexpr (ENTRY == kEntryCount) {
+    if (lane == 0 && p.trace != nullptr) {
+      unsigned long long *const rec = p.trace + 2 * (size_t)(blockIdx.x * (THREADS / 64) + wave);
+      rec[0] = ec_lists; rec[1] = ec_fall;
+    }
+  }
   if (STATS) {
     atomicAdd(&p.stats[0], n_rays);
     atomicAdd(&p.stats[1], n_box);
@@ -2009,13 +2066,61 @@ static hipError_t launch_pooled_key(const PooledKey &k, const KParams &p, int gr
   return e;
 }
 
-hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays) {
+// The ENTRY twins of the one key pooled_entry_ok admits: `entry` = kEntryLists, or kEntryCount (the counting one: p.trace holds two words per wave)
+static hipError_t launch_pooled_entry(const PooledKey &k, const KParams &p, int grid, hipStream_t stream, int entry) {
+  if (!pooled_entry_ok(k) || p.entry == nullptr || p.rays != nullptr || (entry != kEntryLists && entry != kEntryCount) || (entry == kEntryCount && p.trace == nullptr))
+    return hipErrorInvalidValue;
+  const size_t lds = pooled_lds_bytes(p.lds_nodes, p.lds_sph, p.capb, p.capl, p.ray_planes, 16);
+  auto kfn = entry == kEntryCount ? pooled_kernel<1024, true, false, false, 0, false, false, 0, 0, kEntryCount>
+                                  : pooled_kernel<1024, true, false, false, 0, false, false, 0, 0, kEntryLists>;
+  if (hipError_t e = allow_full_lds(reinterpret_cast<const void *>(kfn)); e != hipSuccess) return e;
+  hipLaunchKernelGGL(kfn, dim3(grid), dim3(1024), lds, stream, p);
+  return hipGetLastError();
+}
+
+// The table of entry lists of a launch (p.entry: p.nchunks positions of kEntryDw dwords -- with a camera per frame p.nframes * p.nchunks, frame-major), one
+// lane per position, from the launch's own parameters:
+// the frame's camera, the tile's corner pixels THAT EXIST through the u / v tables, the records in nodes64, the filter as the launch applies it.
+// `ref_shift`, `node_mul`: the form of the consuming kernel's items (PRESORT: byte offsets of 56-byte records from bit 11; else node indices from bit 8);
+// `filter`: that kernel's BOX drops leaf children whose own box fails (p.leaf_box on an instantiation that honours it).
+__global__ __launch_bounds__(256) void tile_entry_kernel(KParams p, int ref_shift, int node_mul, int filter) {
+  const unsigned pos = blockIdx.x * 256u + threadIdx.x;
+  if (pos >= (p.cams != nullptr ? (unsigned)p.nframes : 1u) * (unsigned)p.nchunks) return;
+  const unsigned f = pos / (unsigned)p.nchunks;
+  const int tile = (int)(pos - f * (unsigned)p.nchunks);
+  const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
+  const int col0 = tx * 8, col1 = col0 + 7 < p.w ? col0 + 7 : p.w - 1;
+  const int lrow0 = ty * 8, lrow1 = lrow0 + 7 < p.rows_local ? lrow0 + 7 : p.rows_local - 1;
+  auto grow = [&](int lrow) { return (((lrow >> p.rpt_log2) * p.nparts + p.part) << p.rpt_log2) + (lrow & ((1 << p.rpt_log2) - 1)); };
+  const Cam cam = p.cams != nullptr ? p.cams[f] : p.cam;
+  TileRays t;
+  const bool ok = tile_rays(cam, p.u_tab[col0], p.u_tab[col1], p.v_tab[grow(lrow0)], p.v_tab[grow(lrow1)], &t);
+  unsigned e[kEntryDw];
+  tile_entry(t, ok, p.root_lo, p.root_hi, reinterpret_cast<const float *>(p.nodes64), p.n_nodes, filter != 0, ref_shift, node_mul, e);
+  uint4 *const out = reinterpret_cast<uint4 *>(const_cast<unsigned *>(p.entry)) + 2 * (size_t)pos;
+  out[0] = make_uint4(e[0], e[1], e[2], e[3]);
+  out[1] = make_uint4(e[4], e[5], e[6], e[7]);
+}
+hipError_t launch_tile_entry(const KParams &p, bool stats, int waves_per_wg, hipStream_t stream) {
+  PooledKey k;
+  if (p.entry == nullptr || p.rays != nullptr || !choose_pooled(p, stats, waves_per_wg, 0, &k) || !pooled_entry_ok(k)) return hipErrorInvalidValue;
+  const unsigned npos = (p.cams != nullptr ? (unsigned)p.nframes : 1u) * (unsigned)p.nchunks;
+  if (npos == 0) return hipSuccess;
+  const bool presort = pooled_presort(k);
+  hipLaunchKernelGGL(tile_entry_kernel, dim3((npos + 255u) / 256u), dim3(256), 0, stream, p, presort ? kPsItemShift : 8, presort ? kPsNodeBytes : 1,
+                     p.leaf_box != 0 && pooled_leaf_box(k) ? 1 : 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays, int entry) {
   if (rays == kRaysAny && p.occluded == nullptr) return hipErrorInvalidValue;
   // (per-ray intervals: the any-hit loop only, both bounds)
   if ((p.ray_tlo_dev != nullptr || p.ray_thi_dev != nullptr) && (rays != kRaysAny || p.ray_tlo_dev == nullptr || p.ray_thi_dev == nullptr)) return hipErrorInvalidValue;
   if (grid <= 0 || (rays && p.nrays <= 0)) return hipSuccess;
   PooledKey k;
   if (!choose_pooled(p, stats, waves_per_wg, rays, &k)) return hipErrorInvalidValue;
+  // (the caller SAYS that p.entry is a table: the field shares its slot with the caller rays' colour3, and nothing is read off the pointer)
+  if (entry != 0) return rays == 0 && !stats ? launch_pooled_entry(k, p, grid, stream, entry) : hipErrorInvalidValue;
   return launch_pooled_key(k, p, grid, stream, std::make_integer_sequence<int, kNumPooledKeys>{});
 }
 
@@ -2055,6 +2160,8 @@ void warm_render_kernels() {
   // (the pooled instantiations a view's first frames and its policy may switch to: a first use inside somebody's timed loop is 0.2-0.3 ms)
   warm_pooled(std::make_integer_sequence<int, kNumPooledKeys>{});
   hipFuncAttributes a;
+  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(pooled_kernel<1024, true, false, false, 0, false, false, 0, 0, kEntryLists>));
+  (void)hipFuncGetAttributes(&a, (const void *)tile_entry_kernel);
   (void)hipFuncGetAttributes(&a, (const void *)px_count_kernel);
   (void)hipFuncGetAttributes(&a, (const void *)px_scan_kernel);
   (void)hipFuncGetAttributes(&a, (const void *)px_place_kernel);

@@ -278,7 +278,13 @@ struct KParams {
   // caller-supplied rays (rt_trace_rays: the RAYS instantiations of the pixel and pooled kernels): ray i is rays[6 i .. 6 i + 6) = {o.xyz, d.xyz};
   // its colour goes to colour3[3 i ..] and / or its packed pixel to out[i] (either pointer may be nullptr, not both)
   const float *rays;
-  float *colour3;
+  // (... in one slot with `entry`: a launch has caller rays or tiles, never both, and the argument block keeps its size and every field its offset)
+  // pooled family, render launches, the ENTRY instantiations: the launch's table of per-tile entry lists (lane_core.h: tile_entry), kEntryDw dwords
+  // per tile -- with a camera per frame (`cams`) per position frame * nchunks + tile --, filled by tile_entry_kernel on the launch's stream ahead of it (nullptr: every ray starts at the root)
+  union {
+    float *colour3;
+    const unsigned *entry;
+  };
   int nrays;
   // rt_occluded_rays (the any-hit instantiations of the pooled kernel): occluded[i] = 1 iff some leaf is reached with every box tested over
   // (ray_tlo, ray_thi) and its sphere has a root strictly inside that interval, else 0
@@ -370,6 +376,15 @@ constexpr bool pooled_warmed(const PooledKey &k) {
   return !k.stats && k.rays == 0 && (k.threads == 1024 || (k.threads == 256 && !k.all_lds && !k.solo && k.spill != kSpillCapbTest - 64));
 }
 
+// The instantiation that exists a second time with ENTRY -- new primary rays start at their tile's entry list (KParams::entry) -- and so the
+// launches that may carry a table: plain tile tickets, no solo loop, no tail, 16 waves with the scene wholly in LDS (rgbbox's batches).  Not the four-wave
+// kernels that read the scene from L2: with lists irreg's batch ran 4 - 5 % SLOWER (0.100 -> 0.105 ms per frame; -0.5 % VALU instructions, +6 % scalar ones:
+// profiles/entry_lists), as with the leaf filter.  launch_pooled takes the ENTRY twin of choose_pooled's key whenever p.entry is set, and refuses a table on
+// any other key
+constexpr bool pooled_entry_ok(const PooledKey &k) {
+  return k.threads == 1024 && k.all_lds && !k.stats && !k.solo && k.tail == 0 && !k.ord && !k.cull && k.spill == 0 && k.rays == 0;
+}
+
 // Which instantiation renders a launch with these parameters (false: none -- hipErrorInvalidValue).  `rays`: 0, kRaysColour, kRaysAny.
 // No HIP runtime calls: the CPU check tools/pooled_choice_check.cpp runs it over its inputs.
 inline bool choose_pooled(const KParams &p, bool stats, int waves_per_wg, int rays, PooledKey *out) {
@@ -448,7 +463,13 @@ hipError_t launch_persistent(const KParams &p, bool stats, int grid, int waves_p
 size_t persistent_lds_bytes(int lds_nodes, int lds_sph, int smax, int lmax, int waves_per_wg);
 // the pooled family: the instantiation choose_pooled picks (grid workgroups of 64 * waves_per_wg threads).  `rays`: 64 consecutive caller rays
 // per ticket (the plain loop; kRaysAny: occlusion of p.nrays rays over (p.ray_tlo, p.ray_thi), or each over its own with p.ray_tlo_dev, into p.occluded)
-hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays = 0);
+// `entry`: 0 = every ray starts at the root (p.entry is not looked at: it shares its slot with colour3); kEntryLists = p.entry is the launch's table of entry lists
+// (launch_tile_entry has filled it) and the ENTRY twin of the chosen instantiation renders -- an error where there is none (pooled_entry_ok) or with caller rays;
+// kEntryCount = the same through the counting twin, p.trace holding two zeroed words per wave
+constexpr int kEntryLists = 1, kEntryCount = 2;
+hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays = 0, int entry = 0);
+// fills p.entry for the launch launch_pooled(p, stats, grid, waves_per_wg, stream) is about to make (hipErrorInvalidValue: that launch has no ENTRY instantiation)
+hipError_t launch_tile_entry(const KParams &p, bool stats, int waves_per_wg, hipStream_t stream);
 size_t pooled_lds_bytes(int lds_nodes, int lds_sph, int capb, int capl, int ray_planes, int waves_per_wg);
 // prepare_scene on the GPU (bvh_build.hip).  Canonical {L, I} arrays + the traversal copy.
 struct GpuBvhOut {

@@ -84,6 +84,13 @@ struct rt_context {
   hipStream_t sort_stream = nullptr, sort_stream_px = nullptr;   // the sort streams (eager_sort): a recorded view's tile order; its pixel list
   hipEvent_t rec_event = nullptr;      // main stream -> sort stream: "the recording frame has been enqueued up to here"
   unsigned *queue_dev = nullptr;
+  int entry_lists = -1;     // pooled family: new primary rays start at their tile's entry list instead of the root (lane_core.h: tile_entry; same pixels, fewer box tests).  -1 (default): the launches whose instantiation exists with ENTRY (rt_device.hpp: pooled_entry_ok) and whose tiles are 8 consecutive image rows; 0: never; 1: every launch with such an instantiation
+  unsigned *entry_dev = nullptr;   // ... the table of the launch in flight (rt_device.hpp: KParams::entry), a block of the arena / pool kept and grown (api.cpp: set_entry)
+  size_t entry_bytes = 0;
+  bool entry_count = false;        // option entry_count: launches that carry a table run the counting twin of the ENTRY kernel (two words per wave; rt_context_entry_counts)
+  unsigned long long *entry_counts_dev = nullptr;
+  size_t entry_counts_bytes = 0;
+  int64_t entry_counts_waves = 0;  // waves of the last pooled render launch if it counted, else 0
   unsigned *spill_dev = nullptr;   // pooled family, twenty waves per CU, trees taller than 15 levels: the waves' box-stack overflow regions (rt_device.hpp: KParams::spill); allocated by rt_prepare_scene of such a tree (api.cpp: ensure_spill)
   size_t spill_bytes = 0;
   int *order_scratch = nullptr;   // the tile-order sort's chunk counts (rtk::kOrderScratchInts), allocated with the first record
