@@ -942,6 +942,27 @@ def nearest_spheres(prepared, points, k, max_dist=1e9, count=True):
         return (cnt.to_host((n,)) if cnt is not None else None, idx.to_host((n, k)), gap.to_host((n, k), np.float32))
 
 
+def _csr_query(scope, n, count, fill, columns):
+    """The two passes of a CSR query of n rows -> (offsets (n + 1,) int64, one numpy array per column).  count(offsets pointer) runs the count
+    pass, fill(offsets pointer, total, a pointer or None per column) the fill pass -- not called when no row has an entry.  columns: (dtype,
+    width, want) per entry array, in fill's order and the result's: want True gives (total,) of dtype, (total, width) for width > 1; False
+    gives None in its place; None leaves it out of the result."""
+    off = scope.alloc(8 * (n + 1))
+    count(off.ptr)
+    offsets = off.to_host((n + 1,), np.int64)
+    total = int(offsets[n])
+    bufs = [scope.alloc(np.dtype(dtype).itemsize * width * total) if want else None for dtype, width, want in columns]
+    if total:
+        fill(off.ptr, total, *(b.ptr if b else None for b in bufs))
+    return (offsets,) + tuple(b.to_host((total,) if width == 1 else (total, width), dtype) if b else None
+                              for b, (dtype, width, want) in zip(bufs, columns) if want is not None)
+
+
+def _gap_columns(gaps, rows):
+    """The columns of the range, box and plane-set queries: index, gap (optional), and with `rows` the row number of every entry."""
+    return (np.int32, 1, True), (np.float32, 1, bool(gaps)), (np.int32, 1, True if rows else None)
+
+
 def spheres_within(prepared, points, max_dist, first=None, gaps=True, rows=False):
     """EVERY sphere within max_dist of every point (rt_spheres_within_count / _fill), with no cap, in CSR form -> (offsets (n + 1,) int64,
     index (total,) int32, gap (total,) float32 or None[, point (total,) int32]) numpy arrays.  The selection rule is nearest_spheres's: sphere
@@ -959,16 +980,10 @@ def spheres_within(prepared, points, max_dist, first=None, gaps=True, rows=False
         md_ptr = _device_bound(s, dev, n, "max_dist", max_dist, per="point") if ranged else None
         md = 0.0 if ranged else max_dist
         first_ptr = _device_first(s, dev, n, first) if first is not None else None
-        off = s.alloc(8 * (n + 1))
-        spheres_within_count_into(ptr, n, prepared, off.ptr, md, md_ptr, first_ptr)
-        offsets = off.to_host((n + 1,), np.int64)
-        total = int(offsets[n])
-        idx, gap, row = (s.alloc(4 * total) if want else None for want in (True, gaps, rows))
-        if total:
-            spheres_within_fill_into(ptr, n, prepared, off.ptr, total, idx.ptr, gap.ptr if gap else None, row.ptr if row else None, md,
-                                     md_ptr, first_ptr)
-        res = (offsets, idx.to_host((total,)), gap.to_host((total,), np.float32) if gap else None)
-        return res + (row.to_host((total,)),) if rows else res
+        return _csr_query(s, n, lambda off: spheres_within_count_into(ptr, n, prepared, off, md, md_ptr, first_ptr),
+                          lambda off, total, idx, gap, row: spheres_within_fill_into(ptr, n, prepared, off, total, idx, gap, row, md, md_ptr,
+                                                                                    first_ptr),
+                          _gap_columns(gaps, rows))
 
 
 def spheres_in_boxes(prepared, boxes, margin=0.0, first=None, gaps=True, rows=False):
@@ -988,16 +1003,10 @@ def spheres_in_boxes(prepared, boxes, margin=0.0, first=None, gaps=True, rows=Fa
         mg_ptr = _device_bound(s, dev, n, "margin", margin, per="box") if ranged else None
         mg = 0.0 if ranged else margin
         first_ptr = _device_first(s, dev, n, first, per="box") if first is not None else None
-        off = s.alloc(8 * (n + 1))
-        spheres_in_boxes_count_into(ptr, n, prepared, off.ptr, mg, mg_ptr, first_ptr)
-        offsets = off.to_host((n + 1,), np.int64)
-        total = int(offsets[n])
-        idx, gap, row = (s.alloc(4 * total) if want else None for want in (True, gaps, rows))
-        if total:
-            spheres_in_boxes_fill_into(ptr, n, prepared, off.ptr, total, idx.ptr, gap.ptr if gap else None, row.ptr if row else None, mg,
-                                       mg_ptr, first_ptr)
-        res = (offsets, idx.to_host((total,)), gap.to_host((total,), np.float32) if gap else None)
-        return res + (row.to_host((total,)),) if rows else res
+        return _csr_query(s, n, lambda off: spheres_in_boxes_count_into(ptr, n, prepared, off, mg, mg_ptr, first_ptr),
+                          lambda off, total, idx, gap, row: spheres_in_boxes_fill_into(ptr, n, prepared, off, total, idx, gap, row, mg, mg_ptr,
+                                                                                      first_ptr),
+                          _gap_columns(gaps, rows))
 
 
 _PLANES_SHAPE = "planes must be (n, K, 4) with 1 <= K <= 8: rows a, b, c, d"
@@ -1038,16 +1047,10 @@ def spheres_in_planes(prepared, planes, margin=0.0, first=None, gaps=True, rows=
         mg_ptr = _device_bound(s, dev, n, "margin", margin, per="query") if ranged else None
         mg = 0.0 if ranged else margin
         first_ptr = _device_first(s, dev, n, first, per="query") if first is not None else None
-        off = s.alloc(8 * (n + 1))
-        spheres_in_planes_count_into(ptr, n, k, prepared, off.ptr, mg, mg_ptr, first_ptr)
-        offsets = off.to_host((n + 1,), np.int64)
-        total = int(offsets[n])
-        idx, gap, row = (s.alloc(4 * total) if want else None for want in (True, gaps, rows))
-        if total:
-            spheres_in_planes_fill_into(ptr, n, k, prepared, off.ptr, total, idx.ptr, gap.ptr if gap else None, row.ptr if row else None, mg,
-                                        mg_ptr, first_ptr)
-        res = (offsets, idx.to_host((total,)), gap.to_host((total,), np.float32) if gap else None)
-        return res + (row.to_host((total,)),) if rows else res
+        return _csr_query(s, n, lambda off: spheres_in_planes_count_into(ptr, n, k, prepared, off, mg, mg_ptr, first_ptr),
+                          lambda off, total, idx, gap, row: spheres_in_planes_fill_into(ptr, n, k, prepared, off, total, idx, gap, row, mg,
+                                                                                       mg_ptr, first_ptr),
+                          _gap_columns(gaps, rows))
 
 
 def _unit(v):
@@ -1128,16 +1131,9 @@ def spheres_along_rays(prepared, rays, radius=0.0, t_min=0.0, t_max=1e9, exclude
             kw["t_min"], kw["t_max"] = t_min, t_max
         kw["exclude_ptr"] = _device_first(s, dev, n, exclude, name="exclude", per="query") if exclude is not None else None
         kw["first_ptr"] = _device_first(s, dev, n, first, per="query") if first is not None else None
-        off = s.alloc(8 * (n + 1))
-        spheres_along_rays_count_into(ptr, n, prepared, off.ptr, **kw)
-        offsets = off.to_host((n + 1,), np.int64)
-        total = int(offsets[n])
-        idx, rts, st, row = (s.alloc(size * total) if want else None for size, want in ((4, True), (8, roots), (1, True), (4, rows)))
-        if total:
-            spheres_along_rays_fill_into(ptr, n, prepared, off.ptr, total, idx.ptr, rts.ptr if rts else None, st.ptr, row.ptr if row else None,
-                                         **kw)
-        res = (offsets, idx.to_host((total,)), rts.to_host((total, 2), np.float32) if rts else None, st.to_host((total,), np.uint8))
-        return res + (row.to_host((total,)),) if rows else res
+        return _csr_query(s, n, lambda off: spheres_along_rays_count_into(ptr, n, prepared, off, **kw),
+                          lambda off, total, idx, rts, st, row: spheres_along_rays_fill_into(ptr, n, prepared, off, total, idx, rts, st, row, **kw),
+                          ((np.int32, 1, True), (np.float32, 2, bool(roots)), (np.uint8, 1, True), (np.int32, 1, True if rows else None)))
 
 
 def _row_bound(n, b):
@@ -1240,14 +1236,9 @@ def contact_pairs(prepared, margin=0.0, gaps=True):
     indices into L (Morton order): prepared.sphere_ids() maps them to the caller's order.  margin: a scalar in [0, 1e9]."""
     n = prepared.num_spheres
     with _Scope(prepared.ctx) as s:
-        off = s.alloc(8 * (n + 1))
-        contact_pairs_count_into(prepared, off.ptr, margin)
-        total = int(off.to_host((n + 1,), np.int64)[n])
-        pair = s.alloc(8 * total)
-        gap = s.alloc(4 * total) if gaps else None
-        if total:
-            contact_pairs_fill_into(prepared, off.ptr, total, pair.ptr, gap.ptr if gap else None, margin)
-        return pair.to_host((total, 2)), gap.to_host((total,), np.float32) if gap else None
+        return _csr_query(s, n, lambda off: contact_pairs_count_into(prepared, off, margin),
+                          lambda off, total, pair, gap: contact_pairs_fill_into(prepared, off, total, pair, gap, margin),
+                          ((np.int32, 2, True), (np.float32, 1, bool(gaps))))[1:]
 
 
 def contact_clusters(prepared, margin=0.0):

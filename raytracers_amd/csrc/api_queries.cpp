@@ -309,15 +309,20 @@ extern "C" int rt_trace_paths_shaped(rt_context *ctx, const rt_prepared *ps, int
                      last_ray6_dev, colour3_dev, rays_per_wave);
 }
 
-// The checks the point entries share, `what` being the entry's name in their messages (self: the points are the scene's own centres, *n
-// their number), and past them the parameter block of n points with exact_depth, the depth from which the walk tests boxes: the boxes
+// The refusals every entry of n points, boxes or queries (`noun`) opens with, `what` being the entry's name in their messages; the checks the
+// point entries share on top of them (self: the points are the scene's own centres, *n their number); and past the checks the parameter
+// block of n points with exact_depth, the depth from which the walk tests boxes: the boxes
 // that contain their subtrees are those of the nodes whose subtree is at most `sweeps` levels tall (the AABB propagation's
 // floor(log2 n) + 2 Jacobi sweeps from zero boxes, bvh.fut:44-58), which every node at depth >= height - sweeps is.
-static int point_entry_checks(rt_context *ctx, const rt_prepared *ps, const char *what, bool self, int64_t *n, const float *points3_dev) {
+static int query_entry_checks(rt_context *ctx, const rt_prepared *ps, const char *what, const char *noun, int64_t n) {
   if (!ps) return fail(ctx, "null prepared scene");
   if (ctx->group) return fail_in(ctx, what, ": a multi-device context is not supported (use a context on one device)");
-  if (self) *n = ps->n;
-  if (*n < 0 || *n >= (int64_t(1) << 31)) return fail_in(ctx, what, ": point count out of range: 0 <= n < 2^31");
+  if (n < 0 || n >= (int64_t(1) << 31)) return fail(ctx, std::string(what) + ": " + noun + " count out of range: 0 <= n < 2^31");
+  return 0;
+}
+static int point_entry_checks(rt_context *ctx, const rt_prepared *ps, const char *what, bool self, int64_t *n, const float *points3_dev) {
+  if (self && ps) *n = ps->n;
+  if (int rc = query_entry_checks(ctx, ps, what, "point", *n)) return rc;
   if (!self && !points3_dev) return fail_in(ctx, what, ": null points pointer");
   return 0;
 }
@@ -382,34 +387,51 @@ static int query_scratch(rt_context *ctx, size_t want, char **out) {
   *out = ctx->within_scratch;
   return 0;
 }
-static int within_scratch(rt_context *ctx, int64_t n, char **out) { return query_scratch(ctx, rtk::within_scratch_bytes(n), out); }
-static int within_entry(rt_context *ctx, const rt_prepared *ps, const char *what, bool fill, bool self, int64_t n, const float *points3_dev,
-                        float max_dist, const float *max_dist_dev, const int32_t *first_dev, int64_t *offsets_dev, int64_t capacity,
-                        int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
-  if (int rc = point_entry_checks(ctx, ps, what, self, &n, points3_dev)) return rc;
+// The CSR entries (count and fill pass of the range, box, plane-set and along-ray queries) share the refusals of a pass ...
+static int csr_pass_checks(rt_context *ctx, const char *what, bool fill, const int64_t *offsets_dev, int64_t capacity, bool outputs) {
   if (!offsets_dev) return fail_in(ctx, what, ": null offsets pointer");
   if (fill && capacity < 0) return fail_in(ctx, what, ": negative capacity");
-  if (fill && !index_dev && !gap_dev && !point_dev) return fail_in(ctx, what, ": every output is NULL");
-  if ((self || !max_dist_dev) && !distance_ok(max_dist))
-    return fail_in(ctx, what, self ? ": need 0 <= margin <= 1e9, finite" : ": need 0 <= max_dist <= 1e9, finite");
+  if (fill && !outputs) return fail_in(ctx, what, ": every output is NULL");
+  return 0;
+}
+// ... and what lies between an entry's argument checks and its name in rt_context_last_launch: the prepared scene's lock, the
+// context's device, the thread's last error cleared, the parameter block of n queries with exact_depth (point_params), and for a count pass
+// of n > 0 queries the cached scratch.  count(p, exact_depth, scratch) / fill(p, exact_depth) enqueue and return the entry's code;
+// rt_context_last_launch is `family`, the pass and `detail`.  The caller holds the context lock.
+template <class Count, class Fill>
+static int csr_entry(rt_context *ctx, const rt_prepared *ps, bool is_fill, int64_t n, const char *family, const std::string &detail, Count &&count,
+                     Fill &&fill) {
   RT_LOCK_PS(ps);
   RT_HIP(ctx, hipSetDevice(ctx->device));
   (void)hipGetLastError();
   int exact_depth;
-  const rtk::KParams p = point_params(ps, n, &exact_depth);
-  if (fill) {
-    ctx->synced_since_render = false;
-    RT_HIP(ctx, rtk::launch_within_fill(p, points3_dev, max_dist_dev, max_dist, first_dev, self, exact_depth, offsets_dev, capacity, index_dev,
-                                        gap_dev, point_dev, ctx->stream));
-  } else {
-    char *scratch = nullptr;
-    if (n > 0 && within_scratch(ctx, n, &scratch) != 0) return 1;
-    ctx->synced_since_render = false;
-    RT_HIP(ctx, rtk::launch_within_count(p, points3_dev, max_dist_dev, max_dist, first_dev, self, exact_depth, scratch, offsets_dev, ctx->stream));
-  }
-  ctx->last_launch = std::string(fill ? "family=within fill" : "family=within count") + (!self && max_dist_dev ? " (per-point)" : "") +
-                     (!self && first_dev ? " first" : "") + (self ? " self" : "");
+  rtk::KParams p = point_params(ps, n, &exact_depth);
+  char *scratch = nullptr;
+  if (!is_fill && n > 0 && query_scratch(ctx, rtk::within_scratch_bytes(n), &scratch) != 0) return 1;
+  ctx->synced_since_render = false;
+  if (int rc = is_fill ? fill(p, exact_depth) : count(p, exact_depth, scratch)) return rc;
+  ctx->last_launch = std::string("family=") + family + (is_fill ? " fill" : " count") + detail;
   return 0;
+}
+static int within_entry(rt_context *ctx, const rt_prepared *ps, const char *what, bool fill, bool self, int64_t n, const float *points3_dev,
+                        float max_dist, const float *max_dist_dev, const int32_t *first_dev, int64_t *offsets_dev, int64_t capacity,
+                        int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
+  if (int rc = point_entry_checks(ctx, ps, what, self, &n, points3_dev)) return rc;
+  if (int rc = csr_pass_checks(ctx, what, fill, offsets_dev, capacity, index_dev || gap_dev || point_dev)) return rc;
+  if ((self || !max_dist_dev) && !distance_ok(max_dist))
+    return fail_in(ctx, what, self ? ": need 0 <= margin <= 1e9, finite" : ": need 0 <= max_dist <= 1e9, finite");
+  const std::string detail = std::string(!self && max_dist_dev ? " (per-point)" : "") + (!self && first_dev ? " first" : "") + (self ? " self" : "");
+  return csr_entry(
+      ctx, ps, fill, n, "within", detail,
+      [&](const rtk::KParams &p, int exact_depth, char *scratch) {
+        RT_HIP(ctx, rtk::launch_within_count(p, points3_dev, max_dist_dev, max_dist, first_dev, self, exact_depth, scratch, offsets_dev, ctx->stream));
+        return 0;
+      },
+      [&](const rtk::KParams &p, int exact_depth) {
+        RT_HIP(ctx, rtk::launch_within_fill(p, points3_dev, max_dist_dev, max_dist, first_dev, self, exact_depth, offsets_dev, capacity, index_dev,
+                                            gap_dev, point_dev, ctx->stream));
+        return 0;
+      });
 }
 
 extern "C" int rt_spheres_within_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
@@ -473,31 +495,21 @@ extern "C" int rt_contact_clusters(rt_context *ctx, const rt_prepared *ps, float
 static int boxes_entry(rt_context *ctx, const rt_prepared *ps, const char *what, bool fill, int64_t n, const float *boxes6_dev, float margin,
                        const float *margin_dev, const int32_t *first_dev, int64_t *offsets_dev, int64_t capacity, int32_t *index_dev,
                        float *gap_dev, int32_t *point_dev) {
-  if (!ps) return fail(ctx, "null prepared scene");
-  if (ctx->group) return fail_in(ctx, what, ": a multi-device context is not supported (use a context on one device)");
-  if (n < 0 || n >= (int64_t(1) << 31)) return fail_in(ctx, what, ": box count out of range: 0 <= n < 2^31");
+  if (int rc = query_entry_checks(ctx, ps, what, "box", n)) return rc;
   if (!boxes6_dev) return fail_in(ctx, what, ": null boxes pointer");
-  if (!offsets_dev) return fail_in(ctx, what, ": null offsets pointer");
-  if (fill && capacity < 0) return fail_in(ctx, what, ": negative capacity");
-  if (fill && !index_dev && !gap_dev && !point_dev) return fail_in(ctx, what, ": every output is NULL");
+  if (int rc = csr_pass_checks(ctx, what, fill, offsets_dev, capacity, index_dev || gap_dev || point_dev)) return rc;
   if (!margin_dev && !distance_ok(margin)) return fail_in(ctx, what, ": need 0 <= margin <= 1e9, finite");
-  RT_LOCK_PS(ps);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  int exact_depth;
-  const rtk::KParams p = point_params(ps, n, &exact_depth);
-  if (fill) {
-    ctx->synced_since_render = false;
-    RT_HIP(ctx, rtk::launch_boxes_fill(p, boxes6_dev, margin_dev, margin, first_dev, exact_depth, offsets_dev, capacity, index_dev, gap_dev, point_dev,
-                                       ctx->stream));
-  } else {
-    char *scratch = nullptr;
-    if (n > 0 && within_scratch(ctx, n, &scratch) != 0) return 1;
-    ctx->synced_since_render = false;
-    RT_HIP(ctx, rtk::launch_boxes_count(p, boxes6_dev, margin_dev, margin, first_dev, exact_depth, scratch, offsets_dev, ctx->stream));
-  }
-  ctx->last_launch = std::string(fill ? "family=boxes fill" : "family=boxes count") + (margin_dev ? " (per-box)" : "") + (first_dev ? " first" : "");
-  return 0;
+  return csr_entry(
+      ctx, ps, fill, n, "boxes", std::string(margin_dev ? " (per-box)" : "") + (first_dev ? " first" : ""),
+      [&](const rtk::KParams &p, int exact_depth, char *scratch) {
+        RT_HIP(ctx, rtk::launch_boxes_count(p, boxes6_dev, margin_dev, margin, first_dev, exact_depth, scratch, offsets_dev, ctx->stream));
+        return 0;
+      },
+      [&](const rtk::KParams &p, int exact_depth) {
+        RT_HIP(ctx, rtk::launch_boxes_fill(p, boxes6_dev, margin_dev, margin, first_dev, exact_depth, offsets_dev, capacity, index_dev, gap_dev,
+                                           point_dev, ctx->stream));
+        return 0;
+      });
 }
 
 extern "C" int rt_spheres_in_boxes_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *boxes6_dev, float margin,
@@ -522,33 +534,22 @@ extern "C" int rt_spheres_in_boxes_fill(rt_context *ctx, const rt_prepared *ps, 
 static int planes_entry(rt_context *ctx, const rt_prepared *ps, const char *what, bool fill, int64_t n, const float *planes4_dev, int32_t nplanes,
                         float margin, const float *margin_dev, const int32_t *first_dev, int64_t *offsets_dev, int64_t capacity,
                         int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
-  if (!ps) return fail(ctx, "null prepared scene");
-  if (ctx->group) return fail_in(ctx, what, ": a multi-device context is not supported (use a context on one device)");
-  if (n < 0 || n >= (int64_t(1) << 31)) return fail_in(ctx, what, ": query count out of range: 0 <= n < 2^31");
+  if (int rc = query_entry_checks(ctx, ps, what, "query", n)) return rc;
   if (nplanes < 1 || nplanes > rtk::kMaxPlanes) return fail_in(ctx, what, ": plane count out of range: 1 <= nplanes <= 8");
   if (!planes4_dev) return fail_in(ctx, what, ": null planes pointer");
-  if (!offsets_dev) return fail_in(ctx, what, ": null offsets pointer");
-  if (fill && capacity < 0) return fail_in(ctx, what, ": negative capacity");
-  if (fill && !index_dev && !gap_dev && !point_dev) return fail_in(ctx, what, ": every output is NULL");
+  if (int rc = csr_pass_checks(ctx, what, fill, offsets_dev, capacity, index_dev || gap_dev || point_dev)) return rc;
   if (!margin_dev && !distance_ok(margin)) return fail_in(ctx, what, ": need 0 <= margin <= 1e9, finite");
-  RT_LOCK_PS(ps);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  int exact_depth;
-  const rtk::KParams p = point_params(ps, n, &exact_depth);
-  if (fill) {
-    ctx->synced_since_render = false;
-    RT_HIP(ctx, rtk::launch_planes_fill(p, planes4_dev, nplanes, margin_dev, margin, first_dev, exact_depth, offsets_dev, capacity, index_dev, gap_dev,
-                                        point_dev, ctx->stream));
-  } else {
-    char *scratch = nullptr;
-    if (n > 0 && within_scratch(ctx, n, &scratch) != 0) return 1;
-    ctx->synced_since_render = false;
-    RT_HIP(ctx, rtk::launch_planes_count(p, planes4_dev, nplanes, margin_dev, margin, first_dev, exact_depth, scratch, offsets_dev, ctx->stream));
-  }
-  ctx->last_launch = std::string(fill ? "family=planes fill k=" : "family=planes count k=") + std::to_string(nplanes) +
-                     (margin_dev ? " (per-query)" : "") + (first_dev ? " first" : "");
-  return 0;
+  return csr_entry(
+      ctx, ps, fill, n, "planes", " k=" + std::to_string(nplanes) + (margin_dev ? " (per-query)" : "") + (first_dev ? " first" : ""),
+      [&](const rtk::KParams &p, int exact_depth, char *scratch) {
+        RT_HIP(ctx, rtk::launch_planes_count(p, planes4_dev, nplanes, margin_dev, margin, first_dev, exact_depth, scratch, offsets_dev, ctx->stream));
+        return 0;
+      },
+      [&](const rtk::KParams &p, int exact_depth) {
+        RT_HIP(ctx, rtk::launch_planes_fill(p, planes4_dev, nplanes, margin_dev, margin, first_dev, exact_depth, offsets_dev, capacity, index_dev,
+                                            gap_dev, point_dev, ctx->stream));
+        return 0;
+      });
 }
 
 extern "C" int rt_spheres_in_planes_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *planes4_dev, int32_t nplanes, float margin,
@@ -574,37 +575,28 @@ static int along_entry(rt_context *ctx, const rt_prepared *ps, const char *what,
                        const float *radius_dev, float t_min, float t_max, const float *t_min_dev, const float *t_max_dev,
                        const int32_t *exclude_dev, const int32_t *first_dev, int64_t *offsets_dev, int64_t capacity, int32_t *index_dev,
                        float *roots_dev, uint8_t *start_dev, int32_t *query_dev) {
-  if (!ps) return fail(ctx, "null prepared scene");
-  if (ctx->group) return fail_in(ctx, what, ": a multi-device context is not supported (use a context on one device)");
-  if (n < 0 || n >= (int64_t(1) << 31)) return fail_in(ctx, what, ": query count out of range: 0 <= n < 2^31");
+  if (int rc = query_entry_checks(ctx, ps, what, "query", n)) return rc;
   if (!rays_dev) return fail_in(ctx, what, ": null rays pointer");
-  if (!offsets_dev) return fail_in(ctx, what, ": null offsets pointer");
-  if (fill && capacity < 0) return fail_in(ctx, what, ": negative capacity");
-  if (fill && !index_dev && !roots_dev && !start_dev && !query_dev) return fail_in(ctx, what, ": every output is NULL");
+  if (int rc = csr_pass_checks(ctx, what, fill, offsets_dev, capacity, index_dev || roots_dev || start_dev || query_dev)) return rc;
   if ((t_min_dev == nullptr) != (t_max_dev == nullptr)) return fail_in(ctx, what, ": t_min_dev and t_max_dev must both be NULL or both be given");
   if (!t_min_dev && !ray_interval_ok(t_min, t_max)) return fail_in(ctx, what, ": need 0 <= t_min <= t_max <= 1e9, both finite");
   if (!radius_dev && !distance_ok(radius)) return fail_in(ctx, what, ": need 0 <= radius <= 1e9, finite");
-  RT_LOCK_PS(ps);
-  RT_HIP(ctx, hipSetDevice(ctx->device));
-  (void)hipGetLastError();
-  rtk::KParams p{};
-  rti::scene_params(ps, &p);
-  p.rays = rays_dev;
-  p.nrays = static_cast<int>(n);
-  if (fill) {
-    ctx->synced_since_render = false;
-    RT_HIP(ctx, rtk::launch_along_fill(p, radius_dev, radius, t_min_dev, t_max_dev, t_min, t_max, exclude_dev, first_dev, offsets_dev, capacity,
-                                       index_dev, roots_dev, start_dev, query_dev, ctx->stream));
-  } else {
-    char *scratch = nullptr;
-    if (n > 0 && within_scratch(ctx, n, &scratch) != 0) return 1;
-    ctx->synced_since_render = false;
-    RT_HIP(ctx, rtk::launch_along_count(p, radius_dev, radius, t_min_dev, t_max_dev, t_min, t_max, exclude_dev, first_dev, scratch, offsets_dev,
-                                        ctx->stream));
-  }
-  ctx->last_launch = std::string(fill ? "family=along fill" : "family=along count") + (radius_dev || t_min_dev ? " (per-query)" : "") +
-                     (exclude_dev ? " exclude" : "") + (first_dev ? " first" : "");
-  return 0;
+  const std::string detail = std::string(radius_dev || t_min_dev ? " (per-query)" : "") + (exclude_dev ? " exclude" : "") + (first_dev ? " first" : "");
+  // (the walk of the along-ray queries tests every node: exact_depth is not used)
+  return csr_entry(
+      ctx, ps, fill, n, "along", detail,
+      [&](rtk::KParams &p, int, char *scratch) {
+        p.rays = rays_dev;
+        RT_HIP(ctx, rtk::launch_along_count(p, radius_dev, radius, t_min_dev, t_max_dev, t_min, t_max, exclude_dev, first_dev, scratch, offsets_dev,
+                                            ctx->stream));
+        return 0;
+      },
+      [&](rtk::KParams &p, int) {
+        p.rays = rays_dev;
+        RT_HIP(ctx, rtk::launch_along_fill(p, radius_dev, radius, t_min_dev, t_max_dev, t_min, t_max, exclude_dev, first_dev, offsets_dev, capacity,
+                                           index_dev, roots_dev, start_dev, query_dev, ctx->stream));
+        return 0;
+      });
 }
 
 extern "C" int rt_spheres_along_rays_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float radius,
@@ -632,9 +624,7 @@ extern "C" int rt_spheres_along_rays_fill(rt_context *ctx, const rt_prepared *ps
 static int pairs_entry(rt_context *ctx, const rt_prepared *ps, const char *what, int64_t n, const float *points3_dev, int64_t m,
                        const float *targets3_dev, int32_t mode, float t_min, float t_max, uint64_t *visible_dev, int32_t *count_dev,
                        int32_t words_per_wave) {
-  if (!ps) return fail(ctx, "null prepared scene");
-  if (ctx->group) return fail_in(ctx, what, ": a multi-device context is not supported (use a context on one device)");
-  if (n < 0 || n >= (int64_t(1) << 31)) return fail_in(ctx, what, ": point count out of range: 0 <= n < 2^31");
+  if (int rc = query_entry_checks(ctx, ps, what, "point", n)) return rc;
   if (m < 1 || m > rtk::kPairsMaxTargets) return fail_in(ctx, what, ": target count out of range: 1 <= m <= 2^24");
   const int64_t words = (m + 63) / 64;
   if (n * words >= (int64_t(1) << 31)) return fail_in(ctx, what, ": too many words: need n * ((m + 63) / 64) < 2^31");

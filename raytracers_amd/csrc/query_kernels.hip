@@ -498,33 +498,106 @@ hipError_t launch_nearest_spheres(const KParams &p, const float *pts, const floa
                 : launch_nearest_cap<false, false>(p, pts, nullptr, max_dist, k, exact_depth, count, index, gap, stream);
 }
 
-// rt_spheres_within_* / rt_contact_pairs_*: EVERY sphere with gap <= the point's bound, in CSR form.  One lane per point,
-// nearest_lane's count-mode walk (the same stack, loads and box_may_hold with T = the point's bound, the untested descent through the partial
-// boxes above exact_depth) without a key list: a row has no length limit.  Rows come out in ASCENDING j with no sort: the leaves below a node
-// are a contiguous run of L and the left child holds the lower part, so a depth-first walk that takes the left child first meets the leaves in
-// ascending j.  The children are therefore pushed right then left, and a right child that is a leaf waits on the stack behind an inner left
-// sibling (a stack entry with depth field 63 is a leaf; a node's depth is capped at 62, above any exact_depth: height <= 63 and at least 3
-// sweeps).  The count pass (FILL false) and the fill pass evaluate the same predicate, so they select the same set; the fill pass writes
-// entry offsets[i] + rank, and only below offsets[i + 1] and below `capacity` -- offsets from another query can misplace entries, never put
-// one outside the caller's arrays.  `first`: sphere j is selected only if j >= first[i], a compare at the leaf (no subtree is pruned by it).
-// SELF (contact pairs): point i is the centre of L[i], its bound fl(radius_i + max_dist), first = i + 1; `point` then is the pair array,
-// rows {i, j}.
+// The CSR queries -- rt_spheres_within_* / rt_contact_pairs_*, rt_spheres_in_boxes_*, rt_spheres_in_planes_*, rt_spheres_along_rays_* -- and the
+// contact clusters' hook share ONE walk and ONE row protocol; this is their contract (i, j, k, m).
+// The walk (OrderedWalk), one lane per query, EVERY selected sphere, no key list: a row has no length limit.
+//  * Order.  Rows come out in ASCENDING j with no sort: the leaves below a node are a contiguous run of L and the left child holds the lower
+//    part, so a depth-first walk that takes the left child first meets the leaves in ascending j.  The children are therefore pushed right
+//    then left, and a right child that is a leaf waits on the stack behind an inner left sibling.
+//  * Stack entries.  The node (< 2^26) and its depth in bits 26..31.  Depth field 63 is the leaf tag: the entry is a sphere index; a node's
+//    depth is capped at 62, above any exact_depth (height <= 63 and at least 3 sweeps).
+//  * Depth.  With DEPTH a node's box is tested only at depth >= exact_depth: above it the reference's AABB propagation leaves boxes that need
+//    not contain their subtrees (nearest_lane), and the walk descends through them untested.  Without DEPTH (the along-ray queries: the
+//    answer is the tree's, as the sweep's) every popped node is tested, the root included, and every node entry carries depth 0.
+//  * Stack bound.  One pending sibling per level: sp <= height + 1 <= kStackPixel.
+//  * Leaves.  Sphere j is offered to the leaf action only if j >= first (first >= 0, so the empty leaf slot, -1, never passes); no subtree is
+//    pruned by `first`.  The action loads the sphere itself, through the walk's descriptor, behind whatever test of j is its own.
+// The row (CsrRow<FILL>).  The count pass (FILL false) and the fill pass evaluate ONE predicate in one order, so they select the same set.
+// The count pass counts; the fill pass writes entry offsets[i] + rank, only below offsets[i + 1] and below `capacity`, and nothing for a
+// negative offsets[i]: offsets from another query can misplace entries, never put one outside the caller's arrays.
 constexpr int kWithinLeaf = 63, kWithinMaxDepth = 62;
 __device__ __forceinline__ int within_node_entry(int node, int depth) {
   return (int)((unsigned)node | ((unsigned)(depth < kWithinMaxDepth ? depth : kWithinMaxDepth) << 26));
 }
 __device__ __forceinline__ int within_leaf_entry(int j) { return (int)((unsigned)j | ((unsigned)kWithinLeaf << 26)); }
 
+struct OrderedWalk {
+  const __amdgpu_buffer_rsrc_t rs_nodes, rs_sph;
+  __device__ __forceinline__ explicit OrderedWalk(const KParams &p)
+      : rs_nodes(make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u)), rs_sph(make_rsrc(p.sph, (unsigned)p.n_sph * 16u)) {}
+  __device__ __forceinline__ float4 sphere(int j) const { return buf_load16(rs_sph, j * 16); }
+  // node_test(lo, hi): may the node's box hold a selected sphere; leaf(j): the action on sphere j >= first
+  template <bool DEPTH, class NodeTest, class Leaf>
+  __device__ __forceinline__ void run(bool valid, int first, int exact_depth, NodeTest &&node_test, Leaf &&leaf) const {
+    __shared__ int stack[kStackPixel][64];
+    const int lane = threadIdx.x;
+    int sp = 0;
+    if (valid) stack[sp++][lane] = within_node_entry(0, 0);
+    while (sp > 0) {
+      const unsigned e = (unsigned)stack[--sp][lane];
+      const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
+      int slot[2] = {-1, -1};
+      if (depth == kWithinLeaf) {
+        slot[0] = ni;
+      } else {
+        const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
+        if ((!DEPTH || depth >= exact_depth) && !node_test(lo, hi)) continue;
+        const int l = f2i(lo.w), r = f2i(hi.w);
+        if (l < 0) {
+          slot[0] = ~l;
+          if (r < 0) slot[1] = ~r;
+          else stack[sp++][lane] = within_node_entry(r, DEPTH ? depth + 1 : 0);
+        } else {
+          stack[sp++][lane] = r < 0 ? within_leaf_entry(~r) : within_node_entry(r, DEPTH ? depth + 1 : 0);
+          stack[sp++][lane] = within_node_entry(l, DEPTH ? depth + 1 : 0);
+        }
+      }
+#pragma unroll
+      for (int c2 = 0; c2 < 2; ++c2)
+        if (slot[c2] >= first) leaf(slot[c2]);
+    }
+  }
+};
+
+// Row i of a CSR query: its length in the count pass, its write cursor in the fill pass (the contract above).
+template <bool FILL>
+struct CsrRow {
+  int cnt = 0;
+  int64_t at = 0, end = 0;
+  __device__ __forceinline__ CsrRow(int i, const int64_t *offsets, int64_t capacity) {
+    if constexpr (FILL) {
+      at = offsets[i];
+      end = offsets[i + 1] < capacity ? offsets[i + 1] : capacity;
+      if (at < 0) at = end;   // (offsets that are not a scan of counts: nothing is written)
+    }
+  }
+  // one offered sphere, selected or not: emit(at) writes a selected one's entry
+  template <class Emit>
+  __device__ __forceinline__ void take(bool selected, Emit &&emit) {
+    if constexpr (FILL) {
+      if (selected) {
+        if (at < end) emit(at);
+        ++at;
+      }
+    } else {
+      cnt += selected ? 1 : 0;
+    }
+  }
+  __device__ __forceinline__ void finish(int i, int32_t *count) const {
+    if constexpr (!FILL) count[i] = cnt;
+  }
+};
+
+// rt_spheres_within_* / rt_contact_pairs_* (DESIGN.md 3.5f): the node test is nearest_lane's box_may_hold with T = the point's bound, the leaf
+// rule gap <= that bound.  SELF (contact pairs): point i is the centre of L[i], its bound fl(radius_i + max_dist), first = i + 1; `point` then
+// is the pair array, rows {i, j}.
 template <bool FILL, bool SELF>
 __device__ __forceinline__ void within_lane(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev,
                                             int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap,
                                             int32_t *point) {
-  __shared__ int stack[kStackPixel][64];
-  const int lane = threadIdx.x;
-  const int i = blockIdx.x * 64 + lane;
+  const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= p.nrays) return;
-  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
-  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const OrderedWalk walk(p);
   float px, py, pz;
   int first = 0;
   bool valid;
@@ -541,61 +614,24 @@ __device__ __forceinline__ void within_lane(const KParams &p, const float *pts, 
     valid = point_ok(px, py, pz) && max_dist_ok(max_dist);
   }
   const float pmag = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
-  int cnt = 0;
-  int64_t at = 0, end = 0;
-  if constexpr (FILL) {
-    at = offsets[i];
-    end = offsets[i + 1] < capacity ? offsets[i + 1] : capacity;
-    if (at < 0) at = end;   // (offsets that are not a scan of counts: nothing is written)
-  }
-  int sp = 0;
-  if (valid) stack[sp++][lane] = within_node_entry(0, 0);
-  while (sp > 0) {
-    const unsigned e = (unsigned)stack[--sp][lane];
-    const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
-    int leaf[2] = {-1, -1};
-    if (depth == kWithinLeaf) {
-      leaf[0] = ni;
-    } else {
-      const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
-      if (depth >= exact_depth && !box_may_hold(px, py, pz, pmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, max_dist)) continue;
-      const int l = f2i(lo.w), r = f2i(hi.w);
-      // (one pending sibling per level: sp <= height + 1 <= kStackPixel)
-      if (l < 0) {
-        leaf[0] = ~l;
-        if (r < 0) leaf[1] = ~r;
-        else stack[sp++][lane] = within_node_entry(r, depth + 1);
-      } else {
-        stack[sp++][lane] = r < 0 ? within_leaf_entry(~r) : within_node_entry(r, depth + 1);
-        stack[sp++][lane] = within_node_entry(l, depth + 1);
-      }
-    }
-#pragma unroll
-    for (int c2 = 0; c2 < 2; ++c2) {
-      const int j = leaf[c2];
-      if (j >= first) {   // (first >= 0: an empty leaf slot, -1, never passes)
-        const float4 s = buf_load16(rs_sph, j * 16);
+  CsrRow<FILL> row(i, offsets, capacity);
+  walk.run<true>(
+      valid, first, exact_depth,
+      [&](const float4 &lo, const float4 &hi) { return box_may_hold(px, py, pz, pmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, max_dist); },
+      [&](int j) {
+        const float4 s = walk.sphere(j);
         const float g = point_gap(px, py, pz, s.x, s.y, s.z, s.w);
-        if (g <= max_dist) {
-          if constexpr (FILL) {
-            if (at < end) {
-              if constexpr (SELF) {
-                if (point != nullptr) *reinterpret_cast<int2 *>(point + 2 * at) = make_int2(i, j);
-              } else {
-                if (index != nullptr) index[at] = j;
-                if (point != nullptr) point[at] = i;
-              }
-              if (gap != nullptr) gap[at] = g;
+        row.take(g <= max_dist, [&](int64_t at) {
+            if constexpr (SELF) {
+              if (point != nullptr) *reinterpret_cast<int2 *>(point + 2 * at) = make_int2(i, j);
+            } else {
+              if (index != nullptr) index[at] = j;
+              if (point != nullptr) point[at] = i;
             }
-            ++at;
-          } else {
-            ++cnt;
-          }
-        }
-      }
-    }
-  }
-  if constexpr (!FILL) count[i] = cnt;
+            if (gap != nullptr) gap[at] = g;
+          });
+      });
+  row.finish(i, count);
 }
 template <bool FILL, bool SELF>
 __global__ __launch_bounds__(64) void within_kernel(KParams p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev,
@@ -677,52 +713,71 @@ __global__ __launch_bounds__(kWithinScanThreads) void within_scan_apply_kernel(c
   }
 }
 
-size_t within_scratch_bytes(int64_t n) {
-  const size_t nblocks = ((size_t)n + kWithinScanItems - 1) / kWithinScanItems;
-  return (((size_t)n * 4 + 255) & ~(size_t)255) + nblocks * 8;
-}
-
-hipError_t launch_within_count(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
-                               int exact_depth, char *scratch, int64_t *offsets, hipStream_t stream) {
-  if (offsets == nullptr) return hipErrorInvalidValue;
-  if (p.nrays <= 0) return hipMemsetAsync(offsets, 0, sizeof(int64_t), stream);
-  if ((!self && pts == nullptr) || scratch == nullptr || p.n_nodes < 1) return hipErrorInvalidValue;
-  if (self && p.nrays != p.n_sph) return hipErrorInvalidValue;
-  if ((self || max_dist_dev == nullptr) && !max_dist_ok(max_dist)) return hipErrorInvalidValue;
-  max_dist += 0.0f;   // (-0.0 -> +0.0)
-  const int n = p.nrays;
-  int32_t *const counts = reinterpret_cast<int32_t *>(scratch);
-  long long *const sums = reinterpret_cast<long long *>(scratch + (((size_t)n * 4 + 255) & ~(size_t)255));
-  const dim3 grid(((unsigned)n + 63u) / 64u), block(64);
-  if (self)
-    hipLaunchKernelGGL((within_kernel<false, true>), grid, block, 0, stream, p, nullptr, nullptr, max_dist, nullptr, exact_depth, counts, nullptr,
-                       (int64_t)0, nullptr, nullptr, nullptr);
-  else
-    hipLaunchKernelGGL((within_kernel<false, false>), grid, block, 0, stream, p, pts, max_dist_dev, max_dist, first_dev, exact_depth, counts, nullptr,
-                       (int64_t)0, nullptr, nullptr, nullptr);
-  const int nblocks = (int)(((int64_t)n + kWithinScanItems - 1) / kWithinScanItems);
+// A count pass's scratch: the n int32 counts, padded to 256 bytes, then the scan's block sums.
+static int scan_blocks(int64_t n) { return (int)((n + kWithinScanItems - 1) / kWithinScanItems); }
+static size_t scan_sums_at(int64_t n) { return ((size_t)n * 4 + 255) & ~(size_t)255; }
+size_t within_scratch_bytes(int64_t n) { return scan_sums_at(n) + (size_t)scan_blocks(n) * 8; }
+// ... and the scan over it: the n counts at the start of `scratch` -> offsets[0 .. n]
+static hipError_t launch_count_scan(char *scratch, int n, int64_t *offsets, hipStream_t stream) {
+  const int32_t *const counts = reinterpret_cast<const int32_t *>(scratch);
+  long long *const sums = reinterpret_cast<long long *>(scratch + scan_sums_at(n));
+  const int nblocks = scan_blocks(n);
   hipLaunchKernelGGL(within_scan_sums_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums);
   hipLaunchKernelGGL(within_scan_carry_kernel, dim3(1), dim3(kWithinScanThreads), 0, stream, sums, nblocks);
   hipLaunchKernelGGL(within_scan_apply_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums, offsets);
   return hipGetLastError();
 }
 
+// What every CSR launcher answers before its family's own argument rules; true: *rc is the launcher's answer.  The count pass (fill false)
+// refuses null offsets, answers no queries with offsets[0] = 0, and needs its scratch; the fill pass answers no queries with success and
+// refuses null offsets, a negative capacity and `outputs` false (every output null).  Both need a tree.
+static bool csr_answered(const KParams &p, bool fill, const int64_t *offsets, const char *scratch, int64_t capacity, bool outputs,
+                         hipStream_t stream, hipError_t *rc) {
+  *rc = hipErrorInvalidValue;
+  if (!fill && offsets == nullptr) return true;
+  if (p.nrays <= 0) {
+    *rc = fill ? hipSuccess : hipMemsetAsync(const_cast<int64_t *>(offsets), 0, sizeof(int64_t), stream);   // (the count pass's own output)
+    return true;
+  }
+  if (fill ? (offsets == nullptr || capacity < 0 || !outputs) : scratch == nullptr) return true;
+  return p.n_nodes < 1;
+}
+static dim3 lane_grid(int n) { return dim3(((unsigned)n + 63u) / 64u); }
+
+static bool within_args_ok(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, bool self) {
+  if (self ? p.nrays != p.n_sph : pts == nullptr) return false;
+  return (!self && max_dist_dev != nullptr) || max_dist_ok(max_dist);
+}
+
+hipError_t launch_within_count(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
+                               int exact_depth, char *scratch, int64_t *offsets, hipStream_t stream) {
+  hipError_t rc;
+  if (csr_answered(p, false, offsets, scratch, 0, true, stream, &rc)) return rc;
+  if (!within_args_ok(p, pts, max_dist_dev, max_dist, self)) return hipErrorInvalidValue;
+  max_dist += 0.0f;   // (-0.0 -> +0.0)
+  int32_t *const counts = reinterpret_cast<int32_t *>(scratch);
+  if (self)
+    hipLaunchKernelGGL((within_kernel<false, true>), lane_grid(p.nrays), dim3(64), 0, stream, p, nullptr, nullptr, max_dist, nullptr, exact_depth,
+                       counts, nullptr, (int64_t)0, nullptr, nullptr, nullptr);
+  else
+    hipLaunchKernelGGL((within_kernel<false, false>), lane_grid(p.nrays), dim3(64), 0, stream, p, pts, max_dist_dev, max_dist, first_dev,
+                       exact_depth, counts, nullptr, (int64_t)0, nullptr, nullptr, nullptr);
+  return launch_count_scan(scratch, p.nrays, offsets, stream);
+}
+
 hipError_t launch_within_fill(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev, bool self,
                               int exact_depth, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point,
                               hipStream_t stream) {
-  if (p.nrays <= 0) return hipSuccess;
-  if ((!self && pts == nullptr) || offsets == nullptr || capacity < 0 || p.n_nodes < 1) return hipErrorInvalidValue;
-  if (self && (p.nrays != p.n_sph || index != nullptr)) return hipErrorInvalidValue;
-  if (index == nullptr && gap == nullptr && point == nullptr) return hipErrorInvalidValue;
-  if ((self || max_dist_dev == nullptr) && !max_dist_ok(max_dist)) return hipErrorInvalidValue;
+  hipError_t rc;
+  if (csr_answered(p, true, offsets, nullptr, capacity, index != nullptr || gap != nullptr || point != nullptr, stream, &rc)) return rc;
+  if (!within_args_ok(p, pts, max_dist_dev, max_dist, self) || (self && index != nullptr)) return hipErrorInvalidValue;
   max_dist += 0.0f;   // (-0.0 -> +0.0)
-  const dim3 grid(((unsigned)p.nrays + 63u) / 64u), block(64);
   if (self)
-    hipLaunchKernelGGL((within_kernel<true, true>), grid, block, 0, stream, p, nullptr, nullptr, max_dist, nullptr, exact_depth, nullptr, offsets,
-                       capacity, nullptr, gap, point);
+    hipLaunchKernelGGL((within_kernel<true, true>), lane_grid(p.nrays), dim3(64), 0, stream, p, nullptr, nullptr, max_dist, nullptr, exact_depth,
+                       nullptr, offsets, capacity, nullptr, gap, point);
   else
-    hipLaunchKernelGGL((within_kernel<true, false>), grid, block, 0, stream, p, pts, max_dist_dev, max_dist, first_dev, exact_depth, nullptr, offsets,
-                       capacity, index, gap, point);
+    hipLaunchKernelGGL((within_kernel<true, false>), lane_grid(p.nrays), dim3(64), 0, stream, p, pts, max_dist_dev, max_dist, first_dev,
+                       exact_depth, nullptr, offsets, capacity, index, gap, point);
   return hipGetLastError();
 }
 
@@ -748,60 +803,32 @@ __global__ __launch_bounds__(kClustersThreads) void clusters_init_kernel(int32_t
   const long long i = (long long)blockIdx.x * kClustersThreads + threadIdx.x;
   if (i < n) root[i] = (int32_t)i;
 }
-// The hook: within_lane<false, true>'s walk -- the same stack entries, loads, box_may_hold with T = the sphere's bound, first = i + 1, the
-// same predicate at the leaf -- and, where the count pass counts, the union of i and j.  `mine` is the lane's own root so far, kept across its
-// row: when j's root equals it (on a dense scene nearly every edge) there is no atomic.  It may have been hooked by another lane since;
-// uf_unite then walks on from it.
+// The hook: within_lane<false, true>'s query, node test and leaf rule over the same walk, with no row -- where the count pass counts, the union
+// of i and j.  `mine` is the lane's own root so far, kept across its row: when j's root equals it (on a dense scene nearly every edge) there
+// is no atomic.  It may have been hooked by another lane since; uf_unite then walks on from it.
 __global__ __launch_bounds__(64) void clusters_hook_kernel(KParams p, float margin, int exact_depth, int32_t *root) {
-  __shared__ int stack[kStackPixel][64];
-  const int lane = threadIdx.x;
-  const int i = blockIdx.x * 64 + lane;
+  const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= p.n_sph) return;
-  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
-  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const OrderedWalk walk(p);
   const ParentOps ops{root};
   const float4 me = p.sph[i];
   const float px = me.x, py = me.y, pz = me.z;
   const float max_dist = (me.w + margin) + 0.0f;
-  const int first = i + 1;
   const bool valid = point_ok(px, py, pz) && max_dist_ok(max_dist);
   const float pmag = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
   int32_t mine = i;
-  int sp = 0;
-  if (valid) stack[sp++][lane] = within_node_entry(0, 0);
-  while (sp > 0) {
-    const unsigned e = (unsigned)stack[--sp][lane];
-    const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
-    int leaf[2] = {-1, -1};
-    if (depth == kWithinLeaf) {
-      leaf[0] = ni;
-    } else {
-      const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
-      if (depth >= exact_depth && !box_may_hold(px, py, pz, pmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, max_dist)) continue;
-      const int l = f2i(lo.w), r = f2i(hi.w);
-      // (one pending sibling per level: sp <= height + 1 <= kStackPixel)
-      if (l < 0) {
-        leaf[0] = ~l;
-        if (r < 0) leaf[1] = ~r;
-        else stack[sp++][lane] = within_node_entry(r, depth + 1);
-      } else {
-        stack[sp++][lane] = r < 0 ? within_leaf_entry(~r) : within_node_entry(r, depth + 1);
-        stack[sp++][lane] = within_node_entry(l, depth + 1);
-      }
-    }
-#pragma unroll
-    for (int c2 = 0; c2 < 2; ++c2) {
-      const int j = leaf[c2];
-      if (j >= first && j < p.n_sph) {   // (first >= 1: an empty leaf slot, -1, never passes; j indexes root[], which no descriptor guards)
-        const float4 s = buf_load16(rs_sph, j * 16);
+  walk.run<true>(
+      valid, i + 1, exact_depth,
+      [&](const float4 &lo, const float4 &hi) { return box_may_hold(px, py, pz, pmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, max_dist); },
+      [&](int j) {
+        if (j >= p.n_sph) return;   // (j indexes root[], which no descriptor guards)
+        const float4 s = walk.sphere(j);
         const float g = point_gap(px, py, pz, s.x, s.y, s.z, s.w);
         if (g <= max_dist) {
           const int32_t theirs = uf_find(ops, j);
           if (theirs != mine) mine = uf_unite(ops, mine, theirs);
         }
-      }
-    }
-  }
+      });
 }
 // In place, and safe: no union runs any more, so every tree has its final root; the only store to word i is its owner's, of that root, and
 // the walk stores nothing else (uf_root, not uf_find: a halving store landing behind the owner's would leave a non-root in the answer).  A
@@ -841,7 +868,9 @@ __global__ __launch_bounds__(kClustersThreads) void clusters_label_kernel(const 
   if (size != nullptr && r != (int32_t)i) size[i] = size[r];
 }
 
-size_t clusters_scratch_bytes(int64_t n) { return ((within_scratch_bytes(n) + 255) & ~(size_t)255) + ((size_t)n + 1) * 8; }
+// the scan's scratch over the root flags, then its n + 1 offsets
+static size_t clusters_offsets_at(int64_t n) { return (within_scratch_bytes(n) + 255) & ~(size_t)255; }
+size_t clusters_scratch_bytes(int64_t n) { return clusters_offsets_at(n) + ((size_t)n + 1) * 8; }
 
 hipError_t launch_contact_clusters(const KParams &p, float margin, int exact_depth, char *scratch, int32_t *root, int32_t *cluster, int32_t *size,
                                    int64_t *num, hipStream_t stream) {
@@ -854,23 +883,20 @@ hipError_t launch_contact_clusters(const KParams &p, float margin, int exact_dep
   const dim3 flat((unsigned)(((int64_t)n + kClustersThreads - 1) / kClustersThreads)), threads(kClustersThreads);
   hipLaunchKernelGGL(clusters_init_kernel, flat, threads, 0, stream, root, n);
   if (n > 1) {   // (one sphere: no tree, no edge)
-    hipLaunchKernelGGL(clusters_hook_kernel, dim3(((unsigned)n + 63u) / 64u), dim3(64), 0, stream, p, margin, exact_depth, root);
+    hipLaunchKernelGGL(clusters_hook_kernel, lane_grid(n), dim3(64), 0, stream, p, margin, exact_depth, root);
     hipLaunchKernelGGL(clusters_flatten_kernel, flat, threads, 0, stream, root, n);
   }
   if (!ids && size == nullptr) return hipGetLastError();
   int32_t *const flag = ids ? reinterpret_cast<int32_t *>(scratch) : nullptr;
-  int64_t *const offsets = ids ? reinterpret_cast<int64_t *>(scratch + ((within_scratch_bytes(n) + 255) & ~(size_t)255)) : nullptr;
+  int64_t *const offsets = ids ? reinterpret_cast<int64_t *>(scratch + clusters_offsets_at(n)) : nullptr;
   if (size != nullptr) {
     const hipError_t rc = hipMemsetAsync(size, 0, sizeof(int32_t) * (size_t)n, stream);
     if (rc != hipSuccess) return rc;
   }
   hipLaunchKernelGGL(clusters_count_kernel, flat, threads, 0, stream, root, n, flag, size);
-  if (ids) {
-    long long *const sums = reinterpret_cast<long long *>(scratch + (((size_t)n * 4 + 255) & ~(size_t)255));
-    const int nblocks = (int)(((int64_t)n + kWithinScanItems - 1) / kWithinScanItems);
-    hipLaunchKernelGGL(within_scan_sums_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, flag, n, sums);
-    hipLaunchKernelGGL(within_scan_carry_kernel, dim3(1), dim3(kWithinScanThreads), 0, stream, sums, nblocks);
-    hipLaunchKernelGGL(within_scan_apply_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, flag, n, sums, offsets);
+  if (ids) {   // (the flags are the scan's counts)
+    const hipError_t rc = launch_count_scan(scratch, n, offsets, stream);
+    if (rc != hipSuccess) return rc;
   }
   if (cluster != nullptr || size != nullptr) hipLaunchKernelGGL(clusters_label_kernel, flat, threads, 0, stream, root, n, offsets, cluster, size);
   const hipError_t rc = hipGetLastError();
@@ -880,79 +906,37 @@ hipError_t launch_contact_clusters(const KParams &p, float margin, int exact_dep
   return hipSuccess;
 }
 
-// rt_spheres_in_boxes_*: EVERY sphere whose gap to the lane's box is <= the box's margin, in CSR form.  One lane per box:
-// within_lane's walk -- the same stack entries, loads, right-then-left pushes with leaf entries (rows in ascending j), the untested descent
-// above exact_depth, the same count / fill protocol and capacity guard -- with box_may_meet at the nodes and box_gap at the leaves
-// (query_core.h).  A row of `boxes` is {lo.xyz, hi.xyz}, 24 bytes: six 4-byte loads, only 4-byte alignment is assumed.  A box failing qbox_ok
-// or a margin failing max_dist_ok does not start its walk.
+// rt_spheres_in_boxes_*: EVERY sphere whose gap to the lane's box is <= the box's margin, in CSR form.  One lane per box over
+// the shared walk and row, with box_may_meet at the nodes and box_gap at the leaves (query_core.h).  A row of `boxes` is {lo.xyz, hi.xyz}, 24
+// bytes: six 4-byte loads, only 4-byte alignment is assumed.  A box failing qbox_ok or a margin failing max_dist_ok does not start its walk.
 template <bool FILL>
 __device__ __forceinline__ void boxes_lane(const KParams &p, const float *boxes, const float *margin_dev, float margin, const int32_t *first_dev,
                                            int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap,
                                            int32_t *point) {
-  __shared__ int stack[kStackPixel][64];
-  const int lane = threadIdx.x;
-  const int i = blockIdx.x * 64 + lane;
+  const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= p.nrays) return;
-  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
-  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
-  const float *const row = boxes + (size_t)i * 6;
-  const QBox q = {row[0], row[1], row[2], row[3], row[4], row[5]};
+  const OrderedWalk walk(p);
+  const float *const row6 = boxes + (size_t)i * 6;
+  const QBox q = {row6[0], row6[1], row6[2], row6[3], row6[4], row6[5]};
   if (margin_dev != nullptr) margin = margin_dev[i] + 0.0f;   // (-0.0 -> +0.0)
   int first = 0;
   if (first_dev != nullptr) first = first_dev[i] > 0 ? first_dev[i] : 0;
   const bool valid = qbox_ok(q) && max_dist_ok(margin);
   const float qmag = box_mag(q.lox, q.loy, q.loz, q.hix, q.hiy, q.hiz);
-  int cnt = 0;
-  int64_t at = 0, end = 0;
-  if constexpr (FILL) {
-    at = offsets[i];
-    end = offsets[i + 1] < capacity ? offsets[i + 1] : capacity;
-    if (at < 0) at = end;   // (offsets that are not a scan of counts: nothing is written)
-  }
-  int sp = 0;
-  if (valid) stack[sp++][lane] = within_node_entry(0, 0);
-  while (sp > 0) {
-    const unsigned e = (unsigned)stack[--sp][lane];
-    const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
-    int leaf[2] = {-1, -1};
-    if (depth == kWithinLeaf) {
-      leaf[0] = ni;
-    } else {
-      const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
-      if (depth >= exact_depth && !box_may_meet(q, qmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, margin)) continue;
-      const int l = f2i(lo.w), r = f2i(hi.w);
-      // (one pending sibling per level: sp <= height + 1 <= kStackPixel)
-      if (l < 0) {
-        leaf[0] = ~l;
-        if (r < 0) leaf[1] = ~r;
-        else stack[sp++][lane] = within_node_entry(r, depth + 1);
-      } else {
-        stack[sp++][lane] = r < 0 ? within_leaf_entry(~r) : within_node_entry(r, depth + 1);
-        stack[sp++][lane] = within_node_entry(l, depth + 1);
-      }
-    }
-#pragma unroll
-    for (int c2 = 0; c2 < 2; ++c2) {
-      const int j = leaf[c2];
-      if (j >= first) {   // (first >= 0: an empty leaf slot, -1, never passes)
-        const float4 s = buf_load16(rs_sph, j * 16);
+  CsrRow<FILL> row(i, offsets, capacity);
+  walk.run<true>(
+      valid, first, exact_depth,
+      [&](const float4 &lo, const float4 &hi) { return box_may_meet(q, qmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, margin); },
+      [&](int j) {
+        const float4 s = walk.sphere(j);
         const float g = box_gap(q, s.x, s.y, s.z, s.w);
-        if (g <= margin) {
-          if constexpr (FILL) {
-            if (at < end) {
-              if (index != nullptr) index[at] = j;
-              if (point != nullptr) point[at] = i;
-              if (gap != nullptr) gap[at] = g;
-            }
-            ++at;
-          } else {
-            ++cnt;
-          }
-        }
-      }
-    }
-  }
-  if constexpr (!FILL) count[i] = cnt;
+        row.take(g <= margin, [&](int64_t at) {
+            if (index != nullptr) index[at] = j;
+            if (point != nullptr) point[at] = i;
+            if (gap != nullptr) gap[at] = g;
+          });
+      });
+  row.finish(i, count);
 }
 template <bool FILL>
 __global__ __launch_bounds__(64) void boxes_kernel(KParams p, const float *boxes, const float *margin_dev, float margin, const int32_t *first_dev,
@@ -961,115 +945,64 @@ __global__ __launch_bounds__(64) void boxes_kernel(KParams p, const float *boxes
   boxes_lane<FILL>(p, boxes, margin_dev, margin, first_dev, exact_depth, count, offsets, capacity, index, gap, point);
 }
 
-// the count pass and the range queries' scan (the same three launches over the same scratch layout), then the fill pass
 hipError_t launch_boxes_count(const KParams &p, const float *boxes, const float *margin_dev, float margin, const int32_t *first_dev, int exact_depth,
                               char *scratch, int64_t *offsets, hipStream_t stream) {
-  if (offsets == nullptr) return hipErrorInvalidValue;
-  if (p.nrays <= 0) return hipMemsetAsync(offsets, 0, sizeof(int64_t), stream);
-  if (boxes == nullptr || scratch == nullptr || p.n_nodes < 1) return hipErrorInvalidValue;
-  if (margin_dev == nullptr && !max_dist_ok(margin)) return hipErrorInvalidValue;
+  hipError_t rc;
+  if (csr_answered(p, false, offsets, scratch, 0, true, stream, &rc)) return rc;
+  if (boxes == nullptr || (margin_dev == nullptr && !max_dist_ok(margin))) return hipErrorInvalidValue;
   margin += 0.0f;   // (-0.0 -> +0.0)
-  const int n = p.nrays;
-  int32_t *const counts = reinterpret_cast<int32_t *>(scratch);
-  long long *const sums = reinterpret_cast<long long *>(scratch + (((size_t)n * 4 + 255) & ~(size_t)255));
-  hipLaunchKernelGGL((boxes_kernel<false>), dim3(((unsigned)n + 63u) / 64u), dim3(64), 0, stream, p, boxes, margin_dev, margin, first_dev, exact_depth,
-                     counts, nullptr, (int64_t)0, nullptr, nullptr, nullptr);
-  const int nblocks = (int)(((int64_t)n + kWithinScanItems - 1) / kWithinScanItems);
-  hipLaunchKernelGGL(within_scan_sums_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums);
-  hipLaunchKernelGGL(within_scan_carry_kernel, dim3(1), dim3(kWithinScanThreads), 0, stream, sums, nblocks);
-  hipLaunchKernelGGL(within_scan_apply_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums, offsets);
-  return hipGetLastError();
+  hipLaunchKernelGGL((boxes_kernel<false>), lane_grid(p.nrays), dim3(64), 0, stream, p, boxes, margin_dev, margin, first_dev, exact_depth,
+                     reinterpret_cast<int32_t *>(scratch), nullptr, (int64_t)0, nullptr, nullptr, nullptr);
+  return launch_count_scan(scratch, p.nrays, offsets, stream);
 }
 
 hipError_t launch_boxes_fill(const KParams &p, const float *boxes, const float *margin_dev, float margin, const int32_t *first_dev, int exact_depth,
                              const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point, hipStream_t stream) {
-  if (p.nrays <= 0) return hipSuccess;
-  if (boxes == nullptr || offsets == nullptr || capacity < 0 || p.n_nodes < 1) return hipErrorInvalidValue;
-  if (index == nullptr && gap == nullptr && point == nullptr) return hipErrorInvalidValue;
-  if (margin_dev == nullptr && !max_dist_ok(margin)) return hipErrorInvalidValue;
+  hipError_t rc;
+  if (csr_answered(p, true, offsets, nullptr, capacity, index != nullptr || gap != nullptr || point != nullptr, stream, &rc)) return rc;
+  if (boxes == nullptr || (margin_dev == nullptr && !max_dist_ok(margin))) return hipErrorInvalidValue;
   margin += 0.0f;   // (-0.0 -> +0.0)
-  hipLaunchKernelGGL((boxes_kernel<true>), dim3(((unsigned)p.nrays + 63u) / 64u), dim3(64), 0, stream, p, boxes, margin_dev, margin, first_dev,
-                     exact_depth, nullptr, offsets, capacity, index, gap, point);
+  hipLaunchKernelGGL((boxes_kernel<true>), lane_grid(p.nrays), dim3(64), 0, stream, p, boxes, margin_dev, margin, first_dev, exact_depth, nullptr,
+                     offsets, capacity, index, gap, point);
   return hipGetLastError();
 }
 
-// rt_spheres_in_planes_*: EVERY sphere whose gap to the lane's K planes is <= the query's margin, in CSR form.  One lane
-// per query: boxes_lane's walk -- the same stack entries, loads, right-then-left pushes with leaf entries (rows in ascending j), the untested
-// descent above exact_depth, the same count / fill protocol and capacity guard -- with planes_may_meet at the nodes and plane_gap at the
-// leaves (query_core.h).  A query's planes are K rows {a, b, c, d} of 16 bytes: 4 K 4-byte loads, only 4-byte alignment is assumed, and one
-// normalisation per plane before the walk.  K is a template parameter, so the planes stay in 4 K registers through the fully unrolled loops.  A
-// query with a plane failing plane_normalise or a margin failing max_dist_ok does not start its walk.
+// rt_spheres_in_planes_*: EVERY sphere whose gap to the lane's K planes is <= the query's margin, in CSR form.  One lane per
+// query over the shared walk and row, with planes_may_meet at the nodes and plane_gap at the leaves (query_core.h).  A query's planes are K
+// rows {a, b, c, d} of 16 bytes: 4 K 4-byte loads, only 4-byte alignment is assumed, and one normalisation per plane before the walk.  K is a
+// template parameter, so the planes stay in 4 K registers through the fully unrolled loops.  A query with a plane failing plane_normalise or a
+// margin failing max_dist_ok does not start its walk.
 template <int K, bool FILL>
 __device__ __forceinline__ void planes_lane(const KParams &p, const float *planes, const float *margin_dev, float margin, const int32_t *first_dev,
                                             int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap,
                                             int32_t *point) {
-  __shared__ int stack[kStackPixel][64];
-  const int lane = threadIdx.x;
-  const int i = blockIdx.x * 64 + lane;
+  const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= p.nrays) return;
-  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
-  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
-  const float *const row = planes + (size_t)i * (4 * K);
+  const OrderedWalk walk(p);
+  const float *const row4 = planes + (size_t)i * (4 * K);
   QPlane pl[K];
   bool valid = true;
 #pragma unroll
-  for (int k = 0; k < K; ++k) valid &= plane_normalise(row[4 * k], row[4 * k + 1], row[4 * k + 2], row[4 * k + 3], &pl[k]);
+  for (int k = 0; k < K; ++k) valid &= plane_normalise(row4[4 * k], row4[4 * k + 1], row4[4 * k + 2], row4[4 * k + 3], &pl[k]);
   if (margin_dev != nullptr) margin = margin_dev[i] + 0.0f;   // (-0.0 -> +0.0)
   int first = 0;
   if (first_dev != nullptr) first = first_dev[i] > 0 ? first_dev[i] : 0;
   valid = valid && max_dist_ok(margin);
   const float wmag = planes_wmag(pl);
-  int cnt = 0;
-  int64_t at = 0, end = 0;
-  if constexpr (FILL) {
-    at = offsets[i];
-    end = offsets[i + 1] < capacity ? offsets[i + 1] : capacity;
-    if (at < 0) at = end;   // (offsets that are not a scan of counts: nothing is written)
-  }
-  int sp = 0;
-  if (valid) stack[sp++][lane] = within_node_entry(0, 0);
-  while (sp > 0) {
-    const unsigned e = (unsigned)stack[--sp][lane];
-    const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
-    int leaf[2] = {-1, -1};
-    if (depth == kWithinLeaf) {
-      leaf[0] = ni;
-    } else {
-      const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
-      if (depth >= exact_depth && !planes_may_meet(pl, wmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, margin)) continue;
-      const int l = f2i(lo.w), r = f2i(hi.w);
-      // (one pending sibling per level: sp <= height + 1 <= kStackPixel)
-      if (l < 0) {
-        leaf[0] = ~l;
-        if (r < 0) leaf[1] = ~r;
-        else stack[sp++][lane] = within_node_entry(r, depth + 1);
-      } else {
-        stack[sp++][lane] = r < 0 ? within_leaf_entry(~r) : within_node_entry(r, depth + 1);
-        stack[sp++][lane] = within_node_entry(l, depth + 1);
-      }
-    }
-#pragma unroll
-    for (int c2 = 0; c2 < 2; ++c2) {
-      const int j = leaf[c2];
-      if (j >= first) {   // (first >= 0: an empty leaf slot, -1, never passes)
-        const float4 s = buf_load16(rs_sph, j * 16);
+  CsrRow<FILL> row(i, offsets, capacity);
+  walk.run<true>(
+      valid, first, exact_depth,
+      [&](const float4 &lo, const float4 &hi) { return planes_may_meet(pl, wmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, margin); },
+      [&](int j) {
+        const float4 s = walk.sphere(j);
         const float g = plane_gap(pl, s.x, s.y, s.z, s.w);
-        if (g <= margin) {
-          if constexpr (FILL) {
-            if (at < end) {
-              if (index != nullptr) index[at] = j;
-              if (point != nullptr) point[at] = i;
-              if (gap != nullptr) gap[at] = g;
-            }
-            ++at;
-          } else {
-            ++cnt;
-          }
-        }
-      }
-    }
-  }
-  if constexpr (!FILL) count[i] = cnt;
+        row.take(g <= margin, [&](int64_t at) {
+            if (index != nullptr) index[at] = j;
+            if (point != nullptr) point[at] = i;
+            if (gap != nullptr) gap[at] = g;
+          });
+      });
+  row.finish(i, count);
 }
 template <int K, bool FILL>
 __global__ __launch_bounds__(64) void planes_kernel(KParams p, const float *planes, const float *margin_dev, float margin, const int32_t *first_dev,
@@ -1082,7 +1015,7 @@ template <bool FILL>
 static void launch_planes_kernel(int nplanes, const KParams &p, const float *planes, const float *margin_dev, float margin, const int32_t *first_dev,
                                  int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap,
                                  int32_t *point, hipStream_t stream) {
-  const dim3 grid(((unsigned)p.nrays + 63u) / 64u), block(64);
+  const dim3 grid = lane_grid(p.nrays), block(64);
 #define RT_PLANES_CASE(KK)                                                                                                                       \
   case KK:                                                                                                                                        \
     hipLaunchKernelGGL((planes_kernel<KK, FILL>), grid, block, 0, stream, p, planes, margin_dev, margin, first_dev, exact_depth, count, offsets, \
@@ -1094,60 +1027,46 @@ static void launch_planes_kernel(int nplanes, const KParams &p, const float *pla
 #undef RT_PLANES_CASE
 }
 
-// the count pass and the range queries' scan (the same three launches over the same scratch layout), then the fill pass
 hipError_t launch_planes_count(const KParams &p, const float *planes, int nplanes, const float *margin_dev, float margin, const int32_t *first_dev,
                                int exact_depth, char *scratch, int64_t *offsets, hipStream_t stream) {
-  if (offsets == nullptr || nplanes < 1 || nplanes > kMaxPlanes) return hipErrorInvalidValue;
-  if (p.nrays <= 0) return hipMemsetAsync(offsets, 0, sizeof(int64_t), stream);
-  if (planes == nullptr || scratch == nullptr || p.n_nodes < 1) return hipErrorInvalidValue;
-  if (margin_dev == nullptr && !max_dist_ok(margin)) return hipErrorInvalidValue;
+  hipError_t rc;
+  if (nplanes < 1 || nplanes > kMaxPlanes) return hipErrorInvalidValue;
+  if (csr_answered(p, false, offsets, scratch, 0, true, stream, &rc)) return rc;
+  if (planes == nullptr || (margin_dev == nullptr && !max_dist_ok(margin))) return hipErrorInvalidValue;
   margin += 0.0f;   // (-0.0 -> +0.0)
-  const int n = p.nrays;
-  int32_t *const counts = reinterpret_cast<int32_t *>(scratch);
-  long long *const sums = reinterpret_cast<long long *>(scratch + (((size_t)n * 4 + 255) & ~(size_t)255));
-  launch_planes_kernel<false>(nplanes, p, planes, margin_dev, margin, first_dev, exact_depth, counts, nullptr, (int64_t)0, nullptr, nullptr, nullptr,
-                              stream);
-  const int nblocks = (int)(((int64_t)n + kWithinScanItems - 1) / kWithinScanItems);
-  hipLaunchKernelGGL(within_scan_sums_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums);
-  hipLaunchKernelGGL(within_scan_carry_kernel, dim3(1), dim3(kWithinScanThreads), 0, stream, sums, nblocks);
-  hipLaunchKernelGGL(within_scan_apply_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums, offsets);
-  return hipGetLastError();
+  launch_planes_kernel<false>(nplanes, p, planes, margin_dev, margin, first_dev, exact_depth, reinterpret_cast<int32_t *>(scratch), nullptr,
+                              (int64_t)0, nullptr, nullptr, nullptr, stream);
+  return launch_count_scan(scratch, p.nrays, offsets, stream);
 }
 
 hipError_t launch_planes_fill(const KParams &p, const float *planes, int nplanes, const float *margin_dev, float margin, const int32_t *first_dev,
                               int exact_depth, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap, int32_t *point,
                               hipStream_t stream) {
+  hipError_t rc;
   if (nplanes < 1 || nplanes > kMaxPlanes) return hipErrorInvalidValue;
-  if (p.nrays <= 0) return hipSuccess;
-  if (planes == nullptr || offsets == nullptr || capacity < 0 || p.n_nodes < 1) return hipErrorInvalidValue;
-  if (index == nullptr && gap == nullptr && point == nullptr) return hipErrorInvalidValue;
-  if (margin_dev == nullptr && !max_dist_ok(margin)) return hipErrorInvalidValue;
+  if (csr_answered(p, true, offsets, nullptr, capacity, index != nullptr || gap != nullptr || point != nullptr, stream, &rc)) return rc;
+  if (planes == nullptr || (margin_dev == nullptr && !max_dist_ok(margin))) return hipErrorInvalidValue;
   margin += 0.0f;   // (-0.0 -> +0.0)
   launch_planes_kernel<true>(nplanes, p, planes, margin_dev, margin, first_dev, exact_depth, nullptr, offsets, capacity, index, gap, point, stream);
   return hipGetLastError();
 }
 
 // rt_spheres_along_rays_*: EVERY sphere a ray crosses or a moving sphere touches over its interval, in CSR form.  One lane
-// per query, two existing lanes combined.  From sweep_lane's RANGED form the SELECTION: every popped node's box widened by the query's rq
-// (six additions) through box_hit_interval over (t_min, t_max) -- the root included, no exact_depth: the answer is the tree's, as the sweep's --
-// the leaf's j != skip, and the contact rule (sweep_contact_roots: sweep_contact's kind, plus the two roots it compared).  From within_lane
-// the ORDER and the protocol: children pushed right then left, a leaf right child waiting on the stack as a leaf entry (within_leaf_entry;
-// a node entry carries depth 0, the walk reads no depth), so the leaves are met in ascending j; the `first` compare at the leaf; count pass
-// and fill pass evaluating the same predicate; the fill's at / end guard.  No sorted list: one counter, or one cursor.  The per-query radius
-// and interval are kernel arguments, each scalar or per query: radius_dev / tlo_dev / thi_dev nullptr means the scalar next to it (tlo_dev and
-// thi_dev: both or neither).  A per-query interval failing interval_ok or radius failing max_dist_ok does not start its walk.  A row of `roots`
-// is {t1, t2}, one 8-byte store; only 4-byte alignment of the array is assumed (as the pair rows of within_lane<.., SELF>).
+// per query.  From sweep_lane's RANGED form the SELECTION: every popped node's box widened by the query's rq (six additions) through
+// box_hit_interval over (t_min, t_max) -- the walk without DEPTH -- the leaf's j != skip, and the contact rule (sweep_contact_roots:
+// sweep_contact's kind, plus the two roots it compared).  From the shared walk and row the ORDER and the protocol.  No sorted list: one
+// counter, or one cursor.  The per-query radius and interval are kernel arguments, each scalar or per query: radius_dev / tlo_dev / thi_dev
+// nullptr means the scalar next to it (tlo_dev and thi_dev: both or neither).  A per-query interval failing interval_ok or radius failing
+// max_dist_ok does not start its walk.  A row of `roots` is {t1, t2}, one 8-byte store; only 4-byte alignment of the array is assumed (as the
+// pair rows of within_lane<.., SELF>).
 template <bool FILL>
 __device__ __forceinline__ void along_lane(const KParams &p, const float *radius_dev, float rq, const float *tlo_dev, const float *thi_dev,
                                            float t_min, float t_max, const int32_t *exclude, const int32_t *first_dev, int32_t *count,
                                            const int64_t *offsets, int64_t capacity, int32_t *index, float *roots, uint8_t *start,
                                            int32_t *query) {
-  __shared__ int stack[kStackPixel][64];
-  const int lane = threadIdx.x;
-  const int i = blockIdx.x * 64 + lane;
+  const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= p.nrays) return;
-  const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes, (unsigned)p.n_nodes * 32u);
-  const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
+  const OrderedWalk walk(p);
   const Ray r = load_ray(p.rays, i);
   bool valid = true;
   if (tlo_dev != nullptr) {
@@ -1162,59 +1081,25 @@ __device__ __forceinline__ void along_lane(const KParams &p, const float *radius
   const int skip = exclude != nullptr ? exclude[i] : -1;
   int first = 0;
   if (first_dev != nullptr) first = first_dev[i] > 0 ? first_dev[i] : 0;
-  int cnt = 0;
-  int64_t at = 0, end = 0;
-  if constexpr (FILL) {
-    at = offsets[i];
-    end = offsets[i + 1] < capacity ? offsets[i + 1] : capacity;
-    if (at < 0) at = end;   // (offsets that are not a scan of counts: nothing is written)
-  }
-  int sp = 0;
-  if (valid) stack[sp++][lane] = within_node_entry(0, 0);
-  while (sp > 0) {
-    const unsigned e = (unsigned)stack[--sp][lane];
-    const int ni = (int)(e & 0x3ffffffu);
-    int leaf[2] = {-1, -1};
-    if ((int)(e >> 26) == kWithinLeaf) {
-      leaf[0] = ni;
-    } else {
-      const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
-      if (!box_hit_interval(r, lo.x - rq, lo.y - rq, lo.z - rq, hi.x + rq, hi.y + rq, hi.z + rq, t_min, t_max)) continue;
-      const int l = f2i(lo.w), rc = f2i(hi.w);
-      // (one pending sibling per level: sp <= height + 1 <= kStackPixel)
-      if (l < 0) {
-        leaf[0] = ~l;
-        if (rc < 0) leaf[1] = ~rc;
-        else stack[sp++][lane] = within_node_entry(rc, 0);
-      } else {
-        stack[sp++][lane] = rc < 0 ? within_leaf_entry(~rc) : within_node_entry(rc, 0);
-        stack[sp++][lane] = within_node_entry(l, 0);
-      }
-    }
-#pragma unroll
-    for (int c2 = 0; c2 < 2; ++c2) {
-      const int j = leaf[c2];
-      if (j >= first && j != skip) {   // (first >= 0: an empty leaf slot, -1, never passes)
-        const float4 s = buf_load16(rs_sph, j * 16);
+  CsrRow<FILL> row(i, offsets, capacity);
+  walk.run<false>(
+      valid, first, 0,
+      [&](const float4 &lo, const float4 &hi) {
+        return box_hit_interval(r, lo.x - rq, lo.y - rq, lo.z - rq, hi.x + rq, hi.y + rq, hi.z + rq, t_min, t_max);
+      },
+      [&](int j) {
+        if (j == skip) return;
+        const float4 s = walk.sphere(j);
         float tau, t1, t2;
         const int what = sweep_contact_roots(r, s.x, s.y, s.z, s.w, rq, t_min, t_max, &tau, &t1, &t2);
-        if (what != kSweepNone) {
-          if constexpr (FILL) {
-            if (at < end) {
-              if (index != nullptr) index[at] = j;
-              if (roots != nullptr) *reinterpret_cast<float2 *>(roots + 2 * at) = make_float2(t1, t2);
-              if (start != nullptr) start[at] = what == kSweepStart ? (uint8_t)1 : (uint8_t)0;
-              if (query != nullptr) query[at] = i;
-            }
-            ++at;
-          } else {
-            ++cnt;
-          }
-        }
-      }
-    }
-  }
-  if constexpr (!FILL) count[i] = cnt;
+        row.take(what != kSweepNone, [&](int64_t at) {
+            if (index != nullptr) index[at] = j;
+            if (roots != nullptr) *reinterpret_cast<float2 *>(roots + 2 * at) = make_float2(t1, t2);
+            if (start != nullptr) start[at] = what == kSweepStart ? (uint8_t)1 : (uint8_t)0;
+            if (query != nullptr) query[at] = i;
+          });
+      });
+  row.finish(i, count);
 }
 template <bool FILL>
 __global__ __launch_bounds__(64) void along_kernel(KParams p, const float *radius_dev, float rq, const float *tlo_dev, const float *thi_dev,
@@ -1231,36 +1116,27 @@ static bool along_args_ok(const float *radius_dev, float radius, const float *tl
   return radius_dev != nullptr || max_dist_ok(radius);
 }
 
-// the count pass and the range queries' scan (the same three launches over the same scratch layout), then the fill pass
 hipError_t launch_along_count(const KParams &p, const float *radius_dev, float radius, const float *tlo_dev, const float *thi_dev, float t_min,
                               float t_max, const int32_t *exclude, const int32_t *first_dev, char *scratch, int64_t *offsets, hipStream_t stream) {
-  if (offsets == nullptr) return hipErrorInvalidValue;
-  if (p.nrays <= 0) return hipMemsetAsync(offsets, 0, sizeof(int64_t), stream);
-  if (p.rays == nullptr || scratch == nullptr || p.n_nodes < 1) return hipErrorInvalidValue;
-  if (!along_args_ok(radius_dev, radius, tlo_dev, thi_dev, t_min, t_max)) return hipErrorInvalidValue;
+  hipError_t rc;
+  if (csr_answered(p, false, offsets, scratch, 0, true, stream, &rc)) return rc;
+  if (p.rays == nullptr || !along_args_ok(radius_dev, radius, tlo_dev, thi_dev, t_min, t_max)) return hipErrorInvalidValue;
   radius += 0.0f;   // (-0.0 -> +0.0)
-  const int n = p.nrays;
-  int32_t *const counts = reinterpret_cast<int32_t *>(scratch);
-  long long *const sums = reinterpret_cast<long long *>(scratch + (((size_t)n * 4 + 255) & ~(size_t)255));
-  hipLaunchKernelGGL((along_kernel<false>), dim3(((unsigned)n + 63u) / 64u), dim3(64), 0, stream, p, radius_dev, radius, tlo_dev, thi_dev, t_min,
-                     t_max, exclude, first_dev, counts, nullptr, (int64_t)0, nullptr, nullptr, nullptr, nullptr);
-  const int nblocks = (int)(((int64_t)n + kWithinScanItems - 1) / kWithinScanItems);
-  hipLaunchKernelGGL(within_scan_sums_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums);
-  hipLaunchKernelGGL(within_scan_carry_kernel, dim3(1), dim3(kWithinScanThreads), 0, stream, sums, nblocks);
-  hipLaunchKernelGGL(within_scan_apply_kernel, dim3(nblocks), dim3(kWithinScanThreads), 0, stream, counts, n, sums, offsets);
-  return hipGetLastError();
+  hipLaunchKernelGGL((along_kernel<false>), lane_grid(p.nrays), dim3(64), 0, stream, p, radius_dev, radius, tlo_dev, thi_dev, t_min, t_max, exclude,
+                     first_dev, reinterpret_cast<int32_t *>(scratch), nullptr, (int64_t)0, nullptr, nullptr, nullptr, nullptr);
+  return launch_count_scan(scratch, p.nrays, offsets, stream);
 }
 
 hipError_t launch_along_fill(const KParams &p, const float *radius_dev, float radius, const float *tlo_dev, const float *thi_dev, float t_min,
                              float t_max, const int32_t *exclude, const int32_t *first_dev, const int64_t *offsets, int64_t capacity,
                              int32_t *index, float *roots, uint8_t *start, int32_t *query, hipStream_t stream) {
-  if (p.nrays <= 0) return hipSuccess;
-  if (p.rays == nullptr || offsets == nullptr || capacity < 0 || p.n_nodes < 1) return hipErrorInvalidValue;
-  if (index == nullptr && roots == nullptr && start == nullptr && query == nullptr) return hipErrorInvalidValue;
-  if (!along_args_ok(radius_dev, radius, tlo_dev, thi_dev, t_min, t_max)) return hipErrorInvalidValue;
+  hipError_t rc;
+  const bool outputs = index != nullptr || roots != nullptr || start != nullptr || query != nullptr;
+  if (csr_answered(p, true, offsets, nullptr, capacity, outputs, stream, &rc)) return rc;
+  if (p.rays == nullptr || !along_args_ok(radius_dev, radius, tlo_dev, thi_dev, t_min, t_max)) return hipErrorInvalidValue;
   radius += 0.0f;   // (-0.0 -> +0.0)
-  hipLaunchKernelGGL((along_kernel<true>), dim3(((unsigned)p.nrays + 63u) / 64u), dim3(64), 0, stream, p, radius_dev, radius, tlo_dev, thi_dev,
-                     t_min, t_max, exclude, first_dev, nullptr, offsets, capacity, index, roots, start, query);
+  hipLaunchKernelGGL((along_kernel<true>), lane_grid(p.nrays), dim3(64), 0, stream, p, radius_dev, radius, tlo_dev, thi_dev, t_min, t_max, exclude,
+                     first_dev, nullptr, offsets, capacity, index, roots, start, query);
   return hipGetLastError();
 }
 
