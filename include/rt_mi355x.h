@@ -93,8 +93,10 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *     nodes (render launches): the layout of the node records staged in LDS -- sign-ordered: the plain instantiations on a scene that is in LDS whole; planes: every other launch
  *     entry (render launches, in the same token: "nodes=sign-ordered,entry=lists"): lists = a new primary ray starts at its 8 x 8 tile's entry list -- at most one inner node and
  *         six leaves that the root walk of every ray of the tile provably reaches -- instead of at the root (option entry_lists: -1, the default, launches of the
- *         instantiation that exists with such lists -- plain tile tickets, 16 waves, the scene in LDS whole -- whose tiles are 8 consecutive image rows; 0 never; 1 every launch of
- *         that instantiation); root = every ray starts at the root
+ *         instantiation that exists with such lists -- plain tile tickets, 16 waves, the scene in LDS whole -- whose tiles are 8 consecutive image rows, while options
+ *         leaf_box and dark_stop are both on: the kernel with lists has the leaf filter and the dark stop compiled in, so leaf_box = 0 or dark_stop = 0 turns the lists
+ *         off, too -- a launch that says dark=0 or leaf_box=0 for a reason of its own, a recording launch or a camera outside the filter's guard, keeps its lists through
+ *         a twin of the kernel that reads the two flags; 0 never; 1 every launch of that instantiation, with a flag at 0 through that twin); root = every ray starts at the root
  *     dark (render launches, in the same token: "nodes=planes,entry=root,dark=1"): 1 = the launch finishes a bounce chain whose light is exactly (0, 0, 0) as pixel 0 instead of tracing it on --
  *         the pixel it ends in whatever it meets (option dark_stop: -1, the default, every render launch that does not record; 0 never; 1 also rt_render_trace's instrumented launch);
  *         0 = full chains: every recording launch (recording != 0), dark_stop = 0
@@ -107,6 +109,13 @@ const char *rt_context_last_launch(const rt_context *ctx);
  * context's LAST pooled render launch, summed, and per wave {lists, fallbacks} into per_wave[2 * cap_waves] when given; *waves = 0: that launch counted nothing
  * (no table, or the option off).  Synchronises the context. */
 int rt_context_entry_counts(rt_context *ctx, uint64_t *lists, uint64_t *fallbacks, int64_t *waves, uint64_t *per_wave, int64_t cap_waves);
+/* What rt_context_last_launch's line has no field for.  Of the context's LAST pooled render launch: *colour_lds = 1 when its kernel staged the colour table in LDS
+ * and read the winner's colour there (an entry=lists launch with both flags set whose table fits next to 16 waves; option "col_lds" = 0: never), *flags_const = 1
+ * when its kernel had the leaf filter and the dark stop compiled in (below); both 0 for entry=root.  Of the context: *tables_built = tables of entry lists its
+ * launches have built, *tables_kept = launches that found their view's table in place -- a view (size, partition, bounce limit, camera) keeps the table its first
+ * entry=lists launch built until the scene is updated, the leaf filter it was built under changes or the view is evicted; a batch with a camera per frame has no
+ * view and builds its table per launch (option "entry_keep" = 0: every launch does).  Any pointer may be NULL.  No device work. */
+int rt_context_entry_info(rt_context *ctx, int32_t *colour_lds, int32_t *flags_const, uint64_t *tables_built, uint64_t *tables_kept);
 int rt_context_sync(rt_context *ctx);
 /* Threads: every entry that takes a context holds that context's lock for the duration of the call (as a Futhark context does:
  * SURVEY.md 8b) -- host threads may share a context, a prepared scene and a scene; their calls are serialised and their frames
@@ -116,7 +125,8 @@ int rt_context_set_variant(rt_context *ctx, int variant);
 /* Tuning knobs by name (see DESIGN.md "knobs"); unknown name -> error.  None changes a pixel.  Among them "dark_stop" (-1 | 0 | 1, see rt_context_last_launch above):
  * rt_render_stats always counts the reference's full chains; rt_render_trace counts the stopped chains under dark_stop = 1 only.  "leaf_box" (-1 | 0 | 1) likewise:
  * rt_render_trace's leaf items are the reference's sphere tests unless leaf_box = 1.  "entry_lists" (-1 | 0 | 1): see rt_context_last_launch above; the instrumented launches
- * always start at the root. */
+ * always start at the root.  "entry_keep" (-1 | 0) and "col_lds" (-1 | 0): see rt_context_entry_info above -- 0 builds the table of entry lists in every launch / loads the
+ * winner's colour from memory in every launch. */
 int rt_context_set_option(rt_context *ctx, const char *name, int64_t value);
 int rt_context_device_info(const rt_context *ctx, int *device, int *num_cu, int *lds_bytes, char *name, int name_len);
 

@@ -91,6 +91,14 @@ class Context:
             self._check(lib.rt_context_entry_counts(self._h, None, None, None, per.ctypes.data_as(C.POINTER(C.c_uint64)), nw.value))
         return {"lists": lists.value, "fallbacks": falls.value, "waves": nw.value, "per_wave": per}
 
+    def entry_info(self):
+        """what last_launch has no room for: {"colour_lds": the last pooled render launch read the winner's colour from LDS, "flags_const": its kernel had
+        the leaf filter and the dark stop compiled in (both False for a launch that says entry=root), "tables_built": tables of entry lists this context's
+        launches have built, "tables_kept": launches that found their view's table in place (option entry_keep)}"""
+        col, const, built, kept = C.c_int32(), C.c_int32(), C.c_uint64(), C.c_uint64()
+        self._check(lib.rt_context_entry_info(self._h, C.byref(col), C.byref(const), C.byref(built), C.byref(kept)))
+        return {"colour_lds": bool(col.value), "flags_const": bool(const.value), "tables_built": built.value, "tables_kept": kept.value}
+
     @property
     def rccl_ranks(self):
         """ranks of the RCCL communicator behind a multi-device context's gather (0: RCCL is not what carries it)"""

@@ -549,16 +549,38 @@ void set_leaf_box(const rt_context *ctx, const rt_prepared *ps, const Plan &pl, 
 // Per-tile entry lists (lane_core.h: tile_entry): which pooled render launches start their primary rays at their tile's list.  Option
 // entry_lists: 0 never; 1 every launch whose instantiation exists with ENTRY (rt_device.hpp: pooled_entry_ok) on a tree with an inner node; -1 (the default)
 // of those the launches whose tiles are 8 consecutive rows of the image -- a tile of a cyclic partition with fewer rows per row tile spans the rows of other
-// parts, and its corner rays bound little.  Called behind set_cull and set_leaf_box (the key and the filter are the launch's).  The table is one block of the
-// context's arena / pool, kept and grown: launches of one context are ordered on its stream, and tile_entry_kernel refills it there ahead of each.
-int set_entry(rt_context *ctx, const Plan &pl, rtk::KParams *p) {
+// parts, and its corner rays bound little -- and only while options leaf_box and dark_stop are both on: the ENTRY kernel has the two flags compiled in
+// (rt_device.hpp: pooled_entry_flags_const), and a context that switches either off renders through the kernels that read them, from the root.  A launch whose
+// flag is clear for a reason of its own (it records its view's chains: no dark stop; a camera outside the filter's guard), and every launch with a flag clear
+// under entry_lists = 1, takes the twin of the ENTRY kernel that reads the flags.
+// Called behind set_cull, set_dark and set_leaf_box (the key, the flags and the filter are the launch's).
+// Where the table lives: a launch of a view `to` (one camera) finds it in the view's block -- built by the view's first launch that wanted one, on this
+// context's stream, under the filter it says; *build tells whether this launch has to (re)fill it.  A launch without a view (a camera per frame), of a view
+// without the region, or of a view another context filled, builds its table in one block of the context's arena / pool, kept and grown: launches of one
+// context are ordered on its stream.  *entry: the ENTRY template value of the launch (0: none).
+int set_entry(rt_context *ctx, const Plan &pl, TileOrder *to, rtk::KParams *p, int *entry, bool *build) {
   p->entry = nullptr;
+  *entry = 0;
+  *build = false;
   rtk::PooledKey k{};
   if (ctx->entry_lists == 0 || pl.variant != RT_VARIANT_POOLED || p->n_nodes < 1 || !rtk::choose_pooled(*p, false, pl.waves, 0, &k) || !rtk::pooled_entry_ok(k)) return 0;
   if (ctx->entry_lists < 0 && p->nparts > 1 && p->rpt_log2 < 3) return 0;
+  if (ctx->entry_lists < 0 && (ctx->leaf_box == 0 || ctx->dark_stop == 0)) return 0;
   // (one camera: a list per tile, shared by the launch's frames.  A camera per frame: a list per frame and tile, found at the TICKET position -- the kernels
   // carry no other index through their loop: only launches whose positions are frame * nchunks + tile, i.e. no order table and one queue over all tiles)
   if (p->cams != nullptr && (p->order != nullptr || !(p->nshards == 1 || p->interleave))) return 0;
+  *entry = rtk::pooled_entry_bits(rtk::kEntryLists, p->leaf_box, p->dark, rtk::pooled_col_lds_bytes(p->n_nodes, p->n_sph, p->capb, p->capl, p->ray_planes),
+                                  static_cast<size_t>(std::min(ctx->lds_bytes, 160 * 1024)), ctx->col_lds != 0);
+  const int filter = p->leaf_box != 0 && rtk::pooled_leaf_box(k) ? 1 : 0;   // (as launch_tile_entry hands it to the kernel)
+  if (to != nullptr && to->entry != nullptr && p->cams == nullptr && ctx->entry_keep != 0 && (to->entry_ctx == nullptr || to->entry_ctx == ctx)) {
+    *build = !(to->entry_valid && to->entry_filter == filter);
+    to->entry_valid = false;   // (valid again once the launch that fills it has been enqueued: enqueue_render)
+    to->entry_filter = filter;
+    to->entry_ctx = ctx;
+    p->entry = to->entry;
+    return 0;
+  }
+  *build = true;
   const size_t need = sizeof(unsigned) * rtk::kEntryDw * static_cast<size_t>(p->cams != nullptr ? p->nframes : 1) * static_cast<size_t>(p->nchunks);
   if (ctx->entry_bytes < need) {
     drain_streams(ctx);
@@ -690,7 +712,10 @@ int find_view(rt_context *ctx, const rt_prepared *ps, const rtk::KParams &p, con
     const size_t px_elems = px_ok ? static_cast<size_t>(p.rows_local) * static_cast<size_t>(p.w) : 0;
     auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t off_order = up(sizeof(int) * static_cast<size_t>(p.nchunks)), off_cost_px = off_order + up(sizeof(int) * static_cast<size_t>(rtk::order_table_ints(p.nchunks))),
-                 off_px_list = off_cost_px + up(px_bytes), need_bytes = off_px_list + up(sizeof(unsigned) * (px_elems + (px_ok ? rtk::kPxHdrInts : 0)));
+                 off_px_list = off_cost_px + up(px_bytes), off_entry = off_px_list + up(sizeof(unsigned) * (px_elems + (px_ok ? rtk::kPxHdrInts : 0)));
+    // (the view's table of entry lists, where a launch of this shape can have one: 16 waves with the scene in LDS -- rt_device.hpp: pooled_entry_ok)
+    const bool entry_ok = ctx->entry_lists != 0 && ctx->entry_keep != 0 && pl.waves == 16 && p.n_nodes >= 1 && pl.lds_nodes == p.n_nodes && pl.lds_sph == p.n_sph;
+    const size_t need_bytes = off_entry + (entry_ok ? up(sizeof(unsigned) * rtk::kEntryDw * static_cast<size_t>(p.nchunks)) : 0);
     if (ps->orders.size() >= 8) {
       size_t lru = 0;
       for (size_t i = 1; i < ps->orders.size(); ++i)
@@ -734,6 +759,7 @@ int find_view(rt_context *ctx, const rt_prepared *ps, const rtk::KParams &p, con
       o.cost_px_bytes = px_bytes;
       o.px_elems = px_elems;
     }
+    if (entry_ok) o.entry = reinterpret_cast<unsigned *>(o.block + off_entry);
     RT_HIP(ctx, hipMemsetAsync(o.cost, 0, sizeof(int) * static_cast<size_t>(o.ntiles), ctx->stream));
     ps->orders.push_back(o);
     to = &ps->orders.back();
@@ -1067,11 +1093,17 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
   set_cull(ctx, ps, pl, cams_dev, &p);
   set_dark(ctx, false, &p);
   set_leaf_box(ctx, ps, pl, cams_dev, false, &p);
-  if (int rc = set_entry(ctx, pl, &p)) return rc;
   int entry = 0;
+  bool build_entry = false;
+  if (int rc = set_entry(ctx, pl, to, &p, &entry, &build_entry)) return rc;
   if (p.entry) {
-    RT_HIP(ctx, rtk::launch_tile_entry(p, false, pl.waves, ctx->stream));
-    entry = rtk::kEntryLists;
+    if (build_entry) {
+      RT_HIP(ctx, rtk::launch_tile_entry(p, false, pl.waves, ctx->stream));
+      ctx->entry_tables_built++;
+    } else {
+      ctx->entry_tables_kept++;
+    }
+    if (to != nullptr && p.entry == to->entry) to->entry_valid = true;
     if (ctx->entry_count) {
       // (option entry_count, a test's aid: the counting twin, two words per wave -- rays started from a list, rays sent back to the root -- read by rt_context_entry_counts)
       const size_t nw = static_cast<size_t>(pl.grid) * static_cast<size_t>(pl.waves), bytes = nw * 2 * sizeof(unsigned long long);
@@ -1084,10 +1116,11 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
       }
       RT_HIP(ctx, hipMemsetAsync(ctx->entry_counts_dev, 0, bytes, ctx->stream));
       p.trace = ctx->entry_counts_dev;
-      entry = rtk::kEntryCount;
+      entry = (entry & ~rtk::kEntryModeMask) | rtk::kEntryCount;
     }
   }
-  ctx->entry_counts_waves = entry == rtk::kEntryCount ? static_cast<int64_t>(pl.grid) * pl.waves : 0;   // (the counts are the LAST pooled render launch's, or none)
+  ctx->entry_counts_waves = (entry & rtk::kEntryModeMask) == rtk::kEntryCount ? static_cast<int64_t>(pl.grid) * pl.waves : 0;   // (the counts are the LAST pooled render launch's, or none)
+  ctx->last_entry = entry;
   tick("before launch");
   RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream, 0, entry));
   tick("launch_pooled");
@@ -1239,6 +1272,19 @@ extern "C" int rt_context_entry_counts(rt_context *ctx, uint64_t *lists, uint64_
   if (lists) *lists = l;
   if (fallbacks) *fallbacks = f;
   if (waves) *waves = nw;
+  return 0;
+}
+
+// What rt_context_last_launch has no room for (its line is parsed field by field): of the last pooled render launch, whether its kernel read the winner's colour
+// from LDS (*colour_lds) and had the leaf filter and the dark stop compiled in (*flags_const) -- both 0 for a launch that started at the root --; of the context,
+// how many tables of entry lists its launches built (launches of tile_entry_kernel) and how many launches found their view's table in place.  No device work.
+extern "C" int rt_context_entry_info(rt_context *ctx, int32_t *colour_lds, int32_t *flags_const, uint64_t *tables_built, uint64_t *tables_kept) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  if (colour_lds) *colour_lds = (ctx->last_entry & rtk::kEntryColLds) != 0;
+  if (flags_const) *flags_const = ctx->last_entry != 0 && (ctx->last_entry & rtk::kEntryRtFlags) == 0;
+  if (tables_built) *tables_built = ctx->entry_tables_built;
+  if (tables_kept) *tables_kept = ctx->entry_tables_kept;
   return 0;
 }
 
@@ -1395,6 +1441,10 @@ extern "C" int rt_context_set_option(rt_context *ctx, const char *name, int64_t 
     ctx->entry_lists = std::max(-1, std::min(1, v));
   } else if (k == "entry_count") {
     ctx->entry_count = v != 0;
+  } else if (k == "entry_keep") {
+    ctx->entry_keep = v == 0 ? 0 : -1;
+  } else if (k == "col_lds") {
+    ctx->col_lds = v == 0 ? 0 : -1;
   } else if (k == "sync_policy") {
     ctx->sync_policy = v != 0;
   } else {

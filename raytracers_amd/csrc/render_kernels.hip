@@ -672,10 +672,18 @@ __device__ __forceinline__ unsigned long long launch_leaf_off() {
 // differs; a position without a list, a scattered ray, and every new ray of a SHADE whose lists would not fit the leaf list start at the root as before.
 // ENTRY == kEntryCount: the same kernel with two counters per wave -- the rays that started from a list, and the rays that had one and took the root because
 // their SHADE's leaves would not fit -- written to p.trace[2 * wave_index ..] when the wave ends (option entry_count; rt_context_entry_counts).
+// The mode sits in ENTRY's low two bits; above it (rt_device.hpp): without kEntryRtFlags the launch's leaf filter and dark stop are ON by construction -- the
+// host sends a launch with either flag clear to the twin that has the bit, or to the kernel without lists (api.cpp: set_entry) -- and BOX / BOX2 / SHADE carry
+// neither launch_leaf_off() nor launch_dark(); with kEntryColLds the colour table is staged behind the sphere prefix and SHADE reads the winner's colour from
+// LDS as it reads its sphere (the table must fit next to 16 waves: pooled_col_fits).
 template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, int RAYS = 0, int ENTRY = 0>
 __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 4) void pooled_kernel(KParams p) {
   constexpr bool COLD = TAIL == 1, DONATE = TAIL == 2;
   constexpr bool ANY = RAYS == kRaysAny;
+  constexpr bool ECOUNT = (ENTRY & kEntryModeMask) == kEntryCount;         // the counting twin
+  constexpr bool ECONST = ENTRY != 0 && (ENTRY & kEntryRtFlags) == 0;      // leaf filter and dark stop on by construction
+  constexpr bool ECOL = (ENTRY & kEntryColLds) != 0;                       // col[n_sph] in LDS behind the sphere prefix
+  static_assert(!ENTRY || ((ENTRY & kEntryModeMask) == kEntryLists || ECOUNT), "ENTRY: lists, or the counting twin");
   static_assert(!ENTRY || (THREADS == 1024 && ALL_LDS && !STATS && !SOLO && TAIL == 0 && !ORD && !CULL && SPILL == 0 && RAYS == 0), "ENTRY: the plain 16-wave kernel of a scene in LDS only");
   static_assert(!RAYS || (!STATS && !SOLO && TAIL == 0 && !ORD && !CULL), "RAYS: the plain instantiations only");
   static_assert(!ORD || TAIL != 1, "ORD: no COLD variant");   // (ORD + DONATE: a frame rendered through a pixel list BORROWED from a neighbouring view, round 6)
@@ -689,10 +697,13 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int plane = p.lds_nodes;          // float4 per node plane
-  const int sph_base = 4 * plane;
+  // (ECOL: the sign-ordered records packed, kPsNodeBytes each -- their addresses do not depend on the planes' pitch -- which is what makes room for the
+  // colour table next to 16 waves: rt_device.hpp, pooled_col_lds_bytes)
+  const int sph_base = ECOL ? (plane * (kPsNodeBytes / 4) + 3) >> 2 : 4 * plane;
   // per-wave region: key[64] (u64) | cnt[64] | dump[4] | rays[ray_planes][64] float4 | box stack[capb] | leaf list[capl]
   const int per_wave_dw = pooled_wave_dw(p.ray_planes, p.capb, p.capl);
-  unsigned *const wbase = reinterpret_cast<unsigned *>(smem + sph_base + p.lds_sph) + wave * per_wave_dw;
+  const int col_base = sph_base + p.lds_sph;   // (ECOL: the colour table, n_sph entries; the waves' regions lie behind it)
+  unsigned *const wbase = reinterpret_cast<unsigned *>(smem + (ECOL ? col_base + p.n_sph : col_base)) + wave * per_wave_dw;
   unsigned long long *const wkey = reinterpret_cast<unsigned long long *>(wbase);
   int *const wcnt = reinterpret_cast<int *>(wbase + 128);
   unsigned *const wdump = wbase + 192;    // where lanes with nothing to append write
@@ -717,6 +728,8 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
     for (int i = threadIdx.x; i < 4 * plane; i += THREADS) smem[(i & 3) * plane + (i >> 2)] = p.nodes64[i];
   }
   for (int i = threadIdx.x; i < p.lds_sph; i += THREADS) smem[sph_base + i] = p.sph[i];
+  if constexpr (ECOL)
+    for (int i = threadIdx.x; i < p.n_sph; i += THREADS) smem[col_base + i] = p.col[i];
   // Zero the wave's region: lanes without an item read a stale entry and compute on it with
   // their results masked off, so every stale entry must decode to valid indices.
   for (int i = lane; i < per_wave_dw; i += 64) wbase[i] = 0u;
@@ -946,7 +959,9 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
             // dependent global latencies in a row were ~10 % of a lone wave's bounce); the sphere
             // comes from the LDS copy when it is staged
             const int wj = hit ? bestj : 0;
-            float4 c = buf_load16(rs_col, wj * 16), s;
+            float4 c, s;
+            if constexpr (ECOL) c = smem[col_base + wj];
+            else c = buf_load16(rs_col, wj * 16);
             if (ALL_LDS) {
               s = smem[sph_base + wj];
             } else {
@@ -977,7 +992,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
             // below: no root, nothing donated.  Mask logic, no branch.  (p.dark: never set with p.cost, api.cpp: set_dark)
             // (SPILL: as a branch that sets the pixel -- in the mask form the plain SPILL kernels spilled one more dword, 20 -> 24 bytes of scratch)
             if constexpr (!RAYS && !SPILL) {
-              const bool dark = launch_dark() != 0, dead = light_is_dead(lr, lg, lb);
+              const bool dark = ECONST || launch_dark() != 0, dead = light_is_dead(lr, lg, lb);
               more = more & !(dark & dead);
             }
             if constexpr (!RAYS && SPILL != 0) {
@@ -1239,11 +1254,11 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
               int total = 0;
               for (int k = 0; k < kEntryLeaves; ++k) total += __popcll(bal(nl > k));
               if (uni(total) > p.capl - nleaf) {
-                if constexpr (ENTRY == kEntryCount) ec_fall += (unsigned)__popcll(bal(ent_hdr != 0u));
+                if constexpr (ECOUNT) ec_fall += (unsigned)__popcll(bal(ent_hdr != 0u));
                 ent_hdr = 0u;
               }
             }
-            if constexpr (ENTRY == kEntryCount) ec_lists += (unsigned)__popcll(bal((ent_hdr & kEntryValid) != 0u));
+            if constexpr (ECOUNT) ec_lists += (unsigned)__popcll(bal((ent_hdr & kEntryValid) != 0u));
             push_box = root_hit & ((ent_hdr & kEntryValid) == 0u || (ent_hdr & kEntryInner) != 0u);
           }
           if (root) {
@@ -1265,6 +1280,8 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
             // the lists' leaves: leaf k of every list that has one, by ranks -- the items LEAF drains next
             const unsigned lf[kEntryLeaves] = {ent0.z, ent0.w, ent1.x, ent1.y, ent1.z, ent1.w};
             const int nl = (ent_hdr & kEntryValid) != 0u ? (int)(ent_hdr >> kEntryCountShift) & 15 : 0;
+            // (one rank for all leaves of a SHADE whose new rays hold ONE list -- leaf k at nleaf + k * cnt + rank behind a compare and a ballot, these rounds
+            // otherwise -- was built and measured: +23 VALU instructions out of line, rgbbox's batch 0.1654 -> 0.1680 ms per frame; profiles/batch_trim)
             for (int k = 0; k < kEntryLeaves; ++k) {
               const unsigned long long m_k = bal(nl > k);
               if (m_k == 0ull) break;          // (wave-uniform: as many rounds as the longest list has leaves)
@@ -1401,7 +1418,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         const unsigned long long m_inl = m_act & ~m_ln & m_hl, m_inr = m_act & ~m_rn & m_hr;
         // (a leaf child's slot holds the sphere's own widened box, lane_core.h: leaf_box_eps -- the test above ran on it as on any slot; where the launch is
         // admitted, m_off == 0, its verdict decides whether the sphere is tested: scalar mask logic only.  The caller-ray loops are never filtered)
-        const unsigned long long m_off = LEAFBOX ? launch_leaf_off() : ~0ull;
+        const unsigned long long m_off = !LEAFBOX ? ~0ull : ECONST ? 0ull : launch_leaf_off();
         const unsigned long long m_lfl = m_act & m_ln & (m_hl | m_off), m_lfr = m_act & m_rn & (m_hr | m_off);
         if (STATS) n_box += __popcll(m_act & ~m_ln & (1ull << lane)) + __popcll(m_act & ~m_rn & (1ull << lane));
         // append: left children first, then right children (two independent prefix ranks per list; the right
@@ -1524,7 +1541,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         const unsigned long long m_inl = m_pass & ~m_ln & m_hl, m_inr = m_pass & ~m_rn & m_hr;
         // leaf appends: the child itself (lanes whose child is a leaf), or its leaf children -- never both for one lane
         // (filtered launches: a leaf grandchild by its slot of the child's record, the leaf child itself by its slot of the item's record -- `own`)
-        const unsigned long long m_off = LEAFBOX ? launch_leaf_off() : ~0ull, m_own = bal(own);
+        const unsigned long long m_off = !LEAFBOX ? ~0ull : ECONST ? 0ull : launch_leaf_off(), m_own = bal(own);
         const unsigned long long m_lfl = (m_pass & m_ln & (m_hl | m_off)) | (m_cleaf & (m_own | m_off)), m_lfr = m_pass & m_rn & (m_hr | m_off);
         if (STATS) n_box += __popcll(m_pass & ~m_ln & (1ull << lane)) + __popcll(m_pass & ~m_rn & (1ull << lane));
         const int c_inl = __popcll(m_inl), c_lfl = __popcll(m_lfl);
@@ -1609,7 +1626,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
     }
   }
   queue_leave(p, nwaves, lane);
-  if constexpr (ENTRY == kEntryCount) {
+  if constexpr (ECOUNT) {
     if (lane == 0 && p.trace != nullptr) {
       unsigned long long *const rec = p.trace + 2 * (size_t)(blockIdx.x * (THREADS / 64) + wave);
       rec[0] = ec_lists; rec[1] = ec_fall;
@@ -2067,15 +2084,32 @@ static hipError_t launch_pooled_key(const PooledKey &k, const KParams &p, int gr
 }
 
 // The ENTRY twins of the one key pooled_entry_ok admits: `entry` = kEntryLists, or kEntryCount (the counting one: p.trace holds two words per wave)
-static hipError_t launch_pooled_entry(const PooledKey &k, const KParams &p, int grid, hipStream_t stream, int entry) {
-  if (!pooled_entry_ok(k) || p.entry == nullptr || p.rays != nullptr || (entry != kEntryLists && entry != kEntryCount) || (entry == kEntryCount && p.trace == nullptr))
-    return hipErrorInvalidValue;
-  const size_t lds = pooled_lds_bytes(p.lds_nodes, p.lds_sph, p.capb, p.capl, p.ray_planes, 16);
-  auto kfn = entry == kEntryCount ? pooled_kernel<1024, true, false, false, 0, false, false, 0, 0, kEntryCount>
-                                  : pooled_kernel<1024, true, false, false, 0, false, false, 0, 0, kEntryLists>;
+template <int ENTRY>
+static hipError_t launch_pooled_entry_t(const KParams &p, int grid, hipStream_t stream) {
+  const size_t lds = (ENTRY & kEntryColLds) ? pooled_col_lds_bytes(p.n_nodes, p.n_sph, p.capb, p.capl, p.ray_planes)
+                                            : pooled_lds_bytes(p.lds_nodes, p.lds_sph, p.capb, p.capl, p.ray_planes, 16);
+  auto kfn = pooled_kernel<1024, true, false, false, 0, false, false, 0, 0, ENTRY>;
   if (hipError_t e = allow_full_lds(reinterpret_cast<const void *>(kfn)); e != hipSuccess) return e;
   hipLaunchKernelGGL(kfn, dim3(grid), dim3(1024), lds, stream, p);
   return hipGetLastError();
+}
+// (the compiled ENTRY values: each mode with the flags constant and the colours in LDS or not, and with the flags read at run time)
+template <int... E>
+static hipError_t launch_pooled_entry_any(const KParams &p, int grid, hipStream_t stream, int entry, std::integer_sequence<int, E...>) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)((E == entry && ((e = launch_pooled_entry_t<E>(p, grid, stream)), true)) || ...);
+  return e;
+}
+static hipError_t launch_pooled_entry(const PooledKey &k, const KParams &p, int grid, hipStream_t stream, int entry) {
+  const int mode = entry & kEntryModeMask;
+  if (!pooled_entry_ok(k) || p.entry == nullptr || p.rays != nullptr || (mode != kEntryLists && mode != kEntryCount) || (mode == kEntryCount && p.trace == nullptr))
+    return hipErrorInvalidValue;
+  // (a kernel with the flags compiled in renders only a launch that has both set; the colour table only where it fits: 160 KB per CU)
+  if (!(entry & kEntryRtFlags) && !pooled_entry_flags_const(p.leaf_box, p.dark)) return hipErrorInvalidValue;
+  if ((entry & kEntryColLds) && !pooled_col_fits(pooled_col_lds_bytes(p.n_nodes, p.n_sph, p.capb, p.capl, p.ray_planes), 160 * 1024)) return hipErrorInvalidValue;
+  return launch_pooled_entry_any(p, grid, stream, entry,
+                                 std::integer_sequence<int, kEntryLists, kEntryLists | kEntryColLds, kEntryLists | kEntryRtFlags, kEntryCount, kEntryCount | kEntryColLds,
+                                                       kEntryCount | kEntryRtFlags>{});
 }
 
 // The table of entry lists of a launch (p.entry: p.nchunks positions of kEntryDw dwords -- with a camera per frame p.nframes * p.nchunks, frame-major), one
@@ -2161,6 +2195,7 @@ void warm_render_kernels() {
   warm_pooled(std::make_integer_sequence<int, kNumPooledKeys>{});
   hipFuncAttributes a;
   (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(pooled_kernel<1024, true, false, false, 0, false, false, 0, 0, kEntryLists>));
+  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(pooled_kernel<1024, true, false, false, 0, false, false, 0, 0, kEntryLists | kEntryColLds>));
   (void)hipFuncGetAttributes(&a, (const void *)tile_entry_kernel);
   (void)hipFuncGetAttributes(&a, (const void *)px_count_kernel);
   (void)hipFuncGetAttributes(&a, (const void *)px_scan_kernel);

@@ -467,6 +467,26 @@ size_t persistent_lds_bytes(int lds_nodes, int lds_sph, int smax, int lmax, int 
 // (launch_tile_entry has filled it) and the ENTRY twin of the chosen instantiation renders -- an error where there is none (pooled_entry_ok) or with caller rays;
 // kEntryCount = the same through the counting twin, p.trace holding two zeroed words per wave
 constexpr int kEntryLists = 1, kEntryCount = 2;
+// ... and what else the ENTRY template value says, in bits above that mode (the caller of launch_pooled ORs them in; pooled_entry_bits is the policy):
+// kEntryColLds: the colour table is staged in LDS behind the sphere prefix and SHADE reads the winner's colour there -- in the layout of pooled_col_lds_bytes;
+// kEntryRtFlags: KParams::leaf_box and KParams::dark are read at run time, as in every other instantiation -- without it both are ON by construction and
+// BOX / BOX2 / SHADE carry neither the scalar load nor the mask term (a launch with either flag clear must not take such a kernel)
+constexpr int kEntryModeMask = 3, kEntryColLds = 4, kEntryRtFlags = 8;
+// The two launch flags the ENTRY kernels without kEntryRtFlags were compiled for
+constexpr bool pooled_entry_flags_const(int leaf_box, int dark) { return leaf_box != 0 && dark != 0; }
+// The LDS of a 16-wave workgroup of a kEntryColLds kernel on a scene of n_nodes inner nodes and n_sph spheres, all of it staged: the sign-ordered records PACKED
+// (kPsNodeBytes each, rounded up to 16 bytes in all: the other kernels keep the 64-byte pitch of the planes and leave 8 bytes per node unused), the spheres, the
+// colours, the waves' regions.  rgbbox: 22 352 + 6 400 + 6 400 + 16 x 7 952 = 162 384 of 163 840 bytes.
+constexpr size_t pooled_col_lds_bytes(int n_nodes, int n_sph, int capb, int capl, int ray_planes) {
+  return (((size_t)n_nodes * kPsNodeBytes + 15) & ~(size_t)15) + (size_t)n_sph * 32 + (size_t)16 * pooled_wave_dw(ray_planes, capb, capl) * sizeof(unsigned);
+}
+// Does that fit a CU (never at the price of a wave: a scene whose table does not fit keeps the load from memory)?
+constexpr bool pooled_col_fits(size_t col_lds_bytes, size_t lds_limit) { return col_lds_bytes <= lds_limit; }
+// The ENTRY template value of a launch whose mode is `mode` (kEntryLists / kEntryCount): flags constant where both are set, colours in LDS where they fit and
+// the flags are constant (the run-time twin is the kernel as it was: it keeps the global load).  `col_lds`: the context's option (0: never)
+constexpr int pooled_entry_bits(int mode, int leaf_box, int dark, size_t col_lds_bytes, size_t lds_limit, bool col_lds = true) {
+  return !pooled_entry_flags_const(leaf_box, dark) ? mode | kEntryRtFlags : mode | (col_lds && pooled_col_fits(col_lds_bytes, lds_limit) ? kEntryColLds : 0);
+}
 hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays = 0, int entry = 0);
 // fills p.entry for the launch launch_pooled(p, stats, grid, waves_per_wg, stream) is about to make (hipErrorInvalidValue: that launch has no ENTRY instantiation)
 hipError_t launch_tile_entry(const KParams &p, bool stats, int waves_per_wg, hipStream_t stream);

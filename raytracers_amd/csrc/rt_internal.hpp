@@ -84,9 +84,13 @@ struct rt_context {
   hipStream_t sort_stream = nullptr, sort_stream_px = nullptr;   // the sort streams (eager_sort): a recorded view's tile order; its pixel list
   hipEvent_t rec_event = nullptr;      // main stream -> sort stream: "the recording frame has been enqueued up to here"
   unsigned *queue_dev = nullptr;
-  int entry_lists = -1;     // pooled family: new primary rays start at their tile's entry list instead of the root (lane_core.h: tile_entry; same pixels, fewer box tests).  -1 (default): the launches whose instantiation exists with ENTRY (rt_device.hpp: pooled_entry_ok) and whose tiles are 8 consecutive image rows; 0: never; 1: every launch with such an instantiation
-  unsigned *entry_dev = nullptr;   // ... the table of the launch in flight (rt_device.hpp: KParams::entry), a block of the arena / pool kept and grown (api.cpp: set_entry)
+  int entry_lists = -1;     // pooled family: new primary rays start at their tile's entry list instead of the root (lane_core.h: tile_entry; same pixels, fewer box tests).  -1 (default): the launches whose instantiation exists with ENTRY (rt_device.hpp: pooled_entry_ok), whose tiles are 8 consecutive image rows, while options leaf_box and dark_stop are both on (the ENTRY kernel has both flags compiled in; a launch whose flag is clear anyway -- it records, or a camera fails the filter's guard -- takes the twin that reads them); 0: never; 1: every launch with such an instantiation, one with a flag clear through that twin
+  unsigned *entry_dev = nullptr;   // ... the table of a launch that has no view to keep it (a camera per frame; entry_keep = 0): a block of the arena / pool kept and grown, refilled ahead of each such launch (api.cpp: set_entry)
   size_t entry_bytes = 0;
+  int entry_keep = -1;      // a view keeps its table of entry lists between its launches (TileOrder::entry; built by the first launch that wants it).  0: every launch builds its table in entry_dev
+  int col_lds = -1;         // the ENTRY kernels stage the colour table in LDS where it fits next to 16 waves (rt_device.hpp: pooled_col_fits).  0: SHADE loads the winner's colour from memory
+  uint64_t entry_tables_built = 0, entry_tables_kept = 0;   // launches of tile_entry_kernel by this context / launches that found their view's table in place (rt_context_entry_info)
+  int last_entry = 0;       // the ENTRY template value of the last pooled render launch (0: it started at the root)
   bool entry_count = false;        // option entry_count: launches that carry a table run the counting twin of the ENTRY kernel (two words per wave; rt_context_entry_counts)
   unsigned long long *entry_counts_dev = nullptr;
   size_t entry_counts_bytes = 0;
@@ -165,6 +169,13 @@ struct TileOrder {
   int *cost = nullptr;    // [ntiles] record written by the render kernel
   int *order = nullptr;   // [rtk::order_table_ints(ntiles)] position -> tile table for the next frames, then the shards' class tables
   bool valid = false;     // order[] has been computed from a previous frame
+  // the view's table of entry lists (rt_device.hpp: KParams::entry; kEntryDw dwords per tile), one more region of the block -- nullptr: the view was made for a
+  // launch shape that has no ENTRY kernel.  Its inputs are the view's key, the scene's tree (a scene update resets every view: reset_views) and the leaf
+  // filter it was built under; built on entry_ctx's stream, so only that context's launches read it without building it again
+  unsigned *entry = nullptr;
+  bool entry_valid = false;
+  int entry_filter = 0;
+  rt_context *entry_ctx = nullptr;
   // pixel tickets (single frames of the view; rt_device.hpp): the per-pixel record of the first frame, the list sorted from it
   unsigned char *cost_px = nullptr;   // [cost_px_bytes] rays traced per pixel, indexed like the framebuffer (h * w: a part rendered in place stores at its rows' places)
   unsigned *px_list = nullptr;        // [px_elems] the part's pixels, longest chains first; then the header (rtk::kPxHdrInts)
