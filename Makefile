@@ -146,6 +146,12 @@ build/entry_check: tools/entry_check.cpp $(CSRC)/lane_core.h $(CSRC)/rt_host.hpp
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -fopenmp -I$(CSRC) -o $@ tools/entry_check.cpp $(OBJ)/host_build.o
 
+# the exit lists of the kEntryExit kernels on the CPU: every bounce ray of a frame from the root and from the list of the sphere it leaves,
+# over the product's records and the tables exit_tables_path writes; the lemma against sampled rays; two mutants that must be found; in the CPU test suite
+build/exit_check: tools/exit_check.cpp $(CSRC)/lane_core.h $(CSRC)/rt_host.hpp $(OBJ)/host_build.o
+	@mkdir -p build
+	$(CXX) $(HOSTFLAGS) -fopenmp -I$(CSRC) -o $@ tools/exit_check.cpp $(OBJ)/host_build.o
+
 # box_hit_presorted on operands picked by the ray's sign offsets out of a sign-ordered record (lane_core.h) against box_hit_interval; in the CPU test suite
 build/box_presorted_check: tools/box_presorted_check.cpp $(CSRC)/lane_core.h
 	@mkdir -p build
@@ -222,7 +228,7 @@ build/first_call_probe: tools/first_call_probe.c include/ray.h $(LIB)
 	@mkdir -p build
 	$(CC) -O2 -std=gnu99 -Wall -Iinclude -o $@ tools/first_call_probe.c -Lraytracers_amd -lray_mi355x -Wl,-rpath,'$$ORIGIN/../raytracers_amd'
 
-tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/batch_trim_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/dark_stop_check build/leaf_box_check build/entry_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/plane_query_bound_check build/box_presorted_check build/sweep_check build/along_check build/path_check build/clusters_check build/view_order_check
+tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/batch_trim_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/dark_stop_check build/leaf_box_check build/entry_check build/exit_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/plane_query_bound_check build/box_presorted_check build/sweep_check build/along_check build/path_check build/clusters_check build/view_order_check
 
 oracle:
 	$(MAKE) -s -C oracle

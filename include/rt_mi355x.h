@@ -116,6 +116,14 @@ int rt_context_entry_counts(rt_context *ctx, uint64_t *lists, uint64_t *fallback
  * entry=lists launch built until the scene is updated, the leaf filter it was built under changes or the view is evicted; a batch with a camera per frame has no
  * view and builds its table per launch (option "entry_keep" = 0: every launch does).  Any pointer may be NULL.  No device work. */
 int rt_context_entry_info(rt_context *ctx, int32_t *colour_lds, int32_t *flags_const, uint64_t *tables_built, uint64_t *tables_kept);
+/* Exit lists (option "exit_lists": -1, the default, and 1: every launch of the kernel that has the leaf filter and the dark stop compiled in and the colours in
+ * LDS, where the tables fit next to its 16 waves; 0: never): a ray that has just scattered starts at the list of the sphere it leaves -- a node of even depth
+ * <= *dmax on that sphere's chain, and the siblings of the chain above it two to a record -- when it passes that node's box, else at the root (same
+ * pixels, fewer box tests).  Of the context's LAST pooled render launch: *active = 1 when its scattered rays did; under option "entry_count" = 1 also *lists = the
+ * scattered rays that started from a list and *fallbacks = those that had one and took the root (both 0 otherwise).  Of the context: *tables_built = times its
+ * launches built the tables, *tables_kept = launches that found their scene's tables in place (a context keeps the tables of the last tree it rendered;
+ * rt_prepared_update_spheres makes a new tree).  *dmax is a compile-time constant.  Any pointer may be NULL.  Synchronises the context when it reads counts. */
+int rt_context_exit_info(rt_context *ctx, int32_t *active, int32_t *dmax, uint64_t *tables_built, uint64_t *tables_kept, uint64_t *lists, uint64_t *fallbacks);
 int rt_context_sync(rt_context *ctx);
 /* Threads: every entry that takes a context holds that context's lock for the duration of the call (as a Futhark context does:
  * SURVEY.md 8b) -- host threads may share a context, a prepared scene and a scene; their calls are serialised and their frames
@@ -125,7 +133,7 @@ int rt_context_set_variant(rt_context *ctx, int variant);
 /* Tuning knobs by name (see DESIGN.md "knobs"); unknown name -> error.  None changes a pixel.  Among them "dark_stop" (-1 | 0 | 1, see rt_context_last_launch above):
  * rt_render_stats always counts the reference's full chains; rt_render_trace counts the stopped chains under dark_stop = 1 only.  "leaf_box" (-1 | 0 | 1) likewise:
  * rt_render_trace's leaf items are the reference's sphere tests unless leaf_box = 1.  "entry_lists" (-1 | 0 | 1): see rt_context_last_launch above; the instrumented launches
- * always start at the root.  "entry_keep" (-1 | 0) and "col_lds" (-1 | 0): see rt_context_entry_info above -- 0 builds the table of entry lists in every launch / loads the
+ * always start at the root.  "exit_lists" (-1 | 0 | 1): see rt_context_exit_info above.  "entry_keep" (-1 | 0) and "col_lds" (-1 | 0): see rt_context_entry_info above -- 0 builds the table of entry lists in every launch / loads the
  * winner's colour from memory in every launch. */
 int rt_context_set_option(rt_context *ctx, const char *name, int64_t value);
 int rt_context_device_info(const rt_context *ctx, int *device, int *num_cu, int *lds_bytes, char *name, int name_len);

@@ -99,6 +99,17 @@ class Context:
         self._check(lib.rt_context_entry_info(self._h, C.byref(col), C.byref(const), C.byref(built), C.byref(kept)))
         return {"colour_lds": bool(col.value), "flags_const": bool(const.value), "tables_built": built.value, "tables_kept": kept.value}
 
+    def exit_info(self):
+        """exit lists (option exit_lists: -1 default, 0 never, 1 wherever legal): {"active": the last pooled render launch started its scattered rays at
+        their origin sphere's exit list, "dmax": the depth the lists resume at (compile time), "tables_built" / "tables_kept": times this context's launches
+        built the tables / found them in place, "lists" / "fallbacks": under option entry_count = 1 the scattered rays of that launch that started from a
+        list / had one and took the root}"""
+        act, dmax = C.c_int32(), C.c_int32()
+        built, kept, lists, falls = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(lib.rt_context_exit_info(self._h, C.byref(act), C.byref(dmax), C.byref(built), C.byref(kept), C.byref(lists), C.byref(falls)))
+        return {"active": bool(act.value), "dmax": dmax.value, "tables_built": built.value, "tables_kept": kept.value, "lists": lists.value,
+                "fallbacks": falls.value}
+
     @property
     def rccl_ranks(self):
         """ranks of the RCCL communicator behind a multi-device context's gather (0: RCCL is not what carries it)"""

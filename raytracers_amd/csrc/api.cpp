@@ -596,6 +596,35 @@ int set_entry(rt_context *ctx, const Plan &pl, TileOrder *to, rtk::KParams *p, i
   return 0;
 }
 
+// Exit lists (lane_core.h: exit_tables_path): which launches start their scattered rays below the root.  Called behind set_entry: only the ENTRY
+// kernel with the flags compiled in and the colours in LDS has the twin, and only where the pair records fit next to its 16 waves (never a wave fewer); a launch
+// that does not qualify runs without them, as one whose colour table does not fit keeps its load.  The tables belong to the TREE (rt_prepared::tree_gen), not
+// to a view: the context keeps the last tree's, built on its stream; *build tells whether this launch has to fill them.
+int set_exit(rt_context *ctx, const rt_prepared *ps, const Plan &pl, rtk::KParams *p, int *entry, bool *build) {
+  p->exit_tab = nullptr; p->exit_room = 0;
+  *build = false;
+  if (ctx->exit_lists == 0 || (*entry & (rtk::kEntryColLds | rtk::kEntryRtFlags)) != rtk::kEntryColLds || pl.lds_nodes != p->n_nodes) return 0;
+  if (!rtk::pooled_exit_fits(p->n_nodes, p->n_sph, p->capb, p->capl, p->ray_planes, static_cast<size_t>(std::min(ctx->lds_bytes, 160 * 1024)))) return 0;
+  // what one SHADE may find plus add under the box stack's bound: the blocks above the SHADE's hold at most 64 (H - 3) + 128 items
+  const int room = p->capb - 64 * std::max(0, ps->height - 3) - 128;
+  if (room < 64 + 63) return 0;
+  const size_t need = rtk::exit_tab_bytes(p->n_sph);
+  if (ctx->exit_bytes < need) {
+    drain_streams(ctx);
+    pool_free(ctx, reinterpret_cast<char *>(ctx->exit_dev), ctx->exit_bytes);
+    ctx->exit_dev = nullptr; ctx->exit_bytes = 0; ctx->exit_gen = 0;
+    char *blk = nullptr;
+    size_t bytes = need;
+    RT_HIP(ctx, pool_alloc(ctx, &blk, &bytes));
+    ctx->exit_dev = reinterpret_cast<float4 *>(blk);
+    ctx->exit_bytes = bytes;
+  }
+  *build = ctx->exit_gen != ps->tree_gen;
+  p->exit_tab = ctx->exit_dev; p->exit_room = room;
+  *entry |= rtk::kEntryExit;
+  return 0;
+}
+
 // The name of the pooled instantiation these parameters launch (rt_context_last_launch)
 std::string pooled_launch_name(const rtk::KParams &p, int waves, int rays = 0) {
   rtk::PooledKey k{};
@@ -1096,6 +1125,18 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
   int entry = 0;
   bool build_entry = false;
   if (int rc = set_entry(ctx, pl, to, &p, &entry, &build_entry)) return rc;
+  bool build_exit = false;
+  if (int rc = set_exit(ctx, ps, pl, &p, &entry, &build_exit)) return rc;
+  if (p.exit_tab) {
+    if (build_exit) {
+      ctx->exit_gen = 0;
+      RT_HIP(ctx, rtk::launch_exit_tables(p, ctx->exit_dev, ctx->stream));
+      ctx->exit_gen = ps->tree_gen;
+      ctx->exit_tables_built++;
+    } else {
+      ctx->exit_tables_kept++;
+    }
+  }
   if (p.entry) {
     if (build_entry) {
       RT_HIP(ctx, rtk::launch_tile_entry(p, false, pl.waves, ctx->stream));
@@ -1106,7 +1147,8 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
     if (to != nullptr && p.entry == to->entry) to->entry_valid = true;
     if (ctx->entry_count) {
       // (option entry_count, a test's aid: the counting twin, two words per wave -- rays started from a list, rays sent back to the root -- read by rt_context_entry_counts)
-      const size_t nw = static_cast<size_t>(pl.grid) * static_cast<size_t>(pl.waves), bytes = nw * 2 * sizeof(unsigned long long);
+      // (... and with exit lists two more behind those: scattered rays started from a list, and sent back to the root -- rt_context_exit_info)
+      const size_t nw = static_cast<size_t>(pl.grid) * static_cast<size_t>(pl.waves), bytes = nw * 4 * sizeof(unsigned long long);
       if (ctx->entry_counts_bytes < bytes) {
         drain_streams(ctx);
         if (ctx->entry_counts_dev) (void)hipFree(ctx->entry_counts_dev);
@@ -1235,6 +1277,7 @@ extern "C" void rt_context_destroy(rt_context *ctx) {
   if (ctx->queue_dev) (void)hipFree(ctx->queue_dev);
   if (ctx->spill_dev) (void)hipFree(ctx->spill_dev);
   pool_free(ctx, reinterpret_cast<char *>(ctx->entry_dev), ctx->entry_bytes);
+  pool_free(ctx, reinterpret_cast<char *>(ctx->exit_dev), ctx->exit_bytes);
   if (ctx->entry_counts_dev) (void)hipFree(ctx->entry_counts_dev);
   if (ctx->order_scratch) (void)hipFree(ctx->order_scratch);
   if (ctx->px_scratch) (void)hipFree(ctx->px_scratch);
@@ -1285,6 +1328,32 @@ extern "C" int rt_context_entry_info(rt_context *ctx, int32_t *colour_lds, int32
   if (flags_const) *flags_const = ctx->last_entry != 0 && (ctx->last_entry & rtk::kEntryRtFlags) == 0;
   if (tables_built) *tables_built = ctx->entry_tables_built;
   if (tables_kept) *tables_kept = ctx->entry_tables_kept;
+  return 0;
+}
+
+// Exit lists (option "exit_lists"): of the last pooled render launch, whether its scattered rays started from exit lists (*active) and the compile-time depth
+// the lists resume at (*dmax); of the context, how many times its launches built the tables (launches of exit_tables_kernel) and how many launches found their
+// scene's tables in place; and, when that launch ran the counting twin (option entry_count), the scattered rays that started from a list and the ones that had
+// a list and took the root (their list's box failed, or the box stack had no room) -- both 0 otherwise.  Synchronises the context's stream for the counts.
+extern "C" int rt_context_exit_info(rt_context *ctx, int32_t *active, int32_t *dmax, uint64_t *tables_built, uint64_t *tables_kept, uint64_t *lists, uint64_t *fallbacks) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  const bool on = (ctx->last_entry & rtk::kEntryExit) != 0;
+  if (active) *active = on;
+  if (dmax) *dmax = rtk::kExitDmax;
+  if (tables_built) *tables_built = ctx->exit_tables_built;
+  if (tables_kept) *tables_kept = ctx->exit_tables_kept;
+  uint64_t l = 0, f = 0;
+  const int64_t nw = ctx->entry_counts_waves;
+  if (on && nw > 0 && (lists || fallbacks)) {
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<unsigned long long> h(static_cast<size_t>(nw) * 2);
+    RT_HIP(ctx, hipMemcpy(h.data(), ctx->entry_counts_dev + 2 * nw, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < nw; ++i) { l += h[2 * i]; f += h[2 * i + 1]; }
+  }
+  if (lists) *lists = l;
+  if (fallbacks) *fallbacks = f;
   return 0;
 }
 
@@ -1439,6 +1508,8 @@ extern "C" int rt_context_set_option(rt_context *ctx, const char *name, int64_t 
     ctx->leaf_box = std::max(-1, std::min(1, v));
   } else if (k == "entry_lists") {
     ctx->entry_lists = std::max(-1, std::min(1, v));
+  } else if (k == "exit_lists") {
+    ctx->exit_lists = std::max(-1, std::min(1, v));
   } else if (k == "entry_count") {
     ctx->entry_count = v != 0;
   } else if (k == "entry_keep") {
@@ -1824,6 +1895,7 @@ extern "C" int rt_prepared_update_spheres(rt_context *ctx, rt_prepared *ps, cons
   RT_HIP(ctx, hipSetDevice(ctx->device));
   (void)hipGetLastError();
   reset_views(ctx, ps);
+  ps->tree_gen = next_tree_gen();   // (exit tables built from the old tree are no longer this scene's)
   hipError_t e = hipSuccess;
   if (int rc = build_from_device(ctx, ps, spheres7_dev, &e)) return rc;
   if (e != hipSuccess) return hip_fail(ctx, e, "rt_prepared_update_spheres");

@@ -525,4 +525,97 @@ RT_HD void tile_entry(const TileRays &t, bool rays_ok, const float root_lo[3], c
     if (i < nl) out[2 + i] = (uint32_t)~leaf[i] << ref_shift;
 }
 
+// ---- exit lists: a ray that has just scattered starts below the root -------------------------------------
+// For a leaf j take its chain of ancestors c_0 = root, c_1, ... and the siblings s_k (the child of c_{k-1} that is not on the chain).
+// A walk from the root whose ray passes the box of every c_k, k <= e, tests exactly the leaves that the walks from c_e and from
+// s_1 ... s_e test, each sibling under the verdict of its own box.  Two siblings make one PAIR RECORD -- a node record whose two child
+// slots are copied bit for bit from the siblings' slots in their real parents' records -- so that an ordinary BOX item naming it gives
+// both verdicts.  The list of j: the node E = c_e, e even and <= kExitDmax, its box, and the e / 2 pair records above it.
+// Legality: (host side of it, here) every c_k, k < e, CONTAINS E's box component-wise on the floats as stored, all of them finite;
+// (per ray, in SHADE) the ray passes box_hit on E's box.  The lemma of DESIGN.md 3.4c then gives a pass on every c_k.
+// The table: kExitPairs pair records of 16 floats in the nodes64 format, then 8 dwords per sphere:
+//   {E.lo.xyz, E's ref | pair 1's ref << 16} {E.hi.xyz, pair 2's ref | pair 3's ref << 16},
+// a ref being the record's index (pair record p: n_nodes + p) times `ref_mul` -- the kernel's: kPsNodeBytes / 8, the byte offset of the staged record / 8 --
+// in 16 bits (the caller checks that the scene fits: rt_device.hpp, pooled_exit_fits); E's ref 0: no list.
+// `MUT`: the faults tools/exit_check.cpp must find (1: no nesting check); 0 everywhere else.
+constexpr int kExitDmax = 4;
+constexpr int kExitPairs = (4 << kExitDmax) / 3 - 1;   // 4 + 16 + ... + 2^Dmax: one pair record per node of depth 2, 4, ... Dmax (4: 20; 6: 84)
+constexpr int kExitStack = 48;                         // exit_tables_path's private stack (overflow: the leaves not reached get no list)
+// pair record i (1-based: the siblings of depth 2i - 1 and 2i) of the paths whose first 2i turns are `prefix` (left = 0, the first turn in the highest bit)
+constexpr int exit_pair_id(int i, int prefix) { return ((4 << (2 * (i - 1))) / 3 - 1) + prefix; }
+
+// Path t of kExitDmax turns from the root (bit kExitDmax - k of t is turn k): writes the pair records the path is the first to reach and
+// the entries of the leaves whose list resumes on it.  The table must be zeroed beforehand; paths write disjoint words.
+template <int MUT = 0>
+RT_HD void exit_tables_path(int t, const float root_lo[3], const float root_hi[3], const float *nodes64, int n_nodes, int n_sph, float *tab, int ref_mul = kPsNodeBytes / 8) {
+  constexpr int D = kExitDmax;
+  if (n_nodes < 1) return;
+  float clo[D + 1][3], chi[D + 1][3];    // the chain's boxes, [0] the root's
+  int cidx[D + 1];                       // ... and node indices
+  float srec[D + 1][8];                  // sibling k's slot: lo.xyz, w of the lo quarter, hi.xyz, its reference word
+  for (int a = 0; a < 3; ++a) { clo[0][a] = root_lo[a]; chi[0][a] = root_hi[a]; }
+  cidx[0] = 0;
+  int depth = 0, leaf = -1, cur = 0;
+  for (int k = 1; k <= D; ++k) {
+    if (leaf >= 0) continue;
+    const int bit = (t >> (D - k)) & 1;
+    const float *const rec = nodes64 + 16 * (size_t)cur;
+    for (int s = 0; s < 2; ++s) {
+      if (s == bit) {
+        for (int a = 0; a < 3; ++a) { clo[k][a] = rec[8 * s + a]; chi[k][a] = rec[8 * s + 4 + a]; }
+      } else {
+        for (int a = 0; a < 3; ++a) { srec[k][a] = rec[8 * s + a]; srec[k][4 + a] = rec[8 * s + 4 + a]; }
+        srec[k][3] = 0.0f;
+        srec[k][7] = rec[4 * s + 3];
+      }
+    }
+    int32_t w;
+    __builtin_memcpy(&w, rec + 4 * bit + 3, 4);
+    depth = k;
+    if ((w >> 8) < 0) leaf = ~(w >> 8);
+    else { cur = w >> 8; cidx[k] = cur; }
+  }
+  // (a path that ends at a leaf of depth < D is shared by the paths that differ in the turns behind it: the one whose are all left does the work)
+  if (leaf >= 0 && (t & ((1 << (D - depth)) - 1)) != 0) return;
+  for (int i = 1; 2 * i <= depth; ++i) {
+    if ((t & ((1 << (D - 2 * i)) - 1)) != 0) continue;
+    float *const out = tab + 16 * (size_t)exit_pair_id(i, t >> (D - 2 * i));
+    const float *const a = srec[2 * i - 1], *const b = srec[2 * i];
+    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[7];      // {L.lo, left ref}
+    out[4] = a[4]; out[5] = a[5]; out[6] = a[6]; out[7] = b[7];      // {L.hi, right ref}
+    out[8] = b[0]; out[9] = b[1]; out[10] = b[2]; out[11] = 0.0f;    // {R.lo, .}
+    out[12] = b[4]; out[13] = b[5]; out[14] = b[6]; out[15] = 0.0f;  // {R.hi, .}
+  }
+  // the node the lists of this path resume at: the deepest INNER node of even depth on it
+  const int e = leaf >= 0 ? (depth - 1) & ~1 : D;
+  if (e < 2) return;
+  bool nested = true;
+  for (int a = 0; a < 3; ++a) nested = nested & (clo[e][a] > -kNoHit) & (chi[e][a] < kNoHit);
+  for (int k = 0; k < e; ++k)
+    for (int a = 0; a < 3; ++a) nested = nested & (clo[k][a] <= clo[e][a]) & (chi[k][a] >= chi[e][a]) & (clo[k][a] > -kNoHit) & (chi[k][a] < kNoHit);
+  if (MUT != 1 && !nested) return;
+  uint32_t ref[4] = {(uint32_t)cidx[e] * (uint32_t)ref_mul, 0u, 0u, 0u};
+  for (int i = 1; 2 * i <= e; ++i) ref[i] = (uint32_t)(n_nodes + exit_pair_id(i, t >> (D - 2 * i))) * (uint32_t)ref_mul;
+  const uint32_t w0 = ref[0] | ref[1] << 16, w1 = ref[2] | ref[3] << 16;
+  auto put = [&](int j) {
+    if (j < 0 || j >= n_sph) return;
+    float *const out = tab + 16 * (size_t)kExitPairs + 8 * (size_t)j;
+    for (int a = 0; a < 3; ++a) { out[a] = clo[e][a]; out[4 + a] = chi[e][a]; }
+    __builtin_memcpy(out + 3, &w0, 4);
+    __builtin_memcpy(out + 7, &w1, 4);
+  };
+  if (leaf >= 0) { put(leaf); return; }
+  int stack[kExitStack], sp = 0;
+  stack[sp++] = cur;
+  while (sp > 0) {
+    const float *const rec = nodes64 + 16 * (size_t)stack[--sp];
+    for (int s = 0; s < 2; ++s) {
+      int32_t w;
+      __builtin_memcpy(&w, rec + 4 * s + 3, 4);
+      if ((w >> 8) < 0) put(~(w >> 8));
+      else if (sp < kExitStack) stack[sp++] = w >> 8;
+    }
+  }
+}
+
 }  // namespace rtk

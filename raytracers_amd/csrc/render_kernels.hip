@@ -683,6 +683,8 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
   constexpr bool ECOUNT = (ENTRY & kEntryModeMask) == kEntryCount;         // the counting twin
   constexpr bool ECONST = ENTRY != 0 && (ENTRY & kEntryRtFlags) == 0;      // leaf filter and dark stop on by construction
   constexpr bool ECOL = (ENTRY & kEntryColLds) != 0;                       // col[n_sph] in LDS behind the sphere prefix
+  constexpr bool EXIT = (ENTRY & kEntryExit) != 0;                         // scattered rays start at their origin sphere's exit list
+  static_assert(!EXIT || (ECONST && ECOL), "EXIT: the kernel with the flags compiled in and the colours in LDS only");
   static_assert(!ENTRY || ((ENTRY & kEntryModeMask) == kEntryLists || ECOUNT), "ENTRY: lists, or the counting twin");
   static_assert(!ENTRY || (THREADS == 1024 && ALL_LDS && !STATS && !SOLO && TAIL == 0 && !ORD && !CULL && SPILL == 0 && RAYS == 0), "ENTRY: the plain 16-wave kernel of a scene in LDS only");
   static_assert(!RAYS || (!STATS && !SOLO && TAIL == 0 && !ORD && !CULL), "RAYS: the plain instantiations only");
@@ -696,7 +698,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
   extern __shared__ float4 smem[];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int plane = p.lds_nodes;          // float4 per node plane
+  const int plane = EXIT ? p.lds_nodes + kExitPairs : p.lds_nodes;          // float4 per node plane (EXIT: the pair records are staged behind the nodes)
   // (ECOL: the sign-ordered records packed, kPsNodeBytes each -- their addresses do not depend on the planes' pitch -- which is what makes room for the
   // colour table next to 16 waves: rt_device.hpp, pooled_col_lds_bytes)
   const int sph_base = ECOL ? (plane * (kPsNodeBytes / 4) + 3) >> 2 : 4 * plane;
@@ -721,7 +723,9 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
     // and from bit 11 the byte offset of the node's record, or ~leaf.  The staged child references are stored in that form)
     auto ref_of = [](float w) { const int c = f2i(w) >> 8; return (unsigned)(c < 0 ? c : c * kPsNodeBytes) << kPsItemShift; };
     for (int i = threadIdx.x; i < plane; i += THREADS) {
-      const float4 ll = p.nodes64[4 * i], lh = p.nodes64[4 * i + 1], rl = p.nodes64[4 * i + 2], rh = p.nodes64[4 * i + 3];
+      const float4 *src = p.nodes64 + 4 * i;
+      if constexpr (EXIT) src = i < p.lds_nodes ? src : p.exit_tab + 4 * (i - p.lds_nodes);   // (a pair record: two siblings of a chain as one node's children)
+      const float4 ll = src[0], lh = src[1], rl = src[2], rh = src[3];
       presort_pack(reinterpret_cast<unsigned *>(smem) + (kPsNodeBytes / 4) * i, &ll.x, &lh.x, &rl.x, &rh.x, ref_of(ll.w), ref_of(lh.w));
     }
   } else {
@@ -750,6 +754,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
   // ---- wave state (uniform) ----
   int nbox = 0, nleaf = 0;
   unsigned ec_lists = 0u, ec_fall = 0u;   // (ENTRY == kEntryCount)
+  unsigned ex_lists = 0u, ex_fall = 0u;   // (... with EXIT: scattered rays started from an exit list / that had one and took the root)
   // SPILL (four-wave workgroups in the shape of twenty waves per CU, tall trees): p.capb is smaller than the stack's bound (trees taller than 15 levels do not
   // leave a wave 64 H + 63 dwords there).  A full BOX operation that could push beyond it first moves the OLDEST half of the stack -- its bottom -- to the wave's
   // region of p.spill; the newest spilled chunk comes back when the LDS stack has run empty; no SHADE while anything is spilled.  The order of the operations is
@@ -942,6 +947,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           // ---- SHADE: finish completed folds, refill vacant slots, push the new roots ----
           RT_MARK("SHADE_BEGIN");
           bool root = false;
+          uint4 ent0 = make_uint4(0u, 0u, 0u, 0u), ent1 = ent0;   // (ENTRY) the list of a new primary ray's position; header 0: none.  (EXIT) a scattered ray's exit list
           if (STATS) tr_ops[2]++;
           const unsigned long long tr_s0 = STATS ? clock64() : 0ull;
           if constexpr (ANY) {
@@ -1003,6 +1009,11 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
             }
             if (more) {
               root = true;
+              if constexpr (EXIT) {   // the exit list of the sphere the ray leaves (it only picks the list: the list's own box test decides, below)
+                const uint4 *const xp = reinterpret_cast<const uint4 *>(p.exit_tab + 4 * kExitPairs) + 2 * wj;
+                ent0 = xp[0];
+                ent1 = xp[1];
+              }
             } else if constexpr (RAYS) {
               pix = -1;
             } else {
@@ -1017,7 +1028,6 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           }
           bool want = (pix < 0) & !exhausted & !hold;
           int slot = -1;
-          uint4 ent0 = make_uint4(0u, 0u, 0u, 0u), ent1 = ent0;   // (ENTRY) the list of a new primary ray's position; header 0: none
           float a_lo = p.ray_tlo, a_hi = p.ray_thi;   // (ANY: the interval of the ray a lane draws)
           unsigned long long m = bal(want);
           while (ORD && m != 0ull) {     // pixel tickets: the next pixels of the view's list
@@ -1240,8 +1250,43 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           }
           // A new fold starts with the ROOT's box test (items are nodes whose own box passed).
           if (root) ray_derive(r);   // one place for both scattered and primary rays
-          const bool root_hit = root && (ANY ? interval_ok(a_lo, a_hi) && box_hit_interval(r, p.root_lo[0], p.root_lo[1], p.root_lo[2], p.root_hi[0], p.root_hi[1], p.root_hi[2], a_lo, a_hi)
-                                             : box_hit(r, p.root_lo[0], p.root_lo[1], p.root_lo[2], p.root_hi[0], p.root_hi[1], p.root_hi[2]));
+          bool root_hit;
+          bool xl = false;       // (EXIT) the lane's ray starts from its exit list: E's item and xnp pair items
+          int xnp = 0;
+          if constexpr (!EXIT) {
+            root_hit = root && (ANY ? interval_ok(a_lo, a_hi) && box_hit_interval(r, p.root_lo[0], p.root_lo[1], p.root_lo[2], p.root_hi[0], p.root_hi[1], p.root_hi[2], a_lo, a_hi)
+                                    : box_hit(r, p.root_lo[0], p.root_lo[1], p.root_lo[2], p.root_hi[0], p.root_hi[1], p.root_hi[2]));
+          } else {
+            // A scattered ray with a list tests the box of the node E its list resumes at in place of the root's -- the same code on other operands: E's box is
+            // nested in every ancestor's (the table's builder checked the floats), so a pass on it is a pass on all of them and the walk from
+            // {E, the siblings of E's chain} tests the leaves the walk from the root tests.  A ray that fails E's box, and every list ray of a SHADE whose items
+            // would not leave the box stack its bound, takes the root's test and the root item.
+            xl = root & (slot < 0) & ((ent0.w & 0xffffu) != 0u);
+            float blx = p.root_lo[0], bly = p.root_lo[1], blz = p.root_lo[2], bhx = p.root_hi[0], bhy = p.root_hi[1], bhz = p.root_hi[2];
+            if (xl) {
+              blx = __uint_as_float(ent0.x); bly = __uint_as_float(ent0.y); blz = __uint_as_float(ent0.z);
+              bhx = __uint_as_float(ent1.x); bhy = __uint_as_float(ent1.y); bhz = __uint_as_float(ent1.z);
+            }
+            root_hit = root && box_hit(r, blx, bly, blz, bhx, bhy, bhz);
+            const unsigned long long m_x = bal(xl);
+            if (m_x != 0ull) {
+              xnp = xl ? ((ent0.w >> 16) != 0u) + ((ent1.w & 0xffffu) != 0u) + ((ent1.w >> 16) != 0u) : 0;
+              bool back = xl & !root_hit;       // E's box failed
+              // (the stack: what this SHADE found plus what it adds, counted exactly -- ballots and popcounts -- against KParams::exit_room)
+              int added = __popcll(bal(root_hit));
+              for (int k = 0; k < kExitDmax / 2; ++k) added += __popcll(bal(root_hit & (xnp > k)));
+              if (__builtin_expect(uni(nbox + added) > p.exit_room, 0)) back = xl;
+              if (__builtin_expect(bal(back) != 0ull, 0)) {
+                if (back) {
+                  root_hit = box_hit(r, p.root_lo[0], p.root_lo[1], p.root_lo[2], p.root_hi[0], p.root_hi[1], p.root_hi[2]);
+                  xl = false;
+                }
+                if constexpr (ECOUNT) ex_fall += (unsigned)__popcll(bal(back));
+              }
+              xnp = xl ? xnp : 0;
+              if constexpr (ECOUNT) ex_lists += (unsigned)__popcll(bal(xl));
+            }
+          }
           // ENTRY: which new primary rays start from their list, and the inner item each ray pushes.  The leaves must fit: the leaf list holds nleaf (0 behind
           // a drained list) + at most 64 * kEntryLeaves new items in p.capl -- decided for the wave as a whole, on the exact count (ballots and popcounts only)
           unsigned ent_hdr = 0u;
@@ -1263,7 +1308,8 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           }
           if (root) {
             wkey[lane] = ANY ? any_key_seed(a_hi) : kKeyInit;
-            wcnt[lane] = push_box ? 1 : 0;    // 0: the fold is already complete (a miss, or a list of leaves alone), shaded next time
+            if constexpr (EXIT) wcnt[lane] = push_box ? 1 + xnp : 0;   // (E's item and the pair items)
+            else wcnt[lane] = push_box ? 1 : 0;    // 0: the fold is already complete (a miss, or a list of leaves alone), shaded next time
             wray[lane] = make_float4(r.ox, r.oy, r.oz, r.a);
             wray[64 + lane] = make_float4(r.ix, r.iy, r.iz, CULL ? cull_weight(r, p.cull_c2) : ANY ? a_lo : 0.0f);   // (CULL: the ray's W2; ANY: t_min)
             if (p.ray_planes == 3) wray[128 + lane] = make_float4(r.dx, r.dy, r.dz, 0.0f);
@@ -1275,8 +1321,22 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
             nbox = uni(nbox + __popcll(m_root));
           } else {
             const unsigned low = (unsigned)lane << 2 | (PRESORT ? sign_offsets(r) << 5 : 0u);   // (slot = lane; PRESORT: + the ray's signs)
-            if (push_box) wbox[nbox + lane_rank(m_root)] = ((ent_hdr & kEntryValid) != 0u ? ent0.y : 0u) | low;   // (node 0, or the list's inner item)
+            if constexpr (!EXIT) {
+              if (push_box) wbox[nbox + lane_rank(m_root)] = ((ent_hdr & kEntryValid) != 0u ? ent0.y : 0u) | low;   // (node 0, or the list's inner item)
+            } else {   // (... or the node the exit list resumes at)
+              if (push_box) wbox[nbox + lane_rank(m_root)] = (xl ? (ent0.w & 0xffffu) << (kPsItemShift + 3) : (ent_hdr & kEntryValid) != 0u ? ent0.y : 0u) | low;
+            }
             nbox = uni(nbox + __popcll(m_root));
+            if constexpr (EXIT) {
+              // the exit lists' pair items: pair k of every list that has one, by ranks (the table holds record offsets / 8)
+              const unsigned pr[3] = {ent0.w >> 16, ent1.w & 0xffffu, ent1.w >> 16};
+              for (int k = 0; k < kExitDmax / 2; ++k) {
+                const unsigned long long m_k = bal(xnp > k);
+                if (m_k == 0ull) break;
+                if (xnp > k) wbox[nbox + lane_rank(m_k)] = pr[k] << (kPsItemShift + 3) | low;
+                nbox = uni(nbox + __popcll(m_k));
+              }
+            }
             // the lists' leaves: leaf k of every list that has one, by ranks -- the items LEAF drains next
             const unsigned lf[kEntryLeaves] = {ent0.z, ent0.w, ent1.x, ent1.y, ent1.z, ent1.w};
             const int nl = (ent_hdr & kEntryValid) != 0u ? (int)(ent_hdr >> kEntryCountShift) & 15 : 0;
@@ -1630,6 +1690,10 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
     if (lane == 0 && p.trace != nullptr) {
       unsigned long long *const rec = p.trace + 2 * (size_t)(blockIdx.x * (THREADS / 64) + wave);
       rec[0] = ec_lists; rec[1] = ec_fall;
+      if constexpr (EXIT) {
+        unsigned long long *const rex = p.trace + 2 * (size_t)nwaves + 2 * (size_t)(blockIdx.x * (THREADS / 64) + wave);
+        rex[0] = ex_lists; rex[1] = ex_fall;
+      }
     }
   }
   if (STATS) {
@@ -2086,7 +2150,7 @@ static hipError_t launch_pooled_key(const PooledKey &k, const KParams &p, int gr
 // The ENTRY twins of the one key pooled_entry_ok admits: `entry` = kEntryLists, or kEntryCount (the counting one: p.trace holds two words per wave)
 template <int ENTRY>
 static hipError_t launch_pooled_entry_t(const KParams &p, int grid, hipStream_t stream) {
-  const size_t lds = (ENTRY & kEntryColLds) ? pooled_col_lds_bytes(p.n_nodes, p.n_sph, p.capb, p.capl, p.ray_planes)
+  const size_t lds = (ENTRY & kEntryColLds) ? pooled_col_lds_bytes(p.n_nodes + ((ENTRY & kEntryExit) ? kExitPairs : 0), p.n_sph, p.capb, p.capl, p.ray_planes)
                                             : pooled_lds_bytes(p.lds_nodes, p.lds_sph, p.capb, p.capl, p.ray_planes, 16);
   auto kfn = pooled_kernel<1024, true, false, false, 0, false, false, 0, 0, ENTRY>;
   if (hipError_t e = allow_full_lds(reinterpret_cast<const void *>(kfn)); e != hipSuccess) return e;
@@ -2107,9 +2171,13 @@ static hipError_t launch_pooled_entry(const PooledKey &k, const KParams &p, int 
   // (a kernel with the flags compiled in renders only a launch that has both set; the colour table only where it fits: 160 KB per CU)
   if (!(entry & kEntryRtFlags) && !pooled_entry_flags_const(p.leaf_box, p.dark)) return hipErrorInvalidValue;
   if ((entry & kEntryColLds) && !pooled_col_fits(pooled_col_lds_bytes(p.n_nodes, p.n_sph, p.capb, p.capl, p.ray_planes), 160 * 1024)) return hipErrorInvalidValue;
+  // (exit lists: only in the kernel with the flags compiled in and the colours in LDS, with tables that fit it, on a scene staged whole)
+  if ((entry & kEntryExit) && ((entry & (kEntryColLds | kEntryRtFlags)) != kEntryColLds || p.exit_tab == nullptr || p.lds_nodes != p.n_nodes ||
+                               !pooled_exit_fits(p.n_nodes, p.n_sph, p.capb, p.capl, p.ray_planes, 160 * 1024)))
+    return hipErrorInvalidValue;
   return launch_pooled_entry_any(p, grid, stream, entry,
                                  std::integer_sequence<int, kEntryLists, kEntryLists | kEntryColLds, kEntryLists | kEntryRtFlags, kEntryCount, kEntryCount | kEntryColLds,
-                                                       kEntryCount | kEntryRtFlags>{});
+                                                       kEntryCount | kEntryRtFlags, kEntryLists | kEntryColLds | kEntryExit, kEntryCount | kEntryColLds | kEntryExit>{});
 }
 
 // The table of entry lists of a launch (p.entry: p.nchunks positions of kEntryDw dwords -- with a camera per frame p.nframes * p.nchunks, frame-major), one
@@ -2143,6 +2211,20 @@ hipError_t launch_tile_entry(const KParams &p, bool stats, int waves_per_wg, hip
   const bool presort = pooled_presort(k);
   hipLaunchKernelGGL(tile_entry_kernel, dim3((npos + 255u) / 256u), dim3(256), 0, stream, p, presort ? kPsItemShift : 8, presort ? kPsNodeBytes : 1,
                      p.leaf_box != 0 && pooled_leaf_box(k) ? 1 : 0);
+  return hipGetLastError();
+}
+
+// The exit tables of a scene (KParams::exit_tab; the rule itself: lane_core.h, exit_tables_path).  One lane per path of kExitDmax turns from the
+// root; the caller has zeroed the block: a sphere without an entry has no list.
+__global__ __launch_bounds__(64) void exit_tables_kernel(KParams p, float4 *tab) {
+  const int t = (int)threadIdx.x;
+  if (t >= (1 << kExitDmax)) return;
+  exit_tables_path<0>(t, p.root_lo, p.root_hi, reinterpret_cast<const float *>(p.nodes64), p.n_nodes, p.n_sph, reinterpret_cast<float *>(tab));
+}
+hipError_t launch_exit_tables(const KParams &p, float4 *tab, hipStream_t stream) {
+  if (tab == nullptr || p.n_nodes < 1) return hipErrorInvalidValue;
+  if (hipError_t e = hipMemsetAsync(tab, 0, exit_tab_bytes(p.n_sph), stream); e != hipSuccess) return e;
+  hipLaunchKernelGGL(exit_tables_kernel, dim3(1), dim3(64), 0, stream, p, tab);
   return hipGetLastError();
 }
 

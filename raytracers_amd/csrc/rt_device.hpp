@@ -285,10 +285,20 @@ struct KParams {
     float *colour3;
     const unsigned *entry;
   };
-  int nrays;
+  // (... in one slot with `exit_room`, and `occluded` below with `exit_tab`: a launch has caller rays or exit lists, never both; the block keeps its size and every field its offset)
+  // pooled family, render launches, the ENTRY instantiations with kEntryExit: a ray that has just scattered off sphere j starts at the exit list of j
+  // instead of the root.  exit_tab: kExitPairs pair records in the 64-byte format of nodes64 -- staged in LDS behind the n_nodes real records --, then two uint4 per
+  // sphere (exit_tables_kernel).  exit_room: the box-stack items one SHADE may find plus add (what capb leaves under the bound of DESIGN.md 3.1).
+  union {
+    int nrays;
+    int exit_room;
+  };
   // rt_occluded_rays (the any-hit instantiations of the pooled kernel): occluded[i] = 1 iff some leaf is reached with every box tested over
   // (ray_tlo, ray_thi) and its sphere has a root strictly inside that interval, else 0
-  unsigned char *occluded;
+  union {
+    unsigned char *occluded;
+    const float4 *exit_tab;
+  };
   float ray_tlo, ray_thi;
   // rt_intersect_rays_ranged / rt_occluded_rays_ranged: ray i's own interval (ray_tlo_dev[i], ray_thi_dev[i]) in place of (ray_tlo, ray_thi); a ray
   // whose interval fails 0 <= t_min <= t_max <= 1e9 (NaN included) is a miss.  nullptr: the scalar interval (both set, or neither)
@@ -472,6 +482,18 @@ constexpr int kEntryLists = 1, kEntryCount = 2;
 // kEntryRtFlags: KParams::leaf_box and KParams::dark are read at run time, as in every other instantiation -- without it both are ON by construction and
 // BOX / BOX2 / SHADE carry neither the scalar load nor the mask term (a launch with either flag clear must not take such a kernel)
 constexpr int kEntryModeMask = 3, kEntryColLds = 4, kEntryRtFlags = 8;
+// kEntryExit (only with kEntryColLds and without kEntryRtFlags): scattered rays start at their origin sphere's exit list (KParams::exit_tab).
+// kExitDmax (lane_core.h): the deepest (even) depth of a node a list resumes at -- a compile-time constant of the kernel and of the tables; a list holds that
+// node's item and one pair item per two levels above it.  The counting twin then writes two more words per wave behind the 2 * waves words of the entry counts.
+constexpr int kEntryExit = 16;
+constexpr int kExitItems = 1 + kExitDmax / 2;          // items of a full list
+// The exit tables of a scene fit the item format (record offsets / 8 in 16 bits) and the LDS next to 16 waves
+constexpr bool pooled_exit_fits(int n_nodes, int n_sph, int capb, int capl, int ray_planes, size_t lds_limit) {
+  return n_nodes >= 1 && (size_t)(n_nodes + kExitPairs) * (kPsNodeBytes / 8) < 65536u &&
+         (((size_t)(n_nodes + kExitPairs) * kPsNodeBytes + 15) & ~(size_t)15) + (size_t)n_sph * 32 + (size_t)16 * pooled_wave_dw(ray_planes, capb, capl) * sizeof(unsigned) <= lds_limit;
+}
+// (bytes of KParams::exit_tab)
+constexpr size_t exit_tab_bytes(int n_sph) { return (size_t)kExitPairs * 64 + (size_t)n_sph * 32; }
 // The two launch flags the ENTRY kernels without kEntryRtFlags were compiled for
 constexpr bool pooled_entry_flags_const(int leaf_box, int dark) { return leaf_box != 0 && dark != 0; }
 // The LDS of a 16-wave workgroup of a kEntryColLds kernel on a scene of n_nodes inner nodes and n_sph spheres, all of it staged: the sign-ordered records PACKED
@@ -490,6 +512,8 @@ constexpr int pooled_entry_bits(int mode, int leaf_box, int dark, size_t col_lds
 hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays = 0, int entry = 0);
 // fills p.entry for the launch launch_pooled(p, stats, grid, waves_per_wg, stream) is about to make (hipErrorInvalidValue: that launch has no ENTRY instantiation)
 hipError_t launch_tile_entry(const KParams &p, bool stats, int waves_per_wg, hipStream_t stream);
+// fills `tab` (exit_tab_bytes(p.n_sph) bytes) from p's scene: the pair records and the per-sphere exit lists of the kEntryExit kernels
+hipError_t launch_exit_tables(const KParams &p, float4 *tab, hipStream_t stream);
 size_t pooled_lds_bytes(int lds_nodes, int lds_sph, int capb, int capl, int ray_planes, int waves_per_wg);
 // prepare_scene on the GPU (bvh_build.hip).  Canonical {L, I} arrays + the traversal copy.
 struct GpuBvhOut {

@@ -2,6 +2,7 @@
 // queries), futhark_shim.cpp (the Futhark boundary) and multi_gpu.cpp (one process, several devices).  Not installed; the public
 // surfaces are include/*.h.
 #pragma once
+#include <atomic>
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -91,6 +92,11 @@ struct rt_context {
   int col_lds = -1;         // the ENTRY kernels stage the colour table in LDS where it fits next to 16 waves (rt_device.hpp: pooled_col_fits).  0: SHADE loads the winner's colour from memory
   uint64_t entry_tables_built = 0, entry_tables_kept = 0;   // launches of tile_entry_kernel by this context / launches that found their view's table in place (rt_context_entry_info)
   int last_entry = 0;       // the ENTRY template value of the last pooled render launch (0: it started at the root)
+  int exit_lists = -1;      // pooled family: a ray that has just scattered starts at its origin sphere's exit list instead of the root (lane_core.h: exit_tables_path; same pixels, fewer box tests).  -1 (default) and 1: the launches of the ENTRY kernel with the flags compiled in and the colours in LDS whose tables fit next to 16 waves (rt_device.hpp: pooled_exit_fits); 0: never
+  float4 *exit_dev = nullptr;   // ... the tables (rt_device.hpp: KParams::exit_tab) of the prepared scene whose tree is exit_gen (rt_prepared::tree_gen; 0: none), built on this context's stream by the first launch that wants them and kept until a launch of another tree
+  size_t exit_bytes = 0;
+  uint64_t exit_gen = 0;
+  uint64_t exit_tables_built = 0, exit_tables_kept = 0;   // launches of exit_tables_kernel by this context / launches that found their scene's tables in place (rt_context_exit_info)
   bool entry_count = false;        // option entry_count: launches that carry a table run the counting twin of the ENTRY kernel (two words per wave; rt_context_entry_counts)
   unsigned long long *entry_counts_dev = nullptr;
   size_t entry_counts_bytes = 0;
@@ -198,7 +204,13 @@ struct TileOrder {
 constexpr int kClassSlotInts = 16, kClassSlots = 8;   // per prepared scene: one pinned slot per kept view
 constexpr int kClassChunks = 64;                       // per context: chunks of the pinned slab (prepared scenes with ordered views alive at a time; more: own allocations)
 
+inline uint64_t next_tree_gen() {
+  static std::atomic<uint64_t> g{0};
+  return ++g;
+}
+
 struct rt_prepared {
+  uint64_t tree_gen = next_tree_gen();   // names the tree in nodes64: a new number with every prepared scene and every rt_prepared_update_spheres (what a context's exit tables were built from)
   rt_context *home = nullptr;        // the context that prepared it (its arena serves the views' blocks when it also renders them)
   mutable std::recursive_mutex mu;   // the views' orders are state of the prepared scene that render entries update: held while a frame is set up
   mutable std::vector<TileOrder> orders;
