@@ -83,6 +83,11 @@ build/batch_trim_check: tools/batch_trim_check.cpp $(CSRC)/rt_device.hpp $(CSRC)
 	@mkdir -p build
 	$(HIPCC) -O2 -std=c++17 -Wall -I$(CSRC) -o $@ $<
 
+# the predicates behind the kernels with the twenty-wave shape's constants compiled in (rt_device.hpp: pooled_wide_plan, pooled_wide_ok) printed for the CPU test suite
+build/wide_const_check: tools/wide_const_check.cpp $(CSRC)/rt_device.hpp $(CSRC)/lane_core.h $(CSRC)/treelet.h
+	@mkdir -p build
+	$(HIPCC) -O2 -std=c++17 -Wall -I$(CSRC) -o $@ $<
+
 # the DONATE instantiation's mailbox protocol (render_kernels.hip) as a model, random interleavings; in the CPU test suite
 build/donate_check: tools/donate_check.cpp
 	@mkdir -p build
@@ -228,7 +233,7 @@ build/first_call_probe: tools/first_call_probe.c include/ray.h $(LIB)
 	@mkdir -p build
 	$(CC) -O2 -std=gnu99 -Wall -Iinclude -o $@ tools/first_call_probe.c -Lraytracers_amd -lray_mi355x -Wl,-rpath,'$$ORIGIN/../raytracers_amd'
 
-tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/batch_trim_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/dark_stop_check build/leaf_box_check build/entry_check build/exit_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/plane_query_bound_check build/box_presorted_check build/sweep_check build/along_check build/path_check build/clusters_check build/view_order_check
+tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/batch_trim_check build/wide_const_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/dark_stop_check build/leaf_box_check build/entry_check build/exit_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/plane_query_bound_check build/box_presorted_check build/sweep_check build/along_check build/path_check build/clusters_check build/view_order_check
 
 oracle:
 	$(MAKE) -s -C oracle

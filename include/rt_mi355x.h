@@ -124,6 +124,11 @@ int rt_context_entry_info(rt_context *ctx, int32_t *colour_lds, int32_t *flags_c
  * launches built the tables, *tables_kept = launches that found their scene's tables in place (a context keeps the tables of the last tree it rendered;
  * rt_prepared_update_spheres makes a new tree).  *dmax is a compile-time constant.  Any pointer may be NULL.  Synchronises the context when it reads counts. */
 int rt_context_exit_info(rt_context *ctx, int32_t *active, int32_t *dmax, uint64_t *tables_built, uint64_t *tables_kept, uint64_t *lists, uint64_t *fallbacks);
+/* The twenty-wave shape (option "wide_waves": workgroups of four waves, five per CU, no scene prefix in LDS, two ray planes): its plain, CULL and spilling
+ * kernels exist a second time with those constants compiled in (same pixels).  Option "wide_const": -1, the default: every render launch of that
+ * shape runs the twin; 0: the generic four-wave kernels.  rt_context_last_launch reads the same either way; *shape_const = 1 when the context's LAST pooled launch
+ * ran a twin.  The pointer may be NULL.  No device work. */
+int rt_context_wide_info(rt_context *ctx, int32_t *shape_const);
 int rt_context_sync(rt_context *ctx);
 /* Threads: every entry that takes a context holds that context's lock for the duration of the call (as a Futhark context does:
  * SURVEY.md 8b) -- host threads may share a context, a prepared scene and a scene; their calls are serialised and their frames

@@ -110,6 +110,13 @@ class Context:
         return {"active": bool(act.value), "dmax": dmax.value, "tables_built": built.value, "tables_kept": kept.value, "lists": lists.value,
                 "fallbacks": falls.value}
 
+    def wide_info(self):
+        """the twenty-wave shape's constants (option wide_const: -1 default, 0 the generic four-wave kernels): {"shape_const": the last pooled launch ran a
+        kernel with lds_nodes = lds_sph = 0 and two ray planes compiled in}; last_launch reads the same either way"""
+        const = C.c_int32()
+        self._check(lib.rt_context_wide_info(self._h, C.byref(const)))
+        return {"shape_const": bool(const.value)}
+
     @property
     def rccl_ranks(self):
         """ranks of the RCCL communicator behind a multi-device context's gather (0: RCCL is not what carries it)"""

@@ -261,6 +261,7 @@ int make_plan(rt_context *ctx, const rt_prepared *ps, Plan *pl, int64_t ntiles, 
     return fail(ctx, "LDS budget too small for the per-wave traversal scratch");
   }
   const int wgs = shapes[static_cast<size_t>(pick)].wgs;
+  pl->wgs = wgs;
   pl->waves = shapes[static_cast<size_t>(pick)].waves;
   pl->ray_planes = shapes[static_cast<size_t>(pick)].planes;
   pl->capb = capb_of(shapes[static_cast<size_t>(pick)]);
@@ -623,6 +624,16 @@ int set_exit(rt_context *ctx, const rt_prepared *ps, const Plan &pl, rtk::KParam
   p->exit_tab = ctx->exit_dev; p->exit_room = room;
   *entry |= rtk::kEntryExit;
   return 0;
+}
+
+// The shape's constants (rt_device.hpp: pooled_wide_plan, pooled_wide_ok): which pooled render launches run the twin of their kernel that has
+// lds_nodes = lds_sph = 0 and ray_planes = 2 compiled in.  Every launch whose PLAN is that shape -- four waves, five workgroups per CU, no prefix staged, two ray
+// planes -- and whose instantiation has the twin (plain and CULL, spilling or not); a four-wave plan that stages a prefix keeps the generic kernel.  Option
+// wide_const = 0: never.  Called behind set_cull (the key is the launch's).
+bool wide_const_launch(const rt_context *ctx, const Plan &pl, const rtk::KParams &p) {
+  rtk::PooledKey k{};
+  return ctx->wide_const != 0 && pl.variant == RT_VARIANT_POOLED && rtk::pooled_wide_plan(pl.waves, pl.wgs, pl.lds_nodes, pl.lds_sph, pl.ray_planes) &&
+         p.lds_nodes == pl.lds_nodes && p.lds_sph == pl.lds_sph && p.ray_planes == pl.ray_planes && rtk::choose_pooled(p, false, pl.waves, 0, &k) && rtk::pooled_wide_ok(k);
 }
 
 // The name of the pooled instantiation these parameters launch (rt_context_last_launch)
@@ -994,6 +1005,7 @@ int rti::pooled_rays_params(rt_context *ctx, const rt_prepared *ps, const Plan &
 // The launch of the pooled family's loop on caller rays (`rays`: kRaysColour, kRaysAny), and its rt_context_last_launch (" intervals=per-ray"
 // appended when each ray carries its own interval)
 int rti::launch_pooled_rays(rt_context *ctx, const rtk::KParams &p, const Plan &pl, int rays) {
+  ctx->last_wide = false;   // (the caller-ray loops have no twin with the shape's constants)
   RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream, rays));
   char buf[256];
   std::snprintf(buf, sizeof buf, "family=pooled tickets=rays instantiation=%s frames=1 tiles=%d grid=%d waves=%d counters=%d%s deep_class=0 deep_split=0 recording=0%s",
@@ -1163,8 +1175,10 @@ int rti::enqueue_render(rt_context *ctx, const rt_prepared *ps, int64_t h, int64
   }
   ctx->entry_counts_waves = (entry & rtk::kEntryModeMask) == rtk::kEntryCount ? static_cast<int64_t>(pl.grid) * pl.waves : 0;   // (the counts are the LAST pooled render launch's, or none)
   ctx->last_entry = entry;
+  const bool wide_const = entry == 0 && wide_const_launch(ctx, pl, p);
+  ctx->last_wide = wide_const;
   tick("before launch");
-  RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream, 0, entry));
+  RT_HIP(ctx, rtk::launch_pooled(p, false, pl.grid, pl.waves, ctx->stream, 0, entry, wide_const));
   tick("launch_pooled");
   char buf[352];
   std::snprintf(buf, sizeof buf, "family=pooled tickets=%s%s instantiation=%s frames=%d tiles=%d grid=%d waves=%d counters=%d%s deep_class=%d deep_split=%d recording=%d nodes=%s,entry=%s,dark=%d,leaf_box=%d",
@@ -1357,6 +1371,15 @@ extern "C" int rt_context_exit_info(rt_context *ctx, int32_t *active, int32_t *d
   return 0;
 }
 
+// The twenty-wave shape's constants (option "wide_const"): whether the context's last pooled launch ran a kernel that has them compiled in.  The launch line
+// is the generic kernel's either way.  No device work.
+extern "C" int rt_context_wide_info(rt_context *ctx, int32_t *shape_const) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  if (shape_const) *shape_const = ctx->last_wide ? 1 : 0;
+  return 0;
+}
+
 extern "C" const char *rt_context_last_launch(const rt_context *ctx) { return ctx ? ctx->last_launch.c_str() : ""; }
 
 extern "C" int rt_context_sync(rt_context *ctx) {
@@ -1516,6 +1539,8 @@ extern "C" int rt_context_set_option(rt_context *ctx, const char *name, int64_t 
     ctx->entry_keep = v == 0 ? 0 : -1;
   } else if (k == "col_lds") {
     ctx->col_lds = v == 0 ? 0 : -1;
+  } else if (k == "wide_const") {
+    ctx->wide_const = v == 0 ? 0 : -1;
   } else if (k == "sync_policy") {
     ctx->sync_policy = v != 0;
   } else {
@@ -2213,6 +2238,7 @@ extern "C" int rt_render_trace(rt_context *ctx, const rt_prepared *ps, int64_t h
     set_cull(ctx, ps, pl, nullptr, &p);   // as enqueue_render launches this view
     set_dark(ctx, true, &p);              // (dark_stop = 1: the stopped chains of production; else the full chains, the reference's counts)
     set_leaf_box(ctx, ps, pl, nullptr, true, &p);   // (leaf_box = 1: production's filtered sphere tests; else every leaf child of a passing node, the reference's)
+    ctx->last_wide = false;   // (the instrumented kernels read the shape at run time)
     e = rtk::launch_pooled(p, true, pl.grid, pl.waves, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) e = hipMemcpy(records, trace, sizeof(unsigned long long) * rtk::kTraceWords * static_cast<size_t>(nw), hipMemcpyDeviceToHost);

@@ -676,8 +676,16 @@ __device__ __forceinline__ unsigned long long launch_leaf_off() {
 // host sends a launch with either flag clear to the twin that has the bit, or to the kernel without lists (api.cpp: set_entry) -- and BOX / BOX2 / SHADE carry
 // neither launch_leaf_off() nor launch_dark(); with kEntryColLds the colour table is staged behind the sphere prefix and SHADE reads the winner's colour from
 // LDS as it reads its sphere (the table must fit next to 16 waves: pooled_col_fits).
-template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL = 0, int RAYS = 0, int ENTRY = 0>
+// WIDE (the bit kSpillWide of the SPILL argument, rt_device.hpp): the plain and CULL four-wave kernels, with or without a spilling stack, a second time for the
+// one shape they run batches and large frames in -- five workgroups per CU, which stage NO scene prefix and keep two ray planes (api.cpp: make_plan).  lds_nodes,
+// lds_sph and the node planes' pitch are the literal 0 and ray_planes the literal 2: BOX, BOX2, LEAF and SHADE load their records from memory without the read
+// of a prefix that is not there, its compare and select, and the exec-masked region around the loads; the staging loops and LEAF's {d} plane are gone.  Nothing
+// else differs.  The host hands these kernels only plans of that shape (rt_device.hpp: pooled_wide_plan).
+template <int THREADS, bool ALL_LDS, bool STATS, bool SOLO, int TAIL = 0, bool ORD = false, bool CULL = false, int SPILL_ = 0, int RAYS = 0, int ENTRY = 0>
 __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 4) void pooled_kernel(KParams p) {
+  constexpr bool WIDE = (SPILL_ & kSpillWide) != 0;
+  constexpr int SPILL = SPILL_ & ~kSpillWide;
+  static_assert(!WIDE || (THREADS == 256 && !ALL_LDS && !STATS && !SOLO && TAIL == 0 && !ORD && RAYS == 0 && ENTRY == 0), "WIDE: the plain and CULL render kernels of the four-wave workgroups");
   constexpr bool COLD = TAIL == 1, DONATE = TAIL == 2;
   constexpr bool ANY = RAYS == kRaysAny;
   constexpr bool ECOUNT = (ENTRY & kEntryModeMask) == kEntryCount;         // the counting twin
@@ -698,19 +706,21 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
   extern __shared__ float4 smem[];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int plane = EXIT ? p.lds_nodes + kExitPairs : p.lds_nodes;          // float4 per node plane (EXIT: the pair records are staged behind the nodes)
+  // (WIDE: the shape's constants)
+  const int lds_nodes = WIDE ? 0 : p.lds_nodes, lds_sph = WIDE ? 0 : p.lds_sph, ray_planes = WIDE ? 2 : p.ray_planes;
+  const int plane = EXIT ? lds_nodes + kExitPairs : lds_nodes;          // float4 per node plane (EXIT: the pair records are staged behind the nodes)
   // (ECOL: the sign-ordered records packed, kPsNodeBytes each -- their addresses do not depend on the planes' pitch -- which is what makes room for the
   // colour table next to 16 waves: rt_device.hpp, pooled_col_lds_bytes)
   const int sph_base = ECOL ? (plane * (kPsNodeBytes / 4) + 3) >> 2 : 4 * plane;
   // per-wave region: key[64] (u64) | cnt[64] | dump[4] | rays[ray_planes][64] float4 | box stack[capb] | leaf list[capl]
-  const int per_wave_dw = pooled_wave_dw(p.ray_planes, p.capb, p.capl);
-  const int col_base = sph_base + p.lds_sph;   // (ECOL: the colour table, n_sph entries; the waves' regions lie behind it)
+  const int per_wave_dw = pooled_wave_dw(ray_planes, p.capb, p.capl);
+  const int col_base = sph_base + lds_sph;   // (ECOL: the colour table, n_sph entries; the waves' regions lie behind it)
   unsigned *const wbase = reinterpret_cast<unsigned *>(smem + (ECOL ? col_base + p.n_sph : col_base)) + wave * per_wave_dw;
   unsigned long long *const wkey = reinterpret_cast<unsigned long long *>(wbase);
   int *const wcnt = reinterpret_cast<int *>(wbase + 128);
   unsigned *const wdump = wbase + 192;    // where lanes with nothing to append write
   float4 *const wray = reinterpret_cast<float4 *>(wbase + kPooledWaveFixedDw);   // [0..63] {o.xyz, a}  [64..127] {1/d, 0}  ([128..191] {d, 0})
-  unsigned *const wbox = wbase + kPooledWaveFixedDw + 256 * p.ray_planes;
+  unsigned *const wbox = wbase + kPooledWaveFixedDw + 256 * ray_planes;
   unsigned *const wleaf = wbox + p.capb;
   const __amdgpu_buffer_rsrc_t rs_nodes = make_rsrc(p.nodes64, (unsigned)p.n_nodes * 64u);
   const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
@@ -724,14 +734,14 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
     auto ref_of = [](float w) { const int c = f2i(w) >> 8; return (unsigned)(c < 0 ? c : c * kPsNodeBytes) << kPsItemShift; };
     for (int i = threadIdx.x; i < plane; i += THREADS) {
       const float4 *src = p.nodes64 + 4 * i;
-      if constexpr (EXIT) src = i < p.lds_nodes ? src : p.exit_tab + 4 * (i - p.lds_nodes);   // (a pair record: two siblings of a chain as one node's children)
+      if constexpr (EXIT) src = i < lds_nodes ? src : p.exit_tab + 4 * (i - lds_nodes);   // (a pair record: two siblings of a chain as one node's children)
       const float4 ll = src[0], lh = src[1], rl = src[2], rh = src[3];
       presort_pack(reinterpret_cast<unsigned *>(smem) + (kPsNodeBytes / 4) * i, &ll.x, &lh.x, &rl.x, &rh.x, ref_of(ll.w), ref_of(lh.w));
     }
   } else {
     for (int i = threadIdx.x; i < 4 * plane; i += THREADS) smem[(i & 3) * plane + (i >> 2)] = p.nodes64[i];
   }
-  for (int i = threadIdx.x; i < p.lds_sph; i += THREADS) smem[sph_base + i] = p.sph[i];
+  for (int i = threadIdx.x; i < lds_sph; i += THREADS) smem[sph_base + i] = p.sph[i];
   if constexpr (ECOL)
     for (int i = threadIdx.x; i < p.n_sph; i += THREADS) smem[col_base + i] = p.col[i];
   // Zero the wave's region: lanes without an item read a stale entry and compute on it with
@@ -740,7 +750,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
   // DONATE: two words of the workgroup in wave 0's spare dump dwords -- [0] the waves that wait for a ray (bit = wave), [1] the
   // waves that are still in the pooled loop -- and every wave's own inbox flag in its dump[3]; the inbox itself is the first
   // three float4 of the waiting wave's ray table
-  unsigned *const wg_words = reinterpret_cast<unsigned *>(smem + sph_base + p.lds_sph) + 193;
+  unsigned *const wg_words = reinterpret_cast<unsigned *>(smem + sph_base + lds_sph) + 193;
   if (DONATE && threadIdx.x == 0) wg_words[1] = THREADS / 64;
   __syncthreads();
   wkey[lane] = kKeyInit;
@@ -970,9 +980,11 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
             else c = buf_load16(rs_col, wj * 16);
             if (ALL_LDS) {
               s = smem[sph_base + wj];
+            } else if constexpr (WIDE) {
+              s = buf_load16(rs_sph, wj * 16);
             } else {
-              s = smem[sph_base + (wj < p.lds_sph ? wj : 0)];
-              if (wj >= p.lds_sph) s = buf_load16(rs_sph, wj * 16);
+              s = smem[sph_base + (wj < lds_sph ? wj : 0)];
+              if (wj >= lds_sph) s = buf_load16(rs_sph, wj * 16);
             }
             if (!hit) {
               s = make_float4(0.f, 0.f, 0.f, 1.f);
@@ -1312,7 +1324,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
             else wcnt[lane] = push_box ? 1 : 0;    // 0: the fold is already complete (a miss, or a list of leaves alone), shaded next time
             wray[lane] = make_float4(r.ox, r.oy, r.oz, r.a);
             wray[64 + lane] = make_float4(r.ix, r.iy, r.iz, CULL ? cull_weight(r, p.cull_c2) : ANY ? a_lo : 0.0f);   // (CULL: the ray's W2; ANY: t_min)
-            if (p.ray_planes == 3) wray[128 + lane] = make_float4(r.dx, r.dy, r.dz, 0.0f);
+            if (ray_planes == 3) wray[128 + lane] = make_float4(r.dx, r.dy, r.dz, 0.0f);
             if (STATS) { n_rays++; n_box++; }
           }
           const unsigned long long m_root = bal(push_box);
@@ -1381,7 +1393,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
       const float4 ra = wray[sl];
       Ray q;
       q.ox = ra.x; q.oy = ra.y; q.oz = ra.z; q.a = ra.w;
-      if (p.ray_planes == 3) {                // wave-uniform
+      if (ray_planes == 3) {                // wave-uniform
         const float4 rd = wray[128 + sl];
         asm volatile("" ::"v"(rd.w));         // keep it a 16-byte read (ds_read_b96 is slower)
         q.dx = rd.x; q.dy = rd.y; q.dz = rd.z;
@@ -1393,9 +1405,11 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
       float4 s;
       if (ALL_LDS) {
         s = smem[sph_base + jj];
+      } else if constexpr (WIDE) {
+        s = buf_load16(rs_sph, jj * 16);
       } else {
-        s = smem[sph_base + (jj < p.lds_sph ? jj : 0)];
-        if (jj >= p.lds_sph) s = buf_load16(rs_sph, jj * 16);
+        s = smem[sph_base + (jj < lds_sph ? jj : 0)];
+        if (jj >= lds_sph) s = buf_load16(rs_sph, jj * 16);
       }
       if (STATS) n_sph += act ? 1 : 0;
       if constexpr (ANY) {
@@ -1448,7 +1462,12 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
           m_hr = bal(box_hit_presorted(q, nx.y, fx.y, ny.y, fy.y, nz.y, fz.y, 0.0f, kTMax));
         } else {
         float4 q0, q1, q2, q3;
-        {
+        if constexpr (WIDE) {
+          q0 = buf_load16(rs_nodes, ni16 * 4);
+          q1 = buf_load16(rs_nodes, ni16 * 4 + 16);
+          q2 = buf_load16(rs_nodes, ni16 * 4 + 32);
+          q3 = buf_load16(rs_nodes, ni16 * 4 + 48);
+        } else {
           const int lo16 = ALL_LDS ? ni16 : (ni16 < 16 * plane ? ni16 : 0);
           const float4 *const np = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(smem) + lo16);
           q0 = np[0]; q1 = np[plane]; q2 = np[2 * plane]; q3 = np[3 * plane];
@@ -1549,7 +1568,11 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         } else {
         // this lane's child: its box is quarters (2 role, 2 role + 1) of the item's record, its reference the .w of quarter `role`
         float4 lo, hi;
-        {
+        if constexpr (WIDE) {
+          lo = buf_load16(rs_nodes, ni16 * 4 + 32 * role);
+          hi = buf_load16(rs_nodes, ni16 * 4 + 32 * role + 16);
+          ref = f2i(buf_load16(rs_nodes, ni16 * 4 + 16 * role).w);
+        } else {
           const bool res = ALL_LDS || ni16 < 16 * plane;
           const int lo16 = res ? ni16 : 0;
           const char *const np = reinterpret_cast<const char *>(smem) + lo16;
@@ -1580,7 +1603,12 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 5 : (THREADS / 64 + 3) / 
         // second level: the child's own record (a virtual item `ref | sl4`)
         const int ci16 = pass ? (int)(((unsigned)ref >> 4) & 0xfffffff0u) : 0;
         float4 q0, q1, q2, q3;
-        {
+        if constexpr (WIDE) {
+          q0 = buf_load16(rs_nodes, ci16 * 4);
+          q1 = buf_load16(rs_nodes, ci16 * 4 + 16);
+          q2 = buf_load16(rs_nodes, ci16 * 4 + 32);
+          q3 = buf_load16(rs_nodes, ci16 * 4 + 48);
+        } else {
           const int lo16 = ALL_LDS ? ci16 : (ci16 < 16 * plane ? ci16 : 0);
           const float4 *const np = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(smem) + lo16);
           q0 = np[0]; q1 = np[plane]; q2 = np[2 * plane]; q3 = np[3 * plane];
@@ -2147,6 +2175,27 @@ static hipError_t launch_pooled_key(const PooledKey &k, const KParams &p, int gr
   return e;
 }
 
+// The WIDE twins of the keys pooled_wide_ok admits (the four-wave plain and CULL kernels, each without SPILL and with both capacities): the same launch, the
+// shape's constants compiled in.  Only a launch whose parameters ARE that shape takes one (pooled_wide_plan: five workgroups per CU is the caller's word)
+template <bool CULL, int SPILL>
+static hipError_t launch_pooled_wide_t(const KParams &p, int grid, hipStream_t stream) {
+  const size_t lds = pooled_lds_bytes(0, 0, p.capb, p.capl, 2, 4);
+  auto kfn = pooled_kernel<256, false, false, false, 0, false, CULL, SPILL | kSpillWide, 0>;
+  if (hipError_t e = allow_full_lds(reinterpret_cast<const void *>(kfn)); e != hipSuccess) return e;
+  hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, stream, p);
+  return hipGetLastError();
+}
+static hipError_t launch_pooled_wide(const PooledKey &k, const KParams &p, int grid, hipStream_t stream) {
+  if (!pooled_wide_ok(k) || !pooled_wide_plan(k.threads / 64, 5, p.lds_nodes, p.lds_sph, p.ray_planes)) return hipErrorInvalidValue;
+  constexpr int SP = kSpillCapb - 64, ST = kSpillCapbTest - 64;
+  switch (k.spill) {
+  case 0: return k.cull ? launch_pooled_wide_t<true, 0>(p, grid, stream) : launch_pooled_wide_t<false, 0>(p, grid, stream);
+  case SP: return k.cull ? launch_pooled_wide_t<true, SP>(p, grid, stream) : launch_pooled_wide_t<false, SP>(p, grid, stream);
+  case ST: return k.cull ? launch_pooled_wide_t<true, ST>(p, grid, stream) : launch_pooled_wide_t<false, ST>(p, grid, stream);
+  default: return hipErrorInvalidValue;
+  }
+}
+
 // The ENTRY twins of the one key pooled_entry_ok admits: `entry` = kEntryLists, or kEntryCount (the counting one: p.trace holds two words per wave)
 template <int ENTRY>
 static hipError_t launch_pooled_entry_t(const KParams &p, int grid, hipStream_t stream) {
@@ -2228,7 +2277,7 @@ hipError_t launch_exit_tables(const KParams &p, float4 *tab, hipStream_t stream)
   return hipGetLastError();
 }
 
-hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays, int entry) {
+hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays, int entry, bool wide) {
   if (rays == kRaysAny && p.occluded == nullptr) return hipErrorInvalidValue;
   // (per-ray intervals: the any-hit loop only, both bounds)
   if ((p.ray_tlo_dev != nullptr || p.ray_thi_dev != nullptr) && (rays != kRaysAny || p.ray_tlo_dev == nullptr || p.ray_thi_dev == nullptr)) return hipErrorInvalidValue;
@@ -2236,7 +2285,8 @@ hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_w
   PooledKey k;
   if (!choose_pooled(p, stats, waves_per_wg, rays, &k)) return hipErrorInvalidValue;
   // (the caller SAYS that p.entry is a table: the field shares its slot with the caller rays' colour3, and nothing is read off the pointer)
-  if (entry != 0) return rays == 0 && !stats ? launch_pooled_entry(k, p, grid, stream, entry) : hipErrorInvalidValue;
+  if (entry != 0) return rays == 0 && !stats && !wide ? launch_pooled_entry(k, p, grid, stream, entry) : hipErrorInvalidValue;
+  if (wide) return launch_pooled_wide(k, p, grid, stream);
   return launch_pooled_key(k, p, grid, stream, std::make_integer_sequence<int, kNumPooledKeys>{});
 }
 
@@ -2278,6 +2328,11 @@ void warm_render_kernels() {
   hipFuncAttributes a;
   (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(pooled_kernel<1024, true, false, false, 0, false, false, 0, 0, kEntryLists>));
   (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(pooled_kernel<1024, true, false, false, 0, false, false, 0, 0, kEntryLists | kEntryColLds>));
+  // (... and the twenty-wave shape's own kernels: plain, CULL, and both with the production stack)
+  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(pooled_kernel<256, false, false, false, 0, false, false, kSpillWide, 0>));
+  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(pooled_kernel<256, false, false, false, 0, false, true, kSpillWide, 0>));
+  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(pooled_kernel<256, false, false, false, 0, false, false, (kSpillCapb - 64) | kSpillWide, 0>));
+  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(pooled_kernel<256, false, false, false, 0, false, true, (kSpillCapb - 64) | kSpillWide, 0>));
   (void)hipFuncGetAttributes(&a, (const void *)tile_entry_kernel);
   (void)hipFuncGetAttributes(&a, (const void *)px_count_kernel);
   (void)hipFuncGetAttributes(&a, (const void *)px_scan_kernel);

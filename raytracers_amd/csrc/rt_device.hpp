@@ -395,6 +395,20 @@ constexpr bool pooled_entry_ok(const PooledKey &k) {
   return k.threads == 1024 && k.all_lds && !k.stats && !k.solo && k.tail == 0 && !k.ord && !k.cull && k.spill == 0 && k.rays == 0;
 }
 
+// WIDE: the four-wave plain and CULL render kernels (no SPILL, and both SPILL capacities) exist a second time with the constants of the twenty-wave shape
+// compiled in -- no scene prefix in LDS, two ray planes (render_kernels.hip).  The flag travels in the SPILL template argument, above any capacity.
+// pooled_wide_ok: the keys that have the twin.  pooled_wide_plan: the launch shapes that may take it -- workgroups of four waves, five of them per CU, nothing of
+// the scene staged, two ray planes; a four-wave workgroup that does stage a prefix keeps the generic kernel, which is the one way the twin could read wrong data.
+// launch_pooled takes the twin of choose_pooled's key when its caller says `wide`, and refuses where either predicate fails.  The key, and so the launch's name
+// in rt_context_last_launch, is the generic kernel's.
+constexpr int kSpillWide = 1 << 20;
+constexpr bool pooled_wide_ok(const PooledKey &k) {
+  return k.threads == 256 && !k.all_lds && !k.stats && !k.solo && k.tail == 0 && !k.ord && k.rays == 0 && (k.spill == 0 || k.spill == kSpillCapb - 64 || k.spill == kSpillCapbTest - 64);
+}
+constexpr bool pooled_wide_plan(int waves_per_wg, int wgs_per_cu, int lds_nodes, int lds_sph, int ray_planes) {
+  return waves_per_wg == 4 && wgs_per_cu == 5 && lds_nodes == 0 && lds_sph == 0 && ray_planes == 2;
+}
+
 // Which instantiation renders a launch with these parameters (false: none -- hipErrorInvalidValue).  `rays`: 0, kRaysColour, kRaysAny.
 // No HIP runtime calls: the CPU check tools/pooled_choice_check.cpp runs it over its inputs.
 inline bool choose_pooled(const KParams &p, bool stats, int waves_per_wg, int rays, PooledKey *out) {
@@ -509,7 +523,8 @@ constexpr bool pooled_col_fits(size_t col_lds_bytes, size_t lds_limit) { return 
 constexpr int pooled_entry_bits(int mode, int leaf_box, int dark, size_t col_lds_bytes, size_t lds_limit, bool col_lds = true) {
   return !pooled_entry_flags_const(leaf_box, dark) ? mode | kEntryRtFlags : mode | (col_lds && pooled_col_fits(col_lds_bytes, lds_limit) ? kEntryColLds : 0);
 }
-hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays = 0, int entry = 0);
+// `wide`: the WIDE twin of the chosen instantiation renders (above: pooled_wide_ok, pooled_wide_plan) -- an error where there is none, or with `entry`
+hipError_t launch_pooled(const KParams &p, bool stats, int grid, int waves_per_wg, hipStream_t stream, int rays = 0, int entry = 0, bool wide = false);
 // fills p.entry for the launch launch_pooled(p, stats, grid, waves_per_wg, stream) is about to make (hipErrorInvalidValue: that launch has no ENTRY instantiation)
 hipError_t launch_tile_entry(const KParams &p, bool stats, int waves_per_wg, hipStream_t stream);
 // fills `tab` (exit_tab_bytes(p.n_sph) bytes) from p's scene: the pair records and the per-sphere exit lists of the kEntryExit kernels

@@ -92,6 +92,8 @@ struct rt_context {
   int col_lds = -1;         // the ENTRY kernels stage the colour table in LDS where it fits next to 16 waves (rt_device.hpp: pooled_col_fits).  0: SHADE loads the winner's colour from memory
   uint64_t entry_tables_built = 0, entry_tables_kept = 0;   // launches of tile_entry_kernel by this context / launches that found their view's table in place (rt_context_entry_info)
   int last_entry = 0;       // the ENTRY template value of the last pooled render launch (0: it started at the root)
+  int wide_const = -1;      // pooled family: launches in the twenty-wave shape (four waves, five workgroups per CU, no scene prefix in LDS, two ray planes) run the twins of their kernels that have the shape's constants compiled in (rt_device.hpp: pooled_wide_plan; same pixels, same launch line).  -1 (default): on; 0: the generic four-wave kernels
+  bool last_wide = false;   // the last pooled launch ran such a twin (rt_context_wide_info)
   int exit_lists = -1;      // pooled family: a ray that has just scattered starts at its origin sphere's exit list instead of the root (lane_core.h: exit_tables_path; same pixels, fewer box tests).  -1 (default) and 1: the launches of the ENTRY kernel with the flags compiled in and the colours in LDS whose tables fit next to 16 waves (rt_device.hpp: pooled_exit_fits); 0: never
   float4 *exit_dev = nullptr;   // ... the tables (rt_device.hpp: KParams::exit_tab) of the prepared scene whose tree is exit_gen (rt_prepared::tree_gen; 0: none), built on this context's stream by the first launch that wants them and kept until a launch of another tree
   size_t exit_bytes = 0;
@@ -269,6 +271,7 @@ int stage_cams(rt_context *ctx, const float *cams12, int32_t nframes, const floa
 struct Plan {
   int variant;
   int lds_nodes, lds_sph, smax, lmax, waves, grid;
+  int wgs;         // persistent workgroups per CU of the chosen shape
   int grid_full;   // every persistent workgroup (grid == grid_full unless grid_div says otherwise)
   int capb, capl, ray_planes;
   int spill_stride;   // > 0: capb is below the box stack's bound -- the launch needs a spill region of this many dwords per wave (the twenty-wave shape, tall trees)
