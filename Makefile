@@ -173,6 +173,17 @@ build/along_check: tools/along_check.cpp $(CSRC)/query_core.h $(CSRC)/lane_core.
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -I$(CSRC) -o $@ tools/along_check.cpp
 
+# the sphere groups' rule, combine and climb (query_core.h: group_seen / group_combine / group_climb) over pairs and a tree read from a file, the
+# node words written out; in the CPU test suite.  build/asan/groups_check: the same program under -fsanitize=address,undefined (host code
+# only, stand-alone)
+build/groups_check: tools/groups_check.cpp $(CSRC)/query_core.h $(CSRC)/lane_core.h
+	@mkdir -p build
+	$(CXX) $(HOSTFLAGS) -I$(CSRC) -o $@ tools/groups_check.cpp
+
+build/asan/groups_check: tools/groups_check.cpp $(CSRC)/query_core.h $(CSRC)/lane_core.h
+	@mkdir -p build/asan
+	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) -o $@ tools/groups_check.cpp
+
 # the contact clusters' union-find (query_core.h: uf_find / uf_unite) behind std::atomic: threads uniting random graphs, a shuffled chain and
 # a clique against a sequential union-find, and four mutants each caught by its case; in the CPU test suite, which also builds and runs
 # build/tsan/clusters_check, the same program under -fsanitize=thread (host code only, stand-alone)
@@ -233,7 +244,7 @@ build/first_call_probe: tools/first_call_probe.c include/ray.h $(LIB)
 	@mkdir -p build
 	$(CC) -O2 -std=gnu99 -Wall -Iinclude -o $@ tools/first_call_probe.c -Lraytracers_amd -lray_mi355x -Wl,-rpath,'$$ORIGIN/../raytracers_amd'
 
-tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/batch_trim_check build/wide_const_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/dark_stop_check build/leaf_box_check build/entry_check build/exit_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/plane_query_bound_check build/box_presorted_check build/sweep_check build/along_check build/path_check build/clusters_check build/view_order_check
+tools: build/first_call_probe build/ctx_threads build/rtbench build/issue_peak build/queue_check build/pooled_choice_check build/batch_trim_check build/wide_const_check build/donate_check build/treelet_probe build/hip_touch build/cull_bound_check build/cull_guard_check build/dark_stop_check build/leaf_box_check build/entry_check build/exit_check build/cull_pooled build/cull_stats_check build/proximity_bound_check build/box_query_bound_check build/plane_query_bound_check build/box_presorted_check build/sweep_check build/along_check build/groups_check build/path_check build/clusters_check build/view_order_check
 
 oracle:
 	$(MAKE) -s -C oracle

@@ -81,6 +81,10 @@ const char *rt_last_error(const rt_context *ctx);       /* "" when no error; own
  *   "family=boxes count|fill[ (per-box)][ first]"   rt_spheres_in_boxes_count / _fill (below)
  *   "family=planes count|fill k=K[ (per-query)][ first]"   rt_spheres_in_planes_count / _fill (below; K: the caller's nplanes)
  *   "family=along count|fill[ (per-query)][ exclude][ first]"   rt_spheres_along_rays_count / _fill (below)
+ *   "<the unmasked entry's string> masked[ mask=per-query]"   rt_intersect_rays_masked, rt_occluded_rays_masked, rt_nearest_spheres_masked,
+ *         rt_spheres_within_masked_count / _fill (below): "family=intersect|occluded[ (per-ray)]", "family=nearest k=K[ pruned][ (per-point)]" or
+ *         "family=within count|fill[ (per-point)][ first]", then " masked", then " mask=per-query" with mask_dev -- e.g.
+ *         "family=within fill (per-point) first masked mask=per-query".  The masked occlusion entry always runs its lane kernel.
  *   "family=pairs targets|directions[ mask][ count][ words/wave=K]"   rt_visible_pairs / rt_visible_pairs_shaped (below; K: the caller's words_per_wave)
  *   "family=none (no rows)"       the part owns no row of the image
  *   "family=pixel" | "family=pixel (instrumented)" | "family=persistent"
@@ -643,6 +647,52 @@ int rt_visible_pairs(rt_context *ctx, const rt_prepared *ps, int64_t n, const fl
 int rt_visible_pairs_shaped(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, int64_t m,
                             const float *targets3_dev, int32_t mode, float t_min, float t_max, uint64_t *visible_dev, int32_t *count_dev,
                             int32_t words_per_wave);
+/* ---- sphere groups: 32-bit masks that filter rays and proximity queries ------------------------------------------------------------------
+ * Shadow rays that ignore the light's own geometry, picking among selectable objects, collision layers, neighbours of one species, probes that
+ * see static but not dynamic bodies: a prepared scene may carry ONE uint32 group word per sphere, and every masked query takes a uint32 mask.
+ * RULE: query i sees sphere j iff (groups[j] & mask_i) != 0, an unsigned test -- bit 31 is a bit like the others.  Mask 0 sees nothing: its
+ * walk does not start and it gets the entry's miss, empty row or zero count.
+ * GROUPS: rt_prepared_set_groups takes n device words in the CALLER's sphere order -- the order rt_prepared_get_sphere_ids maps back to, not
+ * L's -- and n must equal rt_prepared_num_spheres.  groups_dev == NULL: the scene has no groups again (their memory is released; n is not
+ * looked at).  A scene has no groups until they are set, and a masked entry on such a scene fails with a message that names
+ * rt_prepared_set_groups.  Groups survive rt_prepared_update_spheres: sphere c of the caller's order keeps word c wherever the rebuild puts it
+ * in L (the first masked entry or rt_prepared_get_groups behind an update derives the words again for the new tree, on the context's stream,
+ * ahead of its own work).  Only through the context that prepared the scene, and not through a multi-device context; this holds for every
+ * entry of this section.  The words are copied on the context's stream: groups_dev may be reused once that copy has run.
+ * rt_prepared_get_groups: groups_dev gets n words in L order (groups_dev[i] belongs to L[i]), node_groups_dev n - 1 words, the exact OR of the
+ * group words of every leaf below inner node v, v as rt_prepared_get_bvh numbers the inner nodes; either may be NULL, not both.  Enqueued on
+ * the context's stream like rt_prepared_get_sphere_ids (completion: rt_context_sync).
+ * ANSWERS.  The ray entries: the unmasked entry's own definition with every unseen sphere treated as absent at the leaf -- rt_intersect_rays'
+ * fold over the spheres the tree walk visits, every inner box tested with the caller's interval as there, restricted to the seen spheres, with
+ * the same (t, index) tie rule, the same re-intersection and bit-identical {t, p, normal}; occlusion is the OR over the same set.  These are
+ * the TREE's answers, as the unmasked ones are -- not those of a scene rebuilt from the seen spheres, which has other boxes and another
+ * Morton order.  The proximity entries: the unmasked query's definition over the seen spheres only; the gap bits, the (gap, index) order, the
+ * count, the CSR row order and the `first` rule are unchanged, and indices still are indices into the whole of L.
+ * The walks skip an inner node whose word shares no bit with the mask.  That is an optimisation, never part of a definition: the word is the
+ * exact OR of the leaves below, so a skipped subtree holds only unseen spheres.
+ * ARGUMENTS: mask_dev == NULL: the scalar `mask` for every query; otherwise n 4-byte-aligned uint32 in device memory, query i's own, and the
+ * scalar is ignored.  The other optional per-query arrays follow rt_spheres_along_rays_*: a NULL pointer means the scalar next to it is used
+ * and is checked on the host by the unmasked entry's rule; a given pointer means the scalar is ignored and an invalid per-query value makes
+ * that query a miss (an empty row, a zero count) by the kernels' rules.  t_min_dev and t_max_dev come together or not at all.  Every other
+ * argument keeps the meaning, limits and refusals of the unmasked entry it mirrors: k <= 32, count_dev == NULL selects the pruned k-nearest
+ * walk, the CSR two-pass protocol with its capacity guard (foreign offsets can misplace entries, never put one outside the caller's arrays),
+ * n == 0 as there.  One lane per ray or point under every variant. */
+int rt_prepared_set_groups(rt_context *ctx, rt_prepared *ps, const uint32_t *groups_dev, int64_t n);
+int rt_prepared_get_groups(rt_context *ctx, const rt_prepared *ps, uint32_t *groups_dev, uint32_t *node_groups_dev);
+int rt_intersect_rays_masked(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
+                             const float *t_min_dev, const float *t_max_dev, uint32_t mask, const uint32_t *mask_dev, int32_t *index_dev,
+                             float *hit7_dev);
+int rt_occluded_rays_masked(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
+                            const float *t_min_dev, const float *t_max_dev, uint32_t mask, const uint32_t *mask_dev, uint8_t *occluded_dev);
+int rt_nearest_spheres_masked(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
+                              const float *max_dist_dev, uint32_t mask, const uint32_t *mask_dev, int32_t k, int32_t *count_dev,
+                              int32_t *index_dev, float *gap_dev);
+int rt_spheres_within_masked_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
+                                   const float *max_dist_dev, uint32_t mask, const uint32_t *mask_dev, const int32_t *first_dev,
+                                   int64_t *offsets_dev);
+int rt_spheres_within_masked_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
+                                  const float *max_dist_dev, uint32_t mask, const uint32_t *mask_dev, const int32_t *first_dev,
+                                  const int64_t *offsets_dev, int64_t capacity, int32_t *index_dev, float *gap_dev, int32_t *point_dev);
 /* ids_dev: n int32 in the context's device memory; ids_dev[i] = the caller's index of L[i]: the position in spheres7 given to
  * rt_scene_from_spheres / rt_prepare_scene_device / the last rt_prepared_update_spheres, or in the generator's output for rt_scene_rgbbox /
  * _irreg / _floor.  The Morton sort is stable, so both builders (option gpu_build) give the same ids, ascending within a run of equal keys.

@@ -18,4 +18,6 @@ from .api import (Context, Prepared, RtError, Scene, MAX_DEPTH, ROWS_PER_TILE, V
                   spheres_along_rays, spheres_along_rays_count_into, spheres_along_rays_fill_into, row_contacts, row_crossings,
                   visible_pairs, visible_pairs_into, unpack_visible, PAIRS_TARGETS, PAIRS_DIRECTIONS,
                   contact_pairs, contact_pairs_count_into, contact_pairs_fill_into,
-                  contact_clusters, contact_clusters_into, cluster_members)
+                  contact_clusters, contact_clusters_into, cluster_members,
+                  intersect_rays_masked_into, occluded_rays_masked_into, nearest_spheres_masked_into,
+                  spheres_within_masked_count_into, spheres_within_masked_fill_into, nearest_spheres_masked, spheres_within_masked)

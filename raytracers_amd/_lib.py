@@ -27,6 +27,8 @@ RT_SYMBOLS = [
     "rt_spheres_in_planes_count", "rt_spheres_in_planes_fill",
     "rt_spheres_along_rays_count", "rt_spheres_along_rays_fill",
     "rt_visible_pairs", "rt_visible_pairs_shaped",
+    "rt_prepared_set_groups", "rt_prepared_get_groups", "rt_intersect_rays_masked", "rt_occluded_rays_masked", "rt_nearest_spheres_masked",
+    "rt_spheres_within_masked_count", "rt_spheres_within_masked_fill",
     "rt_camera_rays",
     "rt_device_alloc", "rt_device_free", "rt_copy_to_host", "rt_copy_to_device",
 ]
@@ -138,6 +140,13 @@ def _load():
         "rt_spheres_along_rays_fill": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
         "rt_visible_pairs": (C.c_int, [vp, vp, i64, vp, i64, vp, i32, C.c_float, C.c_float, vp, vp]),
         "rt_visible_pairs_shaped": (C.c_int, [vp, vp, i64, vp, i64, vp, i32, C.c_float, C.c_float, vp, vp, i32]),
+        "rt_prepared_set_groups": (C.c_int, [vp, vp, vp, i64]),
+        "rt_prepared_get_groups": (C.c_int, [vp, vp, vp, vp]),
+        "rt_intersect_rays_masked": (C.c_int, [vp, vp, i64, vp, C.c_float, C.c_float, vp, vp, C.c_uint32, vp, vp, vp]),
+        "rt_occluded_rays_masked": (C.c_int, [vp, vp, i64, vp, C.c_float, C.c_float, vp, vp, C.c_uint32, vp, vp]),
+        "rt_nearest_spheres_masked": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, C.c_uint32, vp, i32, vp, vp, vp]),
+        "rt_spheres_within_masked_count": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, C.c_uint32, vp, vp, vp]),
+        "rt_spheres_within_masked_fill": (C.c_int, [vp, vp, i64, vp, C.c_float, vp, C.c_uint32, vp, vp, vp, i64, vp, vp, vp]),
         "rt_camera_rays": (C.c_int, [vp, vp, i64, i64, vp, vp]),
     }
     for name, (res, args) in sig.items():

@@ -285,6 +285,36 @@ class Prepared:
             if keep is not None:
                 keep.free()
 
+    def set_groups(self, groups):
+        """Give every sphere a 32-bit group word (rt_prepared_set_groups), in the CALLER's sphere order -- the order sphere_ids() maps back
+        to -- for the mask= keyword of intersect_rays, occluded_rays, nearest_spheres and spheres_within: a query with mask m sees sphere j
+        iff groups[j] & m != 0.  `groups`: an (n,) integer numpy array with values in [0, 2^32), an (n,) contiguous int32 or uint32 torch
+        tensor on the context's device (its bits are the words; copied on the context's stream), or None: the scene has no groups again.
+        The words survive update_spheres: sphere c of the caller's order keeps word c."""
+        if groups is None:
+            self.ctx._check(lib.rt_prepared_set_groups(self.ctx._h, self._h, None, 0))
+            return
+        with _Scope(self.ctx) as s:
+            ptr, n = _device_words(s, groups, "groups", None)
+            self.ctx._check(lib.rt_prepared_set_groups(self.ctx._h, self._h, C.c_void_p(ptr), n))
+            self.ctx.sync()   # (the copy has run: the scope's buffer may go)
+
+    def groups(self):
+        """(groups (n,) uint32 in L order, node_groups (n - 1,) uint32) numpy arrays (rt_prepared_get_groups): groups[i] is the word of L[i],
+        node_groups[v] the OR of the words of every sphere below inner node v, numbered as in bvh_arrays()."""
+        n = self.num_spheres
+        g, ng = DeviceBuffer(self.ctx, 4 * n), DeviceBuffer(self.ctx, max(4 * (n - 1), 4))
+        try:
+            self.groups_into(g.ptr, ng.ptr)
+            return g.to_host((n,), np.uint32), ng.to_host((n - 1,), np.uint32)
+        finally:
+            g.free()
+            ng.free()
+
+    def groups_into(self, groups_ptr=None, node_groups_ptr=None):
+        """Enqueue the copies of groups() to device pointers (n and n - 1 uint32; either may be None, not both).  Asynchronous."""
+        self.ctx._check(lib.rt_prepared_get_groups(self.ctx._h, self._h, C.c_void_p(groups_ptr), C.c_void_p(node_groups_ptr)))
+
     def stats(self, max_depth=MAX_DEPTH):
         s = (C.c_uint64 * 3)()
         self.ctx._check(lib.rt_render_stats(self.ctx._h, self._h, self.h, self.w, int(max_depth), s))
@@ -832,6 +862,84 @@ def _device_first(scope, dev, n, first, name="first", per="point"):
                           lambda a: np.ascontiguousarray(np.clip(a, -2 ** 31, 2 ** 31 - 1), dtype=np.int32))
 
 
+def _device_words(scope, v, name, n):
+    """(pointer, count) of a vector of 32-bit words (sphere groups, per-query masks): an integer numpy array with values in [0, 2^32) is
+    uploaded as uint32; a contiguous int32 or uint32 torch tensor on the context's device is used in place, its bits being the words.
+    n: the length it must have (None: any)."""
+    if hasattr(v, "data_ptr"):
+        dev = scope.ctx.device_info()["device"]
+        if str(v.dtype) not in ("torch.int32", "torch.uint32") or not v.is_contiguous() or v.device.type != "cuda" or v.device.index != dev:
+            raise ValueError(f"{name}: a contiguous int32 or uint32 tensor on cuda:{dev} is required")
+        if v.dim() != 1 or (n is not None and v.shape[0] != n):
+            raise ValueError(f"{name} must be ({'n' if n is None else n},); got {tuple(v.shape)}")
+        return v.data_ptr(), int(v.shape[0])
+    a = np.asarray(v)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{name}: an integer array is required; got {a.dtype}")
+    if a.ndim != 1 or (n is not None and a.shape[0] != n):
+        raise ValueError(f"{name} must be ({'n' if n is None else n},); got {a.shape}")
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 32):
+        raise ValueError(f"{name}: values must be in [0, 2^32)")
+    return scope.upload(np.ascontiguousarray(a.astype(np.uint32))), int(a.shape[0])
+
+
+def _mask_args(scope, n, mask):
+    """(scalar mask, mask pointer or None) of the mask= keyword: a Python int in [0, 2^32) is the scalar mask of every query; an (n,) integer
+    array or int32 / uint32 device tensor is one mask per query."""
+    if _is_bound_array(mask):
+        return 0, _device_words(scope, mask, "mask", n)[0]
+    m = int(mask)
+    if not 0 <= m < 2 ** 32:
+        raise ValueError(f"mask = {mask!r}: a scalar mask must be in [0, 2^32)")
+    return m, None
+
+
+def intersect_rays_masked_into(rays_ptr, n, prepared, index_ptr, hit_ptr=None, t_min=0.0, t_max=1e9, t_min_ptr=None, t_max_ptr=None, mask=0xFFFFFFFF,
+                               mask_ptr=None):
+    """intersect_rays_into over the spheres the mask sees (rt_intersect_rays_masked; Prepared.set_groups): sphere j is seen iff groups[j] &
+    mask != 0 -- the scalar `mask`, or mask_ptr[i] (n uint32 on the device) for ray i.  t_min_ptr / t_max_ptr: both None (the scalar interval)
+    or both given (n float32 each, the scalars are ignored)."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_intersect_rays_masked(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), float(t_min), float(t_max), C.c_void_p(t_min_ptr),
+                                            C.c_void_p(t_max_ptr), int(mask), C.c_void_p(mask_ptr), C.c_void_p(index_ptr), C.c_void_p(hit_ptr)))
+
+
+def occluded_rays_masked_into(rays_ptr, n, prepared, out_ptr, t_min=0.0, t_max=1e9, t_min_ptr=None, t_max_ptr=None, mask=0xFFFFFFFF, mask_ptr=None):
+    """occluded_rays_into over the spheres the mask sees (rt_occluded_rays_masked); arguments as intersect_rays_masked_into."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_occluded_rays_masked(ctx._h, prepared._h, int(n), C.c_void_p(rays_ptr), float(t_min), float(t_max), C.c_void_p(t_min_ptr),
+                                           C.c_void_p(t_max_ptr), int(mask), C.c_void_p(mask_ptr), C.c_void_p(out_ptr)))
+
+
+def nearest_spheres_masked_into(points_ptr, n, prepared, k, count_ptr, index_ptr, gap_ptr=None, max_dist=1e9, max_dist_ptr=None, mask=0xFFFFFFFF,
+                                mask_ptr=None):
+    """nearest_spheres_into over the spheres the mask sees (rt_nearest_spheres_masked): the scalar `mask`, or mask_ptr[i] (n uint32 on the
+    device) for point i; max_dist_ptr: None (the scalar bound) or n float32 on the device (the scalar is ignored)."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_nearest_spheres_masked(ctx._h, prepared._h, int(n), C.c_void_p(points_ptr), float(max_dist), C.c_void_p(max_dist_ptr),
+                                             int(mask), C.c_void_p(mask_ptr), int(k), C.c_void_p(count_ptr), C.c_void_p(index_ptr),
+                                             C.c_void_p(gap_ptr)))
+
+
+def spheres_within_masked_count_into(points_ptr, n, prepared, offsets_ptr, max_dist=1e9, max_dist_ptr=None, first_ptr=None, mask=0xFFFFFFFF,
+                                     mask_ptr=None):
+    """spheres_within_count_into over the spheres the mask sees (rt_spheres_within_masked_count): the scalar `mask`, or mask_ptr[i] (n uint32
+    on the device) for point i."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_spheres_within_masked_count(ctx._h, prepared._h, int(n), C.c_void_p(points_ptr), float(max_dist), C.c_void_p(max_dist_ptr),
+                                                  int(mask), C.c_void_p(mask_ptr), C.c_void_p(first_ptr), C.c_void_p(offsets_ptr)))
+
+
+def spheres_within_masked_fill_into(points_ptr, n, prepared, offsets_ptr, capacity, index_ptr, gap_ptr=None, point_ptr=None, max_dist=1e9,
+                                    max_dist_ptr=None, first_ptr=None, mask=0xFFFFFFFF, mask_ptr=None):
+    """spheres_within_fill_into for the offsets of spheres_within_masked_count_into on the same points, bounds, masks and scene
+    (rt_spheres_within_masked_fill)."""
+    ctx = prepared.ctx
+    ctx._check(lib.rt_spheres_within_masked_fill(ctx._h, prepared._h, int(n), C.c_void_p(points_ptr), float(max_dist), C.c_void_p(max_dist_ptr),
+                                                 int(mask), C.c_void_p(mask_ptr), C.c_void_p(first_ptr), C.c_void_p(offsets_ptr), int(capacity),
+                                                 C.c_void_p(index_ptr), C.c_void_p(gap_ptr), C.c_void_p(point_ptr)))
+
+
 def trace_rays(prepared, rays, max_depth=MAX_DEPTH):
     """ray_colour of every ray (ray.fut:126-148) -> (colour (n, 3) float32, pixel (n,) int32) numpy arrays."""
     with _Scope(prepared.ctx) as s:
@@ -841,32 +949,50 @@ def trace_rays(prepared, rays, max_depth=MAX_DEPTH):
         return col.to_host((n, 3), np.float32), px.to_host((n,))
 
 
-def intersect_rays(prepared, rays, t_min=0.0, t_max=1e9):
+def intersect_rays(prepared, rays, t_min=0.0, t_max=1e9, mask=None):
     """objs_hit bvh r t_min t_max of every ray (ray.fut:76-86) -> (index (n,) int32, hit (n, 7) float32) numpy arrays.
-    Either bound may be an (n,) array, one per ray (rt_intersect_rays_ranged; a scalar next to it is broadcast)."""
+    Either bound may be an (n,) array, one per ray (rt_intersect_rays_ranged; a scalar next to it is broadcast).
+    mask: None (the default: every sphere, the unmasked entry), or -- on a scene with Prepared.set_groups -- a Python int, the mask of every
+    ray, or an (n,) integer array / int32 or uint32 device tensor, one mask per ray (rt_intersect_rays_masked): sphere j is seen iff groups[j] & mask != 0;
+    indices still are indices into the whole of L."""
     ranged = _is_bound_array(t_min) or _is_bound_array(t_max)
     with _Scope(prepared.ctx) as s:
         ptr, n = _device_rows(s, rays, *_RAYS)
         if ranged:
             lo_ptr, hi_ptr = _device_bounds(s, n, t_min, t_max)
         idx, hit = s.alloc(4 * n), s.alloc(28 * n)
-        if ranged:
+        if mask is not None:
+            m, m_ptr = _mask_args(s, n, mask)
+            if ranged:
+                intersect_rays_masked_into(ptr, n, prepared, idx.ptr, hit.ptr, 0.0, 0.0, lo_ptr, hi_ptr, m, m_ptr)
+            else:
+                intersect_rays_masked_into(ptr, n, prepared, idx.ptr, hit.ptr, t_min, t_max, None, None, m, m_ptr)
+        elif ranged:
             intersect_rays_ranged_into(ptr, n, prepared, lo_ptr, hi_ptr, idx.ptr, hit.ptr)
         else:
             intersect_rays_into(ptr, n, prepared, idx.ptr, hit.ptr, t_min, t_max)
         return idx.to_host((n,)), hit.to_host((n, 7), np.float32)
 
 
-def occluded_rays(prepared, rays, t_min=0.0, t_max=1e9):
+def occluded_rays(prepared, rays, t_min=0.0, t_max=1e9, mask=None):
     """Occlusion of every ray over (t_min, t_max) (rt_occluded_rays) -> (n,) bool numpy array.  Either bound may be an (n,)
-    array, one per ray (rt_occluded_rays_ranged; a scalar next to it is broadcast)."""
+    array, one per ray (rt_occluded_rays_ranged; a scalar next to it is broadcast).
+    mask: None (the default: every sphere, the unmasked entry), or -- on a scene with Prepared.set_groups -- a Python int, the mask of every
+    ray, or an (n,) integer array / int32 or uint32 device tensor, one mask per ray (rt_occluded_rays_masked): sphere j is seen iff groups[j] & mask != 0;
+    indices still are indices into the whole of L."""
     ranged = _is_bound_array(t_min) or _is_bound_array(t_max)
     with _Scope(prepared.ctx) as s:
         ptr, n = _device_rows(s, rays, *_RAYS)
         if ranged:
             lo_ptr, hi_ptr = _device_bounds(s, n, t_min, t_max)
         out = s.alloc(n)
-        if ranged:
+        if mask is not None:
+            m, m_ptr = _mask_args(s, n, mask)
+            if ranged:
+                occluded_rays_masked_into(ptr, n, prepared, out.ptr, 0.0, 0.0, lo_ptr, hi_ptr, m, m_ptr)
+            else:
+                occluded_rays_masked_into(ptr, n, prepared, out.ptr, t_min, t_max, None, None, m, m_ptr)
+        elif ranged:
             occluded_rays_ranged_into(ptr, n, prepared, lo_ptr, hi_ptr, out.ptr)
         else:
             occluded_rays_into(ptr, n, prepared, out.ptr, t_min, t_max)
@@ -950,7 +1076,19 @@ def nearest_spheres(prepared, points, k, max_dist=1e9, count=True):
     its point a miss).  count=False: k-nearest mode -- the walk also prunes by the k-th gap found so far, no count is returned, the slots are
     the same.  `points`: (n, 3) float32, a numpy array or a device tensor.  A point with a non-finite component selects nothing.
     Contacts: the spheres a sphere (c, r) overlaps or touches are those selected at p = c with max_dist = r; for a scene's self-contacts pass
-    its own centres and radii -- every sphere finds itself at gap -r."""
+    its own centres and radii -- every sphere finds itself at gap -r.
+    nearest_spheres_masked: the same over the spheres a group mask sees."""
+    return _nearest_spheres(prepared, points, k, max_dist, count, None)
+
+
+def nearest_spheres_masked(prepared, points, k, max_dist=1e9, count=True, *, mask):
+    """nearest_spheres over the spheres the mask sees (rt_nearest_spheres_masked; the scene needs Prepared.set_groups): sphere j is seen iff
+    groups[j] & mask != 0.  mask: a Python int, the mask of every point, or an (n,) integer array / int32 or uint32 device tensor, one mask per
+    point (a required keyword).  Everything else as nearest_spheres; indices still are indices into the whole of L."""
+    return _nearest_spheres(prepared, points, k, max_dist, count, mask)
+
+
+def _nearest_spheres(prepared, points, k, max_dist, count, mask):
     k = int(k)
     ranged = _is_bound_array(max_dist)
     with _Scope(prepared.ctx) as s:
@@ -961,7 +1099,10 @@ def nearest_spheres(prepared, points, k, max_dist=1e9, count=True):
         cnt = s.alloc(4 * n) if count else None
         idx, gap = s.alloc(4 * nk), s.alloc(4 * nk)
         cptr = cnt.ptr if cnt is not None else None
-        if ranged:
+        if mask is not None:
+            m, m_ptr = _mask_args(s, n, mask)
+            nearest_spheres_masked_into(ptr, n, prepared, k, cptr, idx.ptr, gap.ptr, 0.0 if ranged else max_dist, md_ptr if ranged else None, m, m_ptr)
+        elif ranged:
             nearest_spheres_ranged_into(ptr, n, prepared, md_ptr, k, cptr, idx.ptr, gap.ptr)
         else:
             nearest_spheres_into(ptr, n, prepared, k, cptr, idx.ptr, gap.ptr, max_dist)
@@ -998,7 +1139,19 @@ def spheres_within(prepared, points, max_dist, first=None, gaps=True, rows=False
     tensor, one bound per point (an invalid bound gives an empty row).  first: None, or an (n,) integer array / int32 device tensor: only
     spheres with index >= first[i] are selected for point i.  gaps=False: no gap array (None is returned in its place).  rows=True: also
     `point`, the row number of every entry, so that (point, index) is the list of pairs.  `points`: (n, 3) float32, a numpy array or a device
-    tensor.  A point with a non-finite component has an empty row."""
+    tensor.  A point with a non-finite component has an empty row.
+    spheres_within_masked: the same over the spheres a group mask sees."""
+    return _spheres_within(prepared, points, max_dist, first, gaps, rows, None)
+
+
+def spheres_within_masked(prepared, points, max_dist, first=None, gaps=True, rows=False, *, mask):
+    """spheres_within over the spheres the mask sees (rt_spheres_within_masked_count / _fill; the scene needs Prepared.set_groups): sphere j
+    is seen iff groups[j] & mask != 0.  mask: a Python int, the mask of every point, or an (n,) integer array / int32 or uint32 device tensor,
+    one mask per point (a required keyword).  Everything else as spheres_within; indices still are indices into the whole of L."""
+    return _spheres_within(prepared, points, max_dist, first, gaps, rows, mask)
+
+
+def _spheres_within(prepared, points, max_dist, first, gaps, rows, mask):
     ranged = _is_bound_array(max_dist)
     with _Scope(prepared.ctx) as s:
         ptr, n = _device_rows(s, points, *_POINTS)
@@ -1006,6 +1159,12 @@ def spheres_within(prepared, points, max_dist, first=None, gaps=True, rows=False
         md_ptr = _device_bound(s, dev, n, "max_dist", max_dist, per="point") if ranged else None
         md = 0.0 if ranged else max_dist
         first_ptr = _device_first(s, dev, n, first) if first is not None else None
+        if mask is not None:
+            m, m_ptr = _mask_args(s, n, mask)
+            return _csr_query(s, n, lambda off: spheres_within_masked_count_into(ptr, n, prepared, off, md, md_ptr, first_ptr, m, m_ptr),
+                              lambda off, total, idx, gap, row: spheres_within_masked_fill_into(ptr, n, prepared, off, total, idx, gap, row, md,
+                                                                                               md_ptr, first_ptr, m, m_ptr),
+                              _gap_columns(gaps, rows))
         return _csr_query(s, n, lambda off: spheres_within_count_into(ptr, n, prepared, off, md, md_ptr, first_ptr),
                           lambda off, total, idx, gap, row: spheres_within_fill_into(ptr, n, prepared, off, total, idx, gap, row, md, md_ptr,
                                                                                     first_ptr),

@@ -665,6 +665,209 @@ extern "C" int rt_visible_pairs_shaped(rt_context *ctx, const rt_prepared *ps, i
                      words_per_wave);
 }
 
+// ------------------------------------------------------------------------------------ sphere groups
+// The groups hang off the prepared scene (rt_internal.hpp: PreparedGroups) and are brought up to date lazily: rt_prepared_update_spheres
+// (api.cpp) knows nothing of them, it only gives the scene a new tree_gen.  Every entry below goes through the scene's home context alone, so
+// the derive and every launch that reads its words are ordered by that context's one stream.
+namespace {
+// the refusals the groups' entries share past their own argument checks
+int groups_entry_checks(rt_context *ctx, const rt_prepared *ps, const char *what) {
+  if (!ps) return fail(ctx, "null prepared scene");
+  if (ctx->group) return fail_in(ctx, what, ": a multi-device context is not supported (use a context on one device)");
+  if (ps->home != ctx) return fail_in(ctx, what, ": only through the context that prepared the scene");
+  return 0;
+}
+// ... and of those that need groups: a scene that has none (looked at under its lock)
+int groups_present(rt_context *ctx, const rt_prepared *ps, const char *what) {
+  if (int rc = groups_entry_checks(ctx, ps, what)) return rc;
+  RT_LOCK_PS(ps);
+  if (!ps->groups.block) return fail_in(ctx, what, ": the scene has no groups (rt_prepared_set_groups gives it some)");
+  return 0;
+}
+// ps's block with the derived words valid for its current tree: derived on the context's stream if they are another tree's.  The caller holds
+// both locks and has set the device.
+int groups_ready(rt_context *ctx, const rt_prepared *ps, const char *what, rtk::GroupBlock *b) {
+  if (!ps->groups.block) return fail_in(ctx, what, ": the scene has no groups (rt_prepared_set_groups gives it some)");
+  *b = rtk::groups_carve(ps->groups.block, ps->n);
+  if (ps->groups.derived_gen != ps->tree_gen) {
+    RT_HIP(ctx, rtk::launch_groups_derive(*b, ps->ids, ps->nodes, ps->left, ps->right, ps->parent, static_cast<int>(ps->n), ctx->stream));
+    ps->groups.derived_gen = ps->tree_gen;
+  }
+  return 0;
+}
+int group_args(rt_context *ctx, const rt_prepared *ps, const char *what, uint32_t mask, const uint32_t *mask_dev, rtk::GroupArgs *ga) {
+  rtk::GroupBlock b;
+  if (int rc = groups_ready(ctx, ps, what, &b)) return rc;
+  *ga = rtk::GroupArgs{b.groups, b.trav_groups, mask_dev, mask};
+  return 0;
+}
+std::string masked_suffix(const uint32_t *mask_dev) { return mask_dev ? " masked mask=per-query" : " masked"; }
+// the optional per-ray interval of the masked ray entries (the rt_spheres_along_rays_* convention): both pointers or neither; the scalar pair
+// is checked only where it is used
+int masked_interval(rt_context *ctx, const char *what, float t_min, float t_max, const float *t_min_dev, const float *t_max_dev, rtk::KParams *p) {
+  if ((t_min_dev == nullptr) != (t_max_dev == nullptr)) return fail_in(ctx, what, ": t_min_dev and t_max_dev must both be NULL or both be given");
+  if (!t_min_dev && !ray_interval_ok(t_min, t_max)) return fail_in(ctx, what, ": need 0 <= t_min <= t_max <= 1e9, both finite");
+  p->ray_tlo = t_min;
+  p->ray_thi = t_max;
+  p->ray_tlo_dev = t_min_dev;
+  p->ray_thi_dev = t_max_dev;
+  return 0;
+}
+}  // namespace
+
+extern "C" int rt_prepared_set_groups(rt_context *ctx, rt_prepared *ps, const uint32_t *groups_dev, int64_t n) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  const char *const what = "rt_prepared_set_groups";
+  if (int rc = groups_entry_checks(ctx, ps, what)) return rc;
+  if (groups_dev && n != ps->n) return fail(ctx, std::string(what) + ": n must equal rt_prepared_num_spheres (" + std::to_string(ps->n) + ")");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  PreparedGroups &g = ps->groups;
+  if (!groups_dev) {
+    if (g.block) {
+      RT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (an earlier masked launch may still be reading it)
+      RT_HIP(ctx, hipFree(g.block));
+      g.block = nullptr;
+    }
+    g.derived_gen = 0;
+    return 0;
+  }
+  if (!g.block) RT_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&g.block), rtk::groups_bytes(ps->n)));
+  g.derived_gen = 0;
+  rtk::GroupBlock b = rtk::groups_carve(g.block, ps->n);
+  RT_HIP(ctx, hipMemcpyAsync(b.caller, groups_dev, static_cast<size_t>(ps->n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+  return groups_ready(ctx, ps, what, &b);
+}
+
+extern "C" int rt_prepared_get_groups(rt_context *ctx, const rt_prepared *ps, uint32_t *groups_dev, uint32_t *node_groups_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  const char *const what = "rt_prepared_get_groups";
+  if (int rc = groups_entry_checks(ctx, ps, what)) return rc;
+  if (!groups_dev && !node_groups_dev) return fail_in(ctx, what, ": both outputs are NULL");
+  RT_LOCK_PS(ps);
+  RT_HIP(ctx, hipSetDevice(ctx->device));
+  (void)hipGetLastError();
+  ctx->synced_since_render = false;
+  rtk::GroupBlock b;
+  if (int rc = groups_ready(ctx, ps, what, &b)) return rc;
+  const size_t n = static_cast<size_t>(ps->n);
+  if (groups_dev) RT_HIP(ctx, hipMemcpyAsync(groups_dev, b.groups, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+  if (node_groups_dev)
+    RT_HIP(ctx, hipMemcpyAsync(node_groups_dev, b.node_groups, (n - 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+  return 0;
+}
+
+extern "C" int rt_intersect_rays_masked(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
+                                        const float *t_min_dev, const float *t_max_dev, uint32_t mask, const uint32_t *mask_dev,
+                                        int32_t *index_dev, float *hit7_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  const char *const what = "rt_intersect_rays_masked";
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!index_dev) return fail_in(ctx, what, ": null index pointer");
+  if (int rc = masked_interval(ctx, what, t_min, t_max, t_min_dev, t_max_dev, &p)) return rc;
+  if (int rc = groups_present(ctx, ps, what)) return rc;
+  return locked_launch(ctx, ps, n, kNoRays, [&] {
+    rtk::GroupArgs ga;
+    if (int rc = group_args(ctx, ps, what, mask, mask_dev, &ga)) return rc;
+    RT_HIP(ctx, rtk::launch_intersect_rays_masked(p, ga, t_min, t_max, index_dev, hit7_dev, ctx->stream));
+    ctx->last_launch = std::string(t_min_dev ? "family=intersect (per-ray)" : "family=intersect") + masked_suffix(mask_dev);
+    return 0;
+  });
+}
+
+// (the lane kernel under every variant: the pooled any-hit loop has no masked instantiation)
+extern "C" int rt_occluded_rays_masked(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *rays_dev, float t_min, float t_max,
+                                       const float *t_min_dev, const float *t_max_dev, uint32_t mask, const uint32_t *mask_dev,
+                                       uint8_t *occluded_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  const char *const what = "rt_occluded_rays_masked";
+  rtk::KParams p;
+  if (int rc = ray_entry_params(ctx, ps, n, rays_dev, &p)) return rc;
+  if (!occluded_dev) return fail_in(ctx, what, ": null output pointer");
+  if (int rc = masked_interval(ctx, what, t_min, t_max, t_min_dev, t_max_dev, &p)) return rc;
+  if (int rc = groups_present(ctx, ps, what)) return rc;
+  p.occluded = occluded_dev;
+  return locked_launch(ctx, ps, n, kNoRays, [&] {
+    rtk::GroupArgs ga;
+    if (int rc = group_args(ctx, ps, what, mask, mask_dev, &ga)) return rc;
+    RT_HIP(ctx, rtk::launch_occluded_rays_masked(p, ga, ctx->stream));
+    ctx->last_launch = std::string(t_min_dev ? "family=occluded (per-ray)" : "family=occluded") + masked_suffix(mask_dev);
+    return 0;
+  });
+}
+
+extern "C" int rt_nearest_spheres_masked(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
+                                         const float *max_dist_dev, uint32_t mask, const uint32_t *mask_dev, int32_t k, int32_t *count_dev,
+                                         int32_t *index_dev, float *gap_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  const char *const what = "rt_nearest_spheres_masked";
+  if (int rc = point_entry_checks(ctx, ps, what, false, &n, points3_dev)) return rc;
+  if (!count_dev && !index_dev && !gap_dev) return fail_in(ctx, what, ": all three outputs are NULL");
+  if (k < 1 || k > rtk::kNearestMaxK) return fail_in(ctx, what, ": need 1 <= k <= 32");
+  if (!max_dist_dev && !distance_ok(max_dist)) return fail_in(ctx, what, ": need 0 <= max_dist <= 1e9, finite");
+  if (int rc = groups_present(ctx, ps, what)) return rc;
+  return locked_launch(ctx, ps, n, kNoPoints, [&] {
+    rtk::GroupArgs ga;
+    if (int rc = group_args(ctx, ps, what, mask, mask_dev, &ga)) return rc;
+    int exact_depth;
+    const rtk::KParams p = point_params(ps, n, &exact_depth);
+    RT_HIP(ctx, rtk::launch_nearest_spheres_masked(p, ga, points3_dev, max_dist_dev, max_dist, k, exact_depth, count_dev, index_dev, gap_dev,
+                                                   ctx->stream));
+    ctx->last_launch = "family=nearest k=" + std::to_string(k) + (count_dev ? "" : " pruned") + (max_dist_dev ? " (per-point)" : "") + masked_suffix(mask_dev);
+    return 0;
+  });
+}
+
+static int within_masked_entry(rt_context *ctx, const rt_prepared *ps, const char *what, bool fill, int64_t n, const float *points3_dev,
+                               float max_dist, const float *max_dist_dev, uint32_t mask, const uint32_t *mask_dev, const int32_t *first_dev,
+                               int64_t *offsets_dev, int64_t capacity, int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
+  if (int rc = point_entry_checks(ctx, ps, what, false, &n, points3_dev)) return rc;
+  if (int rc = csr_pass_checks(ctx, what, fill, offsets_dev, capacity, index_dev || gap_dev || point_dev)) return rc;
+  if (!max_dist_dev && !distance_ok(max_dist)) return fail_in(ctx, what, ": need 0 <= max_dist <= 1e9, finite");
+  if (int rc = groups_present(ctx, ps, what)) return rc;
+  const std::string detail = std::string(max_dist_dev ? " (per-point)" : "") + (first_dev ? " first" : "") + masked_suffix(mask_dev);
+  rtk::GroupArgs ga{};
+  return csr_entry(
+      ctx, ps, fill, n, "within", detail,
+      [&](const rtk::KParams &p, int exact_depth, char *scratch) {
+        if (int rc = group_args(ctx, ps, what, mask, mask_dev, &ga)) return rc;
+        RT_HIP(ctx, rtk::launch_within_count_masked(p, ga, points3_dev, max_dist_dev, max_dist, first_dev, exact_depth, scratch, offsets_dev, ctx->stream));
+        return 0;
+      },
+      [&](const rtk::KParams &p, int exact_depth) {
+        if (int rc = group_args(ctx, ps, what, mask, mask_dev, &ga)) return rc;
+        RT_HIP(ctx, rtk::launch_within_fill_masked(p, ga, points3_dev, max_dist_dev, max_dist, first_dev, exact_depth, offsets_dev, capacity, index_dev,
+                                                   gap_dev, point_dev, ctx->stream));
+        return 0;
+      });
+}
+
+extern "C" int rt_spheres_within_masked_count(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
+                                              const float *max_dist_dev, uint32_t mask, const uint32_t *mask_dev, const int32_t *first_dev,
+                                              int64_t *offsets_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return within_masked_entry(ctx, ps, "rt_spheres_within_masked_count", false, n, points3_dev, max_dist, max_dist_dev, mask, mask_dev, first_dev,
+                             offsets_dev, 0, nullptr, nullptr, nullptr);
+}
+
+extern "C" int rt_spheres_within_masked_fill(rt_context *ctx, const rt_prepared *ps, int64_t n, const float *points3_dev, float max_dist,
+                                             const float *max_dist_dev, uint32_t mask, const uint32_t *mask_dev, const int32_t *first_dev,
+                                             const int64_t *offsets_dev, int64_t capacity, int32_t *index_dev, float *gap_dev, int32_t *point_dev) {
+  if (!ctx) return 1;
+  RT_LOCK(ctx);
+  return within_masked_entry(ctx, ps, "rt_spheres_within_masked_fill", true, n, points3_dev, max_dist, max_dist_dev, mask, mask_dev, first_dev,
+                             const_cast<int64_t *>(offsets_dev), capacity, index_dev, gap_dev, point_dev);
+}
+
 extern "C" int rt_prepared_get_sphere_ids(rt_context *ctx, const rt_prepared *ps, int32_t *ids_dev) {
   if (!ctx) return 1;
   RT_LOCK(ctx);

@@ -355,4 +355,30 @@ RT_HD int32_t uf_unite(const A &a, int32_t x, int32_t y) {
   }
 }
 
+// ---- sphere groups: 32-bit masks that filter the masked queries (rt_prepared_set_groups, rt_*_masked) --------------------
+// THE rule: a query with mask m sees a sphere -- or may find a seen sphere below an inner node -- whose word is g iff g and m share a bit.
+// An unsigned test: bit 31 is a bit like the others, and mask 0 sees nothing.
+RT_HD bool group_seen(uint32_t g, uint32_t m) { return (g & m) != 0u; }
+// A node's word is the OR of its two children's: for an inner child its own word, for a leaf child the sphere's group word.
+RT_HD uint32_t group_combine(uint32_t left, uint32_t right) { return left | right; }
+// One step of the derive kernel's climb (query_kernels.hip: groups_climb_kernel): `carry` arrives at a node whose word was `old` before the
+// atomic OR.  What goes on to the parent are the bits this step newly set; bits that were there already have been, or are being, carried up
+// by the lane that set them.  Zero: the climb ends.
+RT_HD uint32_t group_climb_carry(uint32_t old, uint32_t carry) { return carry & ~old; }
+// A node's subtree words through a memory policy A, for hosts and the device alike (the device's: query_kernels.hip's GroupOps, relaxed
+// agent-scope atomics; a host's: plain words, tools/groups_check.cpp):
+//   uint32_t A::fetch_or(int32_t v, uint32_t bits)   node_groups[v] |= bits, returns the value before
+//   int32_t  A::parent(int32_t v)                    the parent of inner node v, negative for the root
+// Every word starts at 0.  Seeded from every inner node with the combine of its LEAF children's words, the result is the exact OR of the leaves
+// below each node: a bit of leaf j reaches every ancestor, because a climb that drops it at node v does so only where another climb set it at
+// v and carries it on from there -- by induction along the (finite) root path it is set at every ancestor when the last climb ends.  No bit
+// that is not some leaf's is ever set.  Nothing waits: a step is one atomic OR.
+template <class A>
+RT_HD void group_climb(const A &a, int32_t v, uint32_t carry) {
+  while (carry != 0u && v >= 0) {
+    carry = group_climb_carry(a.fetch_or(v, carry), carry);
+    v = a.parent(v);
+  }
+}
+
 }  // namespace rtk

@@ -118,6 +118,36 @@ inline int pairs_auto_words_per_wave(int64_t n, int64_t m, int num_cu) {
 }
 hipError_t launch_visible_pairs(const KParams &p, const float *points, const float *targets, int m, bool directions, int words_per_wave,
                                 float t_min, float t_max, unsigned long long *visible, int32_t *count, hipStream_t stream);
+// Sphere groups (rt_prepared_set_groups, rt_*_masked).  GroupArgs: what a masked launch takes on top of its unmasked twin's
+// arguments -- the scene's group words in L order (n), the exact subtree ORs of the inner nodes in the TRAVERSAL numbering (n - 1: the
+// numbering of p.nodes' child references), and the mask: mask_dev[i] of query i when given (n 4-byte-aligned words), else `mask`.  They are
+// kernel arguments of their own: KParams belongs to the render path.  Query i sees sphere j iff groups[j] & mask_i != 0; a mask of 0 starts no
+// walk.  Each launcher otherwise is its unmasked twin (the ranged forms are selected as there: p.ray_tlo_dev / max_dist_dev set).
+struct GroupArgs {
+  const uint32_t *groups, *node_groups, *mask_dev;
+  uint32_t mask;
+};
+hipError_t launch_intersect_rays_masked(const KParams &p, const GroupArgs &ga, float t_min, float t_max, int32_t *index, float *hit7,
+                                        hipStream_t stream);
+hipError_t launch_occluded_rays_masked(const KParams &p, const GroupArgs &ga, hipStream_t stream);
+hipError_t launch_nearest_spheres_masked(const KParams &p, const GroupArgs &ga, const float *pts, const float *max_dist_dev, float max_dist, int k,
+                                         int exact_depth, int32_t *count, int32_t *index, float *gap, hipStream_t stream);
+hipError_t launch_within_count_masked(const KParams &p, const GroupArgs &ga, const float *pts, const float *max_dist_dev, float max_dist,
+                                      const int32_t *first_dev, int exact_depth, char *scratch, int64_t *offsets, hipStream_t stream);
+hipError_t launch_within_fill_masked(const KParams &p, const GroupArgs &ga, const float *pts, const float *max_dist_dev, float max_dist,
+                                     const int32_t *first_dev, int exact_depth, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap,
+                                     int32_t *point, hipStream_t stream);
+// The groups' device block of a scene of n spheres (groups_bytes(n) bytes, 256-byte aligned pieces): the caller-order words, then what
+// launch_groups_derive makes of them for one tree -- the words in L order (groups[i] = caller[ids[i]]), the subtree ORs in the canonical
+// numbering (left / right / parent) and in the traversal numbering (nodes), and the traversal numbering's parent array it climbs.
+struct GroupBlock {
+  uint32_t *caller = nullptr, *groups = nullptr, *node_groups = nullptr, *trav_groups = nullptr;
+  int32_t *trav_parent = nullptr;
+};
+size_t groups_bytes(int64_t n);
+GroupBlock groups_carve(char *block, int64_t n);
+hipError_t launch_groups_derive(const GroupBlock &b, const int32_t *ids, const float4 *nodes, const int32_t *left, const int32_t *right,
+                                const int32_t *parent, int n, hipStream_t stream);
 // the primary rays of an h x w frame through p.cam (get_ray at pixel_u / pixel_v), row-major from the top row: rays[6 (row w + col) ..]
 hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStream_t stream);
 

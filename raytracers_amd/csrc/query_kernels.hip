@@ -9,6 +9,31 @@
 
 namespace rtk {
 
+// Sphere groups: a lane's view of GroupArgs (query_device.hpp), what a masked lane kernel takes on top of its unmasked twin's
+// arguments.  MASKED false: every test is the constant true and the lanes compile to what they were.  MASKED: both arrays are read
+// through buffer resources of the scene's sizes, 4 bytes per test (an index outside the scene reads 0: unseen).
+template <bool MASKED>
+struct GroupView {
+  __device__ __forceinline__ GroupView(const KParams &, const GroupArgs &, int) {}
+  __device__ __forceinline__ bool start() const { return true; }
+  __device__ __forceinline__ bool node(int) const { return true; }
+  __device__ __forceinline__ bool leaf(int) const { return true; }
+};
+template <>
+struct GroupView<true> {
+  const __amdgpu_buffer_rsrc_t rs_g, rs_ng;
+  const uint32_t m;
+  __device__ __forceinline__ GroupView(const KParams &p, const GroupArgs &ga, int i)
+      : rs_g(make_rsrc(ga.groups, (unsigned)p.n_sph * 4u)), rs_ng(make_rsrc(ga.node_groups, (unsigned)p.n_nodes * 4u)),
+        m(ga.mask_dev != nullptr ? ga.mask_dev[i] : ga.mask) {}
+  // may a seen sphere lie below inner node v: asked where v would be pushed, so an unseen subtree costs neither its record nor a stack slot
+  __device__ __forceinline__ bool node(int v) const { return group_seen((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs_ng, v * 4, 0, 0), m); }
+  // is sphere j seen: asked ahead of its 16-byte load
+  __device__ __forceinline__ bool leaf(int j) const { return group_seen((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs_g, j * 4, 0, 0), m); }
+  // does the walk start at all: mask 0 sees nothing, and the root is a node like the others
+  __device__ __forceinline__ bool start() const { return m != 0u && node(0); }
+};
+
 // A lane's interval in the lane kernels: the caller's (t_min, t_max), or with RANGED ray i's own -- two coalesced 4-byte loads next to its ray.
 // A ray whose own interval fails interval_ok does not start its walk: it is a miss.
 template <bool RANGED>
@@ -21,8 +46,9 @@ __device__ __forceinline__ bool lane_interval(const KParams &p, int i, float &t_
 
 // objs_hit bvh r t_min t_max (ray.fut:76-86), one lane per ray: the pixel family's stack fold with the caller's interval on every box,
 // the spheres folded over (scene_epsilon, best) from best = t_max, then one re-intersection of the winner over (t_min, best + 1).
-template <bool RANGED>
-__device__ __forceinline__ void intersect_lane(const KParams &p, float t_min, float t_max, int32_t *index, float *hit7) {
+template <bool RANGED, bool MASKED = false>
+__device__ __forceinline__ void intersect_lane(const KParams &p, float t_min, float t_max, int32_t *index, float *hit7,
+                                               const GroupArgs &ga = GroupArgs{}) {
   __shared__ int stack[kStackPixel][64];
   const int lane = threadIdx.x;
   const int i = blockIdx.x * 64 + lane;
@@ -31,10 +57,11 @@ __device__ __forceinline__ void intersect_lane(const KParams &p, float t_min, fl
   const __amdgpu_buffer_rsrc_t rs_sph = make_rsrc(p.sph, (unsigned)p.n_sph * 16u);
   const Ray r = load_ray(p.rays, i);
   const bool valid = lane_interval<RANGED>(p, i, t_min, t_max);
+  const GroupView<MASKED> gv(p, ga, i);
   float best = t_max;
   int bestj = -1;
   int sp = 0;
-  if (valid) stack[sp++][lane] = 0;
+  if (valid && gv.start()) stack[sp++][lane] = 0;
   while (sp > 0) {
     const int ni = stack[--sp][lane];
     const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
@@ -45,9 +72,11 @@ __device__ __forceinline__ void intersect_lane(const KParams &p, float t_min, fl
       const int c = kids[k];
       if (c < 0) {
         const int j = ~c;
-        const float4 s = buf_load16(rs_sph, j * 16);
-        closest_update(sphere_root(r, s.x, s.y, s.z, s.w), j, best, bestj);
-      } else {
+        if (gv.leaf(j)) {
+          const float4 s = buf_load16(rs_sph, j * 16);
+          closest_update(sphere_root(r, s.x, s.y, s.z, s.w), j, best, bestj);
+        }
+      } else if (gv.node(c)) {
         stack[sp++][lane] = c;   // (at most one pending sibling per level: sp <= tree height + 1 <= kStackPixel)
       }
     }
@@ -92,8 +121,8 @@ hipError_t launch_intersect_rays_ranged(const KParams &p, int32_t *index, float 
 
 // rt_occluded_rays, one lane per ray: intersect_kernel's stack fold with the caller's interval on every box and on every sphere
 // (sphere_hit_any); the lane leaves the walk at its first accepted sphere -- the fold is an OR, so no order can change the answer.
-template <bool RANGED>
-__device__ __forceinline__ void occluded_lane(const KParams &p) {
+template <bool RANGED, bool MASKED = false>
+__device__ __forceinline__ void occluded_lane(const KParams &p, const GroupArgs &ga = GroupArgs{}) {
   __shared__ int stack[kStackPixel][64];
   const int lane = threadIdx.x;
   const int i = blockIdx.x * 64 + lane;
@@ -103,9 +132,10 @@ __device__ __forceinline__ void occluded_lane(const KParams &p) {
   const Ray r = load_ray(p.rays, i);
   float t_min = p.ray_tlo, t_max = p.ray_thi;
   const bool valid = lane_interval<RANGED>(p, i, t_min, t_max);
+  const GroupView<MASKED> gv(p, ga, i);
   bool hit = false;
   int sp = 0;
-  if (valid) stack[sp++][lane] = 0;
+  if (valid && gv.start()) stack[sp++][lane] = 0;
   while (sp > 0 && !hit) {
     const int ni = stack[--sp][lane];
     const float4 lo = buf_load16(rs_nodes, ni * 32), hi = buf_load16(rs_nodes, ni * 32 + 16);
@@ -115,9 +145,11 @@ __device__ __forceinline__ void occluded_lane(const KParams &p) {
     for (int k = 0; k < 2; ++k) {
       const int c = kids[k];
       if (c < 0) {
-        const float4 s = buf_load16(rs_sph, ~c * 16);
-        hit = hit || sphere_hit_any(r, t_min, t_max, s.x, s.y, s.z, s.w);
-      } else {
+        if (gv.leaf(~c)) {
+          const float4 s = buf_load16(rs_sph, ~c * 16);
+          hit = hit || sphere_hit_any(r, t_min, t_max, s.x, s.y, s.z, s.w);
+        }
+      } else if (gv.node(c)) {
         stack[sp++][lane] = c;   // (at most one pending sibling per level: sp <= tree height + 1 <= kStackPixel)
       }
     }
@@ -388,9 +420,9 @@ __device__ __forceinline__ float kth_gap(const unsigned long long (&list)[CAP], 
 }
 __device__ __forceinline__ int nearest_stack_entry(int node, int depth) { return (int)((unsigned)node | ((unsigned)(depth < 63 ? depth : 63) << 26)); }
 
-template <bool RANGED, bool PRUNED, int CAP>
+template <bool RANGED, bool PRUNED, int CAP, bool MASKED = false>
 __device__ __forceinline__ void nearest_lane(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, int k, int exact_depth,
-                                             int32_t *count, int32_t *index, float *gap) {
+                                             int32_t *count, int32_t *index, float *gap, const GroupArgs &ga = GroupArgs{}) {
   __shared__ int stack[kStackPixel][64];
   const int lane = threadIdx.x;
   const int i = blockIdx.x * 64 + lane;
@@ -401,13 +433,14 @@ __device__ __forceinline__ void nearest_lane(const KParams &p, const float *pts,
   if constexpr (RANGED) max_dist = max_dist_dev[i] + 0.0f;   // (-0.0 -> +0.0)
   const bool valid = point_ok(px, py, pz) && (!RANGED || max_dist_ok(max_dist));
   const float pmag = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
+  const GroupView<MASKED> gv(p, ga, i);
   unsigned long long list[CAP];
 #pragma unroll
   for (int s = 0; s < CAP; ++s) list[s] = ~0ull;
   int cnt = 0;
   float T = max_dist;
   int sp = 0;
-  if (valid) stack[sp++][lane] = nearest_stack_entry(0, 0);
+  if (valid && gv.start()) stack[sp++][lane] = nearest_stack_entry(0, 0);
   while (sp > 0) {
     const unsigned e = (unsigned)stack[--sp][lane];
     const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
@@ -417,7 +450,7 @@ __device__ __forceinline__ void nearest_lane(const KParams &p, const float *pts,
 #pragma unroll
     for (int c2 = 0; c2 < 2; ++c2) {
       const int c = kids[c2];
-      if (c < 0) {
+      if (c < 0 && gv.leaf(~c)) {
         const int j = ~c;
         const float4 s = buf_load16(rs_sph, j * 16);
         const float g = point_gap(px, py, pz, s.x, s.y, s.z, s.w);
@@ -435,7 +468,7 @@ __device__ __forceinline__ void nearest_lane(const KParams &p, const float *pts,
 #pragma unroll
       for (int c2 = 0; c2 < 2; ++c2) {
         const int c = kids[c2];
-        if (c >= 0) {
+        if (c >= 0 && gv.node(c)) {
           const float4 clo = buf_load16(rs_nodes, c * 32), chi = buf_load16(rs_nodes, c * 32 + 16);
           push[c2] = depth + 1 < exact_depth || box_may_hold(px, py, pz, pmag, clo.x, clo.y, clo.z, chi.x, chi.y, chi.z, T);
           b[c2] = box_gap_bound(px, py, pz, clo.x, clo.y, clo.z, chi.x, chi.y, chi.z);
@@ -450,7 +483,7 @@ __device__ __forceinline__ void nearest_lane(const KParams &p, const float *pts,
     } else {
 #pragma unroll
       for (int c2 = 0; c2 < 2; ++c2)
-        if (kids[c2] >= 0) stack[sp++][lane] = nearest_stack_entry(kids[c2], depth + 1);
+        if (kids[c2] >= 0 && gv.node(kids[c2])) stack[sp++][lane] = nearest_stack_entry(kids[c2], depth + 1);
     }
   }
   if (count != nullptr) count[i] = cnt;
@@ -529,10 +562,16 @@ struct OrderedWalk {
   // node_test(lo, hi): may the node's box hold a selected sphere; leaf(j): the action on sphere j >= first
   template <bool DEPTH, class NodeTest, class Leaf>
   __device__ __forceinline__ void run(bool valid, int first, int exact_depth, NodeTest &&node_test, Leaf &&leaf) const {
+    run<DEPTH>(valid, first, exact_depth, node_test, leaf, GroupView<false>(KParams{}, GroupArgs{}, 0));
+  }
+  // ... with a second node predicate, the sphere groups' (GroupView: may the subtree hold a seen sphere).  It is asked of an inner child where
+  // the child would be pushed and of a sphere where it would be offered, so the order of the remaining leaves and the stack bound are the walk's.
+  template <bool DEPTH, class NodeTest, class Leaf, class Groups>
+  __device__ __forceinline__ void run(bool valid, int first, int exact_depth, NodeTest &&node_test, Leaf &&leaf, const Groups &gv) const {
     __shared__ int stack[kStackPixel][64];
     const int lane = threadIdx.x;
     int sp = 0;
-    if (valid) stack[sp++][lane] = within_node_entry(0, 0);
+    if (valid && gv.start()) stack[sp++][lane] = within_node_entry(0, 0);
     while (sp > 0) {
       const unsigned e = (unsigned)stack[--sp][lane];
       const int ni = (int)(e & 0x3ffffffu), depth = (int)(e >> 26);
@@ -546,15 +585,15 @@ struct OrderedWalk {
         if (l < 0) {
           slot[0] = ~l;
           if (r < 0) slot[1] = ~r;
-          else stack[sp++][lane] = within_node_entry(r, DEPTH ? depth + 1 : 0);
+          else if (gv.node(r)) stack[sp++][lane] = within_node_entry(r, DEPTH ? depth + 1 : 0);
         } else {
-          stack[sp++][lane] = r < 0 ? within_leaf_entry(~r) : within_node_entry(r, DEPTH ? depth + 1 : 0);
-          stack[sp++][lane] = within_node_entry(l, DEPTH ? depth + 1 : 0);
+          if (r < 0 || gv.node(r)) stack[sp++][lane] = r < 0 ? within_leaf_entry(~r) : within_node_entry(r, DEPTH ? depth + 1 : 0);
+          if (gv.node(l)) stack[sp++][lane] = within_node_entry(l, DEPTH ? depth + 1 : 0);
         }
       }
 #pragma unroll
       for (int c2 = 0; c2 < 2; ++c2)
-        if (slot[c2] >= first) leaf(slot[c2]);
+        if (slot[c2] >= first && gv.leaf(slot[c2])) leaf(slot[c2]);
     }
   }
 };
@@ -591,10 +630,10 @@ struct CsrRow {
 // rt_spheres_within_* / rt_contact_pairs_* (DESIGN.md 3.5f): the node test is nearest_lane's box_may_hold with T = the point's bound, the leaf
 // rule gap <= that bound.  SELF (contact pairs): point i is the centre of L[i], its bound fl(radius_i + max_dist), first = i + 1; `point` then
 // is the pair array, rows {i, j}.
-template <bool FILL, bool SELF>
+template <bool FILL, bool SELF, bool MASKED = false>
 __device__ __forceinline__ void within_lane(const KParams &p, const float *pts, const float *max_dist_dev, float max_dist, const int32_t *first_dev,
                                             int exact_depth, int32_t *count, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap,
-                                            int32_t *point) {
+                                            int32_t *point, const GroupArgs &ga = GroupArgs{}) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= p.nrays) return;
   const OrderedWalk walk(p);
@@ -615,22 +654,21 @@ __device__ __forceinline__ void within_lane(const KParams &p, const float *pts, 
   }
   const float pmag = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
   CsrRow<FILL> row(i, offsets, capacity);
-  walk.run<true>(
-      valid, first, exact_depth,
-      [&](const float4 &lo, const float4 &hi) { return box_may_hold(px, py, pz, pmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, max_dist); },
-      [&](int j) {
-        const float4 s = walk.sphere(j);
-        const float g = point_gap(px, py, pz, s.x, s.y, s.z, s.w);
-        row.take(g <= max_dist, [&](int64_t at) {
-            if constexpr (SELF) {
-              if (point != nullptr) *reinterpret_cast<int2 *>(point + 2 * at) = make_int2(i, j);
-            } else {
-              if (index != nullptr) index[at] = j;
-              if (point != nullptr) point[at] = i;
-            }
-            if (gap != nullptr) gap[at] = g;
-          });
-      });
+  const auto node_test = [&](const float4 &lo, const float4 &hi) { return box_may_hold(px, py, pz, pmag, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, max_dist); };
+  const auto leaf = [&](int j) {
+    const float4 s = walk.sphere(j);
+    const float g = point_gap(px, py, pz, s.x, s.y, s.z, s.w);
+    row.take(g <= max_dist, [&](int64_t at) {
+      if constexpr (SELF) {
+        if (point != nullptr) *reinterpret_cast<int2 *>(point + 2 * at) = make_int2(i, j);
+      } else {
+        if (index != nullptr) index[at] = j;
+        if (point != nullptr) point[at] = i;
+      }
+      if (gap != nullptr) gap[at] = g;
+    });
+  };
+  walk.run<true>(valid, first, exact_depth, node_test, leaf, GroupView<MASKED>(p, ga, i));
   row.finish(i, count);
 }
 template <bool FILL, bool SELF>
@@ -1451,6 +1489,190 @@ hipError_t launch_camera_rays(const Cam &cam, int h, int w, float *rays, hipStre
   if (n <= 0) return hipSuccess;
   const unsigned grid = (unsigned)((n + 255) / 256 < 16384 ? (n + 255) / 256 : 16384);
   hipLaunchKernelGGL(camera_rays_kernel, dim3(grid), dim3(256), 0, stream, cam, h, w, rays);
+  return hipGetLastError();
+}
+
+// ---- sphere groups ------------------------------------------------------------------------------------------------------
+// The masked lane kernels: the MASKED instantiations of the lanes above -- the same walks, LDS stacks and 64-thread workgroups, with GroupView's
+// two tests -- behind kernel entries of their own.  A masked query sees sphere j iff group_seen(groups[j], mask); the answer is the unmasked
+// entry's with every unseen sphere absent at the leaf, and skipping a subtree whose node word shares no bit with the mask removes only unseen
+// spheres.
+template <bool RANGED>
+__global__ __launch_bounds__(64) void intersect_masked_kernel(KParams p, GroupArgs ga, float t_min, float t_max, int32_t *index, float *hit7) {
+  intersect_lane<RANGED, true>(p, t_min, t_max, index, hit7, ga);
+}
+template <bool RANGED>
+__global__ __launch_bounds__(64) void occluded_masked_kernel(KParams p, GroupArgs ga) {
+  occluded_lane<RANGED, true>(p, ga);
+}
+template <bool RANGED, bool PRUNED, int CAP>
+__global__ __launch_bounds__(64) void nearest_masked_kernel(KParams p, GroupArgs ga, const float *pts, const float *max_dist_dev, float max_dist, int k,
+                                                            int exact_depth, int32_t *count, int32_t *index, float *gap) {
+  nearest_lane<RANGED, PRUNED, CAP, true>(p, pts, max_dist_dev, max_dist, k, exact_depth, count, index, gap, ga);
+}
+template <bool FILL>
+__global__ __launch_bounds__(64) void within_masked_kernel(KParams p, GroupArgs ga, const float *pts, const float *max_dist_dev, float max_dist,
+                                                           const int32_t *first_dev, int exact_depth, int32_t *count, const int64_t *offsets,
+                                                           int64_t capacity, int32_t *index, float *gap, int32_t *point) {
+  within_lane<FILL, false, true>(p, pts, max_dist_dev, max_dist, first_dev, exact_depth, count, offsets, capacity, index, gap, point, ga);
+}
+
+static bool group_args_ok(const KParams &p, const GroupArgs &ga) { return ga.groups != nullptr && ga.node_groups != nullptr && p.n_nodes >= 1; }
+
+hipError_t launch_intersect_rays_masked(const KParams &p, const GroupArgs &ga, float t_min, float t_max, int32_t *index, float *hit7,
+                                        hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (!group_args_ok(p, ga) || index == nullptr || (p.ray_tlo_dev == nullptr) != (p.ray_thi_dev == nullptr)) return hipErrorInvalidValue;
+  if (p.ray_tlo_dev != nullptr)
+    hipLaunchKernelGGL((intersect_masked_kernel<true>), lane_grid(p.nrays), dim3(64), 0, stream, p, ga, 0.0f, 0.0f, index, hit7);
+  else
+    hipLaunchKernelGGL((intersect_masked_kernel<false>), lane_grid(p.nrays), dim3(64), 0, stream, p, ga, t_min, t_max, index, hit7);
+  return hipGetLastError();
+}
+
+hipError_t launch_occluded_rays_masked(const KParams &p, const GroupArgs &ga, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (!group_args_ok(p, ga) || p.occluded == nullptr || (p.ray_tlo_dev == nullptr) != (p.ray_thi_dev == nullptr)) return hipErrorInvalidValue;
+  if (p.ray_tlo_dev != nullptr) hipLaunchKernelGGL((occluded_masked_kernel<true>), lane_grid(p.nrays), dim3(64), 0, stream, p, ga);
+  else hipLaunchKernelGGL((occluded_masked_kernel<false>), lane_grid(p.nrays), dim3(64), 0, stream, p, ga);
+  return hipGetLastError();
+}
+
+template <bool RANGED, bool PRUNED>
+static hipError_t launch_nearest_masked_cap(const KParams &p, const GroupArgs &ga, const float *pts, const float *max_dist_dev, float max_dist, int k,
+                                            int exact_depth, int32_t *count, int32_t *index, float *gap, hipStream_t stream) {
+#define RT_NEAREST_MASKED(CAP)                                                                                                                     \
+  hipLaunchKernelGGL((nearest_masked_kernel<RANGED, PRUNED, CAP>), lane_grid(p.nrays), dim3(64), 0, stream, p, ga, pts, max_dist_dev, max_dist, k, \
+                     exact_depth, count, index, gap)
+  if (k <= 4) RT_NEAREST_MASKED(4);
+  else if (k <= 8) RT_NEAREST_MASKED(8);
+  else if (k <= 16) RT_NEAREST_MASKED(16);
+  else RT_NEAREST_MASKED(32);
+#undef RT_NEAREST_MASKED
+  return hipGetLastError();
+}
+
+hipError_t launch_nearest_spheres_masked(const KParams &p, const GroupArgs &ga, const float *pts, const float *max_dist_dev, float max_dist, int k,
+                                         int exact_depth, int32_t *count, int32_t *index, float *gap, hipStream_t stream) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (!group_args_ok(p, ga) || pts == nullptr || k < 1 || k > kNearestMaxK) return hipErrorInvalidValue;
+  if (count == nullptr && index == nullptr && gap == nullptr) return hipErrorInvalidValue;
+  const bool ranged = max_dist_dev != nullptr, pruned = count == nullptr;
+  if (!ranged && !max_dist_ok(max_dist)) return hipErrorInvalidValue;
+  max_dist += 0.0f;   // (-0.0 -> +0.0)
+  if (ranged) return pruned ? launch_nearest_masked_cap<true, true>(p, ga, pts, max_dist_dev, 0.0f, k, exact_depth, count, index, gap, stream)
+                            : launch_nearest_masked_cap<true, false>(p, ga, pts, max_dist_dev, 0.0f, k, exact_depth, count, index, gap, stream);
+  return pruned ? launch_nearest_masked_cap<false, true>(p, ga, pts, nullptr, max_dist, k, exact_depth, count, index, gap, stream)
+                : launch_nearest_masked_cap<false, false>(p, ga, pts, nullptr, max_dist, k, exact_depth, count, index, gap, stream);
+}
+
+hipError_t launch_within_count_masked(const KParams &p, const GroupArgs &ga, const float *pts, const float *max_dist_dev, float max_dist,
+                                      const int32_t *first_dev, int exact_depth, char *scratch, int64_t *offsets, hipStream_t stream) {
+  hipError_t rc;
+  if (csr_answered(p, false, offsets, scratch, 0, true, stream, &rc)) return rc;
+  if (!group_args_ok(p, ga) || !within_args_ok(p, pts, max_dist_dev, max_dist, false)) return hipErrorInvalidValue;
+  max_dist += 0.0f;   // (-0.0 -> +0.0)
+  hipLaunchKernelGGL((within_masked_kernel<false>), lane_grid(p.nrays), dim3(64), 0, stream, p, ga, pts, max_dist_dev, max_dist, first_dev, exact_depth,
+                     reinterpret_cast<int32_t *>(scratch), nullptr, (int64_t)0, nullptr, nullptr, nullptr);
+  return launch_count_scan(scratch, p.nrays, offsets, stream);
+}
+
+hipError_t launch_within_fill_masked(const KParams &p, const GroupArgs &ga, const float *pts, const float *max_dist_dev, float max_dist,
+                                     const int32_t *first_dev, int exact_depth, const int64_t *offsets, int64_t capacity, int32_t *index, float *gap,
+                                     int32_t *point, hipStream_t stream) {
+  hipError_t rc;
+  if (csr_answered(p, true, offsets, nullptr, capacity, index != nullptr || gap != nullptr || point != nullptr, stream, &rc)) return rc;
+  if (!group_args_ok(p, ga) || !within_args_ok(p, pts, max_dist_dev, max_dist, false)) return hipErrorInvalidValue;
+  max_dist += 0.0f;   // (-0.0 -> +0.0)
+  hipLaunchKernelGGL((within_masked_kernel<true>), lane_grid(p.nrays), dim3(64), 0, stream, p, ga, pts, max_dist_dev, max_dist, first_dev, exact_depth,
+                     nullptr, offsets, capacity, index, gap, point);
+  return hipGetLastError();
+}
+
+// The derive: the caller-order words gathered into L order, then the exact subtree OR of every inner node, twice -- in the canonical numbering
+// (left / right / parent: what rt_prepared_get_groups hands out) and in the traversal numbering (p.nodes: what the walks index).  Each is ONE
+// launch of group_climb (query_core.h) over words zeroed on the stream ahead of it: inner node v seeds the combine of its leaf children's
+// words and climbs the parents with relaxed agent-scope atomic ORs, carrying on only with the bits it newly set.  Vector atomics only, no
+// workgroup waits on another, and the result does not depend on the tree's height (63 levels are as exact as 3).  The traversal records hold
+// no parent: groups_parents_kernel writes one from the child references first (every inner node but the root is the child of exactly one).
+// Every index read from memory is checked against the scene's sizes before it is used as one.
+struct GroupOps {
+  uint32_t *words;
+  const int32_t *up;
+  int n_nodes;
+  __device__ __forceinline__ uint32_t fetch_or(int32_t v, uint32_t bits) const {
+    return __hip_atomic_fetch_or(&words[v], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ int32_t parent(int32_t v) const {
+    const int32_t u = up[v];
+    return u < n_nodes ? u : -1;
+  }
+};
+__global__ __launch_bounds__(256) void groups_gather_kernel(const int32_t *ids, const uint32_t *caller_words, int n, uint32_t *groups) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int c = ids[i];
+  groups[i] = c >= 0 && c < n ? caller_words[c] : 0u;
+}
+__global__ __launch_bounds__(256) void groups_parents_kernel(const float4 *nodes, int n_nodes, int32_t *trav_parent) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= n_nodes) return;
+  const int kids[2] = {f2i(nodes[2 * (size_t)v].w), f2i(nodes[2 * (size_t)v + 1].w)};
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+    if (kids[k] > 0 && kids[k] < n_nodes) trav_parent[kids[k]] = v;   // (the root, 0, is nobody's child: its word stays -1)
+}
+// TRAV: children from the traversal records (a leaf is ~j); else from the canonical left / right (a leaf is -2 - j)
+template <bool TRAV>
+__global__ __launch_bounds__(256) void groups_climb_kernel(const float4 *nodes, const int32_t *left, const int32_t *right, const int32_t *up, int n_nodes,
+                                                           const uint32_t *groups, uint32_t *words) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= n_nodes) return;
+  int kids[2];
+  if constexpr (TRAV) {
+    kids[0] = f2i(nodes[2 * (size_t)v].w);
+    kids[1] = f2i(nodes[2 * (size_t)v + 1].w);
+  } else {
+    kids[0] = left[v] <= -2 ? ~(-2 - left[v]) : 0;   // (an inner child contributes through its own climb)
+    kids[1] = right[v] <= -2 ? ~(-2 - right[v]) : 0;
+  }
+  uint32_t w[2] = {0u, 0u};
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int j = ~kids[k];
+    if (kids[k] < 0 && j <= n_nodes) w[k] = groups[j];   // (n = n_nodes + 1 spheres)
+  }
+  group_climb(GroupOps{words, up, n_nodes}, v, group_combine(w[0], w[1]));
+}
+
+size_t groups_bytes(int64_t n) {
+  const size_t words = ((size_t)n * 4 + 255) & ~(size_t)255;
+  return 5 * words;
+}
+GroupBlock groups_carve(char *block, int64_t n) {
+  const size_t words = ((size_t)n * 4 + 255) & ~(size_t)255;
+  GroupBlock b;
+  b.caller = reinterpret_cast<uint32_t *>(block);
+  b.groups = reinterpret_cast<uint32_t *>(block + words);
+  b.node_groups = reinterpret_cast<uint32_t *>(block + 2 * words);
+  b.trav_groups = reinterpret_cast<uint32_t *>(block + 3 * words);
+  b.trav_parent = reinterpret_cast<int32_t *>(block + 4 * words);
+  return b;
+}
+hipError_t launch_groups_derive(const GroupBlock &b, const int32_t *ids, const float4 *nodes, const int32_t *left, const int32_t *right,
+                                const int32_t *parent, int n, hipStream_t stream) {
+  if (n < 2 || b.caller == nullptr || ids == nullptr || nodes == nullptr || left == nullptr || right == nullptr || parent == nullptr)
+    return hipErrorInvalidValue;
+  const int ni = n - 1;
+  const size_t words = ((size_t)n * 4 + 255) & ~(size_t)255;
+  hipError_t e = hipMemsetAsync(b.node_groups, 0, 2 * words, stream);   // (both numberings' words: adjacent)
+  if (e == hipSuccess) e = hipMemsetAsync(b.trav_parent, 0xff, words, stream);
+  if (e != hipSuccess) return e;
+  const dim3 block(256), gn(((unsigned)n + 255u) / 256u), gi(((unsigned)ni + 255u) / 256u);
+  hipLaunchKernelGGL(groups_gather_kernel, gn, block, 0, stream, ids, b.caller, n, b.groups);
+  hipLaunchKernelGGL(groups_parents_kernel, gi, block, 0, stream, nodes, ni, b.trav_parent);
+  hipLaunchKernelGGL((groups_climb_kernel<false>), gi, block, 0, stream, nodes, left, right, parent, ni, b.groups, b.node_groups);
+  hipLaunchKernelGGL((groups_climb_kernel<true>), gi, block, 0, stream, nodes, left, right, b.trav_parent, ni, b.groups, b.trav_groups);
   return hipGetLastError();
 }
 

@@ -211,7 +211,25 @@ inline uint64_t next_tree_gen() {
   return ++g;
 }
 
+// The sphere groups of a prepared scene (rt_prepared_set_groups and the masked queries, api_queries.cpp): one device
+// allocation (query_device.hpp: GroupBlock) that holds the caller-order words and, derived from them for ONE tree, the words in L order and
+// the inner nodes' subtree ORs.  `derived_gen` names that tree (rt_prepared::tree_gen; 0: nothing derived yet): a masked entry or
+// rt_prepared_get_groups that finds another tree_gen -- after rt_prepared_update_spheres -- derives again, under the prepared scene's lock, on
+// the context's stream, ahead of its launch.  The block dies with the prepared scene: rt_prepared_free has drained the streams and set the
+// device when it deletes it.
+struct PreparedGroups {
+  char *block = nullptr;   // nullptr: the scene has no groups
+  uint64_t derived_gen = 0;
+  PreparedGroups() = default;
+  PreparedGroups(const PreparedGroups &) = delete;
+  PreparedGroups &operator=(const PreparedGroups &) = delete;
+  ~PreparedGroups() {
+    if (block) (void)hipFree(block);
+  }
+};
+
 struct rt_prepared {
+  mutable PreparedGroups groups;   // (state the masked queries bring up to date through a const scene, as the views' orders)
   uint64_t tree_gen = next_tree_gen();   // names the tree in nodes64: a new number with every prepared scene and every rt_prepared_update_spheres (what a context's exit tables were built from)
   rt_context *home = nullptr;        // the context that prepared it (its arena serves the views' blocks when it also renders them)
   mutable std::recursive_mutex mu;   // the views' orders are state of the prepared scene that render entries update: held while a frame is set up
